@@ -9,8 +9,8 @@ A "step" is one frame of the hot path over one batch of resident component pools
         (--sweep mfma|valu: separate sweep and cull launches; fused-valu: the fused pass with the v_fma chain)
 For N > 1 each rank owns one spatial tile, culls it against the same view and the ranks all-gatherv the COMPACTED
 global visible-index lists over RCCL (cfg5 pattern, --payload indices: what BASELINE.json's north_star names); the
-default workload is then cfg5 (12.5M per GPU, frustum-only + the exchange), for N = 1 it is cfg3. The N > 1 line also
-carries: the same ranks' frames WITHOUT the exchange (`n1_same_workload`, what one GPU does with one tile) and
+default workload is then cfg5 (12.5M per GPU, frustum-only + the exchange), for N = 1 it is cfg3. With --full the N > 1
+line also carries: the same ranks' frames WITHOUT the exchange (`n1_same_workload`, what one GPU does with one tile) and
 `scaling_efficiency` = value / (N * that); `exchange_ms` (one isolated exchange) and the bytes each rank's shard puts on
 the links; the bit-shard encoding timed in the same run (`mask_variant`); parity of EVERY rank's tile against the oracle.
 --scaling strong --entities-total T: one world of T entities cut into N tiles (T / N per GPU; N = 1: all of it).
@@ -21,6 +21,11 @@ GPU, and relays their one JSON line and exit code.
 
 Inputs are resident in HBM before the timed region; outputs stay on the device (only a 4-byte count is
 read back per frame). Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps frames and prints the headline (`value`, `ms_per_step`, the spread of the timed
+frames, `config.kernel_ms`). --full adds everything measured or checked beside it: parity of every rank's tile against the CPU
+oracle, the CPU baseline, the roofline, the per-kernel breakdown, the variants and, for N > 1, the exchange's checks and figures.
+--dump-outputs DIR writes what the last timed frame computed as .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -85,8 +90,8 @@ def parse_args():
                          "BASELINE.json names), or one bit per mirror entry behind the count (1/32 word per entry whatever the view: ~7x "
                          "fewer bytes at the bench's 21 %% visibility; timed in the same run as `mask_variant` unless --no-mask-variant). "
                          "auto: the smaller of the two for the view at hand (bits above 1/32 visible), after one trial frame of the bit "
-                         "form has been checked against the exact all-gatherv on every rank. The gathered sets of the timed frames are "
-                         "checked against the exact all-gatherv either way")
+                         "form has been checked against the exact all-gatherv on every rank. With --full the gathered sets of the timed "
+                         "frames are checked against the exact all-gatherv either way")
     ap.add_argument("--no-mask-variant", action="store_true", help="N > 1: skip the bit-shard frames timed beside the index lists")
     ap.add_argument("--no-mode-variants", action="store_true", help="N > 1, c-abi path: skip the frames timed with the other travel patterns")
     ap.add_argument("--no-torch-variant", action="store_true", help="N > 1, c-abi path: skip the frames timed through torch.distributed")
@@ -102,9 +107,19 @@ def parse_args():
                          "same name, on another depth image — they would mix into the profiler's per-kernel average and counters")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the CPU baseline, parity against the oracle, the roofline and per-kernel "
+                         "figures, the variants, and with N > 1 the exchange's checks and figures (the --no-* options above trim it). "
+                         "Without it a run sets up, warms up, times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's view 0 as gv_results_fetch hands it out, "
+                         "records in pool-slot order) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: above that a fixed, "
+                         "seeded sample of the entities (DIR/sampled_entities.npy) and their records")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -112,6 +127,45 @@ def cpu_baseline(wl, sc, view, depth):
     """The `cpu_baseline` leg: the oracle's AVX2 path (+ scalar pyramid / sweep) timed on this box's host cores (oracle/cpu_baseline.py)."""
     from oracle.cpu_baseline import cpu_baseline as timed_oracle
     return timed_oracle(wl, sc, view, depth)
+
+
+DUMP_LIMIT_BYTES, DUMP_SEED = 64 << 20, 0x0D0D5EED
+
+
+def output_arrays(got, n, world=None, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays of one fetched view (GpuVisibility.fetch, records in pool-slot order; `world`: the [n, 12] world
+    matrices of a sweep workload) as float32 / float64 — exact for every value they hold. Above `limit` bytes: a fixed, seeded sample
+    of the n entities (the same slots for every build at this n), their isVisible bytes and world matrices, and the records of
+    exactly those entities."""
+    out = dict(draw_count=np.array([got["draw_count"]], dtype=np.float64),
+               visible_idx=got["visible_idx"].astype(np.float64),
+               baked_model=got["baked_model"].astype(np.float32),
+               distance_sq=got["distance_sq"].astype(np.float32),
+               is_visible=got["is_visible"].astype(np.float32))
+    if world is not None:
+        out["world"] = world.astype(np.float32)
+    full_bytes = total = sum(a.nbytes for a in out.values())
+    k = n
+    while total > limit:
+        # first try: the full arrays' bytes per entity plus its slot number, with 10 % head-room for how the records fall; then halves
+        k = max(1, int(limit / (full_bytes / n + 8) * 0.9) if k == n else k // 2)
+        slots = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+        chosen = np.zeros(n, dtype=bool)
+        chosen[slots] = True
+        rec = chosen[got["visible_idx"]]
+        out = dict(draw_count=out["draw_count"], sampled_entities=slots.astype(np.float64),
+                   visible_idx=got["visible_idx"][rec].astype(np.float64), baked_model=got["baked_model"][rec].astype(np.float32),
+                   distance_sq=got["distance_sq"][rec].astype(np.float32), is_visible=got["is_visible"][slots].astype(np.float32))
+        if world is not None:
+            out["world"] = world[slots].astype(np.float32)
+        total = sum(a.nbytes for a in out.values())
+    return out
+
+
+def dump_outputs(directory, arrays):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def main():
@@ -233,12 +287,62 @@ def main():
     st = vis.stats()
     timed = vis.profile_samples()
     vis.profile_sampling(1)
+    elapsed = run.max_over_ranks(elapsed)
+    median_ms = float(np.median(per_step_ms))
+    # ---- the headline: all a plain run prints; --full adds to it below ----
+    out = {
+        "metric": "entity culls/sec at 10M entities; visible-set bit-match vs CPU ref",
+        "value": n * world * args.steps / elapsed,
+        "unit": "entity culls/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        # from one hipEvent per `frames_per_mark` frame boundaries on the library's stream (rank 0): median / min / max of the
+        # groups' per-frame means (an event per frame costs ~6 us of stream time per frame: not in the timed region)
+        "frames_per_mark": mark_group,
+        "ms_per_step_median": median_ms, "ms_per_step_min": float(per_step_ms.min()), "ms_per_step_max": float(per_step_ms.max()),
+        "value_at_median_step": n * world / (median_ms * 1e-3),
+        "config": {"workload": (wl["name"] if args.scaling == "weak" else
+                                f"{args.workload}-strong: ONE world of {n * world} entities cut into {world} spatial tile(s), "
+                                f"{n} per GPU; per tile as {wl['name']}"),
+                   "untimed_frames_before_warmup": prewarm_frames,  # device bring-up to sustained clocks (0.3 s); then `warmup` frames, then the timed ones
+                   "sweep": args.sweep if wl["sweep"] else None,
+                   "depth": args.depth if wl["hiz"] else None, "entities_per_gpu": n, "entities_total": n * world,
+                   "scaling_mode": (f"strong: one world of {n * world} entities cut into {world} spatial tile(s)" if args.scaling == "strong"
+                                    else f"weak: {n} entities per GPU"),
+                   "hiz": (f"{HIZ_SIZE}x{HIZ_SIZE}" + (" RG16F" if args.hiz_rg16f else "")) if wl["hiz"] else None,
+                   # who runs the timed exchange: the product's own C-ABI step, or torch.distributed over this script's buffers
+                   "exchange_path": (("c-abi" if fx.native else "torch") if exchange else None),
+                   "exchange_path_fallback": (fx.path_fallback if exchange else None),
+                   "exchange_transport": ((fx.transport_note or "RCCL (dlopen'ed by the library)") if exchange and fx.native else ("torch.distributed " + run.backend if exchange else None)),
+                   # the travel pattern of the timed frames: --exchange, or the fastest of the three over five frames each (the probe's ms per frame)
+                   "exchange_mode": fx.mode if exchange else None,
+                   "exchange_mode_probe_ms": fx.mode_probe_ms if exchange else None,
+                   "exchange_payload": (args.payload + (f" ({fx.payload_note})" if fx.payload_note else "")) if exchange else None,
+                   # per frame, in the TIMED region: only the bracketed kernels appear (default: the dominant one; --profile-all: all)
+                   "kernel_ms": {k: (st["device_ms"][k] * (st["launches"][k] / max(1, timed[k])) / max(1, args.steps))
+                                 for k in st["device_ms"] if st["device_ms"][k] > 0},
+                   # untimed frames run before the W warm-up frames so that the device is at its sustained clocks (0.3 s of wall clock)
+                   "prewarm_frames": prewarm_frames},
+    }
+    if args.dump_outputs and rank == 0:  # the last timed frame's results, before anything below runs another frame
+        world_matrices = vis.get_world(0, n) if wl["sweep"] else None
+        dump_outputs(args.dump_outputs, output_arrays(vis.fetch(0, write_back=False, occupancy=n), n, world_matrices))
+    if not args.full:
+        if exchange:
+            fx.settle(last)
+        exchange_watchdog.stop()
+        if rank == 0:
+            run.emit(out)
+        vis.close()
+        run.leave(0)
+
     problem = fx.check_padded(last) if exchange else None
     if not run.all_agree(problem is None):
         if rank == 0:
             run.emit({"error": "exchange check failed", "detail": problem})
         run.leave(1)
-    elapsed = run.max_over_ranks(elapsed)
 
     # With an exchange: the same frames WITHOUT it (same ranks, same run) = what one GPU does with one tile of this workload
     # (`n1_same_workload`), and so what the collective costs and what the scaling efficiency is; one ISOLATED exchange.
@@ -318,22 +422,9 @@ def main():
         if valu_variant and valu_variant["avg_launch_ms"] > 0:  # same algorithmic bytes, the other chain
             valu_variant["frac"] = ab["cull"] / (valu_variant["avg_launch_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
         traffic, traffic_source = counter_traffic(ROOT, args, n)
-        median_ms = float(np.median(per_step_ms))
         words = fx.shard_words_per_rank(fx.ex, timed_frame) if exchange else None
         counts = fx.exact_counts if exchange else None
-        out = {
-            "metric": "entity culls/sec at 10M entities; visible-set bit-match vs CPU ref",
-            "value": n * world * args.steps / elapsed,
-            "unit": "entity culls/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            # from one hipEvent per `frames_per_mark` frame boundaries on the library's stream (rank 0): median / min / max of the
-            # groups' per-frame means (an event per frame costs ~6 us of stream time per frame: not in the timed region)
-            "frames_per_mark": mark_group,
-            "ms_per_step_median": median_ms, "ms_per_step_min": float(per_step_ms.min()), "ms_per_step_max": float(per_step_ms.max()),
-            "value_at_median_step": n * world / (median_ms * 1e-3),
+        out.update({
             # N > 1: ONE GPU on ONE tile of this same workload (these ranks' frames without the exchange step, slowest rank) and
             # value / (N * that). Weak scaling: the efficiency of the job; strong: of the exchange only (the N = 1 run of the same
             # --entities-total is the other half: tools/scale_sweep.sh puts the runs side by side)
@@ -343,53 +434,6 @@ def main():
             "scaling_efficiency": ((n * world * args.steps / elapsed) / (world * no_exchange["value_per_gpu"])) if no_exchange and world > 1 else None,
             # the same frame through GV_CONFIG_BLOCK_BOUNDS (same outputs, checked): reported beside `value`, never as it
             "value_with_block_bounds": bounds_variant["value"] if bounds_variant else None,
-            "config": {"workload": (wl["name"] if args.scaling == "weak" else
-                                    f"{args.workload}-strong: ONE world of {n * world} entities cut into {world} spatial tile(s), "
-                                    f"{n} per GPU; per tile as {wl['name']}"),
-                       "untimed_frames_before_warmup": prewarm_frames,  # device bring-up to sustained clocks (0.3 s); then `warmup` frames, then the timed ones
-                       "sweep": args.sweep if wl["sweep"] else None,
-                       "block_bounds": {"examined_workgroup_fraction": examined} if args.block_bounds else None,
-                       "block_bounds_variant": bounds_variant, "valu_variant": valu_variant,
-                       "engine_flow_variant": engine_flow, "hard_depth_variant": hard_depth, "depth": args.depth if wl["hiz"] else None, "entities_per_gpu": n, "entities_total": n * world,
-                       "scaling_mode": (f"strong: one world of {n * world} entities cut into {world} spatial tile(s)" if args.scaling == "strong"
-                                        else f"weak: {n} entities per GPU"),
-                       "visible_fraction": visible / n, "hiz": (f"{HIZ_SIZE}x{HIZ_SIZE}" + (" RG16F" if args.hiz_rg16f else "")) if wl["hiz"] else None,
-                       "exchange": fx.describe(timed_frame) if exchange else None,
-                       # who runs the timed exchange: the product's own C-ABI step, or torch.distributed over this script's buffers
-                       "exchange_path": (("c-abi" if timed_native else "torch") if exchange else None),
-                       "exchange_path_fallback": (fx.path_fallback if exchange else None),
-                       "exchange_transport": ((fx.transport_note or "RCCL (dlopen'ed by the library)") if exchange and timed_native else ("torch.distributed " + run.backend if exchange else None)),
-                       # the travel pattern of the timed frames: --exchange, or the fastest of the three over five frames each (the probe's ms per frame)
-                       "exchange_mode": fx.mode if exchange else None,
-                       "exchange_mode_probe_ms": fx.mode_probe_ms if exchange else None,
-                       "exchange_payload": (args.payload + (f" ({fx.payload_note})" if fx.payload_note else "")) if exchange else None,
-                       "same_frames_without_exchange": no_exchange,
-                       # one isolated exchange (shard copy + collective + completion; nothing overlapped; host clock, slowest rank)
-                       "exchange_ms": exchange_ms,
-                       # what the exchange adds to a frame when it runs behind the next frame's cull (two slots in flight)
-                       "exchange_overhead_ms_per_step": (elapsed / args.steps * 1e3 - no_exchange["ms_per_step"]) if no_exchange else None,
-                       # bytes rank r's shard puts on each link per frame as it travels (padding included) / of those, list entries
-                       "shard_bytes_per_rank": [4 * w for w in words] if exchange else None,
-                       "list_bytes_per_rank": ([4 * (1 + int(c)) for c in counts] if exchange else None),
-                       "gathered_bytes_per_rank": (4 * sum(words)) if exchange else None,
-                       "gathered_over_list_bytes": ((sum(words) / float(sum(1 + int(c) for c in counts))) if exchange and timed_payload == "indices" else None),
-                       "visible_max_over_mean_by_rank": (float(counts.max() / max(1.0, counts.mean())) if exchange else None),
-                       # the same frames by the other travel patterns / through torch.distributed (same run, each checked)
-                       "exchange_mode_variants": mode_variants, "torch_variant": torch_variant,
-                       "mask_variant": mask_variant,
-                       # per frame, in the TIMED region: only the bracketed kernels appear (default: the dominant one; --profile-all: all)
-                       "kernel_ms": {k: (st["device_ms"][k] * (st["launches"][k] / max(1, timed[k])) / max(1, args.steps))
-                                     for k in st["device_ms"] if st["device_ms"][k] > 0},
-                       # per frame, every kernel, from 10 extra frames outside the timed region (hipEvents around each launch)
-                       "frame_kernel_ms": frame_kernel_ms,
-                       # untimed frames run before the W warm-up frames so that the device is at its sustained clocks (0.3 s of wall clock)
-                       "prewarm_frames": prewarm_frames,
-                       # the library's exchange: every acquired frame is complete; how many needed the second, exactly sized exchange
-                       # of tails to be so (a static camera: the first frame, which has no history to predict from)
-                       "exchange_frames_acquired": fx.frames_acquired if timed_native else None,
-                       "exchange_frames_completed_by_a_second_exchange": fx.frames_completed_late if timed_native else None,
-                       "mirror_upload_s": upload_s, "mirror_upload_bytes": upload_bytes,
-                       "culls_per_s_with_full_trs_upload_each_frame": dirty_rate},
             "roofline": {"bound": "hbm", "kernel": ("gv::sweep_cull_mfma_kernel" if args.sweep == "fused" else "gv::sweep_cull_valu_kernel") if fused else "gv::cull_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                          "algorithmic_bytes_per_launch": ab["cull"], "avg_launch_ms": cull_ms,
@@ -400,7 +444,35 @@ def main():
                          "measured_stream_peak": stream_peak,
                          "frac_of_measured_peak": (achieved / stream_peak) if stream_peak else None},
             "parity": parity,
-        }
+        })
+        out["config"].update({
+            "block_bounds": {"examined_workgroup_fraction": examined} if args.block_bounds else None,
+            "block_bounds_variant": bounds_variant, "valu_variant": valu_variant,
+            "engine_flow_variant": engine_flow, "hard_depth_variant": hard_depth,
+            "visible_fraction": visible / n,
+            "exchange": fx.describe(timed_frame) if exchange else None,
+            "same_frames_without_exchange": no_exchange,
+            # one isolated exchange (shard copy + collective + completion; nothing overlapped; host clock, slowest rank)
+            "exchange_ms": exchange_ms,
+            # what the exchange adds to a frame when it runs behind the next frame's cull (two slots in flight)
+            "exchange_overhead_ms_per_step": (elapsed / args.steps * 1e3 - no_exchange["ms_per_step"]) if no_exchange else None,
+            # bytes rank r's shard puts on each link per frame as it travels (padding included) / of those, list entries
+            "shard_bytes_per_rank": [4 * w for w in words] if exchange else None,
+            "list_bytes_per_rank": ([4 * (1 + int(c)) for c in counts] if exchange else None),
+            "gathered_bytes_per_rank": (4 * sum(words)) if exchange else None,
+            "gathered_over_list_bytes": ((sum(words) / float(sum(1 + int(c) for c in counts))) if exchange and timed_payload == "indices" else None),
+            "visible_max_over_mean_by_rank": (float(counts.max() / max(1.0, counts.mean())) if exchange else None),
+            # the same frames by the other travel patterns / through torch.distributed (same run, each checked)
+            "exchange_mode_variants": mode_variants, "torch_variant": torch_variant,
+            "mask_variant": mask_variant,
+            # per frame, every kernel, from 10 extra frames outside the timed region (hipEvents around each launch)
+            "frame_kernel_ms": frame_kernel_ms,
+            # the library's exchange: every acquired frame is complete; how many needed the second, exactly sized exchange
+            # of tails to be so (a static camera: the first frame, which has no history to predict from)
+            "exchange_frames_acquired": fx.frames_acquired if timed_native else None,
+            "exchange_frames_completed_by_a_second_exchange": fx.frames_completed_late if timed_native else None,
+            "mirror_upload_s": upload_s, "mirror_upload_bytes": upload_bytes,
+            "culls_per_s_with_full_trs_upload_each_frame": dirty_rate})
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl, sc, view, depth)
     if exchange:

@@ -73,6 +73,16 @@ class FrameExchange:
             return self.ex.exchange()
         return None
 
+    def settle(self, last):
+        """A plain run leaves after the headline: the last timed frame's exchange is completed (not checked) on every rank before
+        the contexts go, as --full's check of it does."""
+        r = self.run
+        if isinstance(last, dict):  # a frame of gv_exchange_visible, not yet acquired
+            r.vis.exchange_acquire(last["frame"])
+        elif not self.native:
+            self.ex.drain()
+        r.torch.cuda.synchronize()
+
     # ---- checks against the exact all-gatherv ----
     def check_exchange(self):
         """Exact-size all-gatherv of one frame (host-synchronising form): all ranks hold the same concatenated list;

@@ -16,7 +16,7 @@ def test_bench_prints_one_json_line(exchange):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29577")
     if exchange:
         env["GV_BENCH_EXCHANGE"] = "1"  # 1-rank RCCL group: the communicator's version banner must not reach stdout
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg3", "--entities", "200000", "--steps", "5",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "cfg3", "--entities", "200000", "--steps", "5",
                         "--warmup", "2"] + (["--no-cpu-baseline"] if exchange else []),  # the CPU leg (12 s) once is enough
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -40,6 +40,62 @@ def test_bench_prints_one_json_line(exchange):
 
 
 @pytest.mark.gpu
+def test_plain_bench_prints_the_headline_and_dumps_what_the_last_step_computed(tmp_path, oracle):
+    """Without --full: set-up, warm-up, exactly --steps timed frames and the headline line — nothing measured or checked beside it.
+    --dump-outputs writes the last timed frame's results: the same on a second run, and the CPU oracle's for the same inputs."""
+    import numpy as np
+
+    from garden_amd import scene
+    from garden_amd.benchlib.workloads import HIZ_SIZE, WORKLOADS, make_tile_scene
+    n, dumps = 200000, []
+    for k in range(2):
+        out_dir = tmp_path / f"run{k}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg3", "--entities", str(n), "--steps", "7",
+                            "--warmup", "2", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = p.stdout.splitlines()
+        assert len(lines) == 1, p.stdout[:2000]
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] - n / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+        assert d["metric"].startswith("entity culls/sec") and d["unit"] == "entity culls/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert not {"parity", "roofline", "cpu_baseline", "value_with_block_bounds"} & set(d), sorted(d)
+        assert "frame_kernel_ms" not in d["config"] and set(d["config"]["kernel_ms"]) == {"cull"}
+        arrays = {f.name[:-4]: np.load(f) for f in out_dir.glob("*.npy")}
+        assert set(arrays) == {"draw_count", "visible_idx", "baked_model", "distance_sq", "is_visible"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        dumps.append(arrays)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+    sc = make_tile_scene(WORKLOADS["cfg3"], n, 0, 1)
+    m = sc.meshes.copy()
+    exp = oracle.prepare_meshes(m, sc.transforms, sc.entity_to_transform, scene.main_camera_view(use_hiz=1),
+                                hiz=oracle.Hiz(scene.synthetic_depth(HIZ_SIZE, HIZ_SIZE)))
+    order = np.argsort(exp["visible_idx"], kind="stable")
+    got = dumps[0]
+    assert got["draw_count"][0] == exp["draw_count"] > 0
+    assert np.array_equal(got["visible_idx"], exp["visible_idx"][order].astype(np.float64))
+    assert np.array_equal(got["baked_model"].view(np.uint32), exp["baked_model"][order].view(np.uint32))
+    assert np.array_equal(got["is_visible"], m["isVisible"].astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_bench_gpus_2_prints_the_headline_and_leaves():
+    """A plain N > 1 run (two ranks sharing this box's GPU over gloo, the library's exchange over the tests' transport): the timed
+    frames carry the exchange, then rank 0 prints the headline and every rank leaves — nothing of --full runs."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["GV_BENCH_BACKEND"] = "gloo"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--entities", "200000", "--steps", "6", "--warmup", "1",
+                        "--exchange", "p2p"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[:2000]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 6 and d["value"] > 0 and d["config"]["entities_total"] == 400000
+    assert d["config"]["exchange_path"] == "c-abi" and d["config"]["exchange_mode"] == "p2p"
+    assert not {"parity", "roofline", "n1_same_workload", "scaling_efficiency"} & set(d) and "torch_variant" not in d["config"]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["allgather", "p2p", "broadcast"])
 def test_bench_gpus_2_starts_its_own_ranks(mode):
     """`python bench.py --gpus 2` with no torch.distributed environment: bench.py starts the two ranks itself (fresh
@@ -47,7 +103,7 @@ def test_bench_gpus_2_starts_its_own_ranks(mode):
     measurement), the workload defaults to cfg5's shape, and rank 0 prints the one JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["GV_BENCH_BACKEND"] = "gloo"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--entities", "300000", "--steps", "4",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--entities", "300000", "--steps", "4",
                         "--warmup", "1", "--exchange", mode], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -72,7 +128,7 @@ def test_bench_gpus_2_starts_its_own_ranks(mode):
 def _run_bench(argv, env_extra, timeout=1500):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *argv], capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[:2000]
@@ -142,7 +198,7 @@ def test_bench_mask_payload(ranks):
     else:
         env["GV_BENCH_BACKEND"] = "gloo"
         cmd = ["--gpus", "2", "--entities", "300000"]
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *cmd, "--steps", "4", "--warmup", "1", "--payload", "mask",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *cmd, "--steps", "4", "--warmup", "1", "--payload", "mask",
                         "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -462,6 +462,43 @@ def test_bench_launch_shape_is_checked_before_the_gpu_is_touched():
     assert len(lines) == 1 and "error" in json.loads(lines[0])
 
 
+def test_bench_refuses_a_step_count_below_one():
+    """--steps sets the number of timed frames: 0 is an argument error (rc 2), not a line divided by zero."""
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(__file__), "..")
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 2 and "--steps" in run.stderr and not run.stdout.strip()
+
+
+@pytest.mark.parametrize("sweep", [False, True])
+def test_bench_dumped_outputs_are_float_bounded_and_a_fixed_sample(sweep):
+    """bench.py --dump-outputs: every array float32 / float64 and exact; above the limit a seeded sample of the entities, the same on
+    every call, with the records of exactly those entities."""
+    import bench
+    rng = np.random.default_rng(7)
+    n = 200_000
+    vis = rng.random(n) < 0.2
+    idx = np.nonzero(vis)[0].astype(np.uint32)
+    got = dict(draw_count=int(idx.size), visible_idx=idx, baked_model=rng.random((idx.size, 12), dtype=np.float32),
+               distance_sq=rng.random(idx.size, dtype=np.float32), is_visible=vis.astype(np.uint8))
+    world = rng.random((n, 12), dtype=np.float32) if sweep else None
+    whole = bench.output_arrays(got, n, world)
+    assert "sampled_entities" not in whole and np.array_equal(whole["visible_idx"], idx) and whole["draw_count"][0] == idx.size
+    limit = 1 << 20
+    a, b = bench.output_arrays(got, n, world, limit=limit), bench.output_arrays(got, n, world, limit=limit)
+    assert set(a) == {"draw_count", "sampled_entities", "visible_idx", "baked_model", "distance_sq", "is_visible"} | ({"world"} if sweep else set())
+    assert all(a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) for k in a)
+    assert limit // 2 < sum(x.nbytes for x in a.values()) <= limit
+    slots = a["sampled_entities"].astype(np.int64)
+    assert np.all(np.diff(slots) > 0) and a["draw_count"][0] == idx.size
+    assert np.array_equal(a["is_visible"], vis[slots]) and np.array_equal(a["visible_idx"], slots[vis[slots]])
+    rows = np.searchsorted(idx, slots[vis[slots]])
+    assert np.array_equal(a["baked_model"], got["baked_model"][rows]) and np.array_equal(a["distance_sq"], got["distance_sq"][rows])
+    if sweep:
+        assert np.array_equal(a["world"], world[slots])
+
+
 def test_dirty_ranges_under_address_and_ub_sanitizers(tmp_path):
     """garden_amd/csrc/gv_dirty_ranges.hpp: the itemised dirty marks behind gv_mark_dirty (host-only). Random marks —
     overlapping, adjacent, empty, wrapping first + count — against a bitmap model, built with

@@ -6,7 +6,7 @@ var=$1; shift
 for r in $(seq 1 ${ROUNDS:-2}); do
   for on in 0 1; do
     if [ $on = 1 ]; then export $var=1; else unset $var; fi
-    python bench.py --no-cpu-baseline --no-parity "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-parity "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 c = d['config']

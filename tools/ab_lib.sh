@@ -6,7 +6,7 @@ old=$1; shift
 for r in $(seq 1 ${ROUNDS:-3}); do
   for which in old new; do
     if [ $which = old ]; then export GV_LIB_PATH=$old; else unset GV_LIB_PATH; fi
-    python bench.py --no-cpu-baseline --no-parity "$@" 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-parity "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 c = d['config']

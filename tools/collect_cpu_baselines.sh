@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/baselines
 rm -rf $out; mkdir -p $out
 for w in cfg2 cfg3 cfg4; do
-  python3 bench.py --workload $w > $out/r05_${w}_bench_line.json 2> $out/${w}.err
+  python3 bench.py --full --workload $w > $out/r05_${w}_bench_line.json 2> $out/${w}.err
 done
 threads=$(python3 -c "import bench; print(bench.effective_cores()[0])")
 {

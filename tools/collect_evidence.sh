@@ -58,7 +58,7 @@ run_probe() {  # run_probe <binary> <arguments...>: only a binary build_probe ha
   echo "# cfg3 on the HARD depth image (bench.py --depth noise: per-8x8-block occluders among the entities), then on the walls (SURVEY.md 8d)"
   for d in "--depth noise" ""; do
     echo "## bench.py $d"
-    python3 bench.py $d --no-cpu-baseline --steps 100 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step %.4f  cull kernel %.4f ms  frac %.3f  visible %.4f  frame kernels %s' % (d['ms_per_step'], d['roofline']['avg_launch_ms'], d['roofline']['frac'], d['config']['visible_fraction'], d['config']['frame_kernel_ms']))"
+    python3 bench.py --full $d --no-cpu-baseline --steps 100 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step %.4f  cull kernel %.4f ms  frac %.3f  visible %.4f  frame kernels %s' % (d['ms_per_step'], d['roofline']['avg_launch_ms'], d['roofline']['frac'], d['config']['visible_fraction'], d['config']['frame_kernel_ms']))"
   done
 } > $out/r06_hard_depth.txt 2>&1
 {
@@ -71,7 +71,7 @@ run_probe() {  # run_probe <binary> <arguments...>: only a binary build_probe ha
 } > $out/r06_multiview.txt 2>&1
 # the line an 8-GPU run prints, with 8 ranks SHARING this box's one GPU (torch over gloo, the library's exchange over the tests'
 # shared-memory transport): functional, never a measurement — what it shows is the balance of the ranks and the bytes on the links
-GV_BENCH_BACKEND=gloo timeout 1500 python3 bench.py --gpus 8 --entities 1500000 --steps 10 --warmup 2 > $out/r06_gloo8_sample_line.json 2> $out/gloo8.err
+GV_BENCH_BACKEND=gloo timeout 1500 python3 bench.py --full --gpus 8 --entities 1500000 --steps 10 --warmup 2 > $out/r06_gloo8_sample_line.json 2> $out/gloo8.err
 python3 - $out/r06_gloo8_sample_line.json <<'EOF' > $out/r06_gloo8_summary.txt 2>&1
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

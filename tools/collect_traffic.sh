@@ -23,6 +23,6 @@ rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pmc/stats_cfg
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pmc/stats_cfg4valu -- python3 bench.py --workload cfg4 --sweep fused-valu --no-cpu-baseline --no-parity > gpurun_out/pmc/stats_cfg4valu.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pmc/stats_cfg2_10M -- python3 bench.py --workload cfg2 --entities 10000000 --no-cpu-baseline --no-parity > gpurun_out/pmc/stats_cfg2_10M.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/pmc/stats_cfg5shape -- python3 bench.py --workload cfg5 --no-cpu-baseline --no-parity > gpurun_out/pmc/stats_cfg5shape.log 2>&1
-# the driver's own command (N = 1 default, with the CPU baseline and the parity gate), not under the profiler
+# the driver's own command (N = 1 default: the headline only), not under the profiler
 python3 bench.py > gpurun_out/pmc/stats_default.log 2> gpurun_out/pmc/default.err
 ls gpurun_out/pmc

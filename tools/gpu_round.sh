@@ -25,8 +25,9 @@ elif [ "$what" = tier ]; then
 elif [ "$what" = evidence ]; then
   # the line an 8-GPU run prints, with 8 ranks SHARING this box's one GPU (torch over gloo, the library's exchange over the tests'
   # shared-memory transport): functional, never a measurement — the probe of the travel patterns, the choice, parity on all ranks
-  GV_BENCH_BACKEND=gloo timeout 1500 python3 bench.py --gpus 8 --entities 1500000 --steps 10 --warmup 2 > gpurun_out/r06/gloo8_sample_line.json 2> gpurun_out/r06/gloo8.err
-  python3 - gpurun_out/r06/gloo8_sample_line.json <<'PY' | tee gpurun_out/r06/gloo8_summary.txt
+  gloo8=${OUT:-$TMPDIR}/gloo8
+  GV_BENCH_BACKEND=gloo timeout 1500 python3 bench.py --full --gpus 8 --entities 1500000 --steps 10 --warmup 2 > "${gloo8}_sample_line.json" 2> "$gloo8.err"
+  python3 - "${gloo8}_sample_line.json" <<'PY' | tee "${gloo8}_summary.txt"
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 c = d["config"]

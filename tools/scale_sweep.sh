@@ -30,7 +30,7 @@ for n in $GPUS; do
     for m in $modes; do
         echo "--- --gpus $n --exchange $m ${extra[*]:-} $*" >&2
         # the N = 1 run of a weak sweep is the per-GPU workload of the N > 1 runs (cfg5 shape), not bench.py's N = 1 default (cfg3)
-        python bench.py --gpus "$n" --steps "$STEPS" --warmup "$WARMUP" --exchange "$m" --workload "${WORKLOAD:-cfg5}" --no-cpu-baseline \
+        python bench.py --full --gpus "$n" --steps "$STEPS" --warmup "$WARMUP" --exchange "$m" --workload "${WORKLOAD:-cfg5}" --no-cpu-baseline \
             "${extra[@]}" "$@" 2>>"${OUT%.jsonl}.err" | grep '^{' >> "$OUT" || echo "{\"error\": \"bench.py --gpus $n --exchange $m failed\", \"n_gpus\": $n}" >> "$OUT"
     done
 done

@@ -15,7 +15,7 @@ for n in 10000 100000 1000000 10000000 100000000; do
   steps=200; [ $n -ge 100000000 ] && steps=20
   flags=""
   if [ $n -ge 100000000 ] && [ "$avail_gb" -lt 96 ]; then flags="--no-cpu-baseline"; fi
-  python3 bench.py --workload cfg2 --entities $n --steps $steps --warmup 5 $flags > $out/cfg2_$n.json 2> $out/cfg2_$n.err
+  python3 bench.py --full --workload cfg2 --entities $n --steps $steps --warmup 5 $flags > $out/cfg2_$n.json 2> $out/cfg2_$n.err
 done
 python3 - <<'PY'
 import json, glob
