@@ -212,6 +212,13 @@ struct PoolState {
                                      // little gets its boxes rebuilt once, then patched; one that keeps changing a lot goes without)
     bool patch_valid = false;        // every change of the mirror since then is recorded in d_blk_dirty (flat, exactly paired pools):
                                      // the next cull re-derives the flagged blocks instead of going without boxes
+    // the sphere stream (MeshMirror::hot; flat, exactly paired pools), valid for (hot_xf_epoch, hot_epoch); hot_patch_valid: every
+    // change since then is flagged kDirtyHot in d_blk_dirty, so the next cull re-derives those blocks' entries
+    DeviceBuf<float4> d_hot;
+    uint64_t hot_epoch = 0, hot_xf_epoch = 0;
+    bool hot_patch_valid = false;
+    bool recording() const { return patch_valid || hot_patch_valid; }  // some consumer wants this sync's changes flagged
+    void stop_recording() { patch_valid = hot_patch_valid = false; }
     DeviceBuf<EmitSeed> d_seed;    // emit seeds (gv_kernels.hpp), valid for (seed_xf_epoch, seed_epoch)
     uint64_t seed_epoch = 0, seed_xf_epoch = 0;
     DeviceBuf<uint32_t> d_kept;    // [2 alternating counters, 2 words of padding | list entries] of launch_cull_listed

@@ -75,9 +75,15 @@ __device__ __forceinline__ void reload_cull_args(CullArgs& out)
 // are read afresh at each stage — inlined into a loop, the ~70 SGPRs of planes, matrices and pointers would otherwise be read once
 // in front of it and stay live across it (106 SGPRs, the overflow spilled into VGPRs: six waves per SIMD where cull_kernel runs
 // eight); per stage each field lives only where it is used.
-template <bool HIZ, uint32_t MAP, bool RELOAD = false>
+// HOT (flat, exactly paired pools with a current sphere stream, MeshMirror::hot): every lane loads its 16-byte sphere entry and
+// classifies from it — c3 = pos - cam as translated() computes it, the same r, so the same decision bits; only the lanes that need
+// corners (undecided, or inside with Hi-Z) load the TRS / AABB streams and rebuild the model through prepare_model, exactly as
+// the plain path. A wave whose lanes are all outside (or all inside without Hi-Z) fetches none of their 49 cold bytes. (cull_kernel
+// only: pools culled through block bounds keep no sphere stream, gv_context.cpp.)
+template <bool HIZ, uint32_t MAP, bool RELOAD = false, bool HOT = false>
 __device__ __forceinline__ void cull_block(const CullArgs& args0, uint32_t lb, uint32_t* wave_count)
 {
+    static_assert(!HOT || MAP == kMapExact, "the sphere stream exists for exactly paired pools only");
     CullArgs stage1;
     if (RELOAD)
         reload_cull_args(stage1);
@@ -88,7 +94,35 @@ __device__ __forceinline__ void cull_block(const CullArgs& args0, uint32_t lb, u
     const uint32_t i = lb * kCullBlock + tid;
     const uint32_t lane = tid & 63u, wave = tid >> 6;
     bool visible = false;
-    if (i < args.mesh.count) {
+    if (HOT && i < args.mesh.count) {
+        const float4 h = stream_load(&args.mesh.hot[i]);
+        uint32_t where = kSphereOutside;
+        if (!(h.w < 0.0f)) {  // kHotDropped: filtered out (a NaN r is not dropped: it reaches "undecided")
+            const float tx = h.x - args.view.cam[0], ty = h.y - args.view.cam[1], tz = h.z - args.view.cam[2];
+            where = classify_sphere(tx, ty, tz, sphere_reach(h.w, tx, ty, tz), args.view.planes, args.view.plane_count);
+        }
+        visible = where == kSphereInside;
+        Corners c;
+        if (where == kSphereUndecided || (HIZ && visible)) {
+            Mat34 m;
+            float4 box_a;
+            float2 box_b;
+            if (prepare_model<MAP>(args.mesh, args.xf, args.view.cam, i, m, box_a, box_b)) {  // (always, while the entry is current)
+                aabb_corners(m, box_a, box_b, c);
+                if (where == kSphereUndecided)
+                    visible = !behind_frustum(c, args.view.planes, args.view.plane_count);
+            } else {
+                visible = false;
+            }
+        }
+        if (HIZ && visible) {
+            CullArgs stage2;
+            if (RELOAD)
+                reload_cull_args(stage2);
+            const CullArgs& a2 = RELOAD ? stage2 : args0;
+            visible = !hiz_occluded(a2.hiz, a2.view.vp, c);
+        }
+    } else if (!HOT && i < args.mesh.count) {
         Mat34 m;
         float4 box_a;
         float2 box_b;
@@ -141,14 +175,14 @@ __device__ __forceinline__ void cull_block(const CullArgs& args0, uint32_t lb, u
     }
 }
 
-template <bool HIZ, uint32_t MAP>
+template <bool HIZ, uint32_t MAP, bool HOT = false>
 __global__ __launch_bounds__(kCullBlock) void cull_kernel(const CullArgs args)
 {
     __shared__ uint32_t wave_count[kCullBlock / 64];
     const uint32_t lb = tile_of_workgroup(blockIdx.x, args.xcd_run);
     if (lb >= args.nblocks)
         return;
-    cull_block<HIZ, MAP>(args, lb, wave_count);
+    cull_block<HIZ, MAP, false, HOT>(args, lb, wave_count);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -612,7 +646,12 @@ hipError_t launch_cull(const MeshMirror& mesh, const TransformMirror& xf, const 
     const dim3 grid(grid_for_tiles(a.nblocks, a.xcd_run)), block(kCullBlock);
 #define GV_LAUNCH_CULL(HIZ)                                                                                       \
     switch (mesh.mapping) {                                                                                      \
-    case kMapExact: hipLaunchKernelGGL((cull_kernel<HIZ, kMapExact>), grid, block, 0, stream, a); break;         \
+    case kMapExact:                                                                                              \
+        if (mesh.hot)                                                                                            \
+            hipLaunchKernelGGL((cull_kernel<HIZ, kMapExact, true>), grid, block, 0, stream, a);                  \
+        else                                                                                                     \
+            hipLaunchKernelGGL((cull_kernel<HIZ, kMapExact>), grid, block, 0, stream, a);                        \
+        break;                                                                                                   \
     case kMapSpeculate: hipLaunchKernelGGL((cull_kernel<HIZ, kMapSpeculate>), grid, block, 0, stream, a); break; \
     default: hipLaunchKernelGGL((cull_kernel<HIZ, kMapGeneral>), grid, block, 0, stream, a); break;              \
     }
@@ -731,13 +770,14 @@ __global__ __launch_bounds__(kCullBlock) void block_patch_kernel(const MeshMirro
 {
     __shared__ float red[kCullBlock / 64][7];
     const uint4 word = *reinterpret_cast<const uint4*>(flags + (size_t)blockIdx.x * kPatchSpan);  // workgroup-uniform
-    if ((word.x | word.y | word.z | word.w) == 0u)
+    constexpr uint32_t bit = kDirtyBounds * 0x01010101u;  // this consumer's bit in each of the four flag bytes of a word
+    if (((word.x | word.y | word.z | word.w) & bit) == 0u)
         return;
     const uint32_t w[4] = {word.x, word.y, word.z, word.w};
 #pragma unroll 1
     for (uint32_t k = 0; k < kPatchSpan; k++) {
         const uint32_t lb = blockIdx.x * kPatchSpan + k;
-        if (!((w[k >> 2] >> (8u * (k & 3u))) & 0xFFu) || lb >= nblocks)
+        if (!((w[k >> 2] >> (8u * (k & 3u))) & kDirtyBounds) || lb >= nblocks)
             continue;
         block_bounds_of<MAP>(mesh, xf, lb, red, out_lo, out_hi);
         if (seeds)
@@ -745,7 +785,51 @@ __global__ __launch_bounds__(kCullBlock) void block_patch_kernel(const MeshMirro
         __syncthreads();  // `red` is reused by the next block
     }
     if (threadIdx.x == 0)  // (every lane has read the flags into `word` before anyone gets here: the load precedes the first barrier)
-        *reinterpret_cast<uint4*>(flags + (size_t)blockIdx.x * kPatchSpan) = make_uint4(0, 0, 0, 0);
+        *reinterpret_cast<uint4*>(flags + (size_t)blockIdx.x * kPatchSpan) = make_uint4(word.x & ~bit, word.y & ~bit, word.z & ~bit, word.w & ~bit);
+}
+
+// The sphere stream (MeshMirror::hot) of a flat, exactly paired pool: every entry (a full build: new mirror, re-order, growth) ...
+__global__ __launch_bounds__(256) void hot_build_kernel(const MeshMirror mesh, const TransformMirror xf, float4* __restrict__ hot)
+{
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i < mesh.count)
+        stream_store(hot + i, hot_entry(mesh, xf, i));
+}
+// ... or the entries of the blocks flagged kDirtyHot since it was last current, 16 blocks per workgroup as block_patch_kernel
+__global__ __launch_bounds__(kCullBlock) void hot_patch_kernel(const MeshMirror mesh, const TransformMirror xf, float4* __restrict__ hot,
+                                                               uint8_t* __restrict__ flags /* padded to a multiple of kPatchSpan */)
+{
+    const uint4 word = *reinterpret_cast<const uint4*>(flags + (size_t)blockIdx.x * kPatchSpan);  // workgroup-uniform
+    constexpr uint32_t bit = kDirtyHot * 0x01010101u;
+    if (((word.x | word.y | word.z | word.w) & bit) == 0u)
+        return;
+    const uint32_t w[4] = {word.x, word.y, word.z, word.w};
+#pragma unroll 1
+    for (uint32_t k = 0; k < kPatchSpan; k++) {
+        const uint32_t i = (blockIdx.x * kPatchSpan + k) * kCullBlock + threadIdx.x;
+        if (((w[k >> 2] >> (8u * (k & 3u))) & kDirtyHot) && i < mesh.count)
+            hot[i] = hot_entry(mesh, xf, i);
+    }
+    __syncthreads();  // (every lane has read the flags before they are rewritten)
+    if (threadIdx.x == 0)
+        *reinterpret_cast<uint4*>(flags + (size_t)blockIdx.x * kPatchSpan) = make_uint4(word.x & ~bit, word.y & ~bit, word.z & ~bit, word.w & ~bit);
+}
+
+hipError_t launch_hot_build(const MeshMirror& mesh, const TransformMirror& xf, float4* hot, hipStream_t stream)
+{
+    if (mesh.count == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(hot_build_kernel, dim3((mesh.count + 255) / 256), dim3(256), 0, stream, mesh, xf, hot);
+    return hipGetLastError();
+}
+
+hipError_t launch_hot_patch(const MeshMirror& mesh, const TransformMirror& xf, float4* hot, uint8_t* flags, hipStream_t stream)
+{
+    if (mesh.count == 0)
+        return hipSuccess;
+    const uint32_t nblocks = (mesh.count + kCullBlock - 1) / kCullBlock;
+    hipLaunchKernelGGL(hot_patch_kernel, dim3((nblocks + kPatchSpan - 1) / kPatchSpan), dim3(kCullBlock), 0, stream, mesh, xf, hot, flags);
+    return hipGetLastError();
 }
 
 hipError_t launch_block_patch(const MeshMirror& mesh, const TransformMirror& xf, float4* lo, float4* hi, EmitSeed* seeds, uint8_t* flags,
@@ -763,7 +847,7 @@ hipError_t launch_block_patch(const MeshMirror& mesh, const TransformMirror& xf,
     return hipGetLastError();
 }
 
-// flags[entry >> 8] = 1 for every entry re-mirrored by a sync: thread t is the t-th dirty slot of the sync's ranges (start[k] = slots
+// flags[entry >> 8] = kDirtyAll for every entry re-mirrored by a sync: thread t is the t-th dirty slot of the sync's ranges (start[k] = slots
 // in the ranges before range k, first[k] = its first slot); inv: slot -> mirror entry, a table of `slots` elements (NULL: the
 // mirror is in slot order). The ranges may be TRANSFORM slots (transform-side syncs flag the exactly paired mesh pools through the
 // transform pool's own table): a slot is bounded by the table it indexes, the ENTRY by the flagged pool's occupancy — a paired
@@ -788,7 +872,7 @@ __global__ __launch_bounds__(256) void mark_dirty_blocks_kernel(const uint32_t* 
         return;
     const uint32_t entry = inv ? inv[slot] : slot;
     if (entry < entries)
-        flags[entry / kCullBlock] = 1;
+        flags[entry / kCullBlock] = kDirtyAll;
 }
 
 hipError_t launch_mark_dirty_blocks(const uint32_t* start, const uint32_t* first, uint32_t nranges, uint32_t total, const uint32_t* inv,

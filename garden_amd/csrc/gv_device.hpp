@@ -357,33 +357,60 @@ __device__ __forceinline__ bool prepare_slot(const MeshMirror& mesh, const Trans
 // — a plane within the band, non-finite values (every comparison false) — is "undecided" and takes the exact test.
 // At 10 M entities 0.2-0.5 % of the entries are undecided; 230 -> ~170 VALU instructions per wave with Hi-Z.
 enum : uint32_t { kSphereOutside = 0, kSphereInside = 1, kSphereUndecided = 2 };
-// r + the magnitude-proportional part of the slack (view independent: shadow passes that share the camera share it)
-__device__ __forceinline__ float sphere_reach(const Mat34& m, const float4 a, const float2 b)
+// r alone: depends on the model's columns c0..c2 and the box, not on the camera (the sphere stream stores it; the one copy of it)
+__device__ __forceinline__ float sphere_radius(const Mat34& m, const float4 a, const float2 b)
 {
     // NaN-propagating maxima: a NaN anywhere must reach the comparisons (fmaxf would drop it and decide for the exact test)
     const float ax = max_nan(fabsf(a.x), fabsf(a.w)), ay = max_nan(fabsf(a.y), fabsf(b.x)), az = max_nan(fabsf(a.z), fabsf(b.y));
-    const float r = fmaf(fabsf(m.c0x) + fabsf(m.c0y) + fabsf(m.c0z), ax,
-                         fmaf(fabsf(m.c1x) + fabsf(m.c1y) + fabsf(m.c1z), ay, (fabsf(m.c2x) + fabsf(m.c2y) + fabsf(m.c2z)) * az));
-    const float mag = max_nan(max_nan(fabsf(m.c3x), fabsf(m.c3y)), fabsf(m.c3z)) + r;
+    return fmaf(fabsf(m.c0x) + fabsf(m.c0y) + fabsf(m.c0z), ax,
+                fmaf(fabsf(m.c1x) + fabsf(m.c1y) + fabsf(m.c1z), ay, (fabsf(m.c2x) + fabsf(m.c2y) + fabsf(m.c2z)) * az));
+}
+// r + the magnitude-proportional part of the slack, with (tx, ty, tz) the camera-relative translation c3
+__device__ __forceinline__ float sphere_reach(float r, float tx, float ty, float tz)
+{
+    const float mag = max_nan(max_nan(fabsf(tx), fabsf(ty)), fabsf(tz)) + r;
     return fmaf(4e-5f, mag, r) + 0.01f;
 }
-__device__ __forceinline__ uint32_t classify_sphere(const Mat34& m, float reach, const float (&planes)[6][4], uint32_t plane_count)
+// (view independent: shadow passes that share the camera share it)
+__device__ __forceinline__ float sphere_reach(const Mat34& m, const float4 a, const float2 b)
+{
+    return sphere_reach(sphere_radius(m, a, b), m.c3x, m.c3y, m.c3z);
+}
+__device__ __forceinline__ uint32_t classify_sphere(float tx, float ty, float tz, float reach, const float (&planes)[6][4], uint32_t plane_count)
 {
     bool outside = false, decided = true;
 #pragma unroll
     for (uint32_t p = 0; p < 6; p++)
         if (p < plane_count) {  // wave-uniform: the coefficients stay in SGPRs
             const float bound = fmaf(4e-5f, fabsf(planes[p][3]), reach);
-            const float d = fmaf(planes[p][0], m.c3x, fmaf(planes[p][1], m.c3y, fmaf(planes[p][2], m.c3z, planes[p][3])));
+            const float d = fmaf(planes[p][0], tx, fmaf(planes[p][1], ty, fmaf(planes[p][2], tz, planes[p][3])));
             outside = outside | (d < -bound);  // no short circuit: straight-line code, the masks live in SGPR pairs
             decided = decided & ((d > bound) | (d < -bound));
         }
     return outside ? kSphereOutside : (decided ? kSphereInside : kSphereUndecided);
 }
+__device__ __forceinline__ uint32_t classify_sphere(const Mat34& m, float reach, const float (&planes)[6][4], uint32_t plane_count)
+{
+    return classify_sphere(m.c3x, m.c3y, m.c3z, reach, planes, plane_count);
+}
 __device__ __forceinline__ uint32_t classify_sphere(const Mat34& m, const float4 a, const float2 b, const float (&planes)[6][4],
                                                     uint32_t plane_count)
 {
     return classify_sphere(m, sphere_reach(m, a, b), planes, plane_count);
+}
+
+// The sphere-stream entry of mirror entry i of a flat, exactly paired pool (MeshMirror::hot): the filter chain and model of
+// prepare_model with a zero camera — translated(world, 0, 0, 0) leaves c3 = pos bit for bit, and the cull subtracts the camera
+// from it with the same operation translated() uses — and r from sphere_radius. A dropped entry gets r = kHotDropped.
+__device__ __forceinline__ float4 hot_entry(const MeshMirror& mesh, const TransformMirror& xf, uint32_t i)
+{
+    const float zero[3] = {0.0f, 0.0f, 0.0f};
+    Mat34 m;
+    float4 a;
+    float2 b;
+    if (!prepare_model<kMapExact>(mesh, xf, zero, i, m, a, b))
+        return make_float4(0.0f, 0.0f, 0.0f, kHotDropped);
+    return make_float4(m.c3x, m.c3y, m.c3z, sphere_radius(m, a, b));
 }
 
 // default getReadyMeshesAsync predicate (render/mesh.hpp:142-146). Fully unrolled with a wave-uniform guard so

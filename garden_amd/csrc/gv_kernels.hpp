@@ -7,8 +7,9 @@ namespace gv {
 
 // ---- device mirror of the component pools (HBM layout) ----
 // Streams are split so that a kernel reads only what the pool needs: 65 B per entity for a flat pool whose
-// meshes and transforms pair up 1:1 (TRS 40 + flags 1 + AABB 24: the algorithmic minimum), +4 B parent entry
-// with a hierarchy, +4 B transform entry when mesh and transform pools are ordered independently.
+// meshes and transforms pair up 1:1 (TRS 40 + flags 1 + AABB 24), +4 B parent entry with a hierarchy, +4 B transform
+// entry when mesh and transform pools are ordered independently. A flat, exactly paired pool also keeps a 16 B sphere
+// stream (MeshMirror::hot) from which the cull decides most entries; the 65 B are then read near the frustum only.
 constexpr uint32_t kSlotMask = 0x0FFFFFFFu;
 constexpr uint32_t kSlotNone = 0x0FFFFFFFu;
 constexpr uint32_t kXfActive = 1u;         // selfActive && ancestorsActive (transform.hpp:110)
@@ -46,7 +47,20 @@ struct MeshMirror {
     uint32_t count;
     uint32_t mapping;      // MeshMapping, decided at mirror build (speed only: every mapping is handled correctly)
     const uint32_t* orig;  // mirror entry -> pool slot (null: the mirror is in pool order)
+    const float4* hot;     // flat, exactly paired pools (kMapExact, max_depth 0): the sphere stream, one HotEntry per entry, or null
 };
+// The sphere stream: what the cull's sphere pre-test needs of an entry of a flat, exactly paired pool, 16 bytes instead of 65:
+// (pos.xyz, r) with r the view-independent part of the sphere (sphere_radius), or r = kHotDropped (negative; a computed r is
+// >= +0 or NaN) when the filter chain drops the entry (non-candidate, empty box, inactive transform, no transform entry). The
+// TRS / AABB streams are read only by the lanes that need corners. Derived on the device from the entry's own mirrored fields
+// (launch_hot_build / launch_hot_patch) and kept current at every cull through the dirty-block flags.
+constexpr float kHotDropped = -1.0f;
+// PoolState::d_blk_dirty bits: a block holds an entry re-mirrored since the boxes / the sphere stream were last current
+constexpr uint8_t kDirtyBounds = 1u, kDirtyHot = 2u, kDirtyAll = kDirtyBounds | kDirtyHot;
+constexpr uint32_t kHotMinSlots = 65536;  // smaller pools cull in one launch with their emit (kFusedEmitMaxSlots) or are launch-bound
+hipError_t launch_hot_build(const MeshMirror& mesh, const TransformMirror& xf, float4* hot, hipStream_t stream);
+// re-derives the entries of the blocks flagged kDirtyHot (flags padded to a multiple of 16) and clears that bit
+hipError_t launch_hot_patch(const MeshMirror& mesh, const TransformMirror& xf, float4* hot, uint8_t* flags, hipStream_t stream);
 
 struct HizDevice {
     const float* depth;          // mip 0

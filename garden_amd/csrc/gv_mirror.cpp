@@ -754,7 +754,7 @@ int grow_transforms(GvCtx* ctx, uint32_t n0, uint32_t n1, PhaseTimer& phase)
     GV_HIP(ctx, launch_pack_active(ctx->d_xflags.ptr, n1, ctx->d_xactive.ptr, ctx->stream));
     ctx->xf_mirrored = n1;
     for (auto& q : ctx->pools) {
-        q.patch_valid = false;  // (appended entries: the blocks change; rebuilt once the pools are at rest)
+        q.stop_recording();  // (appended entries: the blocks change; rebuilt once the pools are at rest)
         q.small_streak = 0;
     }
     ctx->xf_appended += n1 - n0;
@@ -794,7 +794,7 @@ int grow_meshes(GvCtx* ctx, PoolState& p, uint32_t n0, uint32_t n1)
     p.appended += n1 - n0;
     p.epoch++;
     p.order_epoch++;
-    p.patch_valid = false;
+    p.stop_recording();
     return GV_OK;
 }
 
@@ -987,7 +987,7 @@ int reorder_meshes_device(GvCtx* ctx, PoolState& p, KeySorter& ks, const uint32_
     p.staging_stale.add(0, n);
     p.epoch++;
     p.order_epoch++;
-    p.patch_valid = false;
+    p.stop_recording();
     p.appended = 0;
     const uint32_t pool_id = (uint32_t)(&p - ctx->pools);
     for (auto& vs : ctx->views[pool_id]) {  // per-entry outputs of earlier culls are in the old order
@@ -1141,10 +1141,10 @@ int sync_mirror(GvCtx* ctx)
                 const uint64_t nblocks = (q.occupancy + kCullBlock - 1) / kCullBlock;
                 const bool few = !dense && !ctx->xf_links_dirty && total * 16 <= nblocks + 16 * 64;
                 q.small_streak = few ? std::min(q.small_streak + 1u, 1000u) : 0u;
-                if (!q.patch_valid)
+                if (!q.recording())
                     continue;
                 if (!few || ctx->max_depth != 0 || q.mapping != kMapExact || !q.d_blk_dirty.ptr) {
-                    q.patch_valid = false;
+                    q.stop_recording();
                 } else {
                     targets.flags[k] = q.d_blk_dirty.ptr;
                     targets.occupancy[k] = q.occupancy;
@@ -1288,7 +1288,7 @@ int sync_mirror(GvCtx* ctx)
             }
             phase.lap("mapping + upload meshes");
             p.need_full = false;
-            p.patch_valid = false;
+            p.stop_recording();
             p.dirty.clear();
             p.staging_stale.clear();  // (every entry has just been gathered)
             p.epoch++;
@@ -1332,7 +1332,7 @@ int sync_mirror(GvCtx* ctx)
                                 break;
                     } else {
                         const uint64_t nb = (p.occupancy + kCullBlock - 1) / kCullBlock;
-                        const bool flag_here = p.patch_valid && p.d_blk_dirty.ptr && total * 16 <= nb + 16 * 64;
+                        const bool flag_here = p.recording() && p.d_blk_dirty.ptr && total * 16 <= nb + 16 * 64;
                         rc = upload_meshes_scattered(ctx, p, left, flag_here ? p.d_blk_dirty.ptr : nullptr);
                         packet_flagged = flag_here;
                     }
@@ -1342,10 +1342,10 @@ int sync_mirror(GvCtx* ctx)
                 const uint64_t nblocks = (p.occupancy + kCullBlock - 1) / kCullBlock;
                 if (total * 16 > nblocks + 16 * 64)
                     p.small_streak = 0;  // (small mesh edits leave the streak to the transform side: no double count)
-                if (p.patch_valid) {  // (see the transform side)
+                if (p.recording()) {  // (see the transform side)
                     const bool most = !left.empty() && !p.inv.empty() && left_total * 2 > p.occupancy;
                     if (most || p.mapping != kMapExact || total * 16 > nblocks + 16 * 64) {
-                        p.patch_valid = false;
+                        p.stop_recording();
                     } else {
                         std::vector<DirtyRanges::R> unflagged;  // what did not travel in a packet that flags blocks itself
                         if (!packet_flagged) {

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void scatter_xf_packets_kernel(const XfPa
 #pragma unroll
     for (uint32_t k = 0; k < kMaxFlaggedPools; k++)
         if (blocks.flags[k] && e < blocks.occupancy[k])
-            blocks.flags[k][e / kCullBlock] = 1;
+            blocks.flags[k][e / kCullBlock] = kDirtyAll;
 }
 
 __global__ __launch_bounds__(kThreads) void scatter_mesh_packets_kernel(const MeshPacket* __restrict__ packets, uint32_t count, float4* __restrict__ a,
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void scatter_mesh_packets_kernel(const Me
     b[p.entry] = p.b;
     link[p.entry] = p.link;
     if (block_flags)
-        block_flags[p.entry / kCullBlock] = 1;
+        block_flags[p.entry / kCullBlock] = kDirtyAll;
 }
 
 }  // namespace

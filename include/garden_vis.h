@@ -82,8 +82,11 @@ typedef enum GvConfigFlags {
                                              every view does. DEFAULT for pools of more than 262144 slots (round 3); this flag
                                              forces it for pools of every size (they then take neither the one-launch cull + emit
                                              nor the batched tick) */
-    GV_CONFIG_LINEAR_SCAN = 1u << 5,      /* never use block bounds: every workgroup reads its streams (the flat loop of
-                                             mesh.cpp:137-175, which SURVEY.md §8d prices; bench.py's headline and roofline kernel) */
+    GV_CONFIG_LINEAR_SCAN = 1u << 5,      /* never use block bounds: every workgroup tests every entity every frame, with no
+                                             block skipping and nothing that can go stale (the flat loop of mesh.cpp:137-175, which
+                                             SURVEY.md §8d prices; bench.py's headline and roofline kernel). A flat, exactly paired
+                                             pool reads its 16-byte sphere stream for every entity and the 49 further bytes of
+                                             TRS + AABB only for the entities near or inside the frustum */
     GV_CONFIG_HIZ_RG16F = 1u << 4         /* keep the pyramid in the reference's image format (HizRenderSystem::bufferFormat =
                                              SfloatR16G16, render/hiz.hpp:41): levels >= 1 are binary16 (min, max) pairs, half the
                                              bytes. The reference lets the render target round to nearest, which can move a min
