@@ -21,7 +21,29 @@
 // per lane over SoA streams so each wave-instruction touches 1 KiB / 768 B contiguous.
 #include "gv_device.hpp"
 
+#include <type_traits>
+
 namespace gv {
+
+// The one map from a pool's run-time MeshMapping (and a view's Hi-Z switch) to the kernel variants: f is called with
+// std::integral_constant arguments, usable as template arguments (host launchers and cull_table_kernel alike).
+template <typename F>
+__host__ __device__ __forceinline__ void with_mapping(uint32_t mapping, F&& f)
+{
+    switch (mapping) {
+    case kMapExact: f(std::integral_constant<uint32_t, kMapExact>{}); break;
+    case kMapSpeculate: f(std::integral_constant<uint32_t, kMapSpeculate>{}); break;
+    default: f(std::integral_constant<uint32_t, kMapGeneral>{}); break;
+    }
+}
+template <typename F>
+__host__ __device__ __forceinline__ void with_variant(bool hiz, uint32_t mapping, F&& f)
+{
+    if (hiz)
+        with_mapping(mapping, [&](auto map) { f(std::true_type{}, map); });
+    else
+        with_mapping(mapping, [&](auto map) { f(std::false_type{}, map); });
+}
 
 // K1: one lane per mesh slot: visibility, isVisible byte, one ballot word per wave, per-chunk counts.
 // Compaction is two-pass (ballot words -> chunk scan -> emit). Measured alternatives, all within a few % of
@@ -55,10 +77,6 @@ __device__ __forceinline__ bool block_behind_planes(const float4 lo, const float
             behind = behind || (d < -fmaf(4e-5f, fabsf(planes[p][3]), margin));  // the plane offset rounds too
         }
     return behind;
-}
-__device__ __forceinline__ bool block_behind_frustum(const float4 lo, const float4 hi, const ViewParams& view, uint32_t max_depth)
-{
-    return block_behind_planes(lo, hi, view.planes, view.plane_count, view.cam, max_depth);
 }
 
 // the kernel's first argument (a CullArgs at the start of the kernarg segment), read again through a pointer the compiler cannot
@@ -94,6 +112,7 @@ __device__ __forceinline__ void cull_block(const CullArgs& args0, uint32_t lb, u
     const uint32_t i = lb * kCullBlock + tid;
     const uint32_t lane = tid & 63u, wave = tid >> 6;
     bool visible = false;
+    Corners c;
     if (HOT && i < args.mesh.count) {
         const float4 h = stream_load(&args.mesh.hot[i]);
         uint32_t where = kSphereOutside;
@@ -102,51 +121,31 @@ __device__ __forceinline__ void cull_block(const CullArgs& args0, uint32_t lb, u
             where = classify_sphere(tx, ty, tz, sphere_reach(h.w, tx, ty, tz), args.view.planes, args.view.plane_count);
         }
         visible = where == kSphereInside;
-        Corners c;
         if (where == kSphereUndecided || (HIZ && visible)) {
             Mat34 m;
             float4 box_a;
             float2 box_b;
-            if (prepare_model<MAP>(args.mesh, args.xf, args.view.cam, i, m, box_a, box_b)) {  // (always, while the entry is current)
-                aabb_corners(m, box_a, box_b, c);
-                if (where == kSphereUndecided)
-                    visible = !behind_frustum(c, args.view.planes, args.view.plane_count);
-            } else {
-                visible = false;
-            }
-        }
-        if (HIZ && visible) {
-            CullArgs stage2;
-            if (RELOAD)
-                reload_cull_args(stage2);
-            const CullArgs& a2 = RELOAD ? stage2 : args0;
-            visible = !hiz_occluded(a2.hiz, a2.view.vp, c);
+            visible = prepare_model<MAP>(args.mesh, args.xf, args.view.cam, i, m, box_a, box_b) &&  // (always, while the entry is current)
+                      settle<HIZ>(where, m, box_a, box_b, args.view.planes, args.view.plane_count, c);
         }
     } else if (!HOT && i < args.mesh.count) {
         Mat34 m;
         float4 box_a;
         float2 box_b;
-        Corners c;
         uint32_t where = kSphereOutside;
         if (prepare_model<MAP>(args.mesh, args.xf, args.view.cam, i, m, box_a, box_b))
             where = classify_sphere(m, box_a, box_b, args.view.planes, args.view.plane_count);
-        visible = where == kSphereInside;
-        if (where == kSphereUndecided) {  // near a plane (or non-finite): the exact 8-corner test; rare, skipped wave-wide otherwise
-            aabb_corners(m, box_a, box_b, c);
-            visible = !behind_frustum(c, args.view.planes, args.view.plane_count);
-        } else if (HIZ && visible) {
-            aabb_corners(m, box_a, box_b, c);
-        }
-        // Hi-Z occlusion query on the survivors. Measured (profiles/r01b_hiz_ablation.txt): compacting the
-        // survivors across the workgroup through LDS first buys nothing — the stage is bound by the texel
-        // gathers (~4.5 M random 64-B sectors per frame), not by divergent VALU work.
-        if (HIZ && visible) {
-            CullArgs stage2;
-            if (RELOAD)
-                reload_cull_args(stage2);
-            const CullArgs& a2 = RELOAD ? stage2 : args0;
-            visible = !hiz_occluded(a2.hiz, a2.view.vp, c);
-        }
+        visible = settle<HIZ>(where, m, box_a, box_b, args.view.planes, args.view.plane_count, c);
+    }
+    // Hi-Z occlusion query on the survivors. Measured (profiles/r01b_hiz_ablation.txt): compacting the
+    // survivors across the workgroup through LDS first buys nothing — the stage is bound by the texel
+    // gathers (~4.5 M random 64-B sectors per frame), not by divergent VALU work.
+    if (HIZ && visible) {
+        CullArgs stage2;
+        if (RELOAD)
+            reload_cull_args(stage2);
+        const CullArgs& a2 = RELOAD ? stage2 : args0;
+        visible = !hiz_occluded(a2.hiz, a2.view.vp, c);
     }
     CullArgs stage3;
     if (RELOAD)
@@ -320,7 +319,7 @@ __global__ __launch_bounds__(64) void block_classify_kernel(const ClassifyArgs a
     BlockWindow win{lb, 0xFFu, 0u, 0.0f};
     if (lb < a.nblocks) {
         const float4 lo = a.bounds.lo[lb], hi = a.bounds.hi[lb];
-        kept = !(lo.x > hi.x || block_behind_frustum(lo, hi, a.view, a.max_depth));
+        kept = !(lo.x > hi.x || block_behind_planes(lo, hi, a.view.planes, a.view.plane_count, a.view.cam, a.max_depth));
         if (HIZ && kept)
             win = block_window(a.hiz, a.view, lo, hi, a.max_depth, lb);
         if (!HIZ || !kept)  // (HIZ survivors: decided by block_window_kernel)
@@ -462,19 +461,9 @@ hipError_t launch_cull_listed(const MeshMirror& mesh, const TransformMirror& xf,
     a.out = out;
     a.nblocks = nblocks;
     const CullListArgs la{kept_count, static_cast<const BlockWindow*>(kept_list), window_test ? kept_flag : nullptr, next_count};
-    const dim3 grid(list_grid), block(kCullBlock);
-#define GV_LAUNCH_LIST(HIZ)                                                                                              \
-    switch (mesh.mapping) {                                                                                             \
-    case kMapExact: hipLaunchKernelGGL((cull_list_kernel<HIZ, kMapExact>), grid, block, 0, stream, a, la); break;         \
-    case kMapSpeculate: hipLaunchKernelGGL((cull_list_kernel<HIZ, kMapSpeculate>), grid, block, 0, stream, a, la); break; \
-    default: hipLaunchKernelGGL((cull_list_kernel<HIZ, kMapGeneral>), grid, block, 0, stream, a, la); break;              \
-    }
-    if (vp.use_hiz) {
-        GV_LAUNCH_LIST(true)
-    } else {
-        GV_LAUNCH_LIST(false)
-    }
-#undef GV_LAUNCH_LIST
+    with_variant(vp.use_hiz, mesh.mapping, [&](auto hiz, auto map) {
+        hipLaunchKernelGGL((cull_list_kernel<hiz, map>), dim3(list_grid), dim3(kCullBlock), 0, stream, a, la);
+    });
     return hipGetLastError();
 }
 size_t cull_list_entry_bytes() { return sizeof(BlockWindow); }
@@ -518,13 +507,7 @@ __global__ __launch_bounds__(kCullBlock) void cull_emit_kernel(const CullArgs ar
         uint32_t where = kSphereOutside;
         if (prepare_model<MAP>(args.mesh, args.xf, args.view.cam, i, m, box_a, box_b))
             where = classify_sphere(m, box_a, box_b, args.view.planes, args.view.plane_count);
-        visible = where == kSphereInside;
-        if (where == kSphereUndecided) {
-            aabb_corners(m, box_a, box_b, c);
-            visible = !behind_frustum(c, args.view.planes, args.view.plane_count);
-        } else if (HIZ && visible) {
-            aabb_corners(m, box_a, box_b, c);
-        }
+        visible = settle<HIZ>(where, m, box_a, box_b, args.view.planes, args.view.plane_count, c);
         if (HIZ && visible)
             visible = !hiz_occluded(args.hiz, args.view.vp, c);
         if (args.view.write_is_visible)
@@ -584,19 +567,10 @@ __global__ __launch_bounds__(kCullBlock) void cull_emit_kernel(const CullArgs ar
     const uint32_t base = base_s;
     if (visible) {  // the record of mesh.cpp:169-173, at its final place
         const uint32_t local = wave_prefix + (uint32_t)__popcll(word & ((1ull << lane) - 1ull));
-        const size_t rank = (size_t)base + local;
-        args.out.visible_idx[rank] = args.mesh.orig ? args.mesh.orig[i] : i;
-        const float tx = m.c3x + args.view.cam_offset[0], ty = m.c3y + args.view.cam_offset[1], tz = m.c3z + args.view.cam_offset[2];
-        args.out.distance_sq[rank] = args.view.distance_2d ? m.c3z + 1.0f : fmaf(tz, tz, fmaf(ty, ty, tx * tx));
-        float4* row = stage + local * 3;
-        row[0] = make_float4(m.c0x, m.c0y, m.c0z, m.c1x);
-        row[1] = make_float4(m.c1y, m.c1z, m.c2x, m.c2y);
-        row[2] = make_float4(m.c2z, m.c3x, m.c3y, m.c3z);
+        put_record(args.view, args.out, (size_t)base + local, args.mesh.orig ? args.mesh.orig[i] : i, m, stage + local * 3);
     }
     __syncthreads();
-    float4* dst = reinterpret_cast<float4*>(args.out.baked_model) + (size_t)base * 3;
-    for (uint32_t q = threadIdx.x; q < total * 3u; q += kCullBlock)
-        dst[q] = stage[q];
+    copy_rows(stage, reinterpret_cast<float4*>(args.out.baked_model) + (size_t)base * 3, total * 3u);
 }
 
 hipError_t launch_cull_emit(const MeshMirror& mesh, const TransformMirror& xf, const HizDevice& hiz, const ViewParams& vp,
@@ -613,19 +587,9 @@ hipError_t launch_cull_emit(const MeshMirror& mesh, const TransformMirror& xf, c
     a.out = out;
     a.nblocks = (mesh.count + kCullBlock - 1) / kCullBlock;
     const FusedEmit fe{status, ticket, ticket_base, epoch};
-    const dim3 grid(a.nblocks), block(kCullBlock);
-#define GV_LAUNCH_FUSED(HIZ)                                                                                          \
-    switch (mesh.mapping) {                                                                                          \
-    case kMapExact: hipLaunchKernelGGL((cull_emit_kernel<HIZ, kMapExact>), grid, block, 0, stream, a, fe); break;         \
-    case kMapSpeculate: hipLaunchKernelGGL((cull_emit_kernel<HIZ, kMapSpeculate>), grid, block, 0, stream, a, fe); break; \
-    default: hipLaunchKernelGGL((cull_emit_kernel<HIZ, kMapGeneral>), grid, block, 0, stream, a, fe); break;              \
-    }
-    if (vp.use_hiz) {
-        GV_LAUNCH_FUSED(true)
-    } else {
-        GV_LAUNCH_FUSED(false)
-    }
-#undef GV_LAUNCH_FUSED
+    with_variant(vp.use_hiz, mesh.mapping, [&](auto hiz, auto map) {
+        hipLaunchKernelGGL((cull_emit_kernel<hiz, map>), dim3(a.nblocks), dim3(kCullBlock), 0, stream, a, fe);
+    });
     return hipGetLastError();
 }
 
@@ -644,23 +608,15 @@ hipError_t launch_cull(const MeshMirror& mesh, const TransformMirror& xf, const 
     // measured: the frustum-only scan gains 6 % from per-XCD runs, the Hi-Z variant does not
     a.xcd_run = vp.use_hiz ? 0 : xcd_run_for_tiles(a.nblocks);
     const dim3 grid(grid_for_tiles(a.nblocks, a.xcd_run)), block(kCullBlock);
-#define GV_LAUNCH_CULL(HIZ)                                                                                       \
-    switch (mesh.mapping) {                                                                                      \
-    case kMapExact:                                                                                              \
-        if (mesh.hot)                                                                                            \
-            hipLaunchKernelGGL((cull_kernel<HIZ, kMapExact, true>), grid, block, 0, stream, a);                  \
-        else                                                                                                     \
-            hipLaunchKernelGGL((cull_kernel<HIZ, kMapExact>), grid, block, 0, stream, a);                        \
-        break;                                                                                                   \
-    case kMapSpeculate: hipLaunchKernelGGL((cull_kernel<HIZ, kMapSpeculate>), grid, block, 0, stream, a); break; \
-    default: hipLaunchKernelGGL((cull_kernel<HIZ, kMapGeneral>), grid, block, 0, stream, a); break;              \
-    }
-    if (vp.use_hiz) {
-        GV_LAUNCH_CULL(true)
-    } else {
-        GV_LAUNCH_CULL(false)
-    }
-#undef GV_LAUNCH_CULL
+    with_variant(vp.use_hiz, mesh.mapping, [&](auto hiz, auto map) {
+        if constexpr (map == kMapExact) {
+            if (mesh.hot) {
+                hipLaunchKernelGGL((cull_kernel<hiz, kMapExact, true>), grid, block, 0, stream, a);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((cull_kernel<hiz, map>), grid, block, 0, stream, a);
+    });
     return hipGetLastError();
 }
 
@@ -838,12 +794,10 @@ hipError_t launch_block_patch(const MeshMirror& mesh, const TransformMirror& xf,
     if (mesh.count == 0)
         return hipSuccess;
     const uint32_t nblocks = (mesh.count + kCullBlock - 1) / kCullBlock;
-    const dim3 grid((nblocks + kPatchSpan - 1) / kPatchSpan), block(kCullBlock);
-    switch (mesh.mapping) {
-    case kMapExact: hipLaunchKernelGGL((block_patch_kernel<kMapExact>), grid, block, 0, stream, mesh, xf, lo, hi, seeds, flags, nblocks); break;
-    case kMapSpeculate: hipLaunchKernelGGL((block_patch_kernel<kMapSpeculate>), grid, block, 0, stream, mesh, xf, lo, hi, seeds, flags, nblocks); break;
-    default: hipLaunchKernelGGL((block_patch_kernel<kMapGeneral>), grid, block, 0, stream, mesh, xf, lo, hi, seeds, flags, nblocks); break;
-    }
+    with_mapping(mesh.mapping, [&](auto map) {
+        hipLaunchKernelGGL((block_patch_kernel<map>), dim3((nblocks + kPatchSpan - 1) / kPatchSpan), dim3(kCullBlock), 0, stream, mesh, xf, lo,
+                           hi, seeds, flags, nblocks);
+    });
     return hipGetLastError();
 }
 
@@ -888,12 +842,10 @@ hipError_t launch_block_bounds(const MeshMirror& mesh, const TransformMirror& xf
 {
     if (mesh.count == 0)
         return hipSuccess;
-    const dim3 grid((mesh.count + kCullBlock - 1) / kCullBlock), block(kCullBlock);
-    switch (mesh.mapping) {
-    case kMapExact: hipLaunchKernelGGL((block_bounds_kernel<kMapExact>), grid, block, 0, stream, mesh, xf, lo, hi); break;
-    case kMapSpeculate: hipLaunchKernelGGL((block_bounds_kernel<kMapSpeculate>), grid, block, 0, stream, mesh, xf, lo, hi); break;
-    default: hipLaunchKernelGGL((block_bounds_kernel<kMapGeneral>), grid, block, 0, stream, mesh, xf, lo, hi); break;
-    }
+    with_mapping(mesh.mapping, [&](auto map) {
+        hipLaunchKernelGGL((block_bounds_kernel<map>), dim3((mesh.count + kCullBlock - 1) / kCullBlock), dim3(kCullBlock), 0, stream, mesh, xf,
+                           lo, hi);
+    });
     return hipGetLastError();
 }
 
@@ -975,15 +927,7 @@ __device__ __forceinline__ void cull_multi_block(const MultiCullArgs& args, Cons
     for (uint32_t v = 0; v < nviews; v++) {
         const MultiViewPlanes pl = view_planes(base, v);
         const uint32_t where = candidate ? classify_sphere(m, reach, pl.planes, pl.plane_count) : kSphereOutside;
-        bool visible = where == kSphereInside;
-        if (where == kSphereUndecided || (HIZ && v == 0 && visible)) {
-            if (!have_corners) {
-                aabb_corners(m, box_a, box_b, c);
-                have_corners = true;
-            }
-            if (where == kSphereUndecided)
-                visible = !behind_frustum(c, pl.planes, pl.plane_count);
-        }
+        bool visible = settle(where, HIZ && v == 0, m, box_a, box_b, pl.planes, pl.plane_count, c, have_corners);
         if (HIZ && v == 0 && visible)
             visible = !hiz_occluded(args.hiz, args.vp0, c);
         const ViewBuffers out = view_outputs(base, v);
@@ -1030,18 +974,9 @@ __global__ __launch_bounds__(kCullBlock) void cull_table_kernel(const MultiCullA
     __builtin_memcpy(&args, (ConstCullTable)table + blockIdx.y, sizeof(args));
     if (blockIdx.x * kCullBlock >= args.mesh.count)
         return;  // the grid is as wide as the largest pool of the tick
-#define GV_TABLE_CULL(HIZ)                                                                              \
-    switch (args.mesh.mapping) {                                                                        \
-    case kMapExact: cull_multi_block<HIZ, kMapExact, false>(args, (ConstCullTable)table + blockIdx.y, blockIdx.x, wave_count); break;       \
-    case kMapSpeculate: cull_multi_block<HIZ, kMapSpeculate, false>(args, (ConstCullTable)table + blockIdx.y, blockIdx.x, wave_count); break; \
-    default: cull_multi_block<HIZ, kMapGeneral, false>(args, (ConstCullTable)table + blockIdx.y, blockIdx.x, wave_count); break;            \
-    }
-    if (args.use_hiz0) {
-        GV_TABLE_CULL(true)
-    } else {
-        GV_TABLE_CULL(false)
-    }
-#undef GV_TABLE_CULL
+    with_variant(args.use_hiz0, args.mesh.mapping, [&](auto hiz, auto map) {
+        cull_multi_block<hiz, map, false>(args, (ConstCullTable)table + blockIdx.y, blockIdx.x, wave_count);
+    });
 }
 
 hipError_t launch_cull_table(const void* device_table, uint32_t jobs, uint32_t max_slots, hipStream_t stream)
@@ -1096,22 +1031,12 @@ hipError_t launch_cull_multi(const MeshMirror& mesh, const TransformMirror& xf, 
     fill_multi_args(a, mesh, xf, hiz, views, outs, nviews);
     const dim3 grid((mesh.count + kCullBlock - 1) / kCullBlock), block(kCullBlock);
     a.bounds = bounds ? *bounds : BlockBounds{};
-#define GV_LAUNCH_MULTI(HIZ, BOUNDS)                                                                                            \
-    switch (mesh.mapping) {                                                                                                    \
-    case kMapExact: hipLaunchKernelGGL((cull_multi_kernel<HIZ, kMapExact, BOUNDS>), grid, block, 0, stream, a); break;         \
-    case kMapSpeculate: hipLaunchKernelGGL((cull_multi_kernel<HIZ, kMapSpeculate, BOUNDS>), grid, block, 0, stream, a); break; \
-    default: hipLaunchKernelGGL((cull_multi_kernel<HIZ, kMapGeneral, BOUNDS>), grid, block, 0, stream, a); break;              \
-    }
-    if (a.use_hiz0 && bounds) {
-        GV_LAUNCH_MULTI(true, true)
-    } else if (a.use_hiz0) {
-        GV_LAUNCH_MULTI(true, false)
-    } else if (bounds) {
-        GV_LAUNCH_MULTI(false, true)
-    } else {
-        GV_LAUNCH_MULTI(false, false)
-    }
-#undef GV_LAUNCH_MULTI
+    with_variant(a.use_hiz0, mesh.mapping, [&](auto hiz, auto map) {
+        if (bounds)
+            hipLaunchKernelGGL((cull_multi_kernel<hiz, map, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((cull_multi_kernel<hiz, map, false>), grid, block, 0, stream, a);
+    });
     return hipGetLastError();
 }
 
@@ -1203,11 +1128,7 @@ __device__ __forceinline__ Mat34 record_model(const EmitArgs& args, uint32_t i, 
         if (args.mesh.mapping != kMapExact)
             slot = args.mesh.link[i] & kSlotMask;
         const float4* w = args.world + (size_t)slot * 3;
-        const float4 w0 = w[0], w1 = w[1], w2 = w[2];
-        world.c0x = w0.x; world.c0y = w0.y; world.c0z = w0.z;
-        world.c1x = w0.w; world.c1y = w1.x; world.c1z = w1.y;
-        world.c2x = w1.z; world.c2y = w1.w; world.c2z = w2.x;
-        world.c3x = w2.y; world.c3y = w2.z; world.c3z = w2.w;
+        world = rows_model(w[0], w[1], w[2]);
     } else {
         uint32_t slot = i;
         XfRecord rec = {};
@@ -1225,14 +1146,6 @@ __device__ __forceinline__ Mat34 record_model(const EmitArgs& args, uint32_t i, 
         world = chain_model(args.xf, local_model(rec), slot, rec.flags);
     }
     return translated(world, args.view.cam[0], args.view.cam[1], args.view.cam[2]);
-}
-
-__device__ __forceinline__ float record_distance(const EmitArgs& args, const Mat34& m)
-{
-    const float tx = m.c3x + args.view.cam_offset[0];
-    const float ty = m.c3y + args.view.cam_offset[1];
-    const float tz = m.c3z + args.view.cam_offset[2];
-    return args.view.distance_2d ? m.c3z + 1.0f : fmaf(tz, tz, fmaf(ty, ty, tx * tx));
 }
 
 // position of the k-th (0-based) set bit of `word`
@@ -1261,9 +1174,6 @@ constexpr uint32_t kSelfPrefixLoads = (kSelfPrefixMaxChunks / 4 + 191) / 192;  /
 // SELF: no scan launch in front — while wave 0 prefixes the ballot words, waves 1-3 sum the chunk totals below this
 // chunk (a few KB of L2 reads) to get its base; workgroup 0 also writes the grand total and clears the OTHER totals
 // buffer for the next frame's cull (the two buffers alternate, so nobody is still reading the one being cleared).
-#ifndef GV_EMIT_PIPELINED  // (A/B builds: tools/ab_lib.sh)
-#define GV_EMIT_PIPELINED 1
-#endif
 template <bool SELF>
 __device__ __forceinline__ void emit_block(const EmitArgs& args, const uint32_t block)
 {
@@ -1388,7 +1298,7 @@ __device__ __forceinline__ void emit_block(const EmitArgs& args, const uint32_t 
     // i): the gathers of round k + 1 are issued before round k's records go through LDS and out, so that a round waits for its
     // stores and the next round's loads together instead of one after the other (a quarter of a full chunk is four rounds). Same-box A/B: emit 53.5 -> 51.2 us at 2.6 M records, 45.3 -> 43.8 us at 2.06 M (a barrier that
     // orders LDS only, so that the gathers fly across it, measured the same).
-    const bool pipelined = GV_EMIT_PIPELINED && !use_seed && !args.world && args.xf.max_depth == 0 &&
+    const bool pipelined = !use_seed && !args.world && args.xf.max_depth == 0 &&
                            args.mesh.mapping == kMapExact;  // uniform
     if (pipelined) {
         uint32_t r0 = prefix[wlo];
@@ -1417,19 +1327,10 @@ __device__ __forceinline__ void emit_block(const EmitArgs& args, const uint32_t 
                 XfRecord rec;
                 rec.a = a_cur, rec.b = b_cur, rec.c = c_cur, rec.flags = 0u;
                 const Mat34 m = translated(local_model(rec), args.view.cam[0], args.view.cam[1], args.view.cam[2]);
-                const size_t rank = (size_t)base + r0 + threadIdx.x;
-                args.out.visible_idx[rank] = orig_cur;
-                args.out.distance_sq[rank] = record_distance(args, m);
-                float4* row = stage + threadIdx.x * 3;
-                row[0] = make_float4(m.c0x, m.c0y, m.c0z, m.c1x);
-                row[1] = make_float4(m.c1y, m.c1z, m.c2x, m.c2y);
-                row[2] = make_float4(m.c2z, m.c3x, m.c3y, m.c3z);
+                put_record(args.view, args.out, (size_t)base + r0 + threadIdx.x, orig_cur, m, stage + threadIdx.x * 3);
             }
             __syncthreads();
-            const uint32_t quads = min(256u, total - r0) * 3u;
-            float4* dst = reinterpret_cast<float4*>(args.out.baked_model) + ((size_t)base + r0) * 3;
-            for (uint32_t q = threadIdx.x; q < quads; q += 256)
-                dst[q] = stage[q];
+            copy_rows(stage, reinterpret_cast<float4*>(args.out.baked_model) + ((size_t)base + r0) * 3, min(256u, total - r0) * 3u);
             __syncthreads();  // the stage is rewritten by the next round
             i_cur = i_nxt, orig_cur = orig_nxt, a_cur = a_nxt, b_cur = b_nxt, c_cur = c_nxt;
         }
@@ -1441,32 +1342,13 @@ __device__ __forceinline__ void emit_block(const EmitArgs& args, const uint32_t 
     for (uint32_t r0 = prefix[wlo]; r0 < total; r0 += 256) {
         const uint32_t r = r0 + threadIdx.x;
         if (r < total) {
-            uint32_t lo = wlo, hi = whi;  // word w in [wlo, whi) with prefix[w] <= r < prefix[w + 1]
-#pragma unroll
-            for (uint32_t span = 64 / kEmitParts; span > 1; span >>= 1) {  // log2(words per workgroup) halvings
-                const uint32_t mid = (lo + hi) >> 1;
-                if (prefix[mid] <= r)
-                    lo = mid;
-                else
-                    hi = mid;
-            }
-            const uint32_t pos = select_bit(words[lo], r - prefix[lo]);
-            const uint32_t i = (first_word + lo) * 64 + pos;
+            const uint32_t i = entry_of(r);
             const Mat34 m = record_model(args, i, use_seed);
-            const size_t rank = (size_t)base + r;
-            // pool slot: componentOffset = slot * componentSize  mesh.cpp:170
-            args.out.visible_idx[rank] = use_seed ? args.seeds[i].orig : (args.mesh.orig ? args.mesh.orig[i] : i);
-            args.out.distance_sq[rank] = record_distance(args, m);
-            float4* row = stage + threadIdx.x * 3;
-            row[0] = make_float4(m.c0x, m.c0y, m.c0z, m.c1x);
-            row[1] = make_float4(m.c1y, m.c1z, m.c2x, m.c2y);
-            row[2] = make_float4(m.c2z, m.c3x, m.c3y, m.c3z);
+            put_record(args.view, args.out, (size_t)base + r, use_seed ? args.seeds[i].orig : (args.mesh.orig ? args.mesh.orig[i] : i), m,
+                       stage + threadIdx.x * 3);
         }
         __syncthreads();
-        const uint32_t quads = min(256u, total - r0) * 3u;
-        float4* dst = reinterpret_cast<float4*>(args.out.baked_model) + ((size_t)base + r0) * 3;
-        for (uint32_t q = threadIdx.x; q < quads; q += 256)
-            dst[q] = stage[q];
+        copy_rows(stage, reinterpret_cast<float4*>(args.out.baked_model) + ((size_t)base + r0) * 3, min(256u, total - r0) * 3u);
         __syncthreads();  // the stage is rewritten by the next round
     }
 }
@@ -1698,45 +1580,6 @@ hipError_t launch_aos_meshes(const uint8_t* raw, const AosMeshLayout& layout, ui
         return hipSuccess;
     hipLaunchKernelGGL(aos_meshes_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, raw, layout, first, count, inv, e2t, entity_capacity,
                        xf_occupancy, xinv, a, b, link, demoted);
-    return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void mark_bytes_kernel(const uint32_t* __restrict__ idx, uint32_t count, uint8_t* __restrict__ dst)
-{
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x)
-        dst[idx[k]] = 1;
-}
-
-hipError_t launch_mark_bytes(const uint32_t* idx, uint32_t count, uint8_t* dst, hipStream_t stream)
-{
-    if (count == 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(mark_bytes_kernel, dim3(min((count + 255u) / 256u, 4096u)), dim3(256), 0, stream, idx, count, dst);
-    return hipGetLastError();
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void scatter_kernel(const uint32_t* __restrict__ idx, uint32_t count,
-                                                      const T* __restrict__ src, T* __restrict__ dst)
-{
-    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x)
-        dst[idx[k]] = src[k];
-}
-
-hipError_t launch_scatter(const uint32_t* idx, uint32_t count, const void* src, void* dst, uint32_t elem_bytes,
-                          hipStream_t stream)
-{
-    if (count == 0)
-        return hipSuccess;
-    const dim3 grid(min((count + 255u) / 256u, 4096u)), block(256);
-    switch (elem_bytes) {
-    case 1: hipLaunchKernelGGL(scatter_kernel<uint8_t>, grid, block, 0, stream, idx, count, (const uint8_t*)src, (uint8_t*)dst); break;
-    case 4: hipLaunchKernelGGL(scatter_kernel<uint32_t>, grid, block, 0, stream, idx, count, (const uint32_t*)src, (uint32_t*)dst); break;
-    case 8: hipLaunchKernelGGL(scatter_kernel<float2>, grid, block, 0, stream, idx, count, (const float2*)src, (float2*)dst); break;
-    case 16: hipLaunchKernelGGL(scatter_kernel<float4>, grid, block, 0, stream, idx, count, (const float4*)src, (float4*)dst); break;
-    case 32: hipLaunchKernelGGL(scatter_kernel<XfAB>, grid, block, 0, stream, idx, count, (const XfAB*)src, (XfAB*)dst); break;
-    default: return hipErrorInvalidValue;
-    }
     return hipGetLastError();
 }
 

@@ -74,6 +74,24 @@ __device__ __forceinline__ Mat34 local_model(const XfRecord& r)
     return calc_model(r.a.x, r.a.y, r.a.z, r.b.x, r.b.y, r.b.z, r.b.w, r.a.w, r.c.x, r.c.y);
 }
 
+// A model as three float4 rows in float4x3 order (12 floats: c0.xyz, c1.xyz, c2.xyz, c3.xyz) — the layout of a record's bakedModel
+// and of the resident world matrices — and back.
+__device__ __forceinline__ void model_rows(const Mat34& m, float4& w0, float4& w1, float4& w2)
+{
+    w0 = make_float4(m.c0x, m.c0y, m.c0z, m.c1x);
+    w1 = make_float4(m.c1y, m.c1z, m.c2x, m.c2y);
+    w2 = make_float4(m.c2z, m.c3x, m.c3y, m.c3z);
+}
+__device__ __forceinline__ Mat34 rows_model(const float4 w0, const float4 w1, const float4 w2)
+{
+    Mat34 m;
+    m.c0x = w0.x; m.c0y = w0.y; m.c0z = w0.z;
+    m.c1x = w0.w; m.c1y = w1.x; m.c1z = w1.y;
+    m.c2x = w1.z; m.c2y = w1.w; m.c2z = w2.x;
+    m.c3x = w2.y; m.c3y = w2.z; m.c3z = w2.w;
+    return m;
+}
+
 // transform.hpp:197-214: model = calcModel(self); while (parent) model = calcModel(parent) * model.
 // `m` is the already-built self model of entry `s`; the parent stream is only touched when the pool has chains.
 __device__ __forceinline__ Mat34 chain_model(const TransformMirror& xf, Mat34 m, uint32_t s, uint32_t flags)
@@ -269,6 +287,14 @@ struct CullArgs {
     uint32_t xcd_run;    // tile_of_workgroup(); 0 = workgroup b takes tile b
 };
 
+// The filter chain's verdict on one mesh entry: mesh.cpp:140-142 skips free slots and disabled meshes (`candidate`) and
+// all(size <= 0) boxes, mesh.cpp:150 inactive transforms (transform.hpp:110).
+__device__ __forceinline__ bool mesh_entry_dropped(bool candidate, const float4& a, const float2& b, uint32_t xf_flags)
+{
+    const bool empty = (a.w - a.x <= 0.0f) && (b.x - a.y <= 0.0f) && (b.y - a.z <= 0.0f);
+    return !candidate || empty || !(xf_flags & kXfActive);
+}
+
 // One mesh entry through the reference's filter chain (mesh.cpp:140-157): candidate / empty-AABB / transform /
 // isActive checks, parent-chain model, camera translate, 8 corners. Returns false when the entry is filtered out;
 // otherwise `m` holds the camera-relative model (bakedModel) and `c` its corners. Nothing here depends on the
@@ -315,12 +341,7 @@ __device__ __forceinline__ bool prepare_model(const MeshMirror& mesh, const Tran
             candidate = own;
         }
     }
-    const float mnx = ma.x, mny = ma.y, mnz = ma.z, mxx = ma.w, mxy = mb.x, mxz = mb.y;
-    // mesh.cpp:140-142: skip free slots, disabled meshes and all(size <= 0) boxes
-    const bool empty = (mxx - mnx <= 0.0f) && (mxy - mny <= 0.0f) && (mxz - mnz <= 0.0f);
-    if (!candidate || empty)
-        return false;
-    if (!(r.flags & kXfActive))  // mesh.cpp:150, transform.hpp:110
+    if (mesh_entry_dropped(candidate, ma, mb, r.flags))
         return false;
     const Mat34 world = chain_model(xf, local_model(r), slot, r.flags);
     // math::translate(-cameraPosition, model)  transform.hpp:211,213
@@ -331,18 +352,6 @@ __device__ __forceinline__ bool prepare_model(const MeshMirror& mesh, const Tran
 __device__ __forceinline__ void aabb_corners(const Mat34& m, const float4 a, const float2 b, Corners& c)
 {
     aabb_corners(m, a.x, a.y, a.z, a.w, b.x, b.y, c);
-}
-
-template <uint32_t MAP>
-__device__ __forceinline__ bool prepare_slot(const MeshMirror& mesh, const TransformMirror& xf, const float (&cam)[3],
-                                             uint32_t i, Mat34& m, Corners& c)
-{
-    float4 a;
-    float2 b;
-    if (!prepare_model<MAP>(mesh, xf, cam, i, m, a, b))
-        return false;
-    aabb_corners(m, a, b, c);
-    return true;
 }
 
 // Sphere pre-test for the default predicate: decides most entries without generating a corner, and agrees with the
@@ -425,11 +434,64 @@ __device__ __forceinline__ bool behind_frustum(const Corners& c, const float (&p
     return behind;
 }
 
-template <uint32_t MAP>
-__device__ __forceinline__ bool evaluate_slot(const MeshMirror& mesh, const TransformMirror& xf, const ViewParams& view,
-                                              uint32_t i, Mat34& m, Corners& c)
+// The default predicate's frustum decision for one view, given the sphere class `where` of the camera-relative model m with
+// box (a, b): the exact 8-corner test settles what the sphere could not (near a plane, or non-finite; rare, skipped wave-wide
+// otherwise). The corners are left in `c` whenever they were needed — undecided, or inside with HIZ (the caller's Hi-Z query of
+// the survivors reads them).
+template <bool HIZ>
+__device__ __forceinline__ bool settle(uint32_t where, const Mat34& m, const float4 a, const float2 b, const float (&planes)[6][4],
+                                       uint32_t plane_count, Corners& c)
 {
-    return prepare_slot<MAP>(mesh, xf, view.cam, i, m, c) && !behind_frustum(c, view.planes, view.plane_count);
+    bool visible = where == kSphereInside;
+    if (where == kSphereUndecided) {
+        aabb_corners(m, a, b, c);
+        visible = !behind_frustum(c, planes, plane_count);
+    } else if (HIZ && visible) {
+        aabb_corners(m, a, b, c);
+    }
+    return visible;
+}
+// The same decision for one of several views of an entity: `have_corners` says the corners are in `c` already, so that they are
+// generated once, by the first view that needs them; `hiz`: this view runs the Hi-Z query.
+__device__ __forceinline__ bool settle(uint32_t where, bool hiz, const Mat34& m, const float4 a, const float2 b,
+                                       const float (&planes)[6][4], uint32_t plane_count, Corners& c, bool& have_corners)
+{
+    bool visible = where == kSphereInside;
+    if (where == kSphereUndecided || (hiz && visible)) {
+        if (!have_corners) {
+            aabb_corners(m, a, b, c);
+            have_corners = true;
+        }
+        if (where == kSphereUndecided)
+            visible = !behind_frustum(c, planes, plane_count);
+    }
+    return visible;
+}
+
+// ------------------------------------------------------------------------------------------------
+// records (mesh.cpp:169-173)
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float record_distance(const ViewParams& view, const Mat34& m)
+{
+    const float tx = m.c3x + view.cam_offset[0];
+    const float ty = m.c3y + view.cam_offset[1];
+    const float tz = m.c3z + view.cam_offset[2];
+    return view.distance_2d ? m.c3z + 1.0f : fmaf(tz, tz, fmaf(ty, ty, tx * tx));
+}
+// The record of a visible entry at output `rank`: pool slot and distance go straight out, the 48-byte model is staged at `row`
+// (three float4 in LDS) for copy_rows.
+__device__ __forceinline__ void put_record(const ViewParams& view, const ViewBuffers& out, size_t rank, uint32_t slot, const Mat34& m,
+                                           float4* row)
+{
+    out.visible_idx[rank] = slot;  // componentOffset = slot * componentSize  mesh.cpp:170
+    out.distance_sq[rank] = record_distance(view, m);
+    model_rows(m, row[0], row[1], row[2]);
+}
+// ... and a round's staged models leave as whole rows: thread k of the 256 stores float4 k, k + 256, k + 512 ... of `quads`.
+__device__ __forceinline__ void copy_rows(const float4* stage, float4* dst, uint32_t quads)
+{
+    for (uint32_t q = threadIdx.x; q < quads; q += 256)
+        dst[q] = stage[q];
 }
 
 }  // namespace gv

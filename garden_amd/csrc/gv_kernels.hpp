@@ -282,9 +282,6 @@ struct AosMeshLayout {
 hipError_t launch_aos_meshes(const uint8_t* raw, const AosMeshLayout& layout, uint32_t first, uint32_t count, const uint32_t* inv,
                              const uint32_t* e2t, uint32_t entity_capacity, uint32_t xf_occupancy, const uint32_t* xinv, float4* a, float2* b,
                              uint32_t* link, uint32_t* demoted, hipStream_t stream);
-// dirty-range upload into a permuted mirror: dst[idx[k]] = src[k], element size 1, 4, 8 or 16 bytes
-hipError_t launch_scatter(const uint32_t* idx, uint32_t count, const void* src, void* dst, uint32_t elem_bytes,
-                          hipStream_t stream);
 // out[k] = world[xinv[first + k]] (3 float4 per slot)
 hipError_t launch_gather_world(const float4* world, const uint32_t* xinv, uint32_t first, uint32_t count, float4* out,
                                hipStream_t stream);
@@ -294,8 +291,6 @@ hipError_t launch_sweep_valu(const TransformMirror& xf, float4* world, hipStream
 hipError_t launch_sweep_mfma(const TransformMirror& xf, float4* world, hipStream_t stream);
 // only the entries whose chain contains an entry flagged in dirty[] (1 byte per mirror entry); same bits
 hipError_t launch_sweep_subtree(const TransformMirror& xf, const uint8_t* dirty, float4* world, hipStream_t stream);
-// dirty[idx[k]] = 1 for k < count (entries re-mirrored through the scattered dirty-range path)
-hipError_t launch_mark_bytes(const uint32_t* idx, uint32_t count, uint8_t* dst, hipStream_t stream);
 // Sweep (MFMA or VALU chain) + cull of an exactly paired pool (mesh.mapping == kMapExact) in one pass: world matrices AND the cull
 // outputs of one view; same bits as launch_sweep_* followed by launch_cull.
 hipError_t launch_sweep_cull(const MeshMirror& mesh, const TransformMirror& xf, const HizDevice& hiz,

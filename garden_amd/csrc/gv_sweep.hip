@@ -38,10 +38,7 @@ __global__ __launch_bounds__(256) void sweep_valu_kernel(const TransformMirror x
     if (s < xf.count) {
         const XfRecord r = stream_xf(xf, s);
         if (r.flags & kXfLive) {
-            const Mat34 m = chain_model(xf, local_model(r), s, r.flags);
-            w0 = make_float4(m.c0x, m.c0y, m.c0z, m.c1x);
-            w1 = make_float4(m.c1y, m.c1z, m.c2x, m.c2y);
-            w2 = make_float4(m.c2z, m.c3x, m.c3y, m.c3z);
+            model_rows(chain_model(xf, local_model(r), s, r.flags), w0, w1, w2);
         }
     }
     store_world_tile(stage, world, lb, min(256u, xf.count - lb * 256u), w0, w1, w2);
@@ -77,12 +74,8 @@ __global__ __launch_bounds__(256) void sweep_subtree_kernel(const TransformMirro
         return;
     const XfRecord r = load_xf(xf, s);
     float4 w0 = make_float4(0, 0, 0, 0), w1 = w0, w2 = w0;
-    if (r.flags & kXfLive) {
-        const Mat34 m = chain_model(xf, local_model(r), s, r.flags);
-        w0 = make_float4(m.c0x, m.c0y, m.c0z, m.c1x);
-        w1 = make_float4(m.c1y, m.c1z, m.c2x, m.c2y);
-        w2 = make_float4(m.c2z, m.c3x, m.c3y, m.c3z);
-    }
+    if (r.flags & kXfLive)
+        model_rows(chain_model(xf, local_model(r), s, r.flags), w0, w1, w2);
     world[(size_t)s * 3 + 0] = w0;
     world[(size_t)s * 3 + 1] = w1;
     world[(size_t)s * 3 + 2] = w2;
@@ -280,6 +273,46 @@ struct SweepCullArgs {
     float4* world;
 };
 
+// cull_kernel's tail on the world matrix in registers (mesh.cpp:140-175), for the lane of mirror entry s = blockIdx.x * 256 +
+// threadIdx.x: filter chain, decision, isVisible byte, the wave's ballot word and the tile's count. (ma, mb): the entry's box,
+// `flags` its transform flags, `in_range`: s has a transform entry, `has_mesh`: a mesh entry. Every thread of the workgroup calls it.
+template <bool HIZ>
+__device__ __forceinline__ void sweep_cull_tail(const SweepCullArgs& args, const Mat34& world, const float4 ma, const float2 mb, uint32_t flags,
+                                                bool in_range, bool has_mesh, uint32_t* wave_count)
+{
+    const uint32_t lb = blockIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t s = lb * 256 + threadIdx.x;
+    bool visible = false;
+    if (has_mesh) {
+        if (!mesh_entry_dropped(in_range, ma, mb, flags)) {
+            const ViewParams& view = args.cull.view;
+            const Mat34 model = translated(world, view.cam[0], view.cam[1], view.cam[2]);
+            Corners c;
+            // sphere pre-test first (gv_device.hpp): corners and the exact test only for entries near a plane
+            visible = settle<HIZ>(classify_sphere(model, ma, mb, view.planes, view.plane_count), model, ma, mb, view.planes,
+                                  view.plane_count, c);
+            if (HIZ && visible)
+                visible = !hiz_occluded(args.cull.hiz, view.vp, c);
+        }
+        if (args.cull.view.write_is_visible)
+            args.cull.out.is_visible[s] = visible ? 1 : 0;
+    }
+    const unsigned long long word = __ballot(visible);
+    const bool mesh_block = lb < args.cull.nblocks;  // workgroups past the mesh range only sweep
+    if (lane == 0) {
+        if (mesh_block)
+            args.cull.out.mask[(size_t)lb * 4 + wave] = word;
+        wave_count[wave] = (uint32_t)__popcll(word);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && mesh_block) {
+        const uint32_t total = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+        if (total)
+            atomicAdd(&args.cull.out.chunk_count[lb / (kEmitChunk / kCullBlock)], total);
+    }
+}
+
 template <bool HIZ>
 __global__ __launch_bounds__(256) void sweep_cull_mfma_kernel(const SweepCullArgs args)
 {
@@ -349,50 +382,12 @@ __global__ __launch_bounds__(256) void sweep_cull_mfma_kernel(const SweepCullArg
     }
     {
         float4 w0 = make_float4(0, 0, 0, 0), w1 = w0, w2 = w0;
-        if (live) {
-            w0 = make_float4(world.c0x, world.c0y, world.c0z, world.c1x);
-            w1 = make_float4(world.c1y, world.c1z, world.c2x, world.c2y);
-            w2 = make_float4(world.c2z, world.c3x, world.c3y, world.c3z);
-        }
+        if (live)
+            model_rows(world, w0, w1, w2);
         const uint32_t wave_first = lb * 256u + wave * 64u;  // (the wave's tile is free again: its products sit in registers)
         store_world_wave(my_tile, args.world, wave_first, wave_first < xf.count ? min(64u, xf.count - wave_first) : 0u, w0, w1, w2);
     }
-    // ---- cull_kernel's tail on the model in registers (mesh.cpp:140-175) ----
-    bool visible = false;
-    if (has_mesh) {
-        const float mnx = ma.x, mny = ma.y, mnz = ma.z, mxx = ma.w, mxy = mb.x, mxz = mb.y;
-        const bool empty = (mxx - mnx <= 0.0f) && (mxy - mny <= 0.0f) && (mxz - mnz <= 0.0f);
-        if (in_range && !empty && (flags & kXfActive)) {
-            const Mat34 model = translated(world, args.cull.view.cam[0], args.cull.view.cam[1], args.cull.view.cam[2]);
-            Corners c;
-            // sphere pre-test first (gv_device.hpp): corners and the exact test only for entries near a plane
-            const uint32_t where = classify_sphere(model, ma, mb, args.cull.view.planes, args.cull.view.plane_count);
-            visible = where == kSphereInside;
-            if (where == kSphereUndecided) {
-                aabb_corners(model, mnx, mny, mnz, mxx, mxy, mxz, c);
-                visible = !behind_frustum(c, args.cull.view.planes, args.cull.view.plane_count);
-            } else if (HIZ && visible) {
-                aabb_corners(model, mnx, mny, mnz, mxx, mxy, mxz, c);
-            }
-            if (HIZ && visible)
-                visible = !hiz_occluded(args.cull.hiz, args.cull.view.vp, c);
-        }
-        if (args.cull.view.write_is_visible)
-            args.cull.out.is_visible[s] = visible ? 1 : 0;
-    }
-    const unsigned long long word = __ballot(visible);
-    const bool mesh_block = lb < args.cull.nblocks;  // workgroups past the mesh range only sweep
-    if (lane == 0) {
-        if (mesh_block)
-            args.cull.out.mask[(size_t)lb * 4 + wave] = word;
-        wave_count[wave] = (uint32_t)__popcll(word);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && mesh_block) {
-        const uint32_t total = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
-        if (total)
-            atomicAdd(&args.cull.out.chunk_count[lb / (kEmitChunk / kCullBlock)], total);
-    }
+    sweep_cull_tail<HIZ>(args, world, ma, mb, flags, in_range, has_mesh, wave_count);
 }
 
 // The same pass with the v_fma_f32 chain (one lane per slot end to end, no LDS hand-over).
@@ -403,7 +398,7 @@ __global__ __launch_bounds__(256) void sweep_cull_valu_kernel(const SweepCullArg
     const TransformMirror& xf = args.cull.xf;
     const MeshMirror& mesh = args.cull.mesh;
     const uint32_t lb = blockIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t wave = threadIdx.x >> 6;
     const uint32_t s = lb * 256 + threadIdx.x;
     const bool in_range = s < xf.count, has_mesh = s < mesh.count;
     float4 ma = make_float4(0, 0, 0, 0);
@@ -422,49 +417,13 @@ __global__ __launch_bounds__(256) void sweep_cull_valu_kernel(const SweepCullArg
             flags = r.flags;
             if (flags & kXfLive) {
                 world = chain_model(xf, local_model(r), s, flags);
-                w0 = make_float4(world.c0x, world.c0y, world.c0z, world.c1x);
-                w1 = make_float4(world.c1y, world.c1z, world.c2x, world.c2y);
-                w2 = make_float4(world.c2z, world.c3x, world.c3y, world.c3z);
+                model_rows(world, w0, w1, w2);
             }
         }
         const uint32_t wave_first = lb * 256u + wave * 64u;
         store_world_wave(world_stage + wave * 192u, args.world, wave_first, wave_first < xf.count ? min(64u, xf.count - wave_first) : 0u, w0, w1, w2);
     }
-    bool visible = false;
-    if (has_mesh) {
-        const float mnx = ma.x, mny = ma.y, mnz = ma.z, mxx = ma.w, mxy = mb.x, mxz = mb.y;
-        const bool empty = (mxx - mnx <= 0.0f) && (mxy - mny <= 0.0f) && (mxz - mnz <= 0.0f);
-        if (in_range && !empty && (flags & kXfActive)) {
-            const Mat34 model = translated(world, args.cull.view.cam[0], args.cull.view.cam[1], args.cull.view.cam[2]);
-            Corners c;
-            // sphere pre-test first (gv_device.hpp): corners and the exact test only for entries near a plane
-            const uint32_t where = classify_sphere(model, ma, mb, args.cull.view.planes, args.cull.view.plane_count);
-            visible = where == kSphereInside;
-            if (where == kSphereUndecided) {
-                aabb_corners(model, mnx, mny, mnz, mxx, mxy, mxz, c);
-                visible = !behind_frustum(c, args.cull.view.planes, args.cull.view.plane_count);
-            } else if (HIZ && visible) {
-                aabb_corners(model, mnx, mny, mnz, mxx, mxy, mxz, c);
-            }
-            if (HIZ && visible)
-                visible = !hiz_occluded(args.cull.hiz, args.cull.view.vp, c);
-        }
-        if (args.cull.view.write_is_visible)
-            args.cull.out.is_visible[s] = visible ? 1 : 0;
-    }
-    const unsigned long long word = __ballot(visible);
-    const bool mesh_block = lb < args.cull.nblocks;
-    if (lane == 0) {
-        if (mesh_block)
-            args.cull.out.mask[(size_t)lb * 4 + wave] = word;
-        wave_count[wave] = (uint32_t)__popcll(word);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && mesh_block) {
-        const uint32_t total = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
-        if (total)
-            atomicAdd(&args.cull.out.chunk_count[lb / (kEmitChunk / kCullBlock)], total);
-    }
+    sweep_cull_tail<HIZ>(args, world, ma, mb, flags, in_range, has_mesh, wave_count);
 }
 
 hipError_t launch_sweep_cull(const MeshMirror& mesh, const TransformMirror& xf, const HizDevice& hiz,
