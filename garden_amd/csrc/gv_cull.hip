@@ -184,6 +184,88 @@ __global__ __launch_bounds__(kCullBlock) void cull_kernel(const CullArgs args)
     cull_block<HIZ, MAP, false, HOT>(args, lb, wave_count);
 }
 
+// The sphere-stream cull of a large pool: K 256-entry tiles per workgroup (a super-tile), K 16-byte loads in flight per lane, and
+// the workgroup's barrier, ballot-word store and chunk atomic paid once per K tiles. One tile per workgroup settles nearly all of a
+// frustum-only view's entries as soon as its one load returns, and that cull streamed at 3.8 TB/s where a bare load stream runs at
+// ~6; with K = 4 it reaches 5.6 (cfg2 at 10 M: 42.6 -> 28.6 us; profiles/r08_hot_mlp.md). Entry first * 256 + k * 256 + tid for
+// k = 0 .. K-1, so each k is one contiguous 4 KB sweep of the workgroup and wave w of tile k holds ballot word (tile k, w) as in
+// cull_kernel.
+//   1. every lane issues its K sphere loads, then reduces each entry to its sphere class (2 bits) at once;
+//   2. the tiles one after another, each through cull_block's HOT per-entity code: only the lanes that need corners run it, and a
+//      wave skips a tile in which none of its lanes does;
+//   3. the 4K ballot words leave as one contiguous store, the super-tile's count as one atomic (K divides the 16 tiles of an emit
+//      chunk: a workgroup never straddles two).
+// Same device functions, same operands: the same decision bits as cull_kernel<HIZ, kMapExact, true>, which K = 1 keeps.
+template <bool HIZ, uint32_t K>
+__global__ __launch_bounds__(kCullBlock) void cull_hot_kernel(const CullArgs args)
+{
+    static_assert(K >= 2 && K <= 16 && (kEmitChunk / kCullBlock) % K == 0, "a super-tile must not straddle an emit chunk");
+    __shared__ unsigned long long words[K * (kCullBlock / 64)];
+    __shared__ uint32_t wave_count[kCullBlock / 64];
+    const uint32_t first = tile_of_workgroup(blockIdx.x, args.xcd_run) * K;  // the super-tile's first tile
+    if (first >= args.nblocks)
+        return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t base = first * kCullBlock + tid;
+    float4 h[K];
+#pragma unroll
+    for (uint32_t k = 0; k < K; k++) {
+        const uint32_t i = base + k * kCullBlock;
+        h[k] = i < args.mesh.count ? stream_load(&args.mesh.hot[i]) : make_float4(0.0f, 0.0f, 0.0f, kHotDropped);
+    }
+    uint32_t where = 0;  // entry k's sphere class in bits 2k, 2k + 1
+#pragma unroll
+    for (uint32_t k = 0; k < K; k++)
+        if (!(h[k].w < 0.0f)) {  // kHotDropped (or past the end): outside
+            const float tx = h[k].x - args.view.cam[0], ty = h[k].y - args.view.cam[1], tz = h[k].z - args.view.cam[2];
+            where |= classify_sphere(tx, ty, tz, sphere_reach(h[k].w, tx, ty, tz), args.view.planes, args.view.plane_count) << (2u * k);
+        }
+    uint32_t count = 0;
+#pragma unroll 1
+    for (uint32_t k = 0; k < K; k++) {  // (the arguments are read afresh at each stage, as in cull_list_kernel: no SGPR spills)
+        const uint32_t i = base + k * kCullBlock;
+        const uint32_t wk = (where >> (2u * k)) & 3u;
+        bool visible = wk == kSphereInside;
+        if (wk == kSphereUndecided || (HIZ && visible)) {
+            CullArgs a1;
+            reload_cull_args(a1);
+            Mat34 m;
+            float4 box_a;
+            float2 box_b;
+            Corners c;
+            visible = prepare_model<kMapExact>(a1.mesh, a1.xf, a1.view.cam, i, m, box_a, box_b) &&
+                      settle<HIZ>(wk, m, box_a, box_b, a1.view.planes, a1.view.plane_count, c);
+            if (HIZ && visible) {
+                CullArgs a2;
+                reload_cull_args(a2);
+                visible = !hiz_occluded(a2.hiz, a2.view.vp, c);
+            }
+        }
+        CullArgs a3;
+        reload_cull_args(a3);
+        if (i < a3.mesh.count && a3.view.write_is_visible)
+            a3.out.is_visible[i] = visible ? 1 : 0;  // mesh.cpp:144,152,161,166
+        const unsigned long long word = __ballot(visible);
+        if (lane == 0) {
+            words[k * (kCullBlock / 64) + wave] = word;
+            count += (uint32_t)__popcll(word);
+        }
+    }
+    if (lane == 0)
+        wave_count[wave] = count;
+    __syncthreads();
+    if (tid < K * (kCullBlock / 64) && first + tid / (kCullBlock / 64) < args.nblocks)
+        args.out.mask[(size_t)first * (kCullBlock / 64) + tid] = words[tid];
+    if (tid == 0) {
+        uint32_t total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kCullBlock / 64; w++)
+            total += wave_count[w];
+        if (total)
+            atomicAdd(&args.out.chunk_count[first / (kEmitChunk / kCullBlock)], total);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Block bounds (GV_CONFIG_BLOCK_BOUNDS) as two or three launches: classify, then cull the kept workgroups only.
 // (Round 2 tested the box inside the cull kernel: a latency chain in front of every workgroup — box load -> 8 projections ->
@@ -608,6 +690,20 @@ hipError_t launch_cull(const MeshMirror& mesh, const TransformMirror& xf, const 
     // measured: the frustum-only scan gains 6 % from per-XCD runs, the Hi-Z variant does not
     a.xcd_run = vp.use_hiz ? 0 : xcd_run_for_tiles(a.nblocks);
     const dim3 grid(grid_for_tiles(a.nblocks, a.xcd_run)), block(kCullBlock);
+    const uint32_t k = mesh.hot && mesh.mapping == kMapExact ? hot_tiles_per_workgroup(a.nblocks) : 1u;
+    if (k > 1) {
+        // the same XCD runs in super-tiles: each run still covers xcd_run_for_tiles() tiles
+        const uint32_t supers = (a.nblocks + k - 1) / k;
+        a.xcd_run = vp.use_hiz ? 0 : xcd_run_for_tiles(a.nblocks) / k;
+        const dim3 hot_grid(grid_for_tiles(supers, a.xcd_run));
+        with_variant(vp.use_hiz, kMapExact, [&](auto hiz, auto) {
+            if (k == 4)
+                hipLaunchKernelGGL((cull_hot_kernel<hiz, 4>), hot_grid, block, 0, stream, a);
+            else
+                hipLaunchKernelGGL((cull_hot_kernel<hiz, 2>), hot_grid, block, 0, stream, a);
+        });
+        return hipGetLastError();
+    }
     with_variant(vp.use_hiz, mesh.mapping, [&](auto hiz, auto map) {
         if constexpr (map == kMapExact) {
             if (mesh.hot) {

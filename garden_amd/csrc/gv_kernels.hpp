@@ -58,6 +58,12 @@ constexpr float kHotDropped = -1.0f;
 // PoolState::d_blk_dirty bits: a block holds an entry re-mirrored since the boxes / the sphere stream were last current
 constexpr uint8_t kDirtyBounds = 1u, kDirtyHot = 2u, kDirtyAll = kDirtyBounds | kDirtyHot;
 constexpr uint32_t kHotMinSlots = 65536;  // smaller pools cull in one launch with their emit (kFusedEmitMaxSlots) or are launch-bound
+// 256-entry tiles per workgroup of the sphere-stream cull (cull_hot_kernel, K sphere loads in flight per lane), chosen so that the
+// grid still fills the chip several times: 4 from 16 Ki tiles (4 Mi entries), 2 from 8 Ki tiles, 1 (cull_kernel) below
+inline uint32_t hot_tiles_per_workgroup(uint32_t tiles)
+{
+    return tiles >= 16384u ? 4u : (tiles >= 8192u ? 2u : 1u);
+}
 hipError_t launch_hot_build(const MeshMirror& mesh, const TransformMirror& xf, float4* hot, hipStream_t stream);
 // re-derives the entries of the blocks flagged kDirtyHot (flags padded to a multiple of 16) and clears that bit
 hipError_t launch_hot_patch(const MeshMirror& mesh, const TransformMirror& xf, float4* hot, uint8_t* flags, hipStream_t stream);
