@@ -200,6 +200,7 @@ struct PoolState {
     DeviceBuf<uint32_t> d_index_map;  // gv_pool_set_index_map: pool slot -> the caller's global id (exchange shards)
     uint32_t index_map_count = 0;     // 0: none
     std::vector<uint32_t> h_index_map;  // the same table on the host (the mapped write-back of isVisible walks it)
+    uint32_t index_map_wide = 0;        // entries of the table that name a slot of 2^28 or more (gv_pick cannot encode them)
     // gv_pool_set_result_mapping: results in the caller's WORLD numbering
     uint32_t result_flags = 0;          // GV_RESULTS_MAP_*
     uint8_t* visible_base = nullptr;    // GV_RESULTS_MAP_VISIBLE: byte of slot i -> visible_base + h_index_map[i] * visible_stride
@@ -329,6 +330,8 @@ struct Context {
     DeviceBuf<MeshPacket> dsc_mesh;
     DeviceBuf<float4> dsc_a;         // device scratch of gv_get_world (the gathered matrices of a permuted mirror) ...
     DeviceBuf<float2> dsc_c;         // ... and of gv_debug_stream_peak (its sink)
+    DeviceBuf<unsigned long long> d_pick_keys;  // gv_pick: one key per ray (its own: no cull buffer is touched)
+    PinnedBuf<unsigned long long> h_pick_keys;
 
     PoolState pools[GV_MAX_POOLS];
     // results are kept per (pool, view): every mesh system's cull can be issued before the first result is read

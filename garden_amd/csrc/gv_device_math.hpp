@@ -179,4 +179,69 @@ __device__ __forceinline__ float2 unpack_rg16f(uint32_t texel)
     return make_float2(half_to_float(texel & 0xFFFFu), half_to_float(texel >> 16));
 }
 
+// ------------------------------------------------------------------------------------------------
+// picking: inverse4x4, Ray, raycast2 and isIntersected of the editor's selector
+// (editor/system/render/mesh-selector.cpp:102-107) for an affine model [A | t]
+// ------------------------------------------------------------------------------------------------
+// A^-1 = adj(A) * (1 / det A), each adjugate entry one fma (p*q - r*s = fma(p, q, -(r*s))), det the first-row cofactor sum nested
+// in fmas. valid = false when det is 0 or not finite: such a model has nothing to hit. Row-major: inv[r][c].
+struct Inv33 {
+    float m[3][3];
+    bool valid;
+};
+__device__ __forceinline__ float cross_term(float p, float q, float r, float s) { return fmaf(p, q, -(r * s)); }
+__device__ __forceinline__ Inv33 affine_inverse(const Mat34& a)
+{
+    // a_rc: row r, column c
+    const float a00 = a.c0x, a10 = a.c0y, a20 = a.c0z;
+    const float a01 = a.c1x, a11 = a.c1y, a21 = a.c1z;
+    const float a02 = a.c2x, a12 = a.c2y, a22 = a.c2z;
+    const float j00 = cross_term(a11, a22, a12, a21), j01 = cross_term(a02, a21, a01, a22), j02 = cross_term(a01, a12, a02, a11);
+    const float j10 = cross_term(a12, a20, a10, a22), j11 = cross_term(a00, a22, a02, a20), j12 = cross_term(a02, a10, a00, a12);
+    const float j20 = cross_term(a10, a21, a11, a20), j21 = cross_term(a01, a20, a00, a21), j22 = cross_term(a00, a11, a01, a10);
+    const float det = fmaf(a00, j00, fmaf(a01, j10, a02 * j20));
+    const float rdet = 1.0f / det;
+    Inv33 r;
+    r.valid = det != 0.0f && fabsf(det) < __builtin_inff();  // (NaN fails the second test)
+    r.m[0][0] = j00 * rdet; r.m[0][1] = j01 * rdet; r.m[0][2] = j02 * rdet;
+    r.m[1][0] = j10 * rdet; r.m[1][1] = j11 * rdet; r.m[1][2] = j12 * rdet;
+    r.m[2][0] = j20 * rdet; r.m[2][1] = j21 * rdet; r.m[2][2] = j22 * rdet;
+    return r;
+}
+__device__ __forceinline__ float row_dot(const float (&r)[3], float x, float y, float z) { return fmaf(r[0], x, fmaf(r[1], y, r[2] * z)); }
+
+// One slab of raycast2: the axis interval [lo, hi] of the ray parameter, or for d == 0 the whole line when lo_box <= o <= hi_box
+// (ok = false otherwise). A NaN plane parameter also clears ok: every comparison with a NaN is false.
+__device__ __forceinline__ void slab(float o, float d, float lo_box, float hi_box, float& t_near, float& t_far, bool& ok)
+{
+    const float inv = 1.0f / d;
+    const float t1 = (lo_box - o) * inv, t2 = (hi_box - o) * inv;
+    const bool moving = d != 0.0f;
+    const float lo = t1 < t2 ? t1 : t2, hi = t1 < t2 ? t2 : t1;
+    const bool axis_ok = moving ? (t1 == t1 && t2 == t2) : (lo_box <= o && o <= hi_box);
+    ok = ok && axis_ok;
+    if (moving) {
+        t_near = lo > t_near ? lo : t_near;
+        t_far = hi < t_far ? hi : t_far;
+    }
+}
+
+// The selector's test of one entry against one ray (origin o, direction d, camera-relative): the 64-bit key of the hit,
+// (bits(distSq) << 32) | (order << 28) | slot, or ~0 for a miss. t = (tx, ty, tz): the model's translation; box in model space.
+__device__ __forceinline__ unsigned long long pick_key(const Inv33& inv, float tx, float ty, float tz, const float4 a, const float2 b,
+                                                       float ox, float oy, float oz, float dx, float dy, float dz, uint32_t order_slot)
+{
+    const float ux = ox - tx, uy = oy - ty, uz = oz - tz;  // o - t
+    const float lox = row_dot(inv.m[0], ux, uy, uz), loy = row_dot(inv.m[1], ux, uy, uz), loz = row_dot(inv.m[2], ux, uy, uz);
+    const float ldx = row_dot(inv.m[0], dx, dy, dz), ldy = row_dot(inv.m[1], dx, dy, dz), ldz = row_dot(inv.m[2], dx, dy, dz);
+    float t_near = -__builtin_inff(), t_far = __builtin_inff();
+    bool ok = inv.valid;
+    slab(lox, ldx, a.x, a.w, t_near, t_far, ok);
+    slab(loy, ldy, a.y, b.x, t_near, t_far, ok);
+    slab(loz, ldz, a.z, b.y, t_near, t_far, ok);
+    const float dist_sq = fmaf(uz, uz, fmaf(uy, uy, ux * ux));
+    const bool hit = ok && t_near >= 0.0f && t_near <= t_far && dist_sq < 3.40282347e+38f;
+    return hit ? ((unsigned long long)__float_as_uint(dist_sq) << 32) | order_slot : ~0ull;
+}
+
 }  // namespace gv

@@ -175,6 +175,20 @@ struct MultiViewPlanes {
 hipError_t launch_cull_multi(const MeshMirror& mesh, const TransformMirror& xf, const HizDevice& hiz,
                              const ViewParams* views, const ViewBuffers* outs, uint32_t nviews, hipStream_t stream,
                              const BlockBounds* bounds = nullptr);
+// gv_pick (gv_pick.hip): every ray against every entry of one pool that passes the cull's filter chain; keys[r] = min(keys[r], the
+// smallest key (bits(distSq) << 32) | order_bits | slot of a hit), keys initialised to ~0 by the caller
+constexpr uint32_t kPickBlock = 256;
+constexpr uint32_t kPickMaxRays = 8;  // GV_MAX_PICK_RAYS
+struct PickLaunch {
+    float cam[3];
+    float ray[kPickMaxRays][6];       // origin xyz, direction xyz (camera-relative)
+    uint32_t rays;
+    uint32_t order_bits;              // the pool's position in the call's list << 28
+    uint32_t exclude;                 // slot never picked (kSlotNone-compatible: GV_NONE = none)
+    const uint32_t* index_map;        // pool slot -> the caller's slot (NULL: none)
+    unsigned long long* keys;         // [rays]
+};
+hipError_t launch_pick(const MeshMirror& mesh, const TransformMirror& xf, const PickLaunch& p, hipStream_t stream);
 // read-only pass over the cull kernel's input streams (65 B per entry); gv_debug_stream_peak
 hipError_t launch_stream_probe(const MeshMirror& mesh, const TransformMirror& xf, float* sink, hipStream_t stream);
 // Table-driven tick (gv_cull_batch_begin): the culls of several small pools in one launch, their emits in one launch.

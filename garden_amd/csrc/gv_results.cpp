@@ -865,6 +865,12 @@ int gv_pool_mirror_epoch(GvCtx* ctx, uint32_t pool_id, uint64_t* epoch)
     return GV_OK;
 }
 
+// entries of [first, last) that name a slot gv_pick cannot put into its 28-bit key (GV_NONE, a hole, is not one)
+static uint32_t wide_slots(const uint32_t* first, const uint32_t* last)
+{
+    return (uint32_t)std::count_if(first, last, [](uint32_t s) { return s != GV_NONE && s > kSlotMask; });
+}
+
 int gv_pool_set_index_map(GvCtx* ctx, uint32_t pool_id, const uint32_t* global_ids, uint32_t count)
 {
     if (!ctx)
@@ -880,6 +886,7 @@ int gv_pool_set_index_map(GvCtx* ctx, uint32_t pool_id, const uint32_t* global_i
     }
     p.index_map_count = count;
     p.h_index_map.assign(global_ids, global_ids + count);
+    p.index_map_wide = wide_slots(p.h_index_map.data(), p.h_index_map.data() + count);
     for (uint32_t v = 0; v < GV_MAX_VIEWS; v++)  // records that carry mapped slots are delivered again
         if (p.result_flags & GV_RESULTS_MAP_RECORDS)
             ctx->views[pool_id][v].published = false, ctx->views[pool_id][v].records_fetched = false;
@@ -904,7 +911,9 @@ int gv_pool_update_index_map(GvCtx* ctx, uint32_t pool_id, uint32_t first, const
         p.index_map_count = end;
         p.h_index_map.resize(end, GV_NONE);
     }
+    p.index_map_wide -= wide_slots(p.h_index_map.data() + first, p.h_index_map.data() + end);
     std::copy(global_ids, global_ids + count, p.h_index_map.begin() + first);
+    p.index_map_wide += wide_slots(p.h_index_map.data() + first, p.h_index_map.data() + end);
     // (out of the library's own host copy, which stays put; stream order keeps queued readers of the old entries in front)
     GV_HIP(ctx, hipMemcpyAsync(p.d_index_map.ptr + first, p.h_index_map.data() + first, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));
     GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (pageable source: the runtime may still be reading it)

@@ -1225,6 +1225,10 @@ private:
                 mergeRuns(shadowTransMeshes[s], shadowTransRuns[s]);
         }
     }
+
+public:
+    // the mesh systems of the last frame in pool order: pool p of every context is meshSystems[p] (mesh_selector.hpp reads it)
+    const std::vector<IMeshRenderSystem*>& getMeshSystems() const noexcept { return meshSystems; }
 };
 
 }  // namespace garden

@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from .pools import mesh_layout_offsets, transform_layout_offsets
+from .pools import GV_NONE, mesh_layout_offsets, transform_layout_offsets
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GV_LIB_PATH: dev A/Bs against another build of the same library (e.g. a previous round's kernels); never a fallback
@@ -92,6 +92,17 @@ class GvExchangeItem(C.Structure):
     _fields_ = [("pool_id", C.c_uint32), ("view_index", C.c_uint32), ("index_base", C.c_uint32)]
 
 
+class GvPickRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 4), ("direction", C.c_float * 4)]
+
+
+class GvPickHit(C.Structure):
+    _fields_ = [("pool_id", C.c_uint32), ("slot", C.c_uint32), ("distance_sq", C.c_float), ("reserved", C.c_uint32)]
+
+
+GV_MAX_PICK_RAYS = 8
+
+
 class GvColumn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("stride", C.c_uint32)]
 
@@ -136,7 +147,7 @@ EXPORTS = [
     "gv_exchange_views", "gv_exchange_views_all", "gv_pool_update_index_map", "gv_pool_set_result_mapping", "gv_host_parallel_ranges", "gv_host_parallel_tasks",
     "gv_pool_results_fetch", "gv_pool_result_count", "gv_pool_results_device", "gv_pool_sort",
     "gv_cull_batch_begin", "gv_cull_batch_end", "gv_pool_set_record_layout", "gv_pool_results_records", "gv_pool_set_record_target",
-    "gv_pool_results_instance_bases", "gv_profile_sampling", "gv_profile_samples", "gv_profile_kernels",
+    "gv_pool_results_instance_bases", "gv_profile_sampling", "gv_profile_samples", "gv_profile_kernels", "gv_pick",
 ]
 
 _lib = None
@@ -246,6 +257,7 @@ def load():
     lib.gv_pool_results_instance_bases.argtypes = [P, u32, u32, C.POINTER(C.POINTER(u32)), C.POINTER(u32)]
     lib.gv_cull_batch_begin.argtypes = [P]
     lib.gv_cull_batch_end.argtypes = [P]
+    lib.gv_pick.argtypes = [P, C.POINTER(u32), u32, C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(GvPickRay), u32, C.POINTER(GvPickHit)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -595,6 +607,27 @@ class GpuVisibility:
             self._check(self.lib.gv_sort(self.ctx, view_index, 1 if descending else 0))
         else:
             self._check(self.lib.gv_pool_sort(self.ctx, pool_id, view_index, 1 if descending else 0))
+
+    # ---- picking ----
+    def pick(self, rays, pool_ids=(0,), camera_position=(0, 0, 0), exclude=None):
+        """gv_pick: rays = up to GV_MAX_PICK_RAYS (origin xyz, direction xyz) pairs, camera-relative (an array of shape [R, 2, 3]
+        or [R, 6] works too); exclude = one slot per pool (None / GV_NONE: none). One (pool_id, slot, distance_sq) or None per ray."""
+        r = np.asarray(rays, dtype=np.float32).reshape(-1, 6)
+        arr = (GvPickRay * max(len(r), 1))()
+        for k, row in enumerate(r):
+            arr[k].origin[:3] = [float(x) for x in row[:3]]
+            arr[k].direction[:3] = [float(x) for x in row[3:]]
+        ids = (C.c_uint32 * max(len(pool_ids), 1))(*[int(p) for p in pool_ids])
+        ex = None
+        if exclude is not None:
+            if len(exclude) != len(pool_ids):
+                raise ValueError(f"pick: {len(exclude)} excluded slots for {len(pool_ids)} pools (one per pool, None: none)")
+            ex = (C.c_uint32 * max(len(pool_ids), 1))(*[GV_NONE if e is None else int(e) for e in exclude])
+        cam = (C.c_float * 4)(*[float(x) for x in list(camera_position)[:3]], 0.0)
+        hits = (GvPickHit * max(len(r), 1))()
+        self._check(self.lib.gv_pick(self.ctx, ids, len(pool_ids), ex, cam, arr, len(r), hits))
+        return [None if hits[k].pool_id == GV_NONE else (int(hits[k].pool_id), int(hits[k].slot), float(hits[k].distance_sq))
+                for k in range(len(r))]
 
     # ---- world matrices ----
     def sweep(self, mode=GV_SWEEP_VALU):

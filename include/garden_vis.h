@@ -504,6 +504,36 @@ int gv_exchange_set_mode(GvCtx* ctx, uint32_t mode);
  * its launches, not by bytes. Larger pools sort at once. */
 int gv_sort(GvCtx* ctx, uint32_t view_index, int descending);
 
+/* ---- picking: the editor's click selection (MeshSelectorEditorSystem::render, editor/system/render/mesh-selector.cpp:67-122) ----
+ * Every ray is tested against every entry of the listed pools that passes the cull's filter chain (free slot, isEnabled, a box
+ * with some extent, a transform, isActive: mesh.cpp:140-150), through the inverse of its camera-relative model
+ * (calcModel(cameraPosition), transform.hpp:197-214). A ray hits a box when its entry point lies at or ahead of the origin
+ * (a ray that starts inside a box does not pick it, :106). Of the hits, the one whose pivot — the model's translation — lies
+ * nearest the ray origin wins (:109-110); ties go to the pool listed first, then to the lower slot (the reference's strict
+ * `<` over its systems and ascending slots). Arithmetic: DESIGN.md §4 item 8. */
+#define GV_MAX_PICK_RAYS 8u
+typedef struct GvPickRay {
+    float origin[4];    /* camera-relative, xyz used: globalOrigin of mesh-selector.cpp:73-74 */
+    float direction[4]; /* camera-relative, xyz used, not normalised: globalDirection (:74-76) */
+} GvPickRay;
+typedef struct GvPickHit {
+    uint32_t pool_id;   /* GV_NONE: the ray hit nothing */
+    uint32_t slot;      /* pool slot, or the pool's index-map slot when one is installed (gv_pool_set_index_map) */
+    float distance_sq;  /* distanceSq3(origin, getTranslation(model)), :109 */
+    uint32_t reserved;
+} GvPickHit;
+/* pool_ids[0 .. pool_count): searched in this order (it decides ties). exclude_slots: NULL, or one slot per listed pool in the
+ * slot space of the hits (GV_NONE: none) — the selected entity, which is never picked again (:110). camera_position: xyz used.
+ * Syncs the mirror as gv_cull does, runs on gv_stream(ctx) and waits; fills hits[0 .. ray_count). The pick has buffers of its
+ * own: cull results, pending sorts and device pointers are left as they were. The sync is gv_sync's, with gv_sync's one caveat:
+ * edits made since a gv_cull that grow or re-order a pool (appended slots, a rebind) change the mirror's slot order, and a
+ * fetch of that cull made after the pick reads is_visible through the new order — fetch before picking when the pools were
+ * edited in between. GV_E_ARG: an unbound pool, ray_count 0 or above GV_MAX_PICK_RAYS, pool_count above GV_MAX_POOLS, a pool of
+ * 2^28 slots or more (or an index map naming such a slot); GV_E_STATE: no transforms bound, an index map that does not cover
+ * its pool, or a call between gv_cull_batch_begin and gv_cull_batch_end. */
+int gv_pick(GvCtx* ctx, const uint32_t* pool_ids, uint32_t pool_count, const uint32_t* exclude_slots,
+            const float camera_position[4], const GvPickRay* rays, uint32_t ray_count, GvPickHit* hits);
+
 /* ---- scene ingest: a Garden scene file straight into column pools, no component AoS ----
  * Reads what ResourceSystem::loadScene (source/system/resource.cpp:2421-2510) hands to TransformSystem::deserialize /
  * postDeserialize (source/system/transform.cpp:517-583) and to the mesh systems' deserialize ("aabb", "isEnabled",
