@@ -671,6 +671,7 @@ void gv_destroy(GvCtx* ctx)
         for (auto& target : p.record_target)
             release_record_target(target);
         p.d_a.release(); p.d_b.release(); p.d_link.release(); p.h_a.release(); p.h_b.release(); p.h_link.release(); p.d_orig.release(); p.d_inv.release(); p.d_index_map.release(); p.d_blk_lo.release(); p.d_blk_hi.release(); p.d_seed.release(); p.d_kept.release(); p.d_kept_flag.release(); p.d_blk_dirty.release(); p.d_hot.release();
+        p.instances.d_data.release(); p.instances.d_starts.release(); p.instances.h_data.release(); p.instances.h_starts.release();
     }
     for (auto& per_pool : ctx->views)
       for (auto& v : per_pool) {
@@ -942,10 +943,12 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
         vs.published = false, vs.records_fetched = false;
         vs.sort_pending = 0;  // a sort of the previous results that nobody asked for any more
         vs.ballots_current = true;  // every cull launch but the one-launch cull + emit of a small pool writes them
+        memcpy(vs.view_proj, views[v].view_proj, sizeof(vs.view_proj));
         build_view_params(views[v], &vps[v]);
         if (p.occupancy == 0)
             GV_HIP(ctx, hipMemsetAsync(vs.draw_count.ptr, 0, 4, ctx->stream));
     }
+    p.instances.views = 0;  // the views' results are replaced from here on: the instance data made from the previous ones ends
     // gv_cull_batch_begin: an engine-sized pool whose views all want records is only RECORDED here; the first read
     // launches every recorded cull together (flush_culls)
     if (ctx->cull_batching) {

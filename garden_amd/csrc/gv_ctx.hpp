@@ -184,6 +184,21 @@ struct PoolState {
     Column ready;              // gv_pool_bind_ready: per-slot ready count (ptr NULL: none, every slot counts 1)
     uint32_t ready_width = 0;  // 1 or 4 bytes
     uint32_t ready_count(size_t i) const { return !ready.ptr ? 1u : (ready_width == 4 ? ready.u32(i) : (uint32_t)ready.u8(i)); }
+    std::vector<uint8_t> ready_many;  // per slot: a candidate whose ready count is above 1 (kept by gather_meshes; empty without a column)
+    uint32_t ready_many_count = 0;    // ... and how many: such draws take several instances (gv_pool_emit_instances refuses them)
+    // gv_pool_set_instance_layout / gv_pool_emit_instances: buffers of their own, nothing a cull produced is touched
+    struct Instances {
+        GvInstanceLayout layout{};      // stride 0: none
+        DeviceBuf<uint8_t> d_data;      // the library-owned target
+        DeviceBuf<uint32_t> d_starts;   // [views + 1]
+        PinnedBuf<uint8_t> h_data;      // staging of gv_pool_instances_fetch
+        PinnedBuf<uint32_t> h_starts;
+        // the last emission (views 0: none since the pool's last gv_cull)
+        uint8_t* target = nullptr;      // d_data.ptr or the caller's device memory
+        uint32_t capacity = 0;          // instances the target holds
+        uint32_t views = 0;
+        GvInstanceLayout emitted{};     // the layout it was made with
+    } instances;
     uint8_t* is_visible = nullptr;  // write-back target (NULL: none), element i at is_visible + i * is_visible_stride
     size_t is_visible_stride = 0;
     uint32_t occupancy = 0;
@@ -267,6 +282,7 @@ struct ViewState {
     std::vector<uint32_t> instance_bases;  // gv_pool_results_instance_bases (built on request)
     uint32_t pool_id = 0, occupancy = 0;
     bool main_pass = false, emitted = false, valid = false;
+    float view_proj[16] = {};  // GvView::view_proj of this view's cull (gv_pool_emit_instances multiplies the records' models by it)
     // fused cull + emit (launch_cull_emit): look-back words, ticket counter and their running epoch / base
     DeviceBuf<unsigned long long> tile_status;
     DeviceBuf<uint32_t> tile_ticket;

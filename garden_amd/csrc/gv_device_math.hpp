@@ -244,4 +244,20 @@ __device__ __forceinline__ unsigned long long pick_key(const Inv33& inv, float t
     return hit ? ((unsigned long long)__float_as_uint(dist_sq) << 32) | order_slot : ~0ull;
 }
 
+// ------------------------------------------------------------------------------------------------
+// instance data: mvp = viewProj * f32x4x4(bakedModel, (0,0,0,1)), the first thing every plugin's drawAsync
+// computes (sprite.cpp:107-108, model completed at mesh.cpp:596)
+// ------------------------------------------------------------------------------------------------
+// One column of the 4x4 product of item 2, all four rows: a = view_proj (column-major, a[4 k + i] = a.c_k[i]), (b0, b1, b2, b3) a
+// column of the completed model. The four-term nesting is kept although b3 is 0 or 1: dropping the term changes the sign of a
+// zero and what a non-finite view_proj produces.
+__device__ __forceinline__ float4 mvp_column(const float (&a)[16], float b0, float b1, float b2, float b3)
+{
+    float o[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        o[i] = fmaf(a[12 + i], b3, fmaf(a[8 + i], b2, fmaf(a[4 + i], b1, fmaf(a[i], b0, 0.0f))));
+    return make_float4(o[0], o[1], o[2], o[3]);
+}
+
 }  // namespace gv

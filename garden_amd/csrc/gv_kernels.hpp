@@ -189,6 +189,31 @@ struct PickLaunch {
     unsigned long long* keys;         // [rays]
 };
 hipError_t launch_pick(const MeshMirror& mesh, const TransformMirror& xf, const PickLaunch& p, hipStream_t stream);
+// gv_pool_emit_instances (gv_instance.hip): the records of up to kMaxInstanceViews views of one pool -> instance structs, back to
+// back in the order listed, in ONE launch. The counts stay on the device: the grid is sized from the views' occupancies
+// (first_block[v]: workgroups in front of view v), every workgroup adds up the counts of the views in front of its own.
+constexpr uint32_t kInstanceBlock = 256;
+constexpr uint32_t kMaxInstanceViews = 8;  // GV_MAX_VIEWS
+constexpr uint32_t kMinInstanceStride = 64, kMaxInstanceStride = 256;
+constexpr uint32_t kNoField = 0xFFFFFFFFu;  // GV_NONE
+struct InstanceView {
+    const uint32_t* count;  // device draw count
+    const uint32_t* idx;    // records in delivery order
+    const float* model;
+    const float* dist;
+    float view_proj[16];    // GvView::view_proj of the view's cull, column-major
+};
+struct InstanceLaunch {
+    InstanceView view[kMaxInstanceViews];
+    uint32_t first_block[kMaxInstanceViews + 1];
+    uint32_t views;
+    uint32_t stride, mvp, model, slot, distance_sq;  // GvInstanceLayout
+    const uint32_t* index_map;                       // pool slot -> the caller's slot (NULL: none)
+    uint8_t* dst;
+    uint32_t capacity;                               // instances dst holds: those at or beyond it are not written
+    uint32_t* starts;                                // [views + 1], written by workgroup 0
+};
+hipError_t launch_instances(const InstanceLaunch& launch, hipStream_t stream);
 // read-only pass over the cull kernel's input streams (65 B per entry); gv_debug_stream_peak
 hipError_t launch_stream_probe(const MeshMirror& mesh, const TransformMirror& xf, float* sink, hipStream_t stream);
 // Table-driven tick (gv_cull_batch_begin): the culls of several small pools in one launch, their emits in one launch.

@@ -287,7 +287,18 @@ void gather_meshes(GvCtx* ctx, PoolState& p, uint32_t lo, uint32_t hi)
 {
     const TransformBinding& xf = ctx->xf;
     std::atomic<bool> demoted{false};
+    // candidates whose ready count is above 1, kept slot by slot (a draw of several instances: gv_pool_emit_instances)
+    const bool counted = p.ready.ptr != nullptr;
+    if (!counted) {
+        p.ready_many.clear();
+        p.ready_many_count = 0;
+    } else if (p.ready_many.size() != std::max(p.occupancy, hi)) {  // (a pool that shrank drops the flags of the slots it lost)
+        p.ready_many.resize(std::max(p.occupancy, hi), 0);
+        p.ready_many_count = (uint32_t)std::count(p.ready_many.begin(), p.ready_many.end(), 1);
+    }
+    std::atomic<int64_t> many_delta{0};
     parallel_ranges(lo, hi - lo, [&](uint32_t a, uint32_t b) {
+        int64_t delta = 0;
         for (uint32_t i = a; i < b; i++) {
             const float* mn = p.aabb_min.f32(i);
             const float* mx = p.aabb_max.f32(i);
@@ -304,8 +315,15 @@ void gather_meshes(GvCtx* ctx, PoolState& p, uint32_t lo, uint32_t hi)
             p.h_link.ptr[j] = slot | (candidate ? kMeshCandidate : 0u);
             if (candidate && slot != j && p.mapping == kMapExact)
                 demoted = true;  // an edited mesh no longer pairs with its own index
+            if (counted) {
+                const uint8_t many = candidate && p.ready_count(i) > 1;
+                delta += (int64_t)many - (int64_t)p.ready_many[i];
+                p.ready_many[i] = many;
+            }
         }
+        many_delta += delta;
     });
+    p.ready_many_count = (uint32_t)((int64_t)p.ready_many_count + many_delta.load());
     if (demoted)
         p.mapping = kMapSpeculate;
 }

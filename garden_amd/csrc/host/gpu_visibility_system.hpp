@@ -1229,6 +1229,9 @@ private:
 public:
     // the mesh systems of the last frame in pool order: pool p of every context is meshSystems[p] (mesh_selector.hpp reads it)
     const std::vector<IMeshRenderSystem*>& getMeshSystems() const noexcept { return meshSystems; }
+    // the passes mesh system p was culled for in the last frame: view v of pool p stands for passes[v] — -1 the light pass, s >= 0
+    // shadow pass s (instance_writer.hpp reads it)
+    const std::vector<int8_t>& getSystemPasses(uint32_t p) const { return plan.at(p).passes; }
 };
 
 }  // namespace garden

@@ -1,0 +1,80 @@
+// instance_writer.hpp — the instance buffers of the drop-in's mesh systems, filled on the device: what prepareDraw / drawAsync /
+// finalizeDraw leave in a system's instanceMap (source/system/render/instance.cpp:120-230) when every draw writes
+// instanceData[instanceIndex].mvp = viewProj * model first (sprite.cpp:107-108,122-126). For a mesh system that declares its
+// instance layout, write() — after the frame's prepare phase (preRender), where the render passes would start — emits the light
+// pass into the system's base instance array and the shadow passes, in pass order, into its shadow array, which the reference
+// fills pass after pass behind shadowInstanceIndex (instance.cpp:164,215), and returns the per-pass starts.
+//
+// One context only. With ranks (GpuVisibilitySystem(devices, ...)) every context holds the records of its own share and the
+// frame's draw order is merged on the host (mergeRanks): no device holds a view's records in draw order, so there is nothing
+// to emit from — isSupported() is false and write() throws.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "gpu_visibility_system.hpp"
+
+namespace garden {
+
+class GpuInstanceWriter {
+    GpuVisibilitySystem* system;
+
+    void check(int rc, const char* what) const
+    {
+        if (rc != GV_OK)
+            throw GardenError(std::string(what) + " failed: " + gv_last_error(system->getContext()));
+    }
+
+public:
+    // what one write() left behind
+    struct Written {
+        uint32_t baseCount = 0;             // instances [0, baseCount) of the base array: the light pass's draws
+        std::vector<uint32_t> shadowStart;  // [shadow passes + 1]: pass s took instances [shadowStart[s], shadowStart[s + 1]) of the
+                                            // shadow array (a pass that was not culled for this system: an empty range)
+    };
+
+    explicit GpuInstanceWriter(GpuVisibilitySystem* system) : system(system) {}
+
+    bool isSupported() const noexcept { return system->getRankCount() == 1; }
+
+    // the instance struct of mesh system p (pool p of the context): see GvInstanceLayout
+    void setLayout(uint32_t p, const GvInstanceLayout& layout) { check(gv_pool_set_instance_layout(system->getContext(), p, &layout), "gv_pool_set_instance_layout"); }
+
+    // base / shadow: the system's mapped instance arrays (NULL: that array is not wanted); only the layout's fields are written
+    Written write(uint32_t p, void* base, size_t baseBytes, void* shadow, size_t shadowBytes, uint32_t shadowPassCount)
+    {
+        if (!isSupported())
+            throw GardenError("GpuInstanceWriter: unsupported with several ranks (the merged draw order is made on the host)");
+        GvCtx* ctx = system->getContext();
+        const std::vector<int8_t>& passes = system->getSystemPasses(p);
+        Written out;
+        out.shadowStart.assign((size_t)shadowPassCount + 1, 0);
+        std::vector<uint32_t> shadowViews;
+        uint32_t starts[GV_MAX_VIEWS + 1];
+        for (uint32_t v = 0; v < passes.size(); v++) {
+            if (passes[v] >= 0) {
+                shadowViews.push_back(v);
+            } else if (base) {
+                check(gv_pool_emit_instances(ctx, p, &v, 1, nullptr, 0), "gv_pool_emit_instances");
+                check(gv_pool_instances_fetch(ctx, p, base, baseBytes, starts, GV_MAX_VIEWS + 1), "gv_pool_instances_fetch");
+                out.baseCount = starts[1];
+            }
+        }
+        if (shadow && !shadowViews.empty()) {
+            check(gv_pool_emit_instances(ctx, p, shadowViews.data(), (uint32_t)shadowViews.size(), nullptr, 0), "gv_pool_emit_instances");
+            check(gv_pool_instances_fetch(ctx, p, shadow, shadowBytes, starts, GV_MAX_VIEWS + 1), "gv_pool_instances_fetch");
+            // the listed views are the culled passes in pass order: spread their starts over all passes
+            uint32_t k = 0;
+            for (uint32_t s = 0; s < shadowPassCount; s++) {
+                out.shadowStart[s] = starts[k];
+                if (k < shadowViews.size() && (uint32_t)passes[shadowViews[k]] == s)
+                    k++;
+            }
+            out.shadowStart[shadowPassCount] = starts[shadowViews.size()];
+        }
+        return out;
+    }
+};
+
+}  // namespace garden

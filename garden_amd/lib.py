@@ -103,6 +103,10 @@ class GvPickHit(C.Structure):
 GV_MAX_PICK_RAYS = 8
 
 
+class GvInstanceLayout(C.Structure):
+    _fields_ = [("stride", C.c_uint32), ("mvp", C.c_uint32), ("model", C.c_uint32), ("slot", C.c_uint32), ("distance_sq", C.c_uint32)]
+
+
 class GvColumn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("stride", C.c_uint32)]
 
@@ -148,6 +152,7 @@ EXPORTS = [
     "gv_pool_results_fetch", "gv_pool_result_count", "gv_pool_results_device", "gv_pool_sort",
     "gv_cull_batch_begin", "gv_cull_batch_end", "gv_pool_set_record_layout", "gv_pool_results_records", "gv_pool_set_record_target",
     "gv_pool_results_instance_bases", "gv_profile_sampling", "gv_profile_samples", "gv_profile_kernels", "gv_pick",
+    "gv_pool_set_instance_layout", "gv_pool_emit_instances", "gv_pool_instances_device", "gv_pool_instances_info", "gv_pool_instances_fetch",
 ]
 
 _lib = None
@@ -258,6 +263,11 @@ def load():
     lib.gv_cull_batch_begin.argtypes = [P]
     lib.gv_cull_batch_end.argtypes = [P]
     lib.gv_pick.argtypes = [P, C.POINTER(u32), u32, C.POINTER(u32), C.POINTER(C.c_float), C.POINTER(GvPickRay), u32, C.POINTER(GvPickHit)]
+    lib.gv_pool_set_instance_layout.argtypes = [P, u32, C.POINTER(GvInstanceLayout)]
+    lib.gv_pool_emit_instances.argtypes = [P, u32, C.POINTER(u32), u32, P, sz]
+    lib.gv_pool_instances_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_pool_instances_info.argtypes = [P, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    lib.gv_pool_instances_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -628,6 +638,58 @@ class GpuVisibility:
         self._check(self.lib.gv_pick(self.ctx, ids, len(pool_ids), ex, cam, arr, len(r), hits))
         return [None if hits[k].pool_id == GV_NONE else (int(hits[k].pool_id), int(hits[k].slot), float(hits[k].distance_sq))
                 for k in range(len(r))]
+
+    # ---- instance data ----
+    def set_instance_layout(self, pool_id, stride=64, mvp=0, model=None, slot=None, distance_sq=None, dtype=None):
+        """gv_pool_set_instance_layout: the plugin's instance struct, by offsets (None: the struct has no such field) or as a numpy
+        structured `dtype` with the fields mvp (16 x f4) and optionally model (12 x f4), slot (u4), distanceSq (f4).
+        stride=None removes the layout."""
+        if dtype is not None:
+            dtype = np.dtype(dtype)
+            at = {name: dtype.fields[name][1] for name in dtype.names}
+            stride, mvp, model, slot, distance_sq = dtype.itemsize, at["mvp"], at.get("model"), at.get("slot"), at.get("distanceSq")
+        if stride is None:
+            self._check(self.lib.gv_pool_set_instance_layout(self.ctx, pool_id, None))
+            return
+        none = lambda x: GV_NONE if x is None else int(x)
+        layout = GvInstanceLayout(int(stride), int(mvp), none(model), none(slot), none(distance_sq))
+        self._check(self.lib.gv_pool_set_instance_layout(self.ctx, pool_id, C.byref(layout)))
+
+    def emit_instances(self, pool_id, views, device=None):
+        """gv_pool_emit_instances: the instance data of the listed views of `pool_id`, back to back, on the context's stream.
+        device: None for the library's own buffer, or (device pointer, capacity in bytes) of caller-owned device memory."""
+        idx = (C.c_uint32 * max(len(views), 1))(*[int(v) for v in views])
+        ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
+        self._check(self.lib.gv_pool_emit_instances(self.ctx, pool_id, idx, len(views), ptr, cap))
+
+    def instances_info(self, pool_id):
+        """(listed views, stride, instances the target holds) of the pool's last emission"""
+        views, stride, capacity = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._check(self.lib.gv_pool_instances_info(self.ctx, pool_id, C.byref(views), C.byref(stride), C.byref(capacity)))
+        return views.value, stride.value, capacity.value
+
+    def instances_device(self, pool_id):
+        """(device pointer of the instances, device pointer of uint32 starts[views + 1]) of the pool's last emission"""
+        inst, starts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_pool_instances_device(self.ctx, pool_id, C.byref(inst), C.byref(starts)))
+        return inst.value, starts.value
+
+    def instances(self, pool_id, out=None, dtype=None):
+        """gv_pool_instances_fetch: waits for the pool's last emission; returns (instances [total, stride] as uint8 — or viewed as
+        the structured `dtype` — and starts[views + 1]). out: the caller's own C-contiguous array to deliver into (only the layout's
+        fields are written: its other bytes stay); default a zero-filled one."""
+        views, stride, _ = self.instances_info(pool_id)
+        starts = np.zeros(views + 1, np.uint32)
+        sp = starts.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self.lib.gv_pool_instances_fetch(self.ctx, pool_id, None, 0, sp, len(starts)))
+        total = int(starts[views])
+        if out is None:
+            out = np.zeros((total, stride), np.uint8)
+        assert out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        self._check(self.lib.gv_pool_instances_fetch(self.ctx, pool_id, out.ctypes.data, out.nbytes, sp, len(starts)))
+        if dtype is not None:
+            out = out.reshape(-1).view(np.uint8)[:total * stride].view(np.dtype(dtype))
+        return out, starts
 
     # ---- world matrices ----
     def sweep(self, mode=GV_SWEEP_VALU):

@@ -340,6 +340,61 @@ int gv_pool_set_record_target(GvCtx* ctx, uint32_t pool_id, uint32_t view_index,
  * of the pool; fetches the results first if that has not happened yet. GV_E_STATE for a count-only view. */
 int gv_pool_results_instance_bases(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, const uint32_t** bases, uint32_t* count);
 
+/* ---- instance data: what every plugin's drawAsync writes first (sprite.cpp:107-108,122-126) ----
+ * `instanceData[instanceIndex].mvp = viewProj * model` for every draw of a view, on the device: the record's bakedModel completed
+ * with the bottom row (0,0,0,1) as mesh.cpp:596 does, multiplied from the left by the GvView::view_proj the view was culled with
+ * (the reference passes the same matrix to prepareMeshes and to the render loops, mesh.cpp:815,824-838). Arithmetic: DESIGN.md
+ * §4 item 9. Instance k of a view belongs to record k of that view as a fetch would deliver it at that moment (after
+ * gv_pool_sort: the sorted order); the instance index of draw k is k, because no system of the reference overrides
+ * getInstancesAsync (mesh.hpp:89 returns 1). The plugin's instance struct is described, not assumed (like GvRecordLayout):
+ * stride: bytes per instance, a multiple of 16, 64 ... 256; mvp: offset of the float4x4 (column-major, 64 bytes, 16-byte aligned),
+ * required; model: offset of a copy of the 12 bakedModel floats, or GV_NONE; slot: offset of a uint32 — the record's pool slot
+ * (index-mapped when the pool has an index map, as in gv_pick), what a device consumer needs to find the component's own data —
+ * or GV_NONE; distance_sq: offset of the record's float key, or GV_NONE. The optional fields are 4-byte aligned; fields lie inside
+ * the stride and do not overlap (GV_E_ARG otherwise). layout == NULL removes it. */
+typedef struct GvInstanceLayout {
+    uint32_t stride;
+    uint32_t mvp;
+    uint32_t model;
+    uint32_t slot;
+    uint32_t distance_sq;
+} GvInstanceLayout;
+int gv_pool_set_instance_layout(GvCtx* ctx, uint32_t pool_id, const GvInstanceLayout* layout);
+/* Instance data of the listed views of one pool, back to back in the order listed: view_indices[0]'s draws take instances
+ * [0, n0), the next view's [n0, n0 + n1), ... — one main-pass view for the base buffer; the shadow passes in pass order for the
+ * shadow buffer, which the reference fills pass after pass behind shadowInstanceIndex (instance.cpp:164,215). One kernel launch
+ * on gv_stream(ctx), asynchronous: the counts are read on the device, the host is not synchronised. Counts as a read: culls
+ * recorded since gv_cull_batch_begin and sorts that are still deferred are launched first.
+ * dst_device NULL: a library-owned device buffer (grown, never shrunk), valid until the next gv_cull of the pool.
+ * dst_device non-NULL: caller-owned device memory of capacity_bytes (16-byte aligned); instances that do not fit are not written
+ * and the true total is still reported. ONLY the bytes of the layout's fields are written — the rest of each instance belongs to
+ * the plugin (sprite.cpp:127-129 writes colour and uv next to mvp). The cull side is left as a read through
+ * gv_pool_results_device leaves it: recorded culls and deferred sorts have been launched (a small sorted pool with a record layout
+ * has then also published its records to the host, and the launches count in GvStats), no result changes.
+ * The library-owned buffer is sized for the sum of the listed views' OCCUPANCIES times the stride — the host does not know the
+ * counts without a synchronisation — and is never shrunk: four views of a 10^7-slot pool with a 128-byte layout are 5.1 GB for
+ * some 2 M records. Large pools should pass a caller-owned target sized for what they expect to draw; what does not fit is
+ * not written and the total says so.
+ * GV_E_ARG: an unbound pool, view_count 0 or above the views of the pool's last gv_cull, a view index of GV_MAX_VIEWS or more or
+ * listed twice, a misaligned dst_device. GV_E_STATE: no instance layout, a count-only view (emit_records == 0), a view with no results,
+ * an index map that does not cover the pool, or a ready column (gv_pool_bind_ready) that holds a live count above 1 — such a
+ * draw takes several instances, which needs a device scan of the counts (not available; counts of 0 / 1 work). */
+int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_indices, uint32_t view_count, void* dst_device,
+                           size_t capacity_bytes);
+/* Device pointers of the pool's last emission: the instances (dst_device, or the library's buffer) and uint32
+ * starts[view_count + 1] (starts[v] = first instance of listed view v, starts[view_count] = the total), both written in stream
+ * order on gv_stream(ctx). GV_E_STATE when the pool has no emission since its last gv_cull. */
+int gv_pool_instances_device(GvCtx* ctx, uint32_t pool_id, const void** instances, const void** starts);
+/* What the pool's last emission was made with (no synchronisation): the number of listed views, the layout's stride and the
+ * instances its target holds (any of the pointers may be NULL). GV_E_STATE when there is none since the pool's last gv_cull. */
+int gv_pool_instances_info(GvCtx* ctx, uint32_t pool_id, uint32_t* view_count, uint32_t* stride, uint32_t* capacity);
+/* Waits for the pool's last emission and delivers it to the host: starts[0 .. view_count] (starts_capacity >= view_count + 1) and
+ * — dst_host non-NULL — the instances into the caller's array (the engine's mapped instance buffer), field by field, so that the
+ * plugin's own bytes survive; they travel through the library's pinned staging, the caller's memory is never page-locked (the
+ * rule of gv_pool_set_record_target). GV_E_ARG when bytes < total * stride or starts_capacity is too small (nothing is written);
+ * instances the emission could not fit into a caller-owned device target are not delivered either. */
+int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* starts, uint32_t starts_capacity);
+
 /* A tick of engine-sized pools (the reference's everyday 10^3..10^4 entities per mesh system) is bound by launches,
  * not by bytes. Between gv_cull_batch_begin and the first call that reads results (gv_pool_results_* / gv_results_* /
  * gv_wait, or gv_cull_batch_end), gv_cull of a pool of up to 32768 slots whose views all emit records only RECORDS the
