@@ -62,7 +62,7 @@ void build_view_params(const GvView& v, ViewParams* out)
 int reserve_view(GvCtx* ctx, ViewState& vs, uint32_t occupancy, bool emit)
 {
     const size_t n = std::max<uint32_t>(occupancy, 1);
-    const size_t blocks = (n + kCullBlock - 1) / kCullBlock;
+    const size_t blocks = blocks_of((uint32_t)n);
     const size_t chunks = (n + kEmitChunk - 1) / kEmitChunk;
     GV_HIP(ctx, vs.mask.reserve(blocks * (kCullBlock / 64)));
     if (chunks > vs.chunk_count.cap) {
@@ -231,260 +231,293 @@ HizDevice hiz_device(const GvCtx* ctx)
     return hz;
 }
 
+// ---- the launches of one gv_cull: sweep, decide, upkeep of what is derived from the pool, cull, emit (cull_launch at the end) ----
+
+static void invalidate_views_beyond(GvCtx* ctx, uint32_t pool_id, uint32_t view_count)
+{
+    for (uint32_t v = view_count; v < GV_MAX_VIEWS; v++)
+        ctx->views[pool_id][v].valid = false;
+}
+
+// Which launches a gv_cull takes. Decided ONCE, before any upkeep, from what is known then; every later step reads it.
+struct CullPlan {
+    // batched: the views share a camera (gv_cull decides), ONE pass over the streams for all of them;
+    // emit_batched: ... and all of them want records, ONE self-prefixing emit launch for all of them
+    bool batched, emit_batched;
+    // fused: GV_SWEEP_WITH_CULL was asked for and the launch that culls view 0 writes the world matrices as well (further views of the
+    // call take the plain cull); patchable: entry i <-> transform entry i, no chains: boxes and seeds can follow a record of the changes
+    bool fused, patchable;
+    // Upkeep asked for; what the launches take is what is current after it. bounds_wanted: the listed cull behind block bounds (not
+    // current: the plain cull); hot_wanted: the single-view cull from the sphere stream; seeds_wanted: emits from seeds
+    bool bounds_wanted, hot_wanted, seeds_wanted;
+    // cull_emit: cull + emit in ONE launch, unless the listed cull is taken; self_prefix: emits derive the chunk bases themselves (no scan)
+    bool cull_emit, self_prefix;
+};
+
+static CullPlan plan_cull(const GvCtx* ctx, uint32_t pool_id, const TransformMirror& xf, uint32_t view_count, bool batched)
+{
+    const PoolState& p = ctx->pools[pool_id];
+    const bool exact = p.mapping == kMapExact, flat = xf.max_depth == 0, paired = exact && p.occupancy <= xf.count;
+    uint32_t emits = 0;  // views that want records
+    for (uint32_t v = 0; v < view_count; v++)
+        emits += ctx->views[pool_id][v].emitted;
+    const bool all_emit = emits == view_count;
+    CullPlan plan{};
+    plan.batched = batched && p.occupancy != 0;
+    plan.self_prefix = (p.occupancy + kEmitChunk - 1) / kEmitChunk <= kSelfPrefixMaxChunks;
+    plan.emit_batched = plan.batched && plan.self_prefix && all_emit;
+    // GV_SWEEP_WITH_CULL: an exactly paired pool takes the fused MFMA sweep + cull for its first view; anything else
+    // gets the same results from the plain MFMA sweep followed by the ordinary cull
+    plan.fused = ctx->sweep_with_cull && !plan.batched && p.occupancy != 0 && paired;
+    // (only pools whose boxes can then be patched — entry i <-> transform entry i, no chains —: any other would be rebuilt every frame)
+    plan.patchable = paired && flat;
+    plan.bounds_wanted = p.occupancy != 0 && !plan.fused &&
+                         ((ctx->config.flags & GV_CONFIG_BLOCK_BOUNDS) || (!(ctx->config.flags & GV_CONFIG_LINEAR_SCAN) && p.occupancy > kAutoBoundsMinSlots));
+    // The sphere stream of a flat, exactly paired pool (gv_kernels.hpp MeshMirror::hot), for the single-view cull that reads it
+    // (launch_cull; the one-launch cull + emit of small pools and the batched views read the full streams).
+    // Pools culled through block bounds go without: the blocks they examine lie in the frustum, where most lanes need corners anyway
+    // (measured at 10 M: the listed cull 54.4 -> 54.2 us, while patching the stream added 6 us to a frame with 10 movers).
+    plan.hot_wanted = !plan.batched && !plan.fused && !plan.bounds_wanted && p.occupancy > kHotMinSlots && exact && flat;
+    // emit seeds: a flat, exactly paired pool of some size whose views want records (gv_kernels.hpp)
+    plan.seeds_wanted = emits != 0 && !plan.batched && p.occupancy >= kEmitSeedMinSlots && plan.patchable;
+    // one view, records wanted, pool small enough for the look-back form to win: cull + emit in ONE launch
+    plan.cull_emit = !plan.batched && !plan.fused && view_count == 1 && all_emit && p.occupancy != 0 && p.occupancy <= kFusedEmitMaxSlots;
+    return plan;
+}
+
+// What is derived from a pool AT REST — block bounds, emit seeds — is (re)built when the pool's mirror is clean, or has just
+// changed after a quiet frame; a pool that changes frame after frame (dynamic scene) goes without
+// ... or keeps changing only a little (kMinSmallStreak syncs in a row that re-mirrored a few entries each): then it gets them
+// once more and they are patched from there on (block_bounds_ready).
+// Returns whether this cull may rebuild; the pool's state as of this cull is noted for the next one.
+static bool may_rebuild_at(PoolState& p, Stamp now, bool patchable)
+{
+    constexpr uint32_t kMinSmallStreak = 4;
+    const bool changed = !(p.seen_at == now);
+    const bool may_rebuild = !(changed && p.changed_prev) || (patchable && changed && p.small_streak >= kMinSmallStreak);
+    p.changed_prev = changed;
+    p.seen_at = now;
+    return may_rebuild;
+}
+
+// d_blk_dirty serves the boxes (kDirtyBounds) and the sphere stream (kDirtyHot): a fresh, cleared array no longer holds the OTHER
+// one's record of changes. The boxes' rebuild clears the array every time; the stream's only when the array is too small (stale
+// kDirtyHot bits only cost a re-derivation). The two (re)allocations below differ in that on purpose.
+//
+// The sphere stream (plan.hot_wanted): *hot = the pointer for MeshMirror::hot, or left null.
+// Current at every cull: what the syncs since the last one re-mirrored is flagged kDirtyHot and re-derived here (16 bytes
+// written per entry of a flagged block). Without such a record — a new mirror, growth, a re-order, a sync that rewrote much
+// of the pool — it is rebuilt over the whole pool, unless the pool changed at the cull before too: a pool rewritten frame
+// after frame culls from the full streams, as without the sphere stream, instead of paying a full pass every frame.
+static int hot_stream_ready(GvCtx* ctx, PoolState& p, const MeshMirror& mesh, const TransformMirror& xf, Stamp now, bool may_rebuild, const float4** hot)
+{
+    bool current = p.hot_at == now && p.d_hot.cap >= p.occupancy;
+    if (!current && p.hot_patch_valid && p.d_hot.cap >= p.occupancy && p.d_blk_dirty.ptr) {
+        GV_LAUNCH(ctx, GV_K_SWEEP, launch_hot_patch(mesh, xf, p.d_hot.ptr, p.d_blk_dirty.ptr, ctx->stream));
+        current = true;
+    }
+    if (!current && may_rebuild) {
+        GV_HIP(ctx, p.d_hot.reserve(p.occupancy));
+        const size_t flag_bytes = (blocks_of(p.occupancy) + 15) & ~(size_t)15;
+        if (flag_bytes > p.d_blk_dirty.cap) {  // (a fresh flag array: whatever the boxes had on record is gone with the old one)
+            GV_HIP(ctx, p.d_blk_dirty.reserve(flag_bytes));
+            GV_HIP(ctx, hipMemsetAsync(p.d_blk_dirty.ptr, 0, p.d_blk_dirty.cap, ctx->stream));
+            p.patch_valid = false;
+        }
+        GV_LAUNCH(ctx, GV_K_SWEEP, launch_hot_build(mesh, xf, p.d_hot.ptr, ctx->stream));
+        p.hot_patch_valid = true;  // from here on every sync flags what it re-mirrors (gv_mirror.cpp); stale kDirtyHot bits only cost a re-derivation
+        current = true;
+    }
+    if (current) {
+        p.hot_at = now;
+        *hot = p.d_hot.ptr;
+    }
+    return GV_OK;
+}
+
+// Block bounds (plan.bounds_wanted): *use_bounds = the boxes are current and the listed cull's buffers are sized.
+static int block_bounds_ready(GvCtx* ctx, PoolState& p, const MeshMirror& mesh, const TransformMirror& xf, Stamp now, bool may_rebuild, bool patchable, bool* use_bounds)
+{
+    bool current = p.bounds_at == now;
+    if (!current && p.patch_valid && patchable && p.d_blk_lo.ptr && p.d_blk_dirty.ptr) {
+        // every change since the boxes were current is on record (sync_mirror flagged the blocks): re-derive those blocks — and
+        // their entries' emit seeds when the seeds were in step with the boxes — instead of culling without boxes until the
+        // pool comes to rest (a scene in which a few entities move every frame never does)
+        const bool seeds_in_step = p.d_seed.ptr && p.d_seed.cap >= p.occupancy && p.seed_at == p.bounds_at;
+        GV_LAUNCH(ctx, GV_K_SWEEP, launch_block_patch(mesh, xf, p.d_blk_lo.ptr, p.d_blk_hi.ptr, seeds_in_step ? p.d_seed.ptr : nullptr, p.d_blk_dirty.ptr,
+                                                      ctx->stream));
+        if (seeds_in_step)
+            p.seed_at = now;
+        p.bounds_at = now;
+        current = true;
+    }
+    if (!current && may_rebuild) {
+        GV_HIP(ctx, p.d_blk_lo.reserve(blocks_of(p.occupancy)));
+        GV_HIP(ctx, p.d_blk_hi.reserve(blocks_of(p.occupancy)));
+        GV_HIP(ctx, p.d_blk_dirty.reserve((blocks_of(p.occupancy) + 15) & ~(size_t)15));
+        GV_HIP(ctx, hipMemsetAsync(p.d_blk_dirty.ptr, 0, p.d_blk_dirty.cap, ctx->stream));
+        p.hot_patch_valid = false;  // (whatever the sphere stream had on record is gone)
+        GV_LAUNCH(ctx, GV_K_SWEEP, launch_block_bounds(mesh, xf, p.d_blk_lo.ptr, p.d_blk_hi.ptr, ctx->stream));  // accounted with the other per-change passes
+        p.bounds_at = now;
+        p.patch_valid = patchable;  // from here on every sync records what it re-mirrors (gv_mirror.cpp mark_dirty_blocks)
+        current = true;
+    }
+    if (current) {
+        const size_t nb = blocks_of(p.occupancy);
+        GV_HIP(ctx, ctx->d_examined.reserve(nb));
+        const size_t list_words = 4 + nb * (cull_list_entry_bytes() / sizeof(uint32_t));
+        GV_HIP(ctx, p.d_kept_flag.reserve(nb));
+        if (list_words > p.d_kept.cap) {
+            GV_HIP(ctx, p.d_kept.reserve(list_words));
+            GV_HIP(ctx, hipMemsetAsync(p.d_kept.ptr, 0, 2 * sizeof(uint32_t), ctx->stream));
+            p.kept_parity = 0;
+        }
+        *use_bounds = true;
+    }
+    return GV_OK;
+}
+
+// Emit seeds (plan.seeds_wanted): *seeds = the pointer for the emits, or left null. (Kept current by block_bounds_ready's patch
+// while they are in step with the boxes; otherwise rebuilt when the pool is at rest.)
+static int emit_seeds_ready(GvCtx* ctx, PoolState& p, const MeshMirror& mesh, const TransformMirror& xf, Stamp now, bool may_rebuild, const EmitSeed** seeds)
+{
+    if (!(p.seed_at == now && p.d_seed.cap >= p.occupancy)) {
+        if (!may_rebuild)
+            return GV_OK;
+        GV_HIP(ctx, p.d_seed.reserve(p.occupancy));
+        GV_LAUNCH(ctx, GV_K_SWEEP, launch_emit_seeds(mesh, xf, p.d_seed.ptr, ctx->stream));
+        p.seed_at = now;
+    }
+    *seeds = p.d_seed.ptr;
+    return GV_OK;
+}
+
+// plan.cull_emit: the cull, the compaction and the records of one view in ONE launch (decoupled look-back over the cull's tiles)
+static int cull_emit_one_launch(GvCtx* ctx, ViewState& vs, const MeshMirror& mesh, const TransformMirror& xf, const HizDevice& hz, const ViewParams& vp, const ViewBuffers& vb)
+{
+    const uint32_t nb = blocks_of(mesh.count);
+    if (nb > vs.tile_status.cap || !vs.tile_ticket.ptr) {
+        GV_HIP(ctx, vs.tile_status.reserve(nb));
+        GV_HIP(ctx, vs.tile_ticket.reserve(1));
+        GV_HIP(ctx, hipMemsetAsync(vs.tile_status.ptr, 0, vs.tile_status.cap * sizeof(unsigned long long), ctx->stream));
+        GV_HIP(ctx, hipMemsetAsync(vs.tile_ticket.ptr, 0, sizeof(uint32_t), ctx->stream));
+        vs.tile_ticket_base = 0;
+        vs.tile_epoch = 0;
+    }
+    vs.ballots_current = false;
+    vs.vis_flags_current = false;  // cull_emit_kernel stores the bytes
+    vs.tile_epoch = vs.tile_epoch == UINT32_MAX ? 1u : vs.tile_epoch + 1u;
+    GV_LAUNCH(ctx, GV_K_CULL, launch_cull_emit(mesh, xf, hz, vp, vb, vs.tile_status.ptr, vs.tile_ticket.ptr, vs.tile_ticket_base, vs.tile_epoch, ctx->stream));
+    vs.tile_ticket_base += nb;
+    return GV_OK;
+}
+
+// Compaction and records of one view behind its cull (vb: its buffers as that cull saw them).
+static int emit_view(GvCtx* ctx, ViewState& vs, const MeshMirror& mesh, const TransformMirror& xf, const ViewParams& vp, const ViewBuffers& vb,
+                     bool self_prefix, const float4* emit_world, const EmitSeed* seeds)
+{
+    const uint32_t chunks = (mesh.count + kEmitChunk - 1) / kEmitChunk;
+    if (vs.emitted && self_prefix) {
+        // no scan launch: emit derives the chunk bases itself and leaves THIS totals buffer as it is; the
+        // next cull of this view adds into the other one, which this emit has cleared
+        if (int rc = emit_flags_ready(ctx, vs))
+            return rc;
+        const uint32_t clear = vs.turn_totals(chunks);
+        GV_LAUNCH(ctx, GV_K_EMIT, launch_emit(mesh, xf, vp, vb, ctx->stream, true, clear, emit_world, seeds));
+        return GV_OK;
+    }
+    GV_LAUNCH(ctx, GV_K_SCAN, launch_scan(vb, chunks, ctx->stream));
+    if (vs.emitted) {
+        vs.vis_flags_current = false;  // (the scan-path emit writes every byte and keeps no flags)
+        GV_LAUNCH(ctx, GV_K_EMIT, launch_emit(mesh, xf, vp, vb, ctx->stream, false, 0, emit_world, seeds));
+    }
+    return GV_OK;
+}
+
 // The launches of one gv_cull (views already reserved and marked valid by gv_cull): the sweep riding on it, block
 // bounds, the cull itself in the form that fits (fused sweep + cull, cull + emit in one launch, batched views, ...),
 // compaction and emission.
 int cull_launch(GvCtx* ctx, uint32_t pool_id, const ViewParams* vps, uint32_t view_count, bool batched)
 {
     PoolState& p = ctx->pools[pool_id];
-    MeshMirror mesh{p.d_a.ptr, p.d_b.ptr, p.d_link.ptr, p.occupancy, p.mapping, p.perm.empty() ? nullptr : p.d_orig.ptr, nullptr};
+    ViewState* views = ctx->views[pool_id];
+    MeshMirror mesh = mesh_mirror(p);
     const TransformMirror xf = xf_mirror(ctx);
     const HizDevice hz = hiz_device(ctx);
-    const uint32_t chunks = (p.occupancy + kEmitChunk - 1) / kEmitChunk;
     ViewBuffers vbs[GV_MAX_VIEWS];
     ViewParams cvps[GV_MAX_VIEWS];  // as the cull kernels see the views: isVisible bytes are left to the emit that follows
     for (uint32_t v = 0; v < view_count; v++) {
-        vbs[v] = view_buffers(ctx->views[pool_id][v]);
+        vbs[v] = view_buffers(views[v]);
         cvps[v] = vps[v];
-        if (ctx->views[pool_id][v].emitted)
+        if (views[v].emitted)
             cvps[v].write_is_visible = 0;
         if (cvps[v].write_is_visible)
-            ctx->views[pool_id][v].vis_flags_current = false;  // the cull stores the bytes itself
+            views[v].vis_flags_current = false;  // the cull stores the bytes itself
     }
+    const CullPlan plan = plan_cull(ctx, pool_id, xf, view_count, batched);
     int rc = GV_OK;
-    // GV_SWEEP_WITH_CULL: an exactly paired pool takes the fused MFMA sweep + cull for its first view; anything else
-    // gets the same results from the plain MFMA sweep followed by the ordinary cull
-    const bool sweep_requested = ctx->sweep_with_cull;
-    ctx->sweep_with_cull = false;
-    const bool fused = sweep_requested && !batched && p.occupancy != 0 && mesh.mapping == kMapExact && mesh.count <= xf.count;
-    if (sweep_requested) {
+    // GV_SWEEP_WITH_CULL: the sweep rides on this cull — in the cull launch of view 0 (plan.fused: it writes every slot of the same
+    // buffer), else as a launch of its own in front
+    if (ctx->sweep_with_cull) {
+        ctx->sweep_with_cull = false;
         GV_HIP(ctx, ctx->d_world.reserve((size_t)std::max(ctx->xf.occupancy, 1u) * 3));
-        if (!fused) {
-            KernelTimer t(ctx, GV_K_SWEEP);
-            if (ctx->sweep_with_cull_mfma)
-                GV_HIP(ctx, launch_sweep_mfma(xf, ctx->d_world.ptr, ctx->stream));
-            else
-                GV_HIP(ctx, launch_sweep_valu(xf, ctx->d_world.ptr, ctx->stream));
-        }
-        if ((rc = world_current(ctx)) != GV_OK)  // (the fused form below writes every slot of the same buffer)
+        if (!plan.fused && ctx->sweep_with_cull_mfma)
+            GV_LAUNCH(ctx, GV_K_SWEEP, launch_sweep_mfma(xf, ctx->d_world.ptr, ctx->stream));
+        else if (!plan.fused)
+            GV_LAUNCH(ctx, GV_K_SWEEP, launch_sweep_valu(xf, ctx->d_world.ptr, ctx->stream));
+        if ((rc = world_current(ctx)) != GV_OK)
             return rc;
     }
-    // What is derived from a pool AT REST — block bounds, emit seeds — is (re)built when the pool's mirror is clean, or has just
-    // changed after a quiet frame; a pool that changes frame after frame (dynamic scene) goes without
-    const bool changed = p.seen_epoch != p.epoch || p.seen_xf_epoch != ctx->xf_epoch;
-    // ... or keeps changing only a little (kMinSmallStreak syncs in a row that re-mirrored a few entries each): then it gets them
-    // once more and they are patched from there on (below)
-    constexpr uint32_t kMinSmallStreak = 4;
-    // (only pools whose boxes can then be patched — entry i <-> transform entry i, no chains —: any other would be rebuilt every frame)
-    const bool patchable = mesh.mapping == kMapExact && xf.max_depth == 0 && mesh.count <= xf.count;
-    const bool may_rebuild = !(changed && p.changed_prev) || (patchable && changed && p.small_streak >= kMinSmallStreak);
-    p.changed_prev = changed;
-    p.seen_epoch = p.epoch;
-    p.seen_xf_epoch = ctx->xf_epoch;
-    // The sphere stream of a flat, exactly paired pool (gv_kernels.hpp MeshMirror::hot), for the single-view cull that reads it
-    // (launch_cull; the one-launch cull + emit of small pools and the batched views read the full streams).
-    // Current at every cull: what the syncs since the last one re-mirrored is flagged kDirtyHot and re-derived here (16 bytes
-    // written per entry of a flagged block). Without such a record — a new mirror, growth, a re-order, a sync that rewrote much
-    // of the pool — it is rebuilt over the whole pool, unless the pool changed at the cull before too: a pool rewritten frame
-    // after frame culls from the full streams, as without the sphere stream, instead of paying a full pass every frame.
-    // Pools culled through block bounds go without: the blocks they examine lie in the frustum, where most lanes need corners anyway
-    // (measured at 10 M: the listed cull 54.4 -> 54.2 us, while patching the stream added 6 us to a frame with 10 movers).
-    const bool bounds_wanted = (ctx->config.flags & GV_CONFIG_BLOCK_BOUNDS) ||
-                               (!(ctx->config.flags & GV_CONFIG_LINEAR_SCAN) && p.occupancy > kAutoBoundsMinSlots);
-    if (!batched && !fused && !bounds_wanted && p.occupancy > kHotMinSlots && mesh.mapping == kMapExact && xf.max_depth == 0) {
-        bool current = p.hot_epoch == p.epoch && p.hot_xf_epoch == ctx->xf_epoch && p.d_hot.cap >= p.occupancy;
-        if (!current && p.hot_patch_valid && p.d_hot.cap >= p.occupancy && p.d_blk_dirty.ptr) {
-            KernelTimer t(ctx, GV_K_SWEEP);
-            GV_HIP(ctx, launch_hot_patch(mesh, xf, p.d_hot.ptr, p.d_blk_dirty.ptr, ctx->stream));
-            current = true;
-        }
-        if (!current && may_rebuild) {
-            const size_t nb = (p.occupancy + kCullBlock - 1) / kCullBlock, flag_bytes = (nb + 15) & ~(size_t)15;
-            GV_HIP(ctx, p.d_hot.reserve(p.occupancy));
-            if (flag_bytes > p.d_blk_dirty.cap) {  // (a fresh flag array: whatever the boxes had on record is gone with the old one)
-                GV_HIP(ctx, p.d_blk_dirty.reserve(flag_bytes));
-                GV_HIP(ctx, hipMemsetAsync(p.d_blk_dirty.ptr, 0, p.d_blk_dirty.cap, ctx->stream));
-                p.patch_valid = false;
-            }
-            KernelTimer t(ctx, GV_K_SWEEP);
-            GV_HIP(ctx, launch_hot_build(mesh, xf, p.d_hot.ptr, ctx->stream));
-            p.hot_patch_valid = true;  // from here on every sync flags what it re-mirrors (gv_mirror.cpp); stale kDirtyHot bits only cost a re-derivation
-            current = true;
-        }
-        if (current) {
-            p.hot_epoch = p.epoch;
-            p.hot_xf_epoch = ctx->xf_epoch;
-            mesh.hot = p.d_hot.ptr;
-        }
-    }
-    BlockBounds bounds;
+
+    // upkeep of what this call's launches read of the pool's derived state
+    const Stamp now{p.epoch, ctx->xf_epoch};
+    const bool may_rebuild = may_rebuild_at(p, now, plan.patchable);
     bool use_bounds = false;
-    if (bounds_wanted && p.occupancy != 0 && !fused) {
-        bool current = p.bounds_epoch == p.epoch && p.bounds_xf_epoch == ctx->xf_epoch;
-        if (!current && p.patch_valid && patchable && p.d_blk_lo.ptr && p.d_blk_dirty.ptr) {
-            // every change since the boxes were current is on record (sync_mirror flagged the blocks): re-derive those blocks — and
-            // their entries' emit seeds when the seeds were in step with the boxes — instead of culling without boxes until the
-            // pool comes to rest (a scene in which a few entities move every frame never does)
-            const bool seeds_in_step = p.d_seed.ptr && p.d_seed.cap >= p.occupancy && p.seed_epoch == p.bounds_epoch && p.seed_xf_epoch == p.bounds_xf_epoch;
-            KernelTimer t(ctx, GV_K_SWEEP);
-            GV_HIP(ctx, launch_block_patch(mesh, xf, p.d_blk_lo.ptr, p.d_blk_hi.ptr, seeds_in_step ? p.d_seed.ptr : nullptr, p.d_blk_dirty.ptr, ctx->stream));
-            if (seeds_in_step) {
-                p.seed_epoch = p.epoch;
-                p.seed_xf_epoch = ctx->xf_epoch;
-            }
-            p.bounds_epoch = p.epoch;
-            p.bounds_xf_epoch = ctx->xf_epoch;
-            current = true;
-        }
-        if (!current && may_rebuild) {
-            const size_t nb = (p.occupancy + kCullBlock - 1) / kCullBlock;
-            GV_HIP(ctx, p.d_blk_lo.reserve(nb));
-            GV_HIP(ctx, p.d_blk_hi.reserve(nb));
-            GV_HIP(ctx, p.d_blk_dirty.reserve((nb + 15) & ~(size_t)15));
-            GV_HIP(ctx, hipMemsetAsync(p.d_blk_dirty.ptr, 0, p.d_blk_dirty.cap, ctx->stream));
-            p.hot_patch_valid = false;  // (whatever the sphere stream had on record is gone)
-            KernelTimer t(ctx, GV_K_SWEEP);  // accounted with the other per-change passes
-            GV_HIP(ctx, launch_block_bounds(mesh, xf, p.d_blk_lo.ptr, p.d_blk_hi.ptr, ctx->stream));
-            p.bounds_epoch = p.epoch;
-            p.bounds_xf_epoch = ctx->xf_epoch;
-            p.patch_valid = patchable;  // from here on every sync records what it re-mirrors (gv_mirror.cpp mark_dirty_blocks)
-            current = true;
-        }
-        if (current) {
-            const size_t nb = (p.occupancy + kCullBlock - 1) / kCullBlock;
-            GV_HIP(ctx, ctx->d_examined.reserve(nb));
-            const size_t list_words = 4 + nb * (cull_list_entry_bytes() / sizeof(uint32_t));
-            GV_HIP(ctx, p.d_kept_flag.reserve(nb));
-            if (list_words > p.d_kept.cap) {
-                GV_HIP(ctx, p.d_kept.reserve(list_words));
-                GV_HIP(ctx, hipMemsetAsync(p.d_kept.ptr, 0, 2 * sizeof(uint32_t), ctx->stream));
-                p.kept_parity = 0;
-            }
-            use_bounds = true;
-        }
-    }
-    // emit seeds: a flat, exactly paired pool of some size whose views want records (gv_kernels.hpp)
     const EmitSeed* seeds = nullptr;
-    bool wants_records = false;
-    for (uint32_t v = 0; v < view_count; v++)
-        wants_records = wants_records || ctx->views[pool_id][v].emitted;
-    if (wants_records && !batched && p.occupancy >= kEmitSeedMinSlots && mesh.mapping == kMapExact && xf.max_depth == 0 &&
-        mesh.count <= xf.count) {
-        bool current = p.seed_epoch == p.epoch && p.seed_xf_epoch == ctx->xf_epoch && p.d_seed.cap >= p.occupancy;
-        if (!current && may_rebuild) {
-            GV_HIP(ctx, p.d_seed.reserve(p.occupancy));
-            KernelTimer t(ctx, GV_K_SWEEP);
-            GV_HIP(ctx, launch_emit_seeds(mesh, xf, p.d_seed.ptr, ctx->stream));
-            p.seed_epoch = p.epoch;
-            p.seed_xf_epoch = ctx->xf_epoch;
-            current = true;
-        }
-        if (current)
-            seeds = p.d_seed.ptr;
-    }
+    if ((plan.hot_wanted && (rc = hot_stream_ready(ctx, p, mesh, xf, now, may_rebuild, &mesh.hot)) != GV_OK) ||
+        (plan.bounds_wanted && (rc = block_bounds_ready(ctx, p, mesh, xf, now, may_rebuild, plan.patchable, &use_bounds)) != GV_OK) ||
+        (plan.seeds_wanted && (rc = emit_seeds_ready(ctx, p, mesh, xf, now, may_rebuild, &seeds)) != GV_OK))
+        return rc;
     // records take the resident world matrices when a sweep of the current mirror has written them (this call's fused
     // or leading sweep, or an earlier gv_sweep with no transform change since): same bits as the chain walk
     const float4* emit_world = (ctx->world_valid && !ctx->world_partial && ctx->max_depth != 0) ? ctx->d_world.ptr : nullptr;
-    if (p.occupancy != 0) {
-        if (use_bounds) {
-            bounds.lo = p.d_blk_lo.ptr;
-            bounds.hi = p.d_blk_hi.ptr;
-            bounds.examined = ctx->d_examined.ptr;
-            ctx->bounds_blocks_total = (p.occupancy + kCullBlock - 1) / kCullBlock;
+
+    // the launch form, final: the listed cull is taken if the boxes are current (use_bounds), and then rules out the one-launch form
+    const bool one_launch = plan.cull_emit && !use_bounds;
+    const BlockBounds bounds{p.d_blk_lo.ptr, p.d_blk_hi.ptr, ctx->d_examined.ptr};  // (handed on only under use_bounds)
+    if (use_bounds)
+        ctx->bounds_blocks_total = blocks_of(p.occupancy);
+    if (plan.batched)
+        GV_LAUNCH(ctx, GV_K_CULL, launch_cull_multi(mesh, xf, hz, cvps, vbs, view_count, ctx->stream, use_bounds ? &bounds : nullptr));
+    if (plan.emit_batched) {
+        uint32_t clear[GV_MAX_VIEWS];
+        for (uint32_t v = 0; v < view_count; v++) {
+            clear[v] = views[v].turn_totals((p.occupancy + kEmitChunk - 1) / kEmitChunk);
+            if ((rc = emit_flags_ready(ctx, views[v])) != GV_OK)
+                return rc;
         }
-        if (batched) {
-            KernelTimer t(ctx, GV_K_CULL);
-            GV_HIP(ctx, launch_cull_multi(mesh, xf, hz, cvps, vbs, view_count, ctx->stream, use_bounds ? &bounds : nullptr));
-        }
-        constexpr uint32_t self_max = kSelfPrefixMaxChunks;
-        // a batched cull whose views all want records: ONE self-prefixing emit launch for all of them
-        bool emit_batched = batched && chunks <= self_max;
-        for (uint32_t v = 0; v < view_count && emit_batched; v++)
-            emit_batched = ctx->views[pool_id][v].emitted;
-        if (emit_batched) {
-            uint32_t clear[GV_MAX_VIEWS];
-            for (uint32_t v = 0; v < view_count; v++) {
-                ViewState& vs = ctx->views[pool_id][v];
-                const uint32_t cur = vs.count_parity, other = cur ^ 1u;
-                clear[v] = std::max(chunks, vs.stale_chunks[other]);
-                vs.stale_chunks[other] = 0;
-                vs.stale_chunks[cur] = chunks;
-                vs.count_parity = other;
-                if ((rc = emit_flags_ready(ctx, vs)) != GV_OK)
-                    return rc;
-            }
-            KernelTimer t(ctx, GV_K_EMIT);
-            GV_HIP(ctx, launch_emit_batch(mesh, xf, vps, vbs, clear, view_count, ctx->stream, emit_world));
-        }
-        // one view, records wanted, pool small enough for the look-back form to win: cull + emit in ONE launch
-        if (!batched && !fused && !use_bounds && view_count == 1 && ctx->views[pool_id][0].emitted && p.occupancy <= kFusedEmitMaxSlots) {
-            ViewState& vs = ctx->views[pool_id][0];
-            const size_t nb = (p.occupancy + kCullBlock - 1) / kCullBlock;
-            if (nb > vs.tile_status.cap || !vs.tile_ticket.ptr) {
-                GV_HIP(ctx, vs.tile_status.reserve(nb));
-                GV_HIP(ctx, vs.tile_ticket.reserve(1));
-                GV_HIP(ctx, hipMemsetAsync(vs.tile_status.ptr, 0, vs.tile_status.cap * sizeof(unsigned long long), ctx->stream));
-                GV_HIP(ctx, hipMemsetAsync(vs.tile_ticket.ptr, 0, sizeof(uint32_t), ctx->stream));
-                vs.tile_ticket_base = 0;
-                vs.tile_epoch = 0;
-            }
-            vs.ballots_current = false;
-            vs.vis_flags_current = false;  // cull_emit_kernel stores the bytes
-            vs.tile_epoch = vs.tile_epoch == UINT32_MAX ? 1u : vs.tile_epoch + 1u;
-            {
-                KernelTimer t(ctx, GV_K_CULL);
-                GV_HIP(ctx, launch_cull_emit(mesh, xf, hz, vps[0], vbs[0], vs.tile_status.ptr, vs.tile_ticket.ptr, vs.tile_ticket_base,
-                                             vs.tile_epoch, ctx->stream));
-            }
-            vs.tile_ticket_base += (uint32_t)nb;
-            for (uint32_t v = view_count; v < GV_MAX_VIEWS; v++)
-                ctx->views[pool_id][v].valid = false;
-            return GV_OK;
-        }
-        for (uint32_t v = 0; v < view_count && !emit_batched; v++) {
-            if (!batched) {
-                KernelTimer t(ctx, GV_K_CULL);
-                // bounds: classify the workgroups first and cull the kept ones from a list
-                if (fused && v == 0)
-                    GV_HIP(ctx, launch_sweep_cull(mesh, xf, hz, cvps[v], vbs[v], ctx->d_world.ptr, ctx->sweep_with_cull_mfma, ctx->stream));
-                else if (use_bounds) {
+        GV_LAUNCH(ctx, GV_K_EMIT, launch_emit_batch(mesh, xf, vps, vbs, clear, view_count, ctx->stream, emit_world));
+    } else if (one_launch) {
+        if ((rc = cull_emit_one_launch(ctx, views[0], mesh, xf, hz, vps[0], vbs[0])) != GV_OK)
+            return rc;
+    } else if (p.occupancy != 0) {  // (an empty pool launches nothing: gv_cull has zeroed the draw counts)
+        for (uint32_t v = 0; v < view_count; v++) {
+            if (!plan.batched) {
+                if (plan.fused && v == 0)
+                    GV_LAUNCH(ctx, GV_K_CULL, launch_sweep_cull(mesh, xf, hz, cvps[v], vbs[v], ctx->d_world.ptr, ctx->sweep_with_cull_mfma, ctx->stream));
+                else if (use_bounds) {  // classify the workgroups first and cull the kept ones from a list
                     uint32_t* counters = p.d_kept.ptr;
-                    GV_HIP(ctx, launch_cull_listed(mesh, xf, hz, cvps[v], vbs[v], bounds, counters + p.kept_parity, counters + (p.kept_parity ^ 1u),
-                                                   counters + 4, p.d_kept_flag.ptr, ctx->stream));
+                    GV_LAUNCH(ctx, GV_K_CULL, launch_cull_listed(mesh, xf, hz, cvps[v], vbs[v], bounds, counters + p.kept_parity,
+                                                                 counters + (p.kept_parity ^ 1u), counters + 4, p.d_kept_flag.ptr, ctx->stream));
                     p.kept_parity ^= 1u;
-                } else {
-                    GV_HIP(ctx, launch_cull(mesh, xf, hz, cvps[v], vbs[v], ctx->stream));
-                }
+                } else
+                    GV_LAUNCH(ctx, GV_K_CULL, launch_cull(mesh, xf, hz, cvps[v], vbs[v], ctx->stream));
             }
-            if (ctx->views[pool_id][v].emitted && chunks <= self_max) {
-                // no scan launch: emit derives the chunk bases itself and leaves THIS totals buffer as it is; the
-                // next cull of this view adds into the other one, which this emit has cleared
-                ViewState& vs = ctx->views[pool_id][v];
-                const uint32_t cur = vs.count_parity, other = cur ^ 1u;
-                if ((rc = emit_flags_ready(ctx, vs)) != GV_OK)
-                    return rc;
-                {
-                    KernelTimer t(ctx, GV_K_EMIT);
-                    GV_HIP(ctx, launch_emit(mesh, xf, vps[v], vbs[v], ctx->stream, true, std::max(chunks, vs.stale_chunks[other]), emit_world, seeds));
-                }
-                vs.stale_chunks[other] = 0;
-                vs.stale_chunks[cur] = chunks;
-                vs.count_parity = other;
-                continue;
-            }
-            {
-                KernelTimer t(ctx, GV_K_SCAN);
-                GV_HIP(ctx, launch_scan(vbs[v], chunks, ctx->stream));
-            }
-            if (ctx->views[pool_id][v].emitted) {
-                ctx->views[pool_id][v].vis_flags_current = false;  // (the scan-path emit writes every byte and keeps no flags)
-                KernelTimer t(ctx, GV_K_EMIT);
-                GV_HIP(ctx, launch_emit(mesh, xf, vps[v], vbs[v], ctx->stream, false, 0, emit_world, seeds));
-            }
+            if ((rc = emit_view(ctx, views[v], mesh, xf, vps[v], vbs[v], plan.self_prefix, emit_world, seeds)) != GV_OK)
+                return rc;
         }
     }
-    for (uint32_t v = view_count; v < GV_MAX_VIEWS; v++)
-        ctx->views[pool_id][v].valid = false;
+    invalidate_views_beyond(ctx, pool_id, view_count);
     return GV_OK;  // (ctx->last_pool is gv_cull's to set: a recorded cull launched later — by a reader of ANOTHER pool's results — must not
                    // turn the view-indexed calls towards its own pool; round 4, found by tools/schedule_soak.py)
 }
@@ -526,27 +559,21 @@ int flush_culls(GvCtx* ctx)
     for (size_t k = 0; k < jobs.size(); k++) {
         const auto& j = jobs[k];
         PoolState& p = ctx->pools[j.pool_id];
-        const MeshMirror mesh{p.d_a.ptr, p.d_b.ptr, p.d_link.ptr, p.occupancy, p.mapping, p.perm.empty() ? nullptr : p.d_orig.ptr, nullptr};
+        const MeshMirror mesh = mesh_mirror(p);
         const uint32_t chunks = (p.occupancy + kEmitChunk - 1) / kEmitChunk;
         ViewBuffers vbs[GV_MAX_VIEWS];
-        for (uint32_t v = 0; v < j.view_count; v++)
-            vbs[v] = view_buffers(ctx->views[j.pool_id][v]);
         ViewParams cvps[GV_MAX_VIEWS];  // (every view of a recorded job emits records: the emit expands isVisible)
         for (uint32_t v = 0; v < j.view_count; v++) {
+            vbs[v] = view_buffers(ctx->views[j.pool_id][v]);
             cvps[v] = j.vps[v];
             cvps[v].write_is_visible = 0;
         }
         fill_cull_table_entry(host + cull_off + k * cull_bytes, mesh, xf, hz, cvps, vbs, j.view_count);
         for (uint32_t v = 0; v < j.view_count; v++) {
             ViewState& vs = ctx->views[j.pool_id][v];
-            const uint32_t cur = vs.count_parity, other = cur ^ 1u;
             if (int rc = emit_flags_ready(ctx, vs))
                 return rc;
-            fill_emit_table_entry(host + emit_off + (size_t)(e++) * emit_bytes, mesh, xf, j.vps[v], vbs[v],
-                                  std::max(chunks, vs.stale_chunks[other]), nullptr);
-            vs.stale_chunks[other] = 0;
-            vs.stale_chunks[cur] = chunks;
-            vs.count_parity = other;
+            fill_emit_table_entry(host + emit_off + (size_t)(e++) * emit_bytes, mesh, xf, j.vps[v], vbs[v], vs.turn_totals(chunks), nullptr);
         }
         max_slots = std::max(max_slots, p.occupancy);
     }
@@ -554,12 +581,8 @@ int flush_culls(GvCtx* ctx)
     GV_HIP(ctx, hipEventRecord(ctx->tick_done[turn], ctx->stream));
     {
         ZoneScope zone("Meshes Prepare");
-        {
-            KernelTimer t(ctx, GV_K_CULL);
-            GV_HIP(ctx, launch_cull_table(ctx->d_tick.ptr + cull_off, (uint32_t)jobs.size(), max_slots, ctx->stream));
-        }
-        KernelTimer t(ctx, GV_K_EMIT);
-        GV_HIP(ctx, launch_emit_table(ctx->d_tick.ptr + emit_off, emit_entries, max_slots, ctx->stream));
+        GV_LAUNCH(ctx, GV_K_CULL, launch_cull_table(ctx->d_tick.ptr + cull_off, (uint32_t)jobs.size(), max_slots, ctx->stream));
+        GV_LAUNCH(ctx, GV_K_EMIT, launch_emit_table(ctx->d_tick.ptr + emit_off, emit_entries, max_slots, ctx->stream));
     }
     return GV_OK;
 }
@@ -964,8 +987,7 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
             for (uint32_t v = 0; v < view_count; v++)
                 job.vps[v] = vps[v];
             ctx->cull_jobs.push_back(job);
-            for (uint32_t v = view_count; v < GV_MAX_VIEWS; v++)
-                ctx->views[pool_id][v].valid = false;
+            invalidate_views_beyond(ctx, pool_id, view_count);
             ctx->last_pool = pool_id;
             return GV_OK;
         }
@@ -1015,15 +1037,12 @@ int gv_sweep(GvCtx* ctx, uint32_t mode)
     const bool subtree = mode == GV_SWEEP_INCREMENTAL && ctx->world_valid && ctx->world_partial;
     if (!subtree)
         GV_HIP(ctx, ctx->d_world.reserve((size_t)std::max(n, 1u) * 3));
-    {
-        KernelTimer t(ctx, GV_K_SWEEP);
-        if (subtree)
-            GV_HIP(ctx, launch_sweep_subtree(xf_mirror(ctx), ctx->d_xdirty.ptr, ctx->d_world.ptr, ctx->stream));
-        else if (mode == GV_SWEEP_MFMA)
-            GV_HIP(ctx, launch_sweep_mfma(xf_mirror(ctx), ctx->d_world.ptr, ctx->stream));
-        else
-            GV_HIP(ctx, launch_sweep_valu(xf_mirror(ctx), ctx->d_world.ptr, ctx->stream));
-    }
+    if (subtree)
+        GV_LAUNCH(ctx, GV_K_SWEEP, launch_sweep_subtree(xf_mirror(ctx), ctx->d_xdirty.ptr, ctx->d_world.ptr, ctx->stream));
+    else if (mode == GV_SWEEP_MFMA)
+        GV_LAUNCH(ctx, GV_K_SWEEP, launch_sweep_mfma(xf_mirror(ctx), ctx->d_world.ptr, ctx->stream));
+    else
+        GV_LAUNCH(ctx, GV_K_SWEEP, launch_sweep_valu(xf_mirror(ctx), ctx->d_world.ptr, ctx->stream));
     return world_current(ctx);
 }
 
@@ -1252,7 +1271,7 @@ int gv_debug_stream_peak(GvCtx* ctx, uint32_t pool_id, uint32_t launches, double
     if (int rc = sync_mirror(ctx))
         return rc;
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    const MeshMirror mesh{p.d_a.ptr, p.d_b.ptr, p.d_link.ptr, p.occupancy, p.mapping, nullptr, nullptr};
+    const MeshMirror mesh{p.d_a.ptr, p.d_b.ptr, p.d_link.ptr, p.occupancy, p.mapping, nullptr, nullptr};  // (no `orig` on purpose: the probe reads the input streams only)
     const TransformMirror xf = xf_mirror(ctx);
     const uint32_t n = std::min(mesh.count, xf.count);
     *gb_per_s = 0.0;

@@ -173,6 +173,15 @@ struct TransformBinding {
     bool bound = false;
 };
 
+// What a piece of state derived from a pool's mirror (block boxes, sphere stream, emit seeds) was made from: the pool's epoch and the
+// transform mirror's. Current when equal to the pair of the moment (gv_context.cpp cull_launch).
+struct Stamp {
+    uint64_t epoch = 0, xf_epoch = 0;
+    bool operator==(const Stamp& o) const { return epoch == o.epoch && xf_epoch == o.xf_epoch; }
+};
+
+inline uint32_t blocks_of(uint32_t occupancy) { return (occupancy + kCullBlock - 1) / kCullBlock; }  // cull workgroups of a pool
+
 struct PoolState {
     Column entity, is_enabled, aabb_min, aabb_max;
     RecordLayout record_layout{};  // gv_pool_set_record_layout (stride 0: none)
@@ -221,29 +230,29 @@ struct PoolState {
     uint8_t* visible_base = nullptr;    // GV_RESULTS_MAP_VISIBLE: byte of slot i -> visible_base + h_index_map[i] * visible_stride
     size_t visible_stride = 0;
     uint32_t visible_count = 0;
-    // GV_CONFIG_BLOCK_BOUNDS: per-workgroup world boxes, valid for (bounds_xf_epoch, bounds_epoch)
+    // GV_CONFIG_BLOCK_BOUNDS: per-workgroup world boxes, valid for bounds_at
     DeviceBuf<float4> d_blk_lo, d_blk_hi;
     DeviceBuf<uint8_t> d_blk_dirty;  // one byte per block: holds an entry re-mirrored since the boxes (and seeds) were last current
     uint32_t small_streak = 0;       // syncs in a row that re-mirrored only a few entries of this pool (a pool that keeps changing a
                                      // little gets its boxes rebuilt once, then patched; one that keeps changing a lot goes without)
     bool patch_valid = false;        // every change of the mirror since then is recorded in d_blk_dirty (flat, exactly paired pools):
                                      // the next cull re-derives the flagged blocks instead of going without boxes
-    // the sphere stream (MeshMirror::hot; flat, exactly paired pools), valid for (hot_xf_epoch, hot_epoch); hot_patch_valid: every
+    // the sphere stream (MeshMirror::hot; flat, exactly paired pools), valid for hot_at; hot_patch_valid: every
     // change since then is flagged kDirtyHot in d_blk_dirty, so the next cull re-derives those blocks' entries
     DeviceBuf<float4> d_hot;
-    uint64_t hot_epoch = 0, hot_xf_epoch = 0;
+    Stamp hot_at;
     bool hot_patch_valid = false;
     bool recording() const { return patch_valid || hot_patch_valid; }  // some consumer wants this sync's changes flagged
     void stop_recording() { patch_valid = hot_patch_valid = false; }
-    DeviceBuf<EmitSeed> d_seed;    // emit seeds (gv_kernels.hpp), valid for (seed_xf_epoch, seed_epoch)
-    uint64_t seed_epoch = 0, seed_xf_epoch = 0;
+    DeviceBuf<EmitSeed> d_seed;    // emit seeds (gv_kernels.hpp), valid for seed_at
+    Stamp seed_at;
     DeviceBuf<uint32_t> d_kept;    // [2 alternating counters, 2 words of padding | list entries] of launch_cull_listed
     DeviceBuf<uint8_t> d_kept_flag;  // per list entry (Hi-Z views)
     uint32_t kept_parity = 0;      // which counter the next classify launch adds into
     uint32_t mirrored = 0, appended = 0;  // entries the mirror holds / of those, appended (unsorted) since the last full build
-    uint64_t epoch = 1, bounds_epoch = 0, bounds_xf_epoch = 0;  // epoch: bumped whenever this pool's mirror changes
-    uint64_t seen_epoch = 0, seen_xf_epoch = 0;                 // state at this pool's previous gv_cull
-    bool changed_prev = false;                                  // ... and whether it had changed then too (dynamic pool)
+    uint64_t epoch = 1;         // bumped whenever this pool's mirror changes
+    Stamp bounds_at, seen_at;   // seen_at: state at this pool's previous gv_cull
+    bool changed_prev = false;  // ... and whether it had changed then too (dynamic pool)
     // device mirror + pinned staging
     DeviceBuf<float4> d_a;
     DeviceBuf<float2> d_b;
@@ -258,6 +267,17 @@ struct ViewState {
     DeviceBuf<uint32_t> chunk_count, chunk_count2, chunk_offset, draw_count;
     uint32_t count_parity = 0;  // which totals buffer the next cull adds into (see launch_emit self_prefix)
     uint32_t stale_chunks[2] = {0, 0};  // entries of each totals buffer that may be non-zero right now
+    // One turn of the totals behind a cull of `chunks` chunks whose self-prefixing emit is about to be launched: that emit leaves the
+    // buffer the cull added into as it is and clears the other one, into which the next cull then adds. Returns how many entries of
+    // the other one it must clear. (view_buffers() of this cull is taken BEFORE the turn.)
+    uint32_t turn_totals(uint32_t chunks)
+    {
+        const uint32_t other = count_parity ^ 1u, clear = std::max(chunks, stale_chunks[other]);
+        stale_chunks[other] = 0;
+        stale_chunks[count_parity] = chunks;
+        count_parity = other;
+        return clear;
+    }
 
     DeviceBuf<uint8_t> is_visible;        // mirror order, written by the cull
     DeviceBuf<uint8_t> vis_flags;         // ViewBuffers::vis_flags: which quarter-chunks of is_visible may hold a non-zero
@@ -518,6 +538,9 @@ struct KernelTimer {
     }
 };
 
+// one launch, counted (and bracketed, when profiling asks for it) as kernel `k`; a failure returns like GV_HIP
+#define GV_LAUNCH(ctx, k, call) do { gv::KernelTimer timer__((ctx), (k)); GV_HIP((ctx), call); } while (0)
+
 // host worker threads for the gathers (AoS component pools -> SoA staging) and the isVisible write-back: gv_workers.hpp
 
 void drain_events(GvCtx* ctx);
@@ -540,5 +563,6 @@ int copy_shard_of_pool(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, void* 
 // gv_mirror.cpp
 int sync_mirror(GvCtx* ctx);                 // brings the device mirror up to date with the bound pools + dirty ranges
 TransformMirror xf_mirror(const GvCtx* ctx);  // the transform mirror as the kernels see it
+MeshMirror mesh_mirror(const PoolState& p);   // a pool's mirror likewise (hot: null; the sphere stream's upkeep in cull_launch sets it)
 
 }  // namespace gv

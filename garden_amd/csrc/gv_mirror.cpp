@@ -1446,4 +1446,9 @@ TransformMirror xf_mirror(const GvCtx* ctx)
     return m;
 }
 
+MeshMirror mesh_mirror(const PoolState& p)
+{
+    return MeshMirror{p.d_a.ptr, p.d_b.ptr, p.d_link.ptr, p.occupancy, p.mapping, p.perm.empty() ? nullptr : p.d_orig.ptr, nullptr};
+}
+
 }  // namespace gv

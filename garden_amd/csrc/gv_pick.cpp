@@ -56,11 +56,10 @@ int gv_pick(GvCtx* ctx, const uint32_t* pool_ids, uint32_t pool_count, const uin
     const TransformMirror xf = xf_mirror(ctx);
     for (uint32_t k = 0; k < pool_count; k++) {
         const PoolState& p = ctx->pools[pool_ids[k]];
-        const MeshMirror mesh{p.d_a.ptr, p.d_b.ptr, p.d_link.ptr, p.occupancy, p.mapping, p.perm.empty() ? nullptr : p.d_orig.ptr, nullptr};
         launch.order_bits = k << 28;
         launch.exclude = exclude_slots ? exclude_slots[k] : GV_NONE;
         launch.index_map = p.index_map_count ? p.d_index_map.ptr : nullptr;
-        GV_HIP(ctx, launch_pick(mesh, xf, launch, ctx->stream));
+        GV_HIP(ctx, launch_pick(mesh_mirror(p), xf, launch, ctx->stream));
     }
     GV_HIP(ctx, hipMemcpyAsync(ctx->h_pick_keys.ptr, ctx->d_pick_keys.ptr, ray_count * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                ctx->stream));
