@@ -695,6 +695,7 @@ void gv_destroy(GvCtx* ctx)
             release_record_target(target);
         p.d_a.release(); p.d_b.release(); p.d_link.release(); p.h_a.release(); p.h_b.release(); p.h_link.release(); p.d_orig.release(); p.d_inv.release(); p.d_index_map.release(); p.d_blk_lo.release(); p.d_blk_hi.release(); p.d_seed.release(); p.d_kept.release(); p.d_kept_flag.release(); p.d_blk_dirty.release(); p.d_hot.release();
         p.instances.d_data.release(); p.instances.d_starts.release(); p.instances.h_data.release(); p.instances.h_starts.release();
+        p.payload.d_rows.release(); p.payload.h_stage.release(); p.payload.d_packet.release();
     }
     for (auto& per_pool : ctx->views)
       for (auto& v : per_pool) {
@@ -872,6 +873,14 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
 {
     if (!ctx)
         return GV_E_ARG;
+    if (kind == GV_DIRTY_PAYLOAD) {  // (no cull reads the payload: what a batch has recorded stays recorded)
+        const uint32_t pool = first >> 28;
+        if (pool >= GV_MAX_POOLS)
+            return ctx->fail(GV_E_ARG, "gv_mark_dirty: pool id %u", pool);
+        if (ctx->pools[pool].payload.count)
+            ctx->pools[pool].payload.dirty.add(first & kSlotMask, count);
+        return GV_OK;
+    }
     if (int rc = flush_recorded_culls(ctx, kind == GV_DIRTY_MESH ? std::min(first >> 28, GV_MAX_POOLS - 1u) : GV_MAX_POOLS))
         return rc;
     switch (kind) {
@@ -891,6 +900,8 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
         if (pool >= GV_MAX_POOLS)
             return ctx->fail(GV_E_ARG, "gv_mark_dirty: pool id %u", pool);
         ctx->pools[pool].dirty.add(lo, count);
+        if (ctx->pools[pool].payload.count)  // a slot filled anew has a new payload
+            ctx->pools[pool].payload.dirty.add(lo, count);
         return GV_OK;
     }
     default:

@@ -207,7 +207,33 @@ struct PoolState {
         uint32_t capacity = 0;          // instances the target holds
         uint32_t views = 0;
         GvInstanceLayout emitted{};     // the layout it was made with
+        uint32_t emitted_payload = 0;   // ... and the payload fields it wrote: (at, bytes) each
+        uint32_t emitted_at[GV_MAX_PAYLOAD_FIELDS] = {}, emitted_bytes[GV_MAX_PAYLOAD_FIELDS] = {};
     } instances;
+    // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
+    // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
+    // transform mirror does not concern it); read by gv_pool_emit_instances only
+    struct Payload {
+        uint32_t count = 0;                        // fields (0: none bound)
+        Column src[GV_MAX_PAYLOAD_FIELDS];         // read only inside upload_payload
+        uint32_t bytes[GV_MAX_PAYLOAD_FIELDS] = {};
+        uint32_t offset[GV_MAX_PAYLOAD_FIELDS] = {};  // of the field inside a row (fields back to back)
+        uint32_t at[GV_MAX_PAYLOAD_FIELDS] = {GV_NONE, GV_NONE, GV_NONE, GV_NONE};  // destinations in the instance
+        uint32_t pitch = 0;                        // 16, 32 or 64: a row never straddles a 64-byte boundary
+        uint32_t occupancy = 0;
+        uint32_t mirrored = 0;                     // rows [0, mirrored) are on the device (0: everything is uploaded)
+        DirtyRanges dirty;                         // GV_DIRTY_PAYLOAD and GV_DIRTY_MESH marks of the pool
+        DeviceBuf<uint8_t> d_rows;
+        PinnedBuf<uint8_t> h_stage;                // the rows (and, behind them, the packet's slots) on their way up
+        DeviceBuf<uint8_t> d_packet;
+        bool any_destination() const
+        {
+            for (uint32_t f = 0; f < count; f++)
+                if (at[f] != GV_NONE)
+                    return true;
+            return false;
+        }
+    } payload;
     uint8_t* is_visible = nullptr;  // write-back target (NULL: none), element i at is_visible + i * is_visible_stride
     size_t is_visible_stride = 0;
     uint32_t occupancy = 0;
@@ -562,6 +588,7 @@ int copy_shard_of_pool(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, void* 
 
 // gv_mirror.cpp
 int sync_mirror(GvCtx* ctx);                 // brings the device mirror up to date with the bound pools + dirty ranges
+int upload_payload(GvCtx* ctx, PoolState& p);  // a pool's payload rows likewise (new slots + its own dirty set); sync_mirror calls it too
 TransformMirror xf_mirror(const GvCtx* ctx);  // the transform mirror as the kernels see it
 MeshMirror mesh_mirror(const PoolState& p);   // a pool's mirror likewise (hot: null; the sphere stream's upkeep in cull_launch sets it)
 

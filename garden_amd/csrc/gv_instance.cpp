@@ -3,6 +3,8 @@
 // drawAsync per draw, and every plugin starts with instanceData[instanceIndex].mvp = viewProj * model, sprite.cpp:107-108,122-126),
 // made on the device from the records a cull left there. One instance_kernel launch per call; buffers of its own (PoolState::
 // instances): the cull side is left as a read through gv_pool_results_device leaves it.
+// gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes a plugin copies next to mvp (sprite.cpp:127-129), mirrored
+// per pool slot (gv_mirror.cpp upload_payload) and written by the same launch (instance_kernel<true>).
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -14,7 +16,7 @@ struct Field {
 };
 
 // the layout's fields in the order mvp, model, slot, distance_sq; returns how many it has
-uint32_t fields_of(const GvInstanceLayout& L, Field (&f)[4])
+uint32_t fields_of(const GvInstanceLayout& L, Field* f)  // (room for four)
 {
     uint32_t n = 0;
     f[n++] = Field{L.mvp, 64, 16};
@@ -27,9 +29,99 @@ uint32_t fields_of(const GvInstanceLayout& L, Field (&f)[4])
     return n;
 }
 
+// the payload destinations `at` against the instance layout (stride 0: none yet — only each other): 4-byte aligned, inside the
+// stride, disjoint from one another and from the layout's fields
+bool payload_fits(const GvInstanceLayout& L, const PoolState::Payload& P, const uint32_t* at)
+{
+    Field f[4 + GV_MAX_PAYLOAD_FIELDS];
+    uint32_t n = L.stride ? fields_of(L, f) : 0;
+    for (uint32_t k = 0; k < P.count; k++) {
+        if (at[k] == GV_NONE)
+            continue;
+        if (at[k] % 4 != 0 || at[k] > kMaxInstanceStride || (L.stride && (at[k] > L.stride || P.bytes[k] > L.stride - at[k])))
+            return false;
+        for (uint32_t j = 0; j < n; j++)
+            if (!(at[k] + P.bytes[k] <= f[j].at || f[j].at + f[j].bytes <= at[k]))
+                return false;
+        f[n++] = Field{at[k], P.bytes[k], 4};
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gv_pool_bind_payload(GvCtx* ctx, uint32_t pool_id, const GvPayloadField* fields, uint32_t count, uint32_t occupancy)
+{
+    static_assert(GV_MAX_PAYLOAD_BYTES == 64 && GV_MAX_PAYLOAD_FIELDS == 4, "InstanceLaunch::piece_at / word_at describe a 64-byte row");
+    if (!ctx)
+        return GV_E_ARG;
+    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
+        return ctx->fail(GV_E_ARG, "gv_pool_bind_payload: pool %u is not bound", pool_id);
+    PoolState::Payload& P = ctx->pools[pool_id].payload;
+    if (count == 0) {  // removed, mirror freed (the stream may still be reading it)
+        GV_HIP(ctx, hipSetDevice(ctx->device));
+        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        P.d_rows.release();
+        P.h_stage.release();
+        P.d_packet.release();
+        P.dirty.clear();
+        P.count = P.occupancy = P.mirrored = P.pitch = 0;
+        std::fill(P.at, P.at + GV_MAX_PAYLOAD_FIELDS, GV_NONE);
+        return GV_OK;
+    }
+    if (count > GV_MAX_PAYLOAD_FIELDS || !fields)
+        return ctx->fail(GV_E_ARG, "gv_pool_bind_payload: %u fields (1 to %u, or 0 to remove the payload)", count, GV_MAX_PAYLOAD_FIELDS);
+    if (occupancy >= kSlotNone)
+        return ctx->fail(GV_E_ARG, "gv_pool_bind_payload: occupancy %u exceeds the 28-bit slot range", occupancy);
+    uint32_t sum = 0;
+    for (uint32_t f = 0; f < count; f++) {
+        const GvPayloadField& g = fields[f];
+        if (!g.data || g.bytes == 0 || g.bytes % 4 != 0 || g.bytes > 64 || g.stride < g.bytes)
+            return ctx->fail(GV_E_ARG, "gv_pool_bind_payload: field %u: data %p, %u bytes (4 to 64, a multiple of 4) every %u bytes (at least its size)",
+                             f, g.data, g.bytes, g.stride);
+        sum += g.bytes;
+    }
+    if (sum > GV_MAX_PAYLOAD_BYTES)
+        return ctx->fail(GV_E_ARG, "gv_pool_bind_payload: %u bytes per slot, at most %u", sum, GV_MAX_PAYLOAD_BYTES);
+    bool same = P.count == count && occupancy >= P.occupancy;
+    for (uint32_t f = 0; same && f < count; f++)
+        same = P.bytes[f] == fields[f].bytes;
+    if (!same) {  // another shape or a smaller occupancy: everything is uploaded
+        P.mirrored = 0;
+        P.dirty.clear();
+    }
+    P.count = count;
+    P.occupancy = occupancy;
+    P.pitch = sum <= 16 ? 16 : (sum <= 32 ? 32 : 64);
+    for (uint32_t f = 0, offset = 0; f < GV_MAX_PAYLOAD_FIELDS; f++) {
+        P.src[f] = f < count ? Column{static_cast<const uint8_t*>(fields[f].data), fields[f].stride} : Column{};
+        P.bytes[f] = f < count ? fields[f].bytes : 0;
+        P.offset[f] = offset;
+        offset += P.bytes[f];
+        P.at[f] = GV_NONE;
+    }
+    return GV_OK;
+}
+
+int gv_pool_set_payload_layout(GvCtx* ctx, uint32_t pool_id, const uint32_t* at, uint32_t count)
+{
+    if (!ctx)
+        return GV_E_ARG;
+    if (pool_id >= GV_MAX_POOLS)
+        return ctx->fail(GV_E_ARG, "gv_pool_set_payload_layout: pool %u out of range", pool_id);
+    PoolState& p = ctx->pools[pool_id];
+    if (!p.payload.count)
+        return ctx->fail(GV_E_STATE, "gv_pool_set_payload_layout: pool %u has no payload (gv_pool_bind_payload)", pool_id);
+    if (!at || count != p.payload.count)
+        return ctx->fail(GV_E_ARG, "gv_pool_set_payload_layout: %u destinations for the %u fields of pool %u", count, p.payload.count, pool_id);
+    if (!payload_fits(p.instances.layout, p.payload, at))
+        return ctx->fail(GV_E_ARG, "gv_pool_set_payload_layout: destinations must be 4-byte aligned, lie inside the instance (stride %u) and be "
+                         "disjoint from each other and from mvp / model / slot / distance_sq", p.instances.layout.stride);
+    std::copy(at, at + count, p.payload.at);  // read by the next emission
+    return GV_OK;
+}
 
 int gv_pool_set_instance_layout(GvCtx* ctx, uint32_t pool_id, const GvInstanceLayout* layout)
 {
@@ -55,6 +147,9 @@ int gv_pool_set_instance_layout(GvCtx* ctx, uint32_t pool_id, const GvInstanceLa
                              "model / slot / distance_sq at %u / %u / %u (4-byte aligned, 0x%x: none): fields must lie inside the instance and "
                              "be disjoint", L.stride, kMinInstanceStride, kMaxInstanceStride, L.mvp, L.model, L.slot, L.distance_sq, GV_NONE);
     }
+    if (layout && ctx->pools[pool_id].payload.count && !payload_fits(L, ctx->pools[pool_id].payload, ctx->pools[pool_id].payload.at))
+        return ctx->fail(GV_E_ARG, "gv_pool_set_instance_layout: the payload destinations of pool %u (gv_pool_set_payload_layout) do not fit "
+                         "this layout: they must lie inside the stride (%u) and be disjoint from mvp / model / slot / distance_sq", pool_id, L.stride);
     ctx->pools[pool_id].instances.layout = L;  // read by the next emission; an emission already made keeps the layout it was made with
     return GV_OK;
 }
@@ -96,6 +191,17 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
             return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: the index map of pool %u covers %u of its %u slots", pool_id, p.index_map_count,
                              vs->occupancy);
     }
+    const PoolState::Payload& P = p.payload;
+    const bool with_payload = P.count && P.any_destination();
+    if (with_payload) {
+        if (!payload_fits(L, P, P.at))
+            return ctx->fail(GV_E_ARG, "gv_pool_emit_instances: the payload destinations of pool %u do not fit its instance layout (stride %u)",
+                             pool_id, L.stride);
+        for (uint32_t k = 0; k < view_count; k++)
+            if (P.occupancy < view_of(ctx, pool_id, view_indices[k])->occupancy)
+                return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: the payload of pool %u covers %u of the %u slots view %u was culled with "
+                                 "(gv_pool_bind_payload)", pool_id, P.occupancy, view_of(ctx, pool_id, view_indices[k])->occupancy, view_indices[k]);
+    }
     if (p.ready.ptr && p.ready_many_count)
         return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: the ready column of pool %u holds %u live counts above 1: such a draw takes several "
                          "instances, and the instance index of draw k is k only while every draw takes one (ready counts of 0 / 1 work)",
@@ -104,6 +210,9 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
     if (int rc = flush_sorts(ctx))  // the emission is a read: recorded culls and deferred sorts first (as gv_pool_results_device)
         return rc;
     GV_HIP(ctx, hipSetDevice(ctx->device));
+    if (P.count)  // marks made since the cull are seen by this emission (the reference reads the component at draw time, mesh.cpp:592)
+        if (int rc = upload_payload(ctx, p))
+            return rc;
     InstanceLaunch launch{};
     uint64_t bound = 0;  // the host's upper bound of the total
     for (uint32_t k = 0; k < view_count; k++) {
@@ -134,6 +243,34 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
     }
     GV_HIP(ctx, I.d_starts.reserve(GV_MAX_VIEWS + 1));
     launch.starts = I.d_starts.ptr;
+    I.emitted_payload = 0;
+    if (with_payload) {
+        // where each word of a row goes; a 16-byte piece whose four words go to one 16-byte aligned place travels whole
+        launch.payload_rows = P.d_rows.ptr;
+        launch.payload_pitch = P.pitch;
+        std::fill(launch.piece_at, launch.piece_at + 4, kNoPayloadPlace);
+        std::fill(launch.word_at, launch.word_at + 16, kNoPayloadPlace);
+        uint32_t covered = 64;  // mvp
+        covered += (L.model != GV_NONE ? 48 : 0) + (L.slot != GV_NONE ? 4 : 0) + (L.distance_sq != GV_NONE ? 4 : 0);
+        for (uint32_t f = 0; f < P.count; f++) {
+            if (P.at[f] == GV_NONE)
+                continue;
+            for (uint32_t w = 0; w < P.bytes[f] / 4; w++)
+                launch.word_at[P.offset[f] / 4 + w] = (uint16_t)(P.at[f] + 4 * w);
+            covered += P.bytes[f];
+            I.emitted_at[I.emitted_payload] = P.at[f];
+            I.emitted_bytes[I.emitted_payload++] = P.bytes[f];
+        }
+        for (uint32_t j = 0; j < 4; j++) {
+            uint16_t* w = launch.word_at + 4 * j;
+            if (w[0] != kNoPayloadPlace && w[0] % 16 == 0 && w[1] == w[0] + 4 && w[2] == w[0] + 8 && w[3] == w[0] + 12) {
+                launch.piece_at[j] = w[0];
+                std::fill(w, w + 4, kNoPayloadPlace);
+            }
+        }
+        // fields and payload are disjoint and inside the stride: together as many bytes as the stride = all of it
+        launch.staged = covered == L.stride && L.stride <= kMaxStagedInstanceStride;
+    }
     GV_HIP(ctx, launch_instances(launch, ctx->stream));
     I.target = launch.dst;
     I.capacity = launch.capacity;
@@ -202,8 +339,10 @@ int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t
     GV_HIP(ctx, I.h_data.reserve((size_t)held * L.stride));
     GV_HIP(ctx, hipMemcpyAsync(I.h_data.ptr, I.target, (size_t)held * L.stride, hipMemcpyDeviceToHost, ctx->stream));
     GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    Field f[4];
-    const uint32_t n = fields_of(L, f);
+    Field f[4 + GV_MAX_PAYLOAD_FIELDS];
+    uint32_t n = fields_of(L, f);
+    for (uint32_t k = 0; k < I.emitted_payload; k++)  // the payload fields the emission wrote
+        f[n++] = Field{I.emitted_at[k], I.emitted_bytes[k], 4};
     uint8_t* const to = static_cast<uint8_t*>(dst_host);
     const uint8_t* const from = I.h_data.ptr;
     parallel_ranges(0, held, [&](uint32_t a, uint32_t b) {

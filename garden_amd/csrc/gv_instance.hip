@@ -12,7 +12,26 @@
 //                     stride 64 and only mvp a wave writes 4 KB contiguous, 1 KB per store instruction (a lane storing its own
 //                     64 bytes would touch 64 lines per instruction). The optional fields are stored by the record's own lane.
 //
-// Only the bytes of the layout's fields are written; instances at or beyond `capacity` are not written at all.
+//   instance_kernel<true>   the same with the pool's payload (gv_pool_bind_payload): launched only when a payload destination is set.
+//                     The lane loads the record's slot first and gathers the slot's packed row (16, 32 or 64 bytes: one sector)
+//                     with 16-byte loads — the one dependent load of the kernel, issued in front of the mvp arithmetic so that the
+//                     fma chains cover it. Where each 16-byte piece / each word of the row goes is a table the host made
+//                     (piece_at / word_at, wave-uniform): no register is indexed dynamically. Two ways out:
+//                       staged   the layout's fields and the payload cover the whole stride (the sprite struct: mvp 0, colour 64,
+//                                uv 80, stride 96): every lane builds its WHOLE instance in LDS (256 x stride bytes, stride <= 128),
+//                                then consecutive lanes store consecutive 16-byte pieces — the launch writes whole lines by
+//                                itself, which is what makes the nontemporal stores right.
+//                                Image layout: linear, piece q of the workgroup at byte 16 q, so that the way out (ds_read_b128,
+//                                banks of 256 B) is conflict-free and needs no division by the piece count. On the way in
+//                                (ds_write_b128: groups of 8 consecutive lanes, banks of 128 B) lanes are `stride` bytes apart:
+//                                conflict-free at stride 80 and 112, 2-way at 96 (16 array cycles against the 13 the store's
+//                                operand transfer takes anyway), and 8-way at 128 — there the piece index is XORed with the
+//                                instance's low three bits, which makes both directions conflict-free.
+//                       direct   otherwise: mvp as in instance_kernel<false>, the payload stored by the record's own lane with plain
+//                                stores like the optional fields.
+//
+// Only the bytes of the layout's fields and of the payload destinations are written; instances at or beyond `capacity` are not
+// written at all. The payload is opaque: moved as bit patterns (no arithmetic touches it), NaNs and -0 included.
 #include "gv_device.hpp"
 
 namespace gv {
@@ -21,9 +40,31 @@ namespace gv {
 // (4 instances x 4 columns on the way out, 16 instances x 1 column on the way in) cover the 16 slots of a bank row
 __device__ __forceinline__ uint32_t stage_slot(uint32_t i, uint32_t c) { return i * 4u + ((c + (i >> 2)) & 3u); }
 
+// the row's pieces and words to where the host's tables send them; put4(offset, float4) / put1(offset, float) write into the instance
+template <typename Put4, typename Put1>
+__device__ __forceinline__ void place_payload(const InstanceLaunch& a, const float4 (&row)[4], Put4 put4, Put1 put1)
+{
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        if (a.piece_at[j] != kNoPayloadPlace) {
+            put4(a.piece_at[j], row[j]);
+        } else {
+            if (a.word_at[4 * j] != kNoPayloadPlace)
+                put1(a.word_at[4 * j], row[j].x);
+            if (a.word_at[4 * j + 1] != kNoPayloadPlace)
+                put1(a.word_at[4 * j + 1], row[j].y);
+            if (a.word_at[4 * j + 2] != kNoPayloadPlace)
+                put1(a.word_at[4 * j + 2], row[j].z);
+            if (a.word_at[4 * j + 3] != kNoPayloadPlace)
+                put1(a.word_at[4 * j + 3], row[j].w);
+        }
+    }
+}
+
+template <bool kPayload>
 __global__ __launch_bounds__(kInstanceBlock) void instance_kernel(const InstanceLaunch a)
 {
-    __shared__ float4 stage[kInstanceBlock * 4];
+    __shared__ float4 stage[kInstanceBlock * (kPayload ? kMaxStagedInstanceStride / 16 : 4)];
     // workgroup-uniform: this workgroup's view, the instances in front of it, the total
     uint32_t v = 0, base = 0;
 #pragma unroll
@@ -50,11 +91,65 @@ __global__ __launch_bounds__(kInstanceBlock) void instance_kernel(const Instance
     const uint32_t k = first + threadIdx.x;
     const bool live = k < n;
     float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0, r2 = r0;
+    [[maybe_unused]] uint32_t own_slot = 0;
+    [[maybe_unused]] float4 row[4] = {r0, r0, r0, r0};
     if (live) {
+        if constexpr (kPayload)
+            own_slot = stream_load(vw.idx + k);
         const float4* rows = reinterpret_cast<const float4*>(vw.model) + (size_t)k * 3;
         r0 = stream_load(rows);
         r1 = stream_load(rows + 1);
         r2 = stream_load(rows + 2);
+        if constexpr (kPayload) {  // (a gather: plain loads — the shadow passes' records name the same rows again)
+            const float4* from = reinterpret_cast<const float4*>(a.payload_rows + (size_t)own_slot * a.payload_pitch);
+            row[0] = from[0];
+            if (a.payload_pitch > 16u)
+                row[1] = from[1];
+            if (a.payload_pitch > 32u) {
+                row[2] = from[2];
+                row[3] = from[3];
+            }
+        }
+    }
+    if constexpr (kPayload) {
+        if (a.staged) {  // (wave-uniform) the whole instance through LDS, whole lines out
+            const uint32_t rot = a.stride == 128u ? 7u : 0u;
+            uint8_t* const mine = reinterpret_cast<uint8_t*>(stage) + threadIdx.x * a.stride;
+            const uint32_t turn = threadIdx.x & rot;
+            auto put4 = [&](uint32_t o, float4 v) { *reinterpret_cast<float4*>(mine + (((o >> 4) ^ turn) << 4)) = v; };
+            auto put1 = [&](uint32_t o, float v) { *reinterpret_cast<float*>(mine + (((o >> 4) ^ turn) << 4) + (o & 15u)) = v; };
+            put4(a.mvp, mvp_column(vw.view_proj, r0.x, r0.y, r0.z, 0.0f));
+            put4(a.mvp + 16u, mvp_column(vw.view_proj, r0.w, r1.x, r1.y, 0.0f));
+            put4(a.mvp + 32u, mvp_column(vw.view_proj, r1.z, r1.w, r2.x, 0.0f));
+            put4(a.mvp + 48u, mvp_column(vw.view_proj, r2.y, r2.z, r2.w, 1.0f));
+            if (a.model != kNoField) {
+                if ((a.model & 15u) == 0) {
+                    put4(a.model, r0);
+                    put4(a.model + 16u, r1);
+                    put4(a.model + 32u, r2);
+                } else {
+                    put1(a.model, r0.x); put1(a.model + 4u, r0.y); put1(a.model + 8u, r0.z); put1(a.model + 12u, r0.w);
+                    put1(a.model + 16u, r1.x); put1(a.model + 20u, r1.y); put1(a.model + 24u, r1.z); put1(a.model + 28u, r1.w);
+                    put1(a.model + 32u, r2.x); put1(a.model + 36u, r2.y); put1(a.model + 40u, r2.z); put1(a.model + 44u, r2.w);
+                }
+            }
+            if (a.slot != kNoField)
+                put1(a.slot, __uint_as_float(live && a.index_map ? a.index_map[own_slot] : own_slot));
+            if (a.distance_sq != kNoField)
+                put1(a.distance_sq, live ? __uint_as_float(stream_load(reinterpret_cast<const uint32_t*>(vw.dist) + k)) : 0.0f);
+            place_payload(a, row, put4, put1);
+            __syncthreads();
+            const uint32_t pieces = a.stride >> 4;  // per instance: 5 .. 8
+            const uint32_t room = min(min(kInstanceBlock, n - first), a.capacity - (base + first)) * pieces;
+            float4* const out = reinterpret_cast<float4*>(a.dst + (size_t)(base + first) * a.stride);
+#pragma unroll
+            for (uint32_t j = 0; j < kMaxStagedInstanceStride / 16; j++) {
+                const uint32_t q = j * kInstanceBlock + threadIdx.x;
+                if (q < room)
+                    stream_store(out + q, stage[q ^ ((q >> 3) & rot)]);
+            }
+            return;
+        }
     }
     // bakedModel: c0 = (r0.x r0.y r0.z), c1 = (r0.w r1.x r1.y), c2 = (r1.z r1.w r2.x), c3 = (r2.y r2.z r2.w); bottom row 0 0 0 1
     stage[stage_slot(threadIdx.x, 0)] = mvp_column(vw.view_proj, r0.x, r0.y, r0.z, 0.0f);
@@ -95,8 +190,13 @@ __global__ __launch_bounds__(kInstanceBlock) void instance_kernel(const Instance
             to[8] = r2.x; to[9] = r2.y; to[10] = r2.z; to[11] = r2.w;
         }
     }
+    if constexpr (kPayload) {
+        auto put4 = [&](uint32_t o, float4 v) { *reinterpret_cast<float4*>(inst + o) = v; };
+        auto put1 = [&](uint32_t o, float v) { *reinterpret_cast<float*>(inst + o) = v; };
+        place_payload(a, row, put4, put1);
+    }
     if (a.slot != kNoField) {
-        uint32_t slot = stream_load(vw.idx + k);
+        uint32_t slot = kPayload ? own_slot : stream_load(vw.idx + k);
         if (a.index_map)
             slot = a.index_map[slot];
         *reinterpret_cast<uint32_t*>(inst + a.slot) = slot;
@@ -108,7 +208,10 @@ __global__ __launch_bounds__(kInstanceBlock) void instance_kernel(const Instance
 hipError_t launch_instances(const InstanceLaunch& launch, hipStream_t stream)
 {
     const dim3 grid(std::max(1u, launch.first_block[launch.views])), block(kInstanceBlock);  // (no record at all: starts[] still)
-    hipLaunchKernelGGL(instance_kernel, grid, block, 0, stream, launch);
+    if (launch.payload_rows)  // (set only when a payload destination is: everything else runs the kernel it always ran)
+        hipLaunchKernelGGL(instance_kernel<true>, grid, block, 0, stream, launch);
+    else
+        hipLaunchKernelGGL(instance_kernel<false>, grid, block, 0, stream, launch);
     return hipGetLastError();
 }
 

@@ -212,7 +212,15 @@ struct InstanceLaunch {
     uint8_t* dst;
     uint32_t capacity;                               // instances dst holds: those at or beyond it are not written
     uint32_t* starts;                                // [views + 1], written by workgroup 0
+    // the pool's payload (gv_pool_bind_payload); payload_rows NULL: none, instance_kernel<false> is launched and reads none of this
+    const uint8_t* payload_rows;                     // one packed row per POOL SLOT (the record's visible_idx, never index-mapped)
+    uint32_t payload_pitch;                          // 16, 32 or 64
+    uint32_t staged;                                 // fields + payload cover the whole stride (<= kMaxStagedInstanceStride): built in LDS
+    uint16_t piece_at[4];                            // 16-byte piece j of the row -> a 16-byte aligned offset in the instance, or
+    uint16_t word_at[16];                            // word w of the row -> its offset (kNoPayloadPlace: not written)
 };
+constexpr uint16_t kNoPayloadPlace = 0xFFFFu;
+constexpr uint32_t kMaxStagedInstanceStride = 128;   // 256 x 128 B = 32 KB of LDS per workgroup
 hipError_t launch_instances(const InstanceLaunch& launch, hipStream_t stream);
 // read-only pass over the cull kernel's input streams (65 B per entry); gv_debug_stream_peak
 hipError_t launch_stream_probe(const MeshMirror& mesh, const TransformMirror& xf, float* sink, hipStream_t stream);

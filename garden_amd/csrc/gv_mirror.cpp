@@ -1047,6 +1047,80 @@ int mark_dirty_blocks(GvCtx* ctx, PoolState& p, const std::vector<DirtyRanges::R
 
 }  // namespace
 
+// The payload rows of a pool (gv_pool_bind_payload): slots appended since the last upload plus the pool's payload dirty set, gathered
+// from the bound fields into packed rows. Ranges of kPayloadCopyMinRows rows or more travel as contiguous copies into their place;
+// everything smaller travels the way small mirror edits do: ONE packet [rows | slots] and ONE scatter launch.
+constexpr uint32_t kPayloadCopyMinRows = 2048;
+int upload_payload(GvCtx* ctx, PoolState& p)
+{
+    PoolState::Payload& P = p.payload;
+    if (!P.count)
+        return GV_OK;
+    P.dirty.normalise(P.mirrored, 0);  // (rows at or beyond `mirrored` are uploaded as new ones below)
+    std::vector<DirtyRanges::R> ranges = P.dirty.items;
+    if (P.mirrored < P.occupancy)
+        ranges.push_back({P.mirrored, P.occupancy});
+    P.dirty.clear();
+    if (ranges.empty())
+        return GV_OK;
+    const uint32_t kept = P.mirrored;
+    P.mirrored = 0;  // (a failure below leaves the rows unknown: the next upload takes everything)
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t pitch = P.pitch;
+    GV_HIP(ctx, P.d_rows.grow((size_t)P.occupancy * pitch, (size_t)kept * pitch, ctx->stream));
+    size_t copied = 0, packed = 0;  // rows that travel as copies / in the packet
+    for (const auto& r : ranges)
+        (r.hi - r.lo >= kPayloadCopyMinRows ? copied : packed) += r.hi - r.lo;
+    const size_t stage_bytes = (copied + packed) * pitch + packed * 4, packet_bytes = packed * (pitch + 4);
+    if (stage_bytes > P.h_stage.cap || packet_bytes > P.d_packet.cap) {  // (buffers about to be replaced: nothing queued may still use them)
+        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GV_HIP(ctx, P.h_stage.reserve(std::max<size_t>(stage_bytes + stage_bytes / 2, 4096)));
+        GV_HIP(ctx, P.d_packet.reserve(std::max<size_t>(packet_bytes + packet_bytes / 2, 4096)));
+    }
+    if (int rc = wait_uploads(ctx))  // the previous upload's copies have read the staging
+        return rc;
+    uint8_t* const stage = P.h_stage.ptr;
+    uint8_t* const packet_rows = stage + copied * pitch;
+    uint32_t* const packet_slots = reinterpret_cast<uint32_t*>(packet_rows + packed * pitch);
+    auto gather = [&](uint8_t* rows, uint32_t* slots, uint32_t lo, uint32_t hi) {
+        parallel_ranges(0, hi - lo, [&](uint32_t a, uint32_t b) {
+            for (uint32_t k = a; k < b; k++) {
+                uint8_t* row = rows + (size_t)k * pitch;
+                uint32_t end = 0;
+                for (uint32_t f = 0; f < P.count; f++) {
+                    memcpy(row + P.offset[f], P.src[f].at(lo + k), P.bytes[f]);  // verbatim: the bytes are opaque
+                    end = P.offset[f] + P.bytes[f];
+                }
+                memset(row + end, 0, pitch - end);
+                if (slots)
+                    slots[k] = lo + k;
+            }
+        });
+    };
+    size_t copy_at = 0, pack_at = 0;
+    for (const auto& r : ranges) {
+        const uint32_t n = r.hi - r.lo;
+        if (n >= kPayloadCopyMinRows) {
+            gather(stage + copy_at * pitch, nullptr, r.lo, r.hi);
+            GV_HIP(ctx, hipMemcpyAsync(P.d_rows.ptr + (size_t)r.lo * pitch, stage + copy_at * pitch, (size_t)n * pitch, hipMemcpyHostToDevice, ctx->stream));
+            copy_at += n;
+        } else {
+            gather(packet_rows + pack_at * pitch, packet_slots + pack_at, r.lo, r.hi);
+            pack_at += n;
+        }
+    }
+    if (packed) {
+        GV_HIP(ctx, hipMemcpyAsync(P.d_packet.ptr, packet_rows, packet_bytes, hipMemcpyHostToDevice, ctx->stream));
+        GV_HIP(ctx, launch_scatter_payload_rows(P.d_packet.ptr, reinterpret_cast<const uint32_t*>(P.d_packet.ptr + packed * pitch), (uint32_t)packed,
+                                                (uint32_t)pitch, P.d_rows.ptr, ctx->stream));
+    }
+    if (int rc = record_uploads(ctx))  // the staging is reused by the next upload: it waits for this
+        return rc;
+    ctx->stats.upload_bytes += stage_bytes;
+    P.mirrored = P.occupancy;
+    return GV_OK;
+}
+
 int sync_mirror(GvCtx* ctx)
 {
     PhaseTimer phase;
@@ -1386,6 +1460,10 @@ int sync_mirror(GvCtx* ctx)
     if (staged)  // whatever copies this sync queued from the pinned staging arrays: the next sync waits for them before it rewrites those
         if (int rrc = record_uploads(ctx))
             return rrc;
+    for (auto& p : ctx->pools)  // (staging of their own; no cull reads them)
+        if (p.bound && p.payload.count)
+            if (int prc = upload_payload(ctx, p))
+                return prc;
     // the re-order itself, behind everything that brought the mirror up to date in its old order
     bool any_reorder = reorder_xf;
     for (bool b : reorder_pool)

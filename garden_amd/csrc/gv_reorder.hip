@@ -239,7 +239,26 @@ __global__ __launch_bounds__(kThreads) void scatter_mesh_packets_kernel(const Me
         block_flags[p.entry / kCullBlock] = kDirtyAll;
 }
 
+__global__ __launch_bounds__(kThreads) void scatter_payload_rows_kernel(const float4* __restrict__ packet, const uint32_t* __restrict__ slots,
+                                                                        uint32_t pieces, uint32_t shift, float4* __restrict__ rows)
+{
+    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;  // piece t of the packet: 16 bytes of row t >> shift
+    if (t >= pieces)
+        return;
+    rows[((size_t)slots[t >> shift] << shift) + (t & ((1u << shift) - 1u))] = packet[t];
+}
+
 }  // namespace
+
+hipError_t launch_scatter_payload_rows(const uint8_t* packet, const uint32_t* slots, uint32_t count, uint32_t pitch, uint8_t* rows,
+                                       hipStream_t stream)
+{
+    const uint32_t shift = pitch == 64u ? 2u : (pitch == 32u ? 1u : 0u);  // 16-byte pieces per row: 4, 2 or 1
+    if (count)
+        hipLaunchKernelGGL(scatter_payload_rows_kernel, grid_for(count << shift), dim3(kThreads), 0, stream, reinterpret_cast<const float4*>(packet),
+                           slots, count << shift, shift, reinterpret_cast<float4*>(rows));
+    return hipGetLastError();
+}
 
 hipError_t launch_scatter_xf_packets(const XfPacket* packets, uint32_t count, XfAB* ab, float2* c, uint8_t* flags, uint32_t* parent,
                                      unsigned long long* active_bits, uint8_t* world_dirty, const BlockFlagTargets& blocks, hipStream_t stream)

@@ -147,6 +147,10 @@ hipError_t launch_scatter_xf_packets(const XfPacket* packets, uint32_t count, Xf
                                      hipStream_t stream);
 hipError_t launch_scatter_mesh_packets(const MeshPacket* packets, uint32_t count, float4* a, float2* b, uint32_t* link,
                                        uint8_t* block_flags /* or NULL */, hipStream_t stream);
+// Payload rows (gv_pool_bind_payload) of scattered dirty slots likewise: row k of the packet (count rows of `pitch` bytes — 16, 32 or
+// 64 — back to back) is written to rows + slots[k] * pitch, one lane per 16-byte piece
+hipError_t launch_scatter_payload_rows(const uint8_t* packet, const uint32_t* slots, uint32_t count, uint32_t pitch, uint8_t* rows,
+                                       hipStream_t stream);
 
 // gv_shard.hip: the visible list of a view as [draw_count | one bit per MIRROR entry]: a copy of the cull kernel's ballot words
 // (or, when `ballots` is NULL, built from the isVisible bytes in mirror order); words >= ceil(entries / 32), the rest is zeroed

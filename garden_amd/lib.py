@@ -24,7 +24,7 @@ GV_CONFIG_KEEP_SLOT_ORDER = 4
 GV_CONFIG_BLOCK_BOUNDS = 8
 GV_CONFIG_HIZ_RG16F = 16
 GV_CONFIG_LINEAR_SCAN = 32
-GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH = 0, 1, 2
+GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH, GV_DIRTY_PAYLOAD = 0, 1, 2, 3
 GV_SWEEP_VALU, GV_SWEEP_MFMA, GV_SWEEP_WITH_CULL, GV_SWEEP_WITH_CULL_VALU, GV_SWEEP_INCREMENTAL = 0, 1, 2, 3, 4
 GV_MEM_HOST, GV_MEM_DEVICE = 0, 1
 GV_EXCHANGE_ALLGATHER, GV_EXCHANGE_P2P, GV_EXCHANGE_BROADCAST, GV_EXCHANGE_PEER = 0, 1, 2, 3
@@ -111,6 +111,14 @@ class GvColumn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("stride", C.c_uint32)]
 
 
+GV_MAX_PAYLOAD_FIELDS = 4
+GV_MAX_PAYLOAD_BYTES = 64
+
+
+class GvPayloadField(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_uint32), ("bytes", C.c_uint32)]
+
+
 class GvTransformColumns(C.Structure):
     _fields_ = [(n, GvColumn) for n in ("entity", "parent", "position", "scale", "rotation", "self_active",
                                         "ancestors_active", "model_with_ancestors")]
@@ -153,6 +161,7 @@ EXPORTS = [
     "gv_cull_batch_begin", "gv_cull_batch_end", "gv_pool_set_record_layout", "gv_pool_results_records", "gv_pool_set_record_target",
     "gv_pool_results_instance_bases", "gv_profile_sampling", "gv_profile_samples", "gv_profile_kernels", "gv_pick",
     "gv_pool_set_instance_layout", "gv_pool_emit_instances", "gv_pool_instances_device", "gv_pool_instances_info", "gv_pool_instances_fetch",
+    "gv_pool_bind_payload", "gv_pool_set_payload_layout",
 ]
 
 _lib = None
@@ -268,6 +277,8 @@ def load():
     lib.gv_pool_instances_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_instances_info.argtypes = [P, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
     lib.gv_pool_instances_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
+    lib.gv_pool_bind_payload.argtypes = [P, u32, C.POINTER(GvPayloadField), u32, u32]
+    lib.gv_pool_set_payload_layout.argtypes = [P, u32, C.POINTER(u32), u32]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -381,7 +392,7 @@ class GpuVisibility:
         self._check(self.lib.gv_pool_bind_ready(self.ctx, pool_id, ready.ctypes.data, ready.strides[0], ready.dtype.itemsize))
 
     def mark_dirty(self, kind, first, count, pool_id=0):
-        if kind == GV_DIRTY_MESH:
+        if kind in (GV_DIRTY_MESH, GV_DIRTY_PAYLOAD):
             first |= pool_id << 28
         self._check(self.lib.gv_mark_dirty(self.ctx, kind, first, count))
 
@@ -654,6 +665,32 @@ class GpuVisibility:
         none = lambda x: GV_NONE if x is None else int(x)
         layout = GvInstanceLayout(int(stride), int(mvp), none(model), none(slot), none(distance_sq))
         self._check(self.lib.gv_pool_set_instance_layout(self.ctx, pool_id, C.byref(layout)))
+
+    def bind_payload(self, pool_id, arrays):
+        """gv_pool_bind_payload: the component bytes the pool's instances carry next to mvp, one numpy array per field (at most 4):
+        row i of an array is slot i's element — C-contiguous rows of 4 .. 64 bytes (a multiple of 4), any row stride, so a field of
+        a structured (AoS) component array works as it is. All arrays have one row per slot. None or [] removes the payload. The
+        caller keeps the arrays alive and unmoved until the calls that upload (sync / cull / emit_instances) have run."""
+        arrays = list(arrays) if arrays is not None else []
+        if not arrays:
+            self._keep.pop(("payload", pool_id), None)
+            self._check(self.lib.gv_pool_bind_payload(self.ctx, pool_id, None, 0, 0))
+            return
+        fields = (GvPayloadField * len(arrays))()
+        for f, a in zip(fields, arrays):
+            width = a.dtype.itemsize
+            for dim, step in zip(a.shape[:0:-1], a.strides[:0:-1]):  # the rows themselves are C-contiguous
+                assert step == width
+                width *= dim
+            assert a.shape[0] == arrays[0].shape[0]
+            f.data, f.stride, f.bytes = a.ctypes.data, a.strides[0], width
+        self._keep[("payload", pool_id)] = arrays
+        self._check(self.lib.gv_pool_bind_payload(self.ctx, pool_id, fields, len(arrays), arrays[0].shape[0]))
+
+    def set_payload_layout(self, pool_id, at):
+        """gv_pool_set_payload_layout: the offset of every payload field in the instance (None: mirrored, not written)."""
+        arr = (C.c_uint32 * max(len(at), 1))(*[GV_NONE if x is None else int(x) for x in at])
+        self._check(self.lib.gv_pool_set_payload_layout(self.ctx, pool_id, arr, len(at)))
 
     def emit_instances(self, pool_id, views, device=None):
         """gv_pool_emit_instances: the instance data of the listed views of `pool_id`, back to back, on the context's stream.

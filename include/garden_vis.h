@@ -175,7 +175,9 @@ typedef enum GvDirtyKind {
                                transform.cpp:130-195): their links are re-gathered in place and depth / cycles
                                re-validated; count == 0: entities came or went (destroy :30-73, create): rebuild and
                                re-order the whole mirror */
-    GV_DIRTY_MESH = 2       /* mesh slots changed; pool id in the top 4 bits of `first` */
+    GV_DIRTY_MESH = 2,      /* mesh slots changed; pool id in the top 4 bits of `first` */
+    GV_DIRTY_PAYLOAD = 3    /* the bound payload bytes (gv_pool_bind_payload) of mesh slots changed; pool id in the top 4 bits of
+                               `first`, like GV_DIRTY_MESH. Read by no cull: a recorded cull of a batch is not launched by it */
 } GvDirtyKind;
 int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count);
 
@@ -368,7 +370,7 @@ int gv_pool_set_instance_layout(GvCtx* ctx, uint32_t pool_id, const GvInstanceLa
  * dst_device NULL: a library-owned device buffer (grown, never shrunk), valid until the next gv_cull of the pool.
  * dst_device non-NULL: caller-owned device memory of capacity_bytes (16-byte aligned); instances that do not fit are not written
  * and the true total is still reported. ONLY the bytes of the layout's fields are written — the rest of each instance belongs to
- * the plugin (sprite.cpp:127-129 writes colour and uv next to mvp). The cull side is left as a read through
+ * the plugin (sprite.cpp:127-129 writes colour and uv next to mvp; a pool may have those written here too: gv_pool_bind_payload below). The cull side is left as a read through
  * gv_pool_results_device leaves it: recorded culls and deferred sorts have been launched (a small sorted pool with a record layout
  * has then also published its records to the host, and the launches count in GvStats), no result changes.
  * The library-owned buffer is sized for the sum of the listed views' OCCUPANCIES times the stride — the host does not know the
@@ -394,6 +396,51 @@ int gv_pool_instances_info(GvCtx* ctx, uint32_t pool_id, uint32_t* view_count, u
  * rule of gv_pool_set_record_target). GV_E_ARG when bytes < total * stride or starts_capacity is too small (nothing is written);
  * instances the emission could not fit into a caller-owned device target are not delivered either. */
 int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* starts, uint32_t starts_capacity);
+
+/* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
+ * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
+ * the record's componentOffset. A pool may bind those bytes (its PAYLOAD: up to GV_MAX_PAYLOAD_FIELDS fields, GV_MAX_PAYLOAD_BYTES
+ * bytes per slot in all); the library mirrors them on the device, one packed row per POOL SLOT (row pitch 16, 32 or 64 bytes),
+ * keeps the rows current through dirty marks, and gv_pool_emit_instances writes the row of each record's slot at the destinations
+ * gv_pool_set_payload_layout names, so that a sprite system's whole instance is produced on the device, in draw order.
+ * The bytes are OPAQUE: copied verbatim, no conversion, no arithmetic — NaN patterns and -0 survive bit for bit. In particular
+ * srgbToRgb(color) (sprite.cpp:127) is NOT applied: the reference's libraries/math is empty, so its text is unpinned,
+ * and a pow cannot be bit-defined across host and device. An engine binds a column that already holds the value it wants in the
+ * buffer; the same goes for the 9-slice borders, which are computed rather than copied.
+ *
+ * gv_pool_bind_payload — the sources. Element i of field f at fields[f].data + i * fields[f].stride (AoS: base + offsetof(field),
+ * stride = sizeof(component)). Lifetime as gv_pool_bind: re-issue when the storage may have moved; the pointers are read only inside
+ * the calls that upload — gv_sync (hence gv_cull) and gv_pool_emit_instances of the pool — and must be valid there; nothing is
+ * retained. count == 0 removes the payload and frees its mirror. A rebind with the same field shape (count and every `bytes`) and
+ * an equal or larger occupancy keeps the rows that are clean and uploads only the new slots; another shape or a smaller occupancy
+ * uploads everything. After every bind all destinations are GV_NONE. GV_E_ARG: an unbound pool, count above GV_MAX_PAYLOAD_FIELDS,
+ * a NULL data, bytes that is 0, not a multiple of 4 or above 64, a sum above GV_MAX_PAYLOAD_BYTES, stride < bytes.
+ *
+ * gv_pool_set_payload_layout — the destinations, kept apart from the bind because the base and the shadow instance structs differ
+ * (instance.hpp:82-86): at[f] is the 4-byte-aligned offset of field f in the instance, GV_NONE: mirrored but not written. Read by
+ * the next emission, like the instance layout. Destinations lie inside the stride and are disjoint from each other and from the
+ * instance layout's mvp / model / slot / distance_sq: checked here against the current instance layout, in
+ * gv_pool_set_instance_layout against the current destinations (only while a payload is bound), and once more at the emission
+ * for the pair as it then stands — GV_E_ARG each time. `count` must be the bound field count (GV_E_ARG); without a bound payload
+ * GV_E_STATE.
+ *
+ * Keeping it current: GV_DIRTY_PAYLOAD marks, and the pool's GV_DIRTY_MESH marks (a slot filled anew has a new payload), add to the
+ * payload's own dirty set, which gv_sync or the pool's gv_pool_emit_instances consumes, whichever comes first: a mark made between
+ * the cull and the emission is seen by that emission (the reference reads the component at draw time too, mesh.cpp:592). Uploaded
+ * bytes count in GvStats::upload_bytes.
+ *
+ * The emission: GV_E_STATE when a destination is set and the payload's occupancy is below a listed view's; with no payload bound
+ * or no destination set it is exactly the emission described above. gv_pool_instances_fetch delivers the payload fields the
+ * emission wrote like the other fields. */
+#define GV_MAX_PAYLOAD_FIELDS 4u
+#define GV_MAX_PAYLOAD_BYTES 64u /* sum over the fields, per slot */
+typedef struct GvPayloadField {
+    const void* data; /* element i at data + i * stride */
+    uint32_t stride;  /* bytes between consecutive elements, >= bytes */
+    uint32_t bytes;   /* 4 .. 64, a multiple of 4 */
+} GvPayloadField;
+int gv_pool_bind_payload(GvCtx* ctx, uint32_t pool_id, const GvPayloadField* fields, uint32_t count, uint32_t occupancy);
+int gv_pool_set_payload_layout(GvCtx* ctx, uint32_t pool_id, const uint32_t* at, uint32_t count);
 
 /* A tick of engine-sized pools (the reference's everyday 10^3..10^4 entities per mesh system) is bound by launches,
  * not by bytes. Between gv_cull_batch_begin and the first call that reads results (gv_pool_results_* / gv_results_* /
