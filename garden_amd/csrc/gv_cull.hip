@@ -94,9 +94,11 @@ __device__ __forceinline__ void reload_cull_args(CullArgs& out)
 // in front of it and stay live across it (106 SGPRs, the overflow spilled into VGPRs: six waves per SIMD where cull_kernel runs
 // eight); per stage each field lives only where it is used.
 // HOT (flat, exactly paired pools with a current sphere stream, MeshMirror::hot): every lane loads its 16-byte sphere entry and
-// classifies from it — c3 = pos - cam as translated() computes it, the same r, so the same decision bits; only the lanes that need
-// corners (undecided, or inside with Hi-Z) load the TRS / AABB streams and rebuild the model through prepare_model, exactly as
-// the plain path. A wave whose lanes are all outside (or all inside without Hi-Z) fetches none of their 49 cold bytes. (cull_kernel
+// classifies from it — c3 = pos - cam as translated() computes it, the same r, so the same decision bits; with Hi-Z an entry that is
+// not outside then asks the pyramid whether its sphere alone proves it occluded (hiz_sphere_occluded: a few cache-resident coarse
+// texels, one load behind the sphere entry) and counts as outside if so; only the lanes that still need corners (undecided, or
+// inside with Hi-Z) load the TRS / AABB streams and rebuild the model through prepare_model, exactly as the plain path. A wave
+// whose lanes are all outside or proven occluded (or all inside without Hi-Z) fetches none of their 49 cold bytes. (cull_kernel
 // only: pools culled through block bounds keep no sphere stream, gv_context.cpp.)
 template <bool HIZ, uint32_t MAP, bool RELOAD = false, bool HOT = false>
 __device__ __forceinline__ void cull_block(const CullArgs& args0, uint32_t lb, uint32_t* wave_count)
@@ -118,7 +120,12 @@ __device__ __forceinline__ void cull_block(const CullArgs& args0, uint32_t lb, u
         uint32_t where = kSphereOutside;
         if (!(h.w < 0.0f)) {  // kHotDropped: filtered out (a NaN r is not dropped: it reaches "undecided")
             const float tx = h.x - args.view.cam[0], ty = h.y - args.view.cam[1], tz = h.z - args.view.cam[2];
-            where = classify_sphere(tx, ty, tz, sphere_reach(h.w, tx, ty, tz), args.view.planes, args.view.plane_count);
+            const float reach = sphere_reach(h.w, tx, ty, tz);
+            where = classify_sphere(tx, ty, tz, reach, args.view.planes, args.view.plane_count);
+            // proven occluded from the sphere alone (hiz_sphere_occluded): not visible whichever exit the exact path would take —
+            // as an outside entry, without its cold bytes
+            if (HIZ && where != kSphereOutside && hiz_sphere_occluded(args.hiz, args.view.vp, tx, ty, tz, reach))
+                where = kSphereOutside;
         }
         visible = where == kSphereInside;
         if (where == kSphereUndecided || (HIZ && visible)) {
@@ -137,9 +144,10 @@ __device__ __forceinline__ void cull_block(const CullArgs& args0, uint32_t lb, u
             where = classify_sphere(m, box_a, box_b, args.view.planes, args.view.plane_count);
         visible = settle<HIZ>(where, m, box_a, box_b, args.view.planes, args.view.plane_count, c);
     }
-    // Hi-Z occlusion query on the survivors. Measured (profiles/r01b_hiz_ablation.txt): compacting the
-    // survivors across the workgroup through LDS first buys nothing — the stage is bound by the texel
-    // gathers (~4.5 M random 64-B sectors per frame), not by divergent VALU work.
+    // Hi-Z occlusion query on the survivors (HOT: on those the sphere query above could not settle). Measured
+    // (profiles/r01b_hiz_ablation.txt): compacting the survivors across the workgroup through LDS first buys nothing — the stage is
+    // bound by the texel gathers (~4.5 M random 64-B sectors per frame when every frustum survivor gets here), not by divergent VALU
+    // work.
     if (HIZ && visible) {
         CullArgs stage2;
         if (RELOAD)
@@ -191,6 +199,10 @@ __global__ __launch_bounds__(kCullBlock) void cull_kernel(const CullArgs args)
 // k = 0 .. K-1, so each k is one contiguous 4 KB sweep of the workgroup and wave w of tile k holds ballot word (tile k, w) as in
 // cull_kernel.
 //   1. every lane issues its K sphere loads, then reduces each entry to its sphere class (2 bits) at once;
+//   1b. Hi-Z views: the lanes with an entry that is not outside ask the pyramid about their K entries two at a time — both queries
+//      worked out, their eight texel loads in flight together — and an entry proven occluded from its sphere (hiz_sphere_occluded)
+//      becomes an outside entry: at cfg3 that settles 95 % of the occluded frustum survivors before any of their 49 cold bytes or
+//      corners are asked for (profiles/r12_hiz_sphere.md);
 //   2. the tiles one after another, each through cull_block's HOT per-entity code: only the lanes that need corners run it, and a
 //      wave skips a tile in which none of its lanes does;
 //   3. the 4K ballot words leave as one contiguous store, the super-tile's count as one atomic (K divides the 16 tiles of an emit
@@ -215,11 +227,37 @@ __global__ __launch_bounds__(kCullBlock) void cull_hot_kernel(const CullArgs arg
     }
     uint32_t where = 0;  // entry k's sphere class in bits 2k, 2k + 1
 #pragma unroll
-    for (uint32_t k = 0; k < K; k++)
-        if (!(h[k].w < 0.0f)) {  // kHotDropped (or past the end): outside
+    for (uint32_t k = 0; k < K; k++) {
+        const bool kept = !(h[k].w < 0.0f);  // kHotDropped (or past the end): outside
+        if (kept || HIZ) {
             const float tx = h[k].x - args.view.cam[0], ty = h[k].y - args.view.cam[1], tz = h[k].z - args.view.cam[2];
-            where |= classify_sphere(tx, ty, tz, sphere_reach(h[k].w, tx, ty, tz), args.view.planes, args.view.plane_count) << (2u * k);
+            const float reach = sphere_reach(h[k].w, tx, ty, tz);
+            if (HIZ)  // from here on the entry is its camera-relative centre and its reach: 1b asks the pyramid about them
+                h[k] = make_float4(tx, ty, tz, reach);
+            if (kept)
+                where |= classify_sphere(tx, ty, tz, reach, args.view.planes, args.view.plane_count) << (2u * k);
         }
+    }
+    if (HIZ && hiz_sphere_usable(args.hiz) && where != 0u) {
+        // two entries at a time: all K at once cost 78 VGPRs at K = 4 (six waves per SIMD where the kernel runs eight)
+#pragma unroll
+        for (uint32_t g = 0; g < K; g += 2) {
+            HizSphereQuery q[2];
+            float texel[2][4];
+#pragma unroll
+            for (uint32_t k = 0; k < 2; k++) {  // (an outside or dropped entry is asked about too, harmlessly: its answer is not used)
+                q[k] = hiz_sphere_query(args.hiz, args.view.vp, h[g + k].x, h[g + k].y, h[g + k].z, h[g + k].w);
+                hiz_sphere_fetch(args.hiz, q[k], texel[k]);
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 2; k++)
+                if (hiz_sphere_proven(q[k], texel[k]))
+                    where &= ~(3u << (2u * (g + k)));  // kSphereOutside
+            if (g + 2 < K)  // the next pair starts when this one is settled: its temporaries are not to overlap this one's
+                asm volatile("" : "+v"(where), "+v"(h[(g + 2) % K].x), "+v"(h[(g + 2) % K].y), "+v"(h[(g + 2) % K].z), "+v"(h[(g + 2) % K].w),
+                             "+v"(h[(g + 3) % K].x), "+v"(h[(g + 3) % K].y), "+v"(h[(g + 3) % K].z), "+v"(h[(g + 3) % K].w));
+        }
+    }
     uint32_t count = 0;
 #pragma unroll 1
     for (uint32_t k = 0; k < K; k++) {  // (the arguments are read afresh at each stage, as in cull_list_kernel: no SGPR spills)

@@ -244,6 +244,117 @@ __device__ __forceinline__ bool hiz_occluded(const HizDevice& hz, const float (&
     return znear < zfar;
 }
 
+// Occlusion proven from an entry's sphere alone (the sphere-stream cull, gv_cull.hip): true only when hiz_occluded would return
+// true for the entity's corners, whatever its TRS and box are; false = not proven (the entry takes the exact path). (tx, ty, tz) is
+// the camera-relative centre, reach = sphere_reach: the argument of block_window for ONE entity, its box the cube C of half-side
+// reach around the centre.
+//   * Every corner of the entity lies within r (L1 column norms, sphere_radius) of the centre in every coordinate; reach adds
+//     0.01 + 4e-5 * magnitude to r, 30x the fp32 rounding of the corner generation (classify_sphere's slack), so C holds every
+//     corner AS COMPUTED, with that much to spare.
+//   * Each clip coordinate is affine in the point: over C it stays within c +- e, c its value at the centre and e = reach * (L1
+//     norm of the row of vp). The three fmas of c and the product e round by <= 4 * 2^-24 of (row norm * magnitude); the spare
+//     4e-5 * magnitude of reach, times the same row norm, is 160x that and covers the rounding of c, e, c +- e here and of
+//     hiz_occluded's own clip coordinates. So every computed clw of the entity is >= wlo: wlo > 0 means hiz_occluded takes no
+//     "cannot bound" exit, and a cube that reaches w <= 0 is never tested.
+//   * With w in [wlo, whi], wlo > 0, a ratio p / w over C is largest at p's upper end over wlo (over whi when that end is
+//     negative) and smallest at p's lower end the other way round: [nx0, nx1] x [ny0, ny1] holds every corner's x/w, y/w, and
+//     znear0 >= every corner's z/w = zNear_e. The divisions and products round by 2^-23 relative: znear is widened by 2e-6
+//     relative (16x), the pixel rect by one pixel each way (the u, v roundings are < 1e-3 pixel at 16 K pixels), so the rect R
+//     contains the entity's R_e.
+//   * The smallest level L at which R touches <= 2x2 texels is >= the entity's L_e (the condition is monotone in the rect), and so
+//     is any level above it. In a NESTED pyramid every level-L_e texel that touches R_e lies inside a level-cl texel that touches
+//     R, cl >= L, and a texel's min bounds everything under it (RG16F mins are rounded down): min over the <= 2x2 level-cl texels
+//     <= zFar_e.
+//   So znear < every one of those texels  =>  zNear_e <= znear < zFar_e: hiz_occluded returns true. A NaN texel, centre, reach or
+//   any non-finite intermediate fails a comparison and declines. cl = L + kHizSphereStep: two levels up the texels come from
+//   the cache-resident 2 MB of level 3 and above, never from the depth image, and still prove 95 % of what L itself would on the
+//   walls image (census of tests/test_hiz_sphere_census.py: L 97.9 %, L + 2 95.5 %, L + 4 83.4 % of the occluded frustum
+//   survivors; profiles/r12_hiz_sphere.md). tests/hiz_sphere_twin.h restates this in C, operation for operation.
+constexpr uint32_t kHizSphereStep = 2;
+// The query in two halves, so that a lane with several entries has the texel loads of all of them in flight together
+// (cull_hot_kernel). hiz_sphere_query is straight-line code: a declined entry leaves with znear = NaN, which fails every
+// comparison, and with texel indices that are in bounds like any other's (clamp01 maps a NaN to 0; the level and the coordinates
+// are clamped to the pyramid). Both halves want hiz_sphere_usable(hz): then level mip_count - 1 >= 2 is a stored level.
+struct HizSphereQuery {
+    float znear;     // widened by its rounding allowance; NaN: declined
+    uint32_t at[4];  // the <= 2x2 texels of level cl, as indices into HizDevice::mips (a repeated texel is repeated)
+};
+__device__ __forceinline__ bool hiz_sphere_usable(const HizDevice& hz)  // uniform
+{
+    return hz.nested && hz.mip_count > 2u;  // (a pyramid of one or two levels stores nothing a query could read)
+}
+__device__ __forceinline__ HizSphereQuery hiz_sphere_query(const HizDevice& hz, const float (&vp)[16], float tx, float ty, float tz, float reach)
+{
+    const float cx = fmaf(vp[0], tx, fmaf(vp[4], ty, fmaf(vp[8], tz, vp[12])));
+    const float cy = fmaf(vp[1], tx, fmaf(vp[5], ty, fmaf(vp[9], tz, vp[13])));
+    const float cz = fmaf(vp[2], tx, fmaf(vp[6], ty, fmaf(vp[10], tz, vp[14])));
+    const float cw = fmaf(vp[3], tx, fmaf(vp[7], ty, fmaf(vp[11], tz, vp[15])));
+    const float ex = reach * (fabsf(vp[0]) + fabsf(vp[4]) + fabsf(vp[8]));  // (the row norms are wave-uniform: scalar)
+    const float ey = reach * (fabsf(vp[1]) + fabsf(vp[5]) + fabsf(vp[9]));
+    const float ez = reach * (fabsf(vp[2]) + fabsf(vp[6]) + fabsf(vp[10]));
+    const float ew = reach * (fabsf(vp[3]) + fabsf(vp[7]) + fabsf(vp[11]));
+    const float wlo = cw - ew, whi = cw + ew;
+    const float rlo = 1.0f / wlo, rhi = 1.0f / whi;  // IEEE divisions, as the twin's
+    const float xlo = cx - ex, xhi = cx + ex, ylo = cy - ey, yhi = cy + ey, zhi = cz + ez;
+    const float nx0 = xlo * (xlo >= 0.0f ? rhi : rlo), nx1 = xhi * (xhi >= 0.0f ? rlo : rhi);
+    const float ny0 = ylo * (ylo >= 0.0f ? rhi : rlo), ny1 = yhi * (yhi >= 0.0f ? rlo : rhi);
+    const float znear0 = zhi * (zhi >= 0.0f ? rlo : rhi);
+    const float probe = fabsf(nx0) + fabsf(nx1) + fabsf(ny0) + fabsf(ny1) + fabsf(znear0) + whi;
+    // the cube reaches w <= 0, or a NaN or an infinity anywhere above: declined
+    const bool bounded = (wlo > 0.0f) & (probe < __builtin_huge_valf());
+    HizSphereQuery q;
+    q.znear = bounded ? fmaf(fabsf(znear0), 2e-6f, znear0) : __builtin_nanf("");
+    const int W = (int)hz.width, H = (int)hz.height;
+    const float umin = clamp01(fmaf(nx0, 0.5f, 0.5f)), umax = clamp01(fmaf(nx1, 0.5f, 0.5f));
+    const float vmin = clamp01(fmaf(ny0, 0.5f, 0.5f)), vmax = clamp01(fmaf(ny1, 0.5f, 0.5f));
+    const int ix0 = max((int)(umin * (float)W) - 1, 0), ix1 = min((int)(umax * (float)W) + 1, W - 1);
+    const int iy0 = max((int)(vmin * (float)H) - 1, 0), iy1 = min((int)(vmax * (float)H) + 1, H - 1);
+    auto axis_level = [](int i0, int i1) -> uint32_t {  // as in hiz_occluded
+        const int n = i1 - i0;
+        if (n <= 1)
+            return 0u;
+        const uint32_t l = 31u - (uint32_t)__clz(n);
+        return ((i1 >> l) - (i0 >> l)) <= 1 ? l : l + 1u;
+    };
+    const uint32_t cl = min(max(axis_level(ix0, ix1), axis_level(iy0, iy1)) + kHizSphereStep, hz.mip_count - 1u);  // >= 2
+    const int lw = max((int)(hz.width >> cl), 1), lh = max((int)(hz.height >> cl), 1);
+    const int x0 = min(ix0 >> cl, lw - 1), x1 = min(ix1 >> cl, lw - 1);
+    const int y0 = min(iy0 >> cl, lh - 1), y1 = min(iy1 >> cl, lh - 1);
+    // 32-bit texel indices: the levels >= 1 of a pyramid hold a third of its depth image's texels, 2^32 are out of reach
+    const uint32_t first = (uint32_t)hz.mip_offset[cl];
+    q.at[0] = first + (uint32_t)(y0 * lw + x0);
+    q.at[1] = first + (uint32_t)(y0 * lw + x1);
+    q.at[2] = first + (uint32_t)(y1 * lw + x0);
+    q.at[3] = first + (uint32_t)(y1 * lw + x1);
+    return q;
+}
+__device__ __forceinline__ float hiz_stored_min(const HizDevice& hz, uint32_t at)  // a stored texel's min (levels >= 2; >= 1 when level 1 is stored)
+{
+    // one load either way: the texel's first 32-bit word is its fp32 min, or its binary16 (min, max) pair
+    const uint32_t word = reinterpret_cast<const uint32_t*>(hz.mips)[hz.rg16f ? at : 2u * at];
+    return hz.rg16f ? half_to_float(word & 0xFFFFu) : __uint_as_float(word);
+}
+// four loads whatever the rect touches: no branch between them
+__device__ __forceinline__ void hiz_sphere_fetch(const HizDevice& hz, const HizSphereQuery& q, float (&t)[4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        t[j] = hiz_stored_min(hz, q.at[j]);
+}
+__device__ __forceinline__ bool hiz_sphere_proven(const HizSphereQuery& q, const float (&t)[4])
+{
+    return (q.znear < t[0]) & (q.znear < t[1]) & (q.znear < t[2]) & (q.znear < t[3]);  // (a NaN texel fails its comparison)
+}
+__device__ __forceinline__ bool hiz_sphere_occluded(const HizDevice& hz, const float (&vp)[16], float tx, float ty, float tz, float reach)
+{
+    if (!hiz_sphere_usable(hz))
+        return false;
+    const HizSphereQuery q = hiz_sphere_query(hz, vp, tx, ty, tz, reach);
+    float t[4];
+    hiz_sphere_fetch(hz, q, t);
+    return hiz_sphere_proven(q, t);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K1: cull — one lane per mesh slot
 // ------------------------------------------------------------------------------------------------
