@@ -320,10 +320,14 @@ struct ViewState {
     PinnedBuf<uint8_t> h_is_visible;
     PinnedBuf<uint8_t> h_records;    // results in the pool's record layout (gv_pool_results_records)
     DeviceBuf<uint8_t> d_records;    // ... packed on the device first for pools too large to publish directly
-    bool records_fetched = false;    // records_at holds this cull's records
-    uint8_t* records_at = nullptr;   // h_records, or the caller's array (gv_pool_set_record_target)
+    // Delivery of the record structs (place_records in gv_results.cpp). A view goes: culled (records_fetched false) -> published by
+    // the publish launch or the small-pool sort / fetched by the large path (records_fetched true: h_records holds this cull's records
+    // once the stream has been waited for; records_staged true while a record target still has to receive them) -> staged copy done
+    // (records_staged false: records_at holds them). A new cull, sort, layout, target or mapping starts over.
+    bool records_fetched = false;
+    uint8_t* records_at = nullptr;   // where the caller reads them: h_records, or the caller's array (gv_pool_set_record_target)
+    bool records_staged = false;     // this view has a record target (never page-locked) that h_records has not been copied into yet
     uint32_t count_hint = 0xFFFFFFFFu;  // draw count of this view's previous fetch (unknown: none)
-    bool records_staged = false;     // the caller's array could not be page-locked: h_records is copied into it after the synchronisation
     bool ballots_current = false;    // `mask` holds this cull's ballot words (not after the one-launch cull + emit of a small pool)
     std::vector<uint32_t> instance_bases;  // gv_pool_results_instance_bases (built on request)
     uint32_t pool_id = 0, occupancy = 0;

@@ -15,7 +15,6 @@ using namespace gv;
 
 namespace gv {
 
-// gv_sort of a pool too large for the one-launch batch: the record count on the device picks rank or radix sort (launch_sort)
 // Buffers and launch arguments of a large sort of `vs`: inputs = the view's current records, outputs = its alternate set.
 static int sort_buffers_of(GvCtx* ctx, ViewState& vs, SortBuffers& b)
 {
@@ -101,9 +100,6 @@ static int sort_large(GvCtx* ctx, ViewState& vs, bool descending)
     return GV_OK;
 }
 
-// gv_sort on a small pool only records the request; the first call that needs the records (fetch, device accessors,
-// gv_wait) sorts every pending view of EVERY pool in ONE launch — five mesh systems with a main camera and three shadow
-// passes each cost one launch, not twenty.
 // Everything queued on the context's stream has finished — where hipStreamSynchronize would do, for the end of an engine-sized
 // tick: a one-lane kernel behind the queue writes a sequence number into pinned memory and the host polls it
 // (launch_done_flag). Falls back to the synchronisation when profiling events wait to be read or when the word does not arrive
@@ -132,11 +128,64 @@ int wait_for_stream(GvCtx* ctx)
     return GV_OK;
 }
 
+// The pool's record layout as the kernels take it: with GV_RESULTS_MAP_RECORDS the records carry the caller's WORLD slots.
+static int delivered_layout(GvCtx* ctx, const PoolState& pool, uint32_t pool_id, uint32_t occupancy, RecordLayout& L)
+{
+    L = pool.record_layout;
+    L.slot_map = nullptr;
+    if (pool.result_flags & GV_RESULTS_MAP_RECORDS) {
+        if (pool.index_map_count < occupancy)
+            return ctx->fail(GV_E_STATE, "gv_results_fetch: pool %u delivers records in world slots (gv_pool_set_result_mapping), but its index map covers %u of "
+                             "%u slots", pool_id, pool.index_map_count, occupancy);
+        L.slot_map = pool.d_index_map.ptr;
+    }
+    return GV_OK;
+}
+
+// Where the record structs of (pool pid, view v) go, for every way of delivering them: they arrive in the view's pinned h_records
+// and are read at records_at — h_records itself or, with a record target, the caller's array, which must hold the whole pool's
+// worth (the count is not known yet) and is filled by the staged copy (copy_staged_records). `delivered`: the layout for the kernel.
+static int place_records(GvCtx* ctx, uint32_t pid, uint32_t v, RecordLayout& delivered)
+{
+    const PoolState& pool = ctx->pools[pid];
+    ViewState& vs = ctx->views[pid][v];
+    const PoolState::RecordTarget& target = pool.record_target[v];
+    const size_t need = (size_t)vs.occupancy * pool.record_layout.stride;
+    if (target.host && target.bytes < need)
+        return ctx->fail(GV_E_ARG, "gv_results_fetch: the record target of pool %u view %u holds %zu bytes, occupancy * stride = %zu", pid, v,
+                         target.bytes, need);
+    GV_HIP(ctx, vs.h_records.reserve(need));
+    vs.records_at = target.host ? target.host : vs.h_records.ptr;
+    vs.records_staged = target.host != nullptr;
+    if (int rc = delivered_layout(ctx, pool, pid, vs.occupancy, delivered))
+        return rc;
+    vs.records_fetched = true;
+    return GV_OK;
+}
+
+// The three host arrays of a view whose records leave as visible_idx / baked_model / distance_sq (a pool without a record layout).
+static int reserve_record_arrays(GvCtx* ctx, ViewState& vs)
+{
+    GV_HIP(ctx, vs.h_visible_idx.reserve(vs.occupancy));
+    GV_HIP(ctx, vs.h_baked_model.reserve((size_t)vs.occupancy * 12));
+    GV_HIP(ctx, vs.h_distance_sq.reserve(vs.occupancy));
+    return GV_OK;
+}
+
+// The isVisible bytes of a spatially ordered pool, back in pool-slot order on the device (the random half of the write-back);
+// `from`: where to copy them from. Callers decide when: the publish kernel does it in LDS up to kPublishLdsSlots slots.
+static int unpermuted_visible(GvCtx* ctx, ViewState& vs, const PoolState& pool, const uint8_t*& from)
+{
+    GV_HIP(ctx, vs.is_visible_slots.reserve(vs.occupancy));
+    GV_HIP(ctx, launch_unpermute_bytes(vs.is_visible.ptr, pool.d_orig.ptr, vs.occupancy, vs.is_visible_slots.ptr, ctx->stream));
+    from = vs.is_visible_slots.ptr;
+    return GV_OK;
+}
+
 // What delivers the results of (pool pid, view v) to the host: the count, the records [0, count) (three arrays, or the
-// pool's record structs — in the library's pinned buffer or the caller's own page-locked array) and, for a main pass, the
-// isVisible bytes in pool-slot order. Buffers are reserved here; used by the publish launch of gv_pool_results_fetch and by the
-// small-pool sort, which publishes what it has just sorted.
-static int delivered_layout(GvCtx* ctx, const PoolState& pool, uint32_t pool_id, uint32_t occupancy, RecordLayout& L);
+// pool's record structs in the library's pinned buffer: place_records) and, for a main pass, the isVisible bytes in pool-slot
+// order. Buffers are reserved here; used by the publish launch of gv_pool_results_fetch and by the small-pool sort, which
+// publishes what it has just sorted.
 int publish_args_of(GvCtx* ctx, uint32_t pid, uint32_t v, PublishArgs& a)
 {
     PoolState& wp = ctx->pools[pid];
@@ -152,22 +201,12 @@ int publish_args_of(GvCtx* ctx, uint32_t pid, uint32_t v, PublishArgs& a)
     a.host_count = w.h_draw_count.ptr;
     w.records_staged = false;
     if (w.emitted && wp.record_layout.stride) {
-        const PoolState::RecordTarget& target = wp.record_target[v];
-        const size_t need = (size_t)w.occupancy * wp.record_layout.stride;
-        if (target.host && target.bytes < need)
-            return ctx->fail(GV_E_ARG, "gv_results_fetch: the record target of pool %u view %u holds %zu bytes, occupancy * stride = %zu", pid, v,
-                             target.bytes, need);
-        GV_HIP(ctx, w.h_records.reserve(need));
-        a.host_records = w.h_records.ptr;
-        w.records_at = target.host ? target.host : w.h_records.ptr;
-        w.records_staged = target.host != nullptr;  // (never page-locked: filled from h_records after the synchronisation)
-        if (int rc = delivered_layout(ctx, wp, pid, w.occupancy, a.layout))
+        if (int rc = place_records(ctx, pid, v, a.layout))
             return rc;
-        w.records_fetched = true;
+        a.host_records = w.h_records.ptr;
     } else if (w.emitted) {
-        GV_HIP(ctx, w.h_visible_idx.reserve(w.occupancy));
-        GV_HIP(ctx, w.h_baked_model.reserve((size_t)w.occupancy * 12));
-        GV_HIP(ctx, w.h_distance_sq.reserve(w.occupancy));
+        if (int rc = reserve_record_arrays(ctx, w))
+            return rc;
         a.host_idx = w.h_visible_idx.ptr;
         a.host_model = w.h_baked_model.ptr;
         a.host_dist = w.h_distance_sq.ptr;
@@ -177,9 +216,8 @@ int publish_args_of(GvCtx* ctx, uint32_t pid, uint32_t v, PublishArgs& a)
         GV_HIP(ctx, w.h_is_visible.reserve(w.occupancy));
         a.host_is_visible = w.h_is_visible.ptr;
         if (wperm && w.occupancy > kPublishLdsSlots) {  // too large for the in-LDS un-permutation
-            GV_HIP(ctx, w.is_visible_slots.reserve(w.occupancy));
-            GV_HIP(ctx, launch_unpermute_bytes(w.is_visible.ptr, wp.d_orig.ptr, w.occupancy, w.is_visible_slots.ptr, ctx->stream));
-            a.is_visible = w.is_visible_slots.ptr;
+            if (int rc = unpermuted_visible(ctx, w, wp, a.is_visible))
+                return rc;
             a.orig = nullptr;
         }
     }
@@ -187,13 +225,11 @@ int publish_args_of(GvCtx* ctx, uint32_t pid, uint32_t v, PublishArgs& a)
     return GV_OK;
 }
 
-int flush_sorts(GvCtx* ctx)
+// Mid-sized pools (beyond the one-launch batch, up to kMidSortMaxSlots slots): ALL the pending lists of the frame by ONE set of
+// launches — the rank-sort launch and the eight radix launches with blockIdx.y = list (launch_sort_batch). A frame of seven mesh
+// systems x four passes at 10^5 slots each was 150-250 short dependent launches, ~2 ms of a 4 ms tick.
+static int flush_mid_sorts(GvCtx* ctx)
 {
-    if (int rc = flush_culls(ctx))  // the records about to be sorted / read may still be waiting to be culled
-        return rc;
-    // Mid-sized pools (beyond the one-launch batch, up to kMidSortMaxSlots slots): ALL the pending lists of the frame by ONE set of
-    // launches — the rank-sort launch and the eight radix launches with blockIdx.y = list (launch_sort_batch). A frame of seven mesh
-    // systems x four passes at 10^5 slots each was 150-250 short dependent launches, ~2 ms of a 4 ms tick.
     for (;;) {
         SortBatchEntry batch[kMaxSortBatch];
         ViewState* taken[kMaxSortBatch];
@@ -222,27 +258,39 @@ int flush_sorts(GvCtx* ctx)
         if (failed != GV_OK)
             return failed;
         if (n == 0)
-            break;
+            return GV_OK;
     }
+}
+
+// The small-pool sort publishes what it has sorted (count, records at their sorted places, isVisible: one kernel boundary and the
+// publish kernel's own dependent loads less per tick) — unless other small views wait for a publish launch anyway (a tick with
+// unsorted OIT buffers): then that launch takes these views along and the sort stays lean ...
+static bool sort_publishes(const GvCtx* ctx)
+{
+    for (uint32_t pool = 0; pool < GV_MAX_POOLS; pool++)
+        for (uint32_t v = 0; v < GV_MAX_VIEWS; v++) {
+            const ViewState& w = ctx->views[pool][v];
+            if (w.valid && !w.published && !w.sort_pending && w.occupancy != 0 && w.occupancy <= kPublishMaxSlots)
+                return false;
+            // ... and only records that leave as whole structs: a record written at its sorted place is one aligned 64- /
+            // 80-byte piece; the three arrays would leave as scattered 4- and 48-byte pieces, which measured slower
+            // (10 k entities: 50.8 vs 46.3 us per tick) than the publish kernel's contiguous rows
+            if (w.valid && w.sort_pending && w.occupancy <= kBatchSortMaxSlots && !ctx->pools[pool].record_layout.stride)
+                return false;
+        }
+    return true;
+}
+
+// Small pools: gv_sort only records the request; the first call that needs the records (fetch, device accessors, gv_wait) sorts
+// every pending view of EVERY pool in ONE launch — five mesh systems with a main camera and three shadow passes each cost one
+// launch, not twenty. (By now only small views are pending.)
+static int flush_small_sorts(GvCtx* ctx)
+{
     for (;;) {
         uint32_t widest = 0, views = 0;
         ViewState* taken[kMaxPublishViews];
         SortBatch batch{};
-        // The sort publishes what it has sorted (count, records at their sorted places, isVisible: one kernel boundary and the
-        // publish kernel's own dependent loads less per tick) — unless other small views wait for a publish launch anyway
-        // (a tick with unsorted OIT buffers): then that launch takes these views along and the sort stays lean.
-        bool fuse_publish = true;
-        for (uint32_t pool = 0; pool < GV_MAX_POOLS && fuse_publish; pool++)
-            for (uint32_t v = 0; v < GV_MAX_VIEWS; v++) {
-                const ViewState& w = ctx->views[pool][v];
-                if (w.valid && !w.published && !w.sort_pending && w.occupancy != 0 && w.occupancy <= kPublishMaxSlots)
-                    fuse_publish = false;
-                // ... and only records that leave as whole structs: a record written at its sorted place is one aligned 64- /
-                // 80-byte piece; the three arrays would leave as scattered 4- and 48-byte pieces, which measured slower
-                // (10 k entities: 50.8 vs 46.3 us per tick) than the publish kernel's contiguous rows
-                if (w.valid && w.sort_pending && w.occupancy <= kBatchSortMaxSlots && !ctx->pools[pool].record_layout.stride)
-                    fuse_publish = false;
-            }
+        const bool fuse_publish = sort_publishes(ctx);
         for (uint32_t pool = 0; pool < GV_MAX_POOLS && views < kMaxPublishViews; pool++)
             for (uint32_t v = 0; v < GV_MAX_VIEWS && views < kMaxPublishViews; v++) {
                 ViewState& vs = ctx->views[pool][v];
@@ -283,7 +331,7 @@ int flush_sorts(GvCtx* ctx)
             std::swap(vs.baked_model, vs.alt_model);
             std::swap(vs.distance_sq, vs.alt_dist);
             vs.sort_pending = 0;
-            if (batch.view[k].fused_publish) {
+            if (fuse_publish) {
                 vs.published = true;  // ... once the stream has been synchronised
                 ctx->publish_sync_pending = true;
             } else {
@@ -293,18 +341,13 @@ int flush_sorts(GvCtx* ctx)
     }
 }
 
-// The pool's record layout as the kernels take it: with GV_RESULTS_MAP_RECORDS the records carry the caller's WORLD slots.
-static int delivered_layout(GvCtx* ctx, const PoolState& pool, uint32_t pool_id, uint32_t occupancy, RecordLayout& L)
+int flush_sorts(GvCtx* ctx)
 {
-    L = pool.record_layout;
-    L.slot_map = nullptr;
-    if (pool.result_flags & GV_RESULTS_MAP_RECORDS) {
-        if (pool.index_map_count < occupancy)
-            return ctx->fail(GV_E_STATE, "gv_results_fetch: pool %u delivers records in world slots (gv_pool_set_result_mapping), but its index map covers %u of "
-                             "%u slots", pool_id, pool.index_map_count, occupancy);
-        L.slot_map = pool.d_index_map.ptr;
-    }
-    return GV_OK;
+    if (int rc = flush_culls(ctx))  // the records about to be sorted / read may still be waiting to be culled
+        return rc;
+    if (int rc = flush_mid_sorts(ctx))
+        return rc;
+    return flush_small_sorts(ctx);
 }
 
 ViewState* view_of(GvCtx* ctx, uint32_t pool_id, uint32_t view_index)
@@ -313,7 +356,6 @@ ViewState* view_of(GvCtx* ctx, uint32_t pool_id, uint32_t view_index)
         return nullptr;
     return &ctx->views[pool_id][view_index];
 }
-
 
 // Is every page of [p, p + bytes) still mapped? (msync fails with ENOMEM otherwise.) A freed std::vector of this size — the
 // engine's combinedMeshes that was let go, or reallocated, while it was still the record target — is an unmapped range.
@@ -333,6 +375,227 @@ bool release_record_target(PoolState::RecordTarget& target)
         intact = range_mapped(target.host, target.bytes);
     target = PoolState::RecordTarget{};
     return intact;
+}
+
+// ---- gv_pool_results_fetch, step by step ----
+// Records that have arrived in a view's h_records and still have to go to its record target. A record target is the caller's own
+// pageable array and is never page-locked (profiles/withdrawn.md item 27), so the records cross the host once more.
+struct StagedCopy {
+    uint32_t pool_id;
+    uint8_t* to;
+    const uint8_t* from;
+    size_t bytes;
+};
+static void take_staged(GvCtx* ctx, ViewState& w, std::vector<StagedCopy>& staged)
+{
+    if (w.records_staged)
+        staged.push_back({w.pool_id, w.records_at, w.h_records.ptr, (size_t)w.h_draw_count.ptr[0] * ctx->pools[w.pool_id].record_layout.stride});
+    w.records_staged = false;
+}
+
+static int validate_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, const GvResult* out)
+{
+    if (!out)
+        return ctx->fail(GV_E_ARG, "gv_results_fetch: out is NULL");
+    if (!view_of(ctx, pool_id, view_index))
+        return ctx->fail(GV_E_ARG, "gv_results_fetch: pool %u view %u has no results", pool_id, view_index);
+    return GV_OK;
+}
+
+// Engine-sized pools (up to kPublishMaxSlots slots) are launch- and round-trip-bound: one kernel writes count, records and
+// isVisible of EVERY unpublished view of EVERY pool culled since the last fetch (the main camera and its shadow passes are fetched
+// one after the other, mesh.cpp:809-843; a frame that culls all its mesh systems first reads afterwards) straight into the pinned
+// host buffers, one wait ends the frame; the sibling views' fetches find their results already there. Views whose small-pool sort
+// has published them already (flush_small_sorts) only wait.
+static int deliver_small(GvCtx* ctx, uint32_t pool_id, const ViewState& vs, std::vector<StagedCopy>& staged)
+{
+    if (vs.published && !ctx->publish_sync_pending)
+        return GV_OK;
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    static_assert(kMaxPublishViews >= GV_MAX_VIEWS, "PublishBatch holds at least one pool's views");
+    PublishBatch batch{};
+    uint32_t views = 0, widest = 0;
+    ViewState* sent[kMaxPublishViews];
+    for (uint32_t q = 0; q < GV_MAX_POOLS && views < kMaxPublishViews; q++) {
+        const uint32_t pid = (pool_id + q) % GV_MAX_POOLS;  // the pool asked for first: it always fits
+        for (uint32_t v = 0; v < GV_MAX_VIEWS && views < kMaxPublishViews; v++) {
+            ViewState& w = ctx->views[pid][v];
+            if (!w.valid || w.published || w.occupancy == 0 || w.occupancy > kPublishMaxSlots)
+                continue;
+            if (int rc = publish_args_of(ctx, pid, v, batch.view[views]))
+                return rc;
+            widest = std::max(widest, w.occupancy);
+            sent[views++] = &w;
+        }
+    }
+    if (views)
+        GV_HIP(ctx, launch_publish(batch, views, widest, ctx->stream));
+    if (int rc = wait_for_stream(ctx))
+        return rc;
+    drain_events(ctx);
+    ctx->publish_sync_pending = false;
+    for (uint32_t k = 0; k < views; k++)
+        sent[k]->published = true;
+    for (auto& per_pool : ctx->views)  // all record targets of the frame are filled in ONE pass
+        for (ViewState& w : per_pool)
+            if (w.valid && w.published)
+                take_staged(ctx, w, staged);
+    return GV_OK;
+}
+
+// Pools beyond the publish launch (and empty ones): the count first, then the records — structs packed on the device, or the
+// three arrays — and the isVisible bytes in pool-slot order by plain copies, one synchronisation.
+static int deliver_large(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, std::vector<StagedCopy>& staged)
+{
+    ViewState& vs = ctx->views[pool_id][view_index];
+    PoolState& pool = ctx->pools[vs.pool_id];
+    uint32_t count = 0;
+    if (int rc = gv_pool_result_count(ctx, pool_id, view_index, &count))
+        return rc;
+    const bool as_records = vs.emitted && pool.record_layout.stride;
+    vs.records_staged = false;
+    RecordLayout delivered;
+    if (as_records)
+        if (int rc = place_records(ctx, pool_id, view_index, delivered))
+            return rc;
+    if (as_records && count) {  // packed on the device, one copy
+        GV_HIP(ctx, vs.d_records.reserve((size_t)vs.occupancy * delivered.stride));
+        GV_HIP(ctx, launch_pack_records(vs.draw_count.ptr, vs.visible_idx.ptr, vs.baked_model.ptr, vs.distance_sq.ptr, delivered,
+                                        count, vs.d_records.ptr, ctx->stream));
+        GV_HIP(ctx, hipMemcpyAsync(vs.h_records.ptr, vs.d_records.ptr, (size_t)count * delivered.stride, hipMemcpyDeviceToHost, ctx->stream));
+    } else if (vs.emitted && count) {
+        if (int rc = reserve_record_arrays(ctx, vs))
+            return rc;
+        GV_HIP(ctx, hipMemcpyAsync(vs.h_visible_idx.ptr, vs.visible_idx.ptr, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+        GV_HIP(ctx, hipMemcpyAsync(vs.h_baked_model.ptr, vs.baked_model.ptr, (size_t)count * 48, hipMemcpyDeviceToHost, ctx->stream));
+        GV_HIP(ctx, hipMemcpyAsync(vs.h_distance_sq.ptr, vs.distance_sq.ptr, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (vs.main_pass && vs.occupancy) {
+        GV_HIP(ctx, vs.h_is_visible.reserve(vs.occupancy));
+        const uint8_t* from = vs.is_visible.ptr;
+        if (!pool.perm.empty() && pool.perm.size() == vs.occupancy)
+            if (int rc = unpermuted_visible(ctx, vs, pool, from))
+                return rc;
+        GV_HIP(ctx, hipMemcpyAsync(vs.h_is_visible.ptr, from, vs.occupancy, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    take_staged(ctx, vs, staged);
+    return GV_OK;
+}
+
+// h_records -> the callers' arrays, after the wait that made the records arrive: in 256 KB pieces over the worker threads from
+// 1 MB up (seven mesh systems' lists at 10^6 entities: 8 MB, ~1 ms of one thread). A freed target is found before anything is written.
+static int copy_staged_records(GvCtx* ctx, const std::vector<StagedCopy>& staged)
+{
+    std::vector<StagedCopy> pieces;
+    size_t total = 0;
+    constexpr size_t kPiece = (size_t)256 << 10;
+    for (const StagedCopy& c : staged) {
+        if (c.bytes && !range_mapped(c.to, c.bytes))
+            return ctx->fail(GV_E_STATE, "gv_results_fetch: the record target of pool %u is not mapped any more (freed while it was "
+                                         "still the target?)", c.pool_id);
+        for (size_t at = 0; at < c.bytes; at += kPiece)
+            pieces.push_back({c.pool_id, c.to + at, c.from + at, std::min(kPiece, c.bytes - at)});
+        total += c.bytes;
+    }
+    const uint32_t parts = total >= ((size_t)1 << 20) ? std::min<uint32_t>((uint32_t)pieces.size(), worker_parts((size_t)1 << 30)) : 1u;
+    run_parts(parts, [&](uint32_t t) {
+        for (size_t k = t; k < pieces.size(); k += parts)
+            memcpy(pieces[k].to, pieces[k].from, pieces[k].bytes);
+    });
+    return GV_OK;
+}
+
+static void fill_result(const ViewState& vs, uint32_t count, GvResult* out)
+{
+    memset(out, 0, sizeof(*out));
+    out->draw_count = count;
+    out->instance_count = count;  // default getReadyMeshesAsync returns 0/1 (render/mesh.hpp:142-146)
+    if (vs.emitted && count && !vs.records_fetched) {
+        out->visible_idx = vs.h_visible_idx.ptr;
+        out->baked_model = vs.h_baked_model.ptr;
+        out->distance_sq = vs.h_distance_sq.ptr;
+    }
+}
+
+// The pool slot of delivered record k of an emitted view: from the index array or, for record structs, componentOffset / component size.
+static inline uint32_t fetched_slot(const ViewState& vs, const PoolState& pool, uint32_t k)
+{
+    if (!vs.records_fetched)
+        return vs.h_visible_idx.ptr[k];
+    const RecordLayout& L = pool.record_layout;
+    uint64_t offset;
+    memcpy(&offset, vs.records_at + (size_t)k * L.stride + L.component_offset, 8);
+    return (uint32_t)(offset / L.component_stride);
+}
+
+template <typename Term>
+static uint32_t parallel_sum(uint32_t count, Term&& term)
+{
+    std::atomic<uint64_t> total{0};
+    parallel_ranges(0, count, [&](uint32_t a, uint32_t b) {
+        uint64_t sum = 0;
+        for (uint32_t i = a; i < b; i++)
+            sum += term(i);
+        total += sum;
+    });
+    return (uint32_t)total.load();
+}
+
+// instanceCount += readyCount (mesh.cpp:174): the drawn meshes' own counts, summed over the fetched list (or, for a count-only
+// main pass, over the isVisible bytes); a count-only shadow view keeps draw_count. The ready column is indexed by pool slot, so
+// results in world slots are not available together with it.
+static int count_instances(GvCtx* ctx, const ViewState& vs, const PoolState& pool, uint32_t count, GvResult* out)
+{
+    if (pool.ready.ptr && pool.result_flags)
+        return ctx->fail(GV_E_STATE, "gv_results_fetch: pool %u has a ready column AND a result mapping (records / isVisible in world slots): not available "
+                         "together", vs.pool_id);
+    if (!pool.ready.ptr || !pool.bound || pool.occupancy != vs.occupancy || !count)
+        return GV_OK;
+    if (vs.emitted) {
+        out->instance_count = parallel_sum(count, [&](uint32_t k) { return pool.ready_count(fetched_slot(vs, pool, k)); });
+    } else if (vs.main_pass && vs.occupancy) {
+        const uint8_t* vis = vs.h_is_visible.ptr;
+        out->instance_count = parallel_sum(vs.occupancy, [&](uint32_t i) { return vis[i] ? pool.ready_count(i) : 0u; });
+    }
+    return GV_OK;
+}
+
+// The main pass's isVisible bytes arrive in pool-slot order; write_back streams them into the components themselves
+// (meshRenderView->isVisible = ...  mesh.cpp:144,152,161,166) or, with GV_RESULTS_MAP_VISIBLE, straight into the caller's WORLD pool
+// through the share's slot -> world slot table (holes and slots past the world's occupancy are skipped; ranks own disjoint world
+// slots). Every store is a cache line of its own: the workers pay from kWriteBackFloor components up (profiles/r06_write_back_ab.txt).
+constexpr uint32_t kWriteBackFloor = 49152;
+static int write_back_visible(GvCtx* ctx, const ViewState& vs, const PoolState& pool, int write_back, GvResult* out)
+{
+    if (!vs.main_pass || !vs.occupancy)
+        return GV_OK;
+    if (write_back && (!pool.bound || pool.occupancy != vs.occupancy))
+        return ctx->fail(GV_E_STATE, "gv_results_fetch: pool %u rebound since gv_cull", vs.pool_id);
+    uint8_t* out_vis = vs.h_is_visible.ptr;
+    if (write_back && (pool.result_flags & GV_RESULTS_MAP_VISIBLE)) {
+        if (pool.h_index_map.size() < vs.occupancy || !pool.visible_base)
+            return ctx->fail(GV_E_STATE, "gv_results_fetch: pool %u writes isVisible through its index map (gv_pool_set_result_mapping), which covers %zu "
+                             "of %u slots", vs.pool_id, pool.h_index_map.size(), vs.occupancy);
+        const uint32_t* map = pool.h_index_map.data();
+        uint8_t* base = pool.visible_base;
+        const size_t stride = pool.visible_stride;
+        const uint32_t limit = pool.visible_count;
+        parallel_ranges(0, vs.occupancy, [&](uint32_t a, uint32_t b) {
+            for (uint32_t i = a; i < b; i++)
+                if (map[i] < limit)  // (GV_NONE: a hole)
+                    base[(size_t)map[i] * stride] = out_vis[i];
+        }, kWriteBackFloor);
+    } else if (write_back && pool.is_visible) {
+        uint8_t* component_vis = pool.is_visible;
+        const size_t component_stride = pool.is_visible_stride;
+        parallel_ranges(0, vs.occupancy, [&](uint32_t a, uint32_t b) {
+            for (uint32_t i = a; i < b; i++)
+                component_vis[(size_t)i * component_stride] = out_vis[i];
+        }, kWriteBackFloor);
+    }
+    out->is_visible = out_vis;
+    return GV_OK;
 }
 
 }  // namespace gv
@@ -381,240 +644,28 @@ int gv_results_fetch(GvCtx* ctx, uint32_t view_index, int write_back, GvResult* 
     return ctx ? gv_pool_results_fetch(ctx, ctx->last_pool, view_index, write_back, out) : GV_E_ARG;
 }
 
-// a byte per component at the component's stride: every store is a cache line of its own
-#ifndef GV_WRITE_BACK_FLOOR  // (A/B builds)
-#define GV_WRITE_BACK_FLOOR 49152
-#endif
-constexpr uint32_t kWriteBackFloor = GV_WRITE_BACK_FLOOR;
-
 int gv_pool_results_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, int write_back, GvResult* out)
 {
     if (!ctx)
         return GV_E_ARG;
-    if (!out)
-        return ctx->fail(GV_E_ARG, "gv_results_fetch: out is NULL");
-    if (!view_of(ctx, pool_id, view_index))
-        return ctx->fail(GV_E_ARG, "gv_results_fetch: pool %u view %u has no results", pool_id, view_index);
+    if (int rc = validate_fetch(ctx, pool_id, view_index, out))
+        return rc;
     if (int rc = flush_sorts(ctx))
         return rc;
     ViewState& vs = *view_of(ctx, pool_id, view_index);
-    PoolState& pool = ctx->pools[vs.pool_id];
-    const bool permuted = !pool.perm.empty() && pool.perm.size() == vs.occupancy;
+    const PoolState& pool = ctx->pools[vs.pool_id];
     const bool small = vs.occupancy != 0 && vs.occupancy <= kPublishMaxSlots;
-    auto reserve_records = [&]() -> int {
-        GV_HIP(ctx, vs.h_visible_idx.reserve(vs.occupancy));
-        GV_HIP(ctx, vs.h_baked_model.reserve((size_t)vs.occupancy * 12));
-        GV_HIP(ctx, vs.h_distance_sq.reserve(vs.occupancy));
-        return GV_OK;
-    };
-    const bool want_vis = vs.main_pass && vs.occupancy;
-    if (want_vis)
-        GV_HIP(ctx, vs.h_is_visible.reserve(vs.occupancy));
-    uint32_t count = 0;
-    if (small) {
-        // engine-sized pools are launch- and round-trip-bound: one kernel writes count, records and isVisible of EVERY
-        // view of this cull (the main camera and its shadow passes are fetched one after the other, mesh.cpp:809-843)
-        // straight into the pinned host buffers, one synchronisation ends the frame; the sibling views' fetches find
-        // their results already there
-        if (!vs.published || ctx->publish_sync_pending) {
-            GV_HIP(ctx, hipSetDevice(ctx->device));
-            static_assert(kMaxPublishViews >= GV_MAX_VIEWS, "PublishBatch holds at least one pool's views");
-            // ... of EVERY pool culled since the last fetch: a frame that culls all its mesh systems first and reads
-            // afterwards (gv_pool_results_fetch) ends with this one launch and one synchronisation. Views whose small-pool
-            // sort has published them already (flush_sorts) only wait for that synchronisation.
-            PublishBatch batch{};
-            uint32_t views = 0, widest = 0;
-            ViewState* sent[kMaxPublishViews];
-            for (uint32_t q = 0; q < GV_MAX_POOLS && views < kMaxPublishViews; q++) {
-                const uint32_t pid = (pool_id + q) % GV_MAX_POOLS;  // the pool asked for first: it always fits
-                for (uint32_t v = 0; v < GV_MAX_VIEWS && views < kMaxPublishViews; v++) {
-                    ViewState& w = ctx->views[pid][v];
-                    if (!w.valid || w.published || w.occupancy == 0 || w.occupancy > kPublishMaxSlots)
-                        continue;
-                    if (int rc = publish_args_of(ctx, pid, v, batch.view[views]))
-                        return rc;
-                    widest = std::max(widest, w.occupancy);
-                    sent[views++] = &w;
-                }
-            }
-            if (views)
-                GV_HIP(ctx, launch_publish(batch, views, widest, ctx->stream));
-            if (int rc = wait_for_stream(ctx))
-                return rc;
-            drain_events(ctx);
-            ctx->publish_sync_pending = false;
-            for (uint32_t k = 0; k < views; k++)
-                sent[k]->published = true;
-            // record targets are the caller's pageable arrays: the records cross the host once more, from the pinned buffer the publish
-            // kernel wrote. All views of the frame in ONE pass — in 256 KB pieces over the worker threads from 1 MB up (seven mesh
-            // systems' lists at 10^6 entities: 8 MB, ~1 ms of one thread)
-            struct Piece {
-                uint8_t* to;
-                const uint8_t* from;
-                size_t bytes;
-            };
-            std::vector<Piece> pieces;
-            size_t staged_bytes = 0;
-            constexpr size_t kPiece = (size_t)256 << 10;
-            for (auto& per_pool : ctx->views)
-                for (ViewState& w : per_pool)
-                    if (w.valid && w.published && w.records_staged) {
-                        const size_t bytes = (size_t)w.h_draw_count.ptr[0] * ctx->pools[w.pool_id].record_layout.stride;
-                        if (bytes && !range_mapped(w.records_at, bytes))
-                            return ctx->fail(GV_E_STATE, "gv_results_fetch: the record target of pool %u is not mapped any more (freed while it was "
-                                                         "still the target?)", w.pool_id);
-                        for (size_t at = 0; at < bytes; at += kPiece)
-                            pieces.push_back(Piece{w.records_at + at, w.h_records.ptr + at, std::min(kPiece, bytes - at)});
-                        staged_bytes += bytes;
-                        w.records_staged = false;
-                    }
-            const uint32_t parts = staged_bytes >= ((size_t)1 << 20) ? std::min<uint32_t>((uint32_t)pieces.size(), worker_parts((size_t)1 << 30)) : 1u;
-            run_parts(parts, [&](uint32_t t) {
-                for (size_t k = t; k < pieces.size(); k += parts)
-                    memcpy(pieces[k].to, pieces[k].from, pieces[k].bytes);
-            });
-        }
-        count = vs.h_draw_count.ptr[0];
-    } else {
-        int rc = gv_pool_result_count(ctx, pool_id, view_index, &count);
-        if (rc != GV_OK)
-            return rc;
-        if (vs.emitted && pool.record_layout.stride)
-            vs.records_fetched = true;
-        const PoolState::RecordTarget& target = pool.record_target[view_index];
-        uint8_t* staged_for = nullptr;  // a target that could not be page-locked: filled from h_records after the copies
-        if (vs.emitted && pool.record_layout.stride) {
-            const size_t need = (size_t)vs.occupancy * pool.record_layout.stride;
-            if (target.host && target.bytes < need)
-                return ctx->fail(GV_E_ARG, "gv_results_fetch: the record target of pool %u view %u holds %zu bytes, occupancy * stride = %zu",
-                                 pool_id, view_index, target.bytes, need);
-            GV_HIP(ctx, vs.h_records.reserve(need));
-            vs.records_at = target.host ? target.host : vs.h_records.ptr;
-        }
-        if (vs.emitted && count && pool.record_layout.stride) {  // packed on the device, one copy
-            const size_t bytes = (size_t)count * pool.record_layout.stride;
-            GV_HIP(ctx, vs.d_records.reserve((size_t)vs.occupancy * pool.record_layout.stride));
-            RecordLayout delivered;
-            if ((rc = delivered_layout(ctx, pool, pool_id, vs.occupancy, delivered)) != GV_OK)
-                return rc;
-            GV_HIP(ctx, launch_pack_records(vs.draw_count.ptr, vs.visible_idx.ptr, vs.baked_model.ptr, vs.distance_sq.ptr, delivered,
-                                            count, vs.d_records.ptr, ctx->stream));
-            staged_for = target.host;
-            GV_HIP(ctx, hipMemcpyAsync(vs.h_records.ptr, vs.d_records.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        } else if (vs.emitted && count) {
-            if ((rc = reserve_records()) != GV_OK)
-                return rc;
-            GV_HIP(ctx, hipMemcpyAsync(vs.h_visible_idx.ptr, vs.visible_idx.ptr, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
-            GV_HIP(ctx, hipMemcpyAsync(vs.h_baked_model.ptr, vs.baked_model.ptr, (size_t)count * 48, hipMemcpyDeviceToHost, ctx->stream));
-            GV_HIP(ctx, hipMemcpyAsync(vs.h_distance_sq.ptr, vs.distance_sq.ptr, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (want_vis) {
-            const uint8_t* src = vs.is_visible.ptr;
-            if (permuted) {  // back into pool-slot order on the device: the random half of the write-back
-                GV_HIP(ctx, vs.is_visible_slots.reserve(vs.occupancy));
-                GV_HIP(ctx, launch_unpermute_bytes(vs.is_visible.ptr, pool.d_orig.ptr, vs.occupancy, vs.is_visible_slots.ptr, ctx->stream));
-                src = vs.is_visible_slots.ptr;
-            }
-            GV_HIP(ctx, hipMemcpyAsync(vs.h_is_visible.ptr, src, vs.occupancy, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (staged_for) {
-            if (!range_mapped(staged_for, (size_t)count * pool.record_layout.stride))
-                return ctx->fail(GV_E_STATE, "gv_results_fetch: the record target of pool %u is not mapped any more (freed while it was still "
-                                             "the target?)", pool_id);
-            // (the caller's array is pageable: the records cross the host once more — on the worker threads from 128 Ki records up,
-            // 14 MB at 10^6 entities was ~1 ms of one thread)
-            const size_t stride = pool.record_layout.stride;
-            uint8_t* const from = vs.h_records.ptr;
-            parallel_ranges(0, count, [&](uint32_t a, uint32_t b) { memcpy(staged_for + (size_t)a * stride, from + (size_t)a * stride, (size_t)(b - a) * stride); });
-        }
-    }
+    std::vector<StagedCopy> staged;
+    if (int rc = small ? deliver_small(ctx, pool_id, vs, staged) : deliver_large(ctx, pool_id, view_index, staged))
+        return rc;
+    if (int rc = copy_staged_records(ctx, staged))
+        return rc;
+    const uint32_t count = vs.h_draw_count.ptr[0];
     vs.count_hint = count;  // (what the next frame's sort of this view expects)
-    memset(out, 0, sizeof(*out));
-    out->draw_count = count;
-    out->instance_count = count;  // default getReadyMeshesAsync returns 0/1 (render/mesh.hpp:142-146)
-    const bool as_records = vs.emitted && vs.records_fetched;
-    if (vs.emitted && count && !as_records) {
-        out->visible_idx = vs.h_visible_idx.ptr;
-        out->baked_model = vs.h_baked_model.ptr;
-        out->distance_sq = vs.h_distance_sq.ptr;
-    }
-    if (pool.ready.ptr && pool.result_flags)
-        return ctx->fail(GV_E_STATE, "gv_results_fetch: pool %u has a ready column AND a result mapping (records / isVisible in world slots): not available "
-                         "together", pool_id);
-    if (pool.ready.ptr && pool.bound && pool.occupancy == vs.occupancy && count) {
-        // instanceCount += readyCount (mesh.cpp:174): the drawn meshes' own counts, summed over the fetched list (or, for
-        // a count-only main pass, over the isVisible bytes); a count-only shadow view keeps draw_count
-        std::atomic<uint64_t> total{0};
-        if (as_records) {  // the slot is componentOffset / component size
-            const RecordLayout L = pool.record_layout;
-            const uint8_t* field = vs.records_at + L.component_offset;
-            parallel_ranges(0, count, [&](uint32_t a, uint32_t b) {
-                uint64_t sum = 0;
-                for (uint32_t k = a; k < b; k++) {
-                    uint64_t offset;
-                    memcpy(&offset, field + (size_t)k * L.stride, 8);
-                    sum += pool.ready_count((uint32_t)(offset / L.component_stride));
-                }
-                total += sum;
-            });
-            out->instance_count = (uint32_t)total.load();
-        } else if (vs.emitted) {
-            const uint32_t* idx = vs.h_visible_idx.ptr;
-            parallel_ranges(0, count, [&](uint32_t a, uint32_t b) {
-                uint64_t sum = 0;
-                for (uint32_t k = a; k < b; k++)
-                    sum += pool.ready_count(idx[k]);
-                total += sum;
-            });
-            out->instance_count = (uint32_t)total.load();
-        } else if (want_vis) {
-            const uint8_t* vis = vs.h_is_visible.ptr;
-            parallel_ranges(0, vs.occupancy, [&](uint32_t a, uint32_t b) {
-                uint64_t sum = 0;
-                for (uint32_t i = a; i < b; i++)
-                    if (vis[i])
-                        sum += pool.ready_count(i);
-                total += sum;
-            });
-            out->instance_count = (uint32_t)total.load();
-        }
-    }
-    if (vs.main_pass && vs.occupancy) {
-        // the bytes arrive in pool-slot order; write_back streams them into the components themselves:
-        // meshRenderView->isVisible = ...  mesh.cpp:144,152,161,166
-        uint8_t* component_vis = nullptr;
-        size_t component_stride = 0;
-        if (write_back) {
-            if (!pool.bound || pool.occupancy != vs.occupancy)
-                return ctx->fail(GV_E_STATE, "gv_results_fetch: pool %u rebound since gv_cull", vs.pool_id);
-            component_vis = pool.is_visible;
-            component_stride = pool.is_visible_stride;
-        }
-        uint8_t* out_vis = vs.h_is_visible.ptr;
-        if (write_back && (pool.result_flags & GV_RESULTS_MAP_VISIBLE)) {
-            // straight into the caller's WORLD pool, through the share's slot -> world slot table (holes and slots past the world's
-            // occupancy are skipped); ranks own disjoint world slots
-            if (pool.h_index_map.size() < vs.occupancy || !pool.visible_base)
-                return ctx->fail(GV_E_STATE, "gv_results_fetch: pool %u writes isVisible through its index map (gv_pool_set_result_mapping), which covers %zu "
-                                 "of %u slots", pool_id, pool.h_index_map.size(), vs.occupancy);
-            const uint32_t* map = pool.h_index_map.data();
-            uint8_t* base = pool.visible_base;
-            const size_t stride = pool.visible_stride;
-            const uint32_t limit = pool.visible_count;
-            parallel_ranges(0, vs.occupancy, [&](uint32_t a, uint32_t b) {
-                for (uint32_t i = a; i < b; i++)
-                    if (map[i] < limit)  // (GV_NONE: a hole)
-                        base[(size_t)map[i] * stride] = out_vis[i];
-            }, kWriteBackFloor);
-        } else if (component_vis)
-            parallel_ranges(0, vs.occupancy, [&](uint32_t a, uint32_t b) {
-                for (uint32_t i = a; i < b; i++)
-                    component_vis[(size_t)i * component_stride] = out_vis[i];
-            }, kWriteBackFloor);
-        out->is_visible = out_vis;
-    }
-    return GV_OK;
+    fill_result(vs, count, out);
+    if (int rc = count_instances(ctx, vs, pool, count, out))
+        return rc;
+    return write_back_visible(ctx, vs, pool, write_back, out);
 }
 
 int gv_pool_set_record_layout(GvCtx* ctx, uint32_t pool_id, const GvRecordLayout* layout)
@@ -725,15 +776,6 @@ int gv_pool_results_instance_bases(GvCtx* ctx, uint32_t pool_id, uint32_t view_i
     vs.instance_bases.resize((size_t)n + 1);
     uint32_t* out = vs.instance_bases.data();
     const bool counted = pool.ready.ptr && pool.bound && pool.occupancy == vs.occupancy;
-    const bool as_records = vs.records_fetched;
-    const RecordLayout L = pool.record_layout;
-    auto slot_of = [&](uint32_t k) -> uint32_t {
-        if (!as_records)
-            return vs.h_visible_idx.ptr[k];
-        uint64_t offset;
-        memcpy(&offset, vs.records_at + (size_t)k * L.stride + L.component_offset, 8);
-        return (uint32_t)(offset / L.component_stride);
-    };
     // exclusive prefix in two passes over fixed chunks: chunk sums in parallel, their prefix serially, the fill in parallel
     constexpr uint32_t kChunk = 1u << 16;
     const uint32_t chunks = (n + kChunk - 1) / kChunk;
@@ -743,7 +785,7 @@ int gv_pool_results_instance_bases(GvCtx* ctx, uint32_t pool_id, uint32_t view_i
             for (uint32_t c = ca; c < cb; c++) {
                 uint64_t sum = 0;
                 for (uint32_t k = c * kChunk, e = std::min(n, (c + 1) * kChunk); k < e; k++)
-                    sum += pool.ready_count(slot_of(k));
+                    sum += pool.ready_count(fetched_slot(vs, pool, k));
                 chunk_base[c + 1] = sum;
             }
         });
@@ -757,7 +799,7 @@ int gv_pool_results_instance_bases(GvCtx* ctx, uint32_t pool_id, uint32_t view_i
             uint32_t at = (uint32_t)chunk_base[c];
             for (uint32_t k = c * kChunk, e = std::min(n, (c + 1) * kChunk); k < e; k++) {
                 out[k] = at;
-                at += counted ? pool.ready_count(slot_of(k)) : 1u;
+                at += counted ? pool.ready_count(fetched_slot(vs, pool, k)) : 1u;
             }
         }
     });

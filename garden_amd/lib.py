@@ -484,11 +484,11 @@ class GpuVisibility:
         and in place; None removes the target): the engine's own combinedMeshes instead of the library's buffer."""
         if array is None:
             self._check(self.lib.gv_pool_set_record_target(self.ctx, pool_id, view_index, None, 0))
-            self._keep.pop(("target", pool_id, view_index), None)  # (only now: the call above synchronises and un-registers)
+            self._keep.pop(("target", pool_id, view_index), None)  # (only now: the call above checks that the range is still mapped)
             return
         assert array.flags["C_CONTIGUOUS"] and array.flags["WRITEABLE"]
         self._check(self.lib.gv_pool_set_record_target(self.ctx, pool_id, view_index, array.ctypes.data, array.nbytes))
-        self._keep[("target", pool_id, view_index)] = array  # page-locked and written by the device until replaced / removed / close()
+        self._keep[("target", pool_id, view_index)] = array  # the fetch copies the records into it (never page-locked) until replaced / removed / close()
 
     def instance_bases(self, pool_id=0, view_index=0):
         """First instance index of every fetched record ([count + 1] words; the last one is instance_count)."""

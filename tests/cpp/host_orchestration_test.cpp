@@ -1771,6 +1771,56 @@ static void exchange_bounded_waits()
                 "GV_E_TIMEOUT, destroy returns; the context recovers: ok\n");
 }
 
+// Two pools on the two sides of the publish launch's size limit — 3 000 slots (one launch for all small views) and 300 000 (device pack +
+// one copy) — with a record layout and a record target each, fetched in the same frame: both ways of delivering place their records
+// by the same rule. A too-small target fails the fetch that places it (for a small pool: the fetch that gathers it, also a
+// sibling's) with GV_E_ARG, and no other. Kernels are no-ops here: codes and bounds only.
+static void record_targets_on_both_delivery_paths()
+{
+    GvConfig cfg{(uint32_t)sizeof(GvConfig), 0, GV_HIZ_RULE_REFERENCE, 0};
+    GvCtx* ctx = nullptr;
+    CHECK(gv_create(&cfg, &ctx));
+    World w;
+    w.build(300000, 0);
+    const uint32_t sizes[2] = {3000, 300000};  // pool 0: the first 3 000 components; pool 1: all of them
+    const GvTransformLayout tl = transform_layout();
+    const GvMeshLayout ml = mesh_layout();
+    const GvRecordLayout layout{64, 0, 8, 56, GV_NONE, (uint32_t)sizeof(Mesh), 0};
+    CHECK(gv_transform_bind(ctx, w.xf.data(), sizeof(Transform), (uint32_t)w.xf.size(), &tl, w.e2t.data(), (uint32_t)w.e2t.size()));
+    auto aligned = [](std::vector<uint8_t>& v) { return reinterpret_cast<void*>(((uintptr_t)v.data() + 15) & ~(uintptr_t)15); };
+    std::vector<uint8_t> target[2][2], small[2];  // [pool][view]
+    for (uint32_t p = 0; p < 2; p++) {
+        CHECK(gv_pool_bind(ctx, p, w.meshes.data(), sizeof(Mesh), sizes[p], &ml));
+        CHECK(gv_pool_set_record_layout(ctx, p, &layout));
+        for (auto& t : target[p])
+            t.resize((size_t)sizes[p] * 64 + 16);
+        small[p].resize((size_t)sizes[p] * 64 - 64 + 16);
+    }
+    // too_small: none / pool 1 view 0 (the large path's own view) / pool 0 view 1 (a sibling of the small view that is fetched)
+    const int too_small[3][2] = {{-1, -1}, {1, 0}, {0, 1}};
+    const int expected[3][2] = {{GV_OK, GV_OK}, {GV_OK, GV_E_ARG}, {GV_E_ARG, GV_OK}};
+    for (int round = 0; round < 3; round++) {
+        GvView views[2] = {make_view(-1, 0, 1), make_view(0, 0, 1)};
+        for (uint32_t p = 0; p < 2; p++) {
+            for (uint32_t v = 0; v < 2; v++) {
+                const bool shrink = too_small[round][0] == (int)p && too_small[round][1] == (int)v;
+                std::vector<uint8_t>& t = shrink ? small[p] : target[p][v];
+                CHECK(gv_pool_set_record_target(ctx, p, v, aligned(t), t.size() - 16));
+            }
+            CHECK(gv_cull(ctx, p, views, 2));
+        }
+        for (uint32_t p : {1u, 0u}) {  // (the large pool first: the small path's gather must not have touched it)
+            GvResult r{};
+            EXPECT(gv_pool_results_fetch(ctx, p, 0, 0, &r), expected[round][p]);
+        }
+    }
+    for (uint32_t p = 0; p < 2; p++)
+        for (uint32_t v = 0; v < 2; v++)
+            CHECK(gv_pool_set_record_target(ctx, p, v, nullptr, 0));
+    gv_destroy(ctx);
+    std::printf("record targets on both delivery paths: ok\n");
+}
+
 int main(int argc, char** argv)
 {
     if (argc > 1) {  // schedule files (tests/schedules.py): replayed instead of the fixed exercise
@@ -1824,6 +1874,7 @@ int main(int argc, char** argv)
             }
         std::printf("host workers (gv_host_parallel_tasks / _ranges): ok\n");
     }
+    record_targets_on_both_delivery_paths();
     allocation_failures();
     exchange_allocation_failures(false);
     exchange_allocation_failures(true);
