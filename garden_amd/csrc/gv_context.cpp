@@ -136,6 +136,8 @@ static float2* mip_ptr(GvCtx* ctx, uint32_t k)
     return ctx->d_mips.ptr + ctx->mip_off[k];
 }
 
+// (The branch conditions below are restated in Python as hiz_plan, tests/hiz_paths_support.py: tests/test_hiz_plan_census.py proves
+// from it that the sizes the GPU tests build reach every branch. Change a condition here and restate it there.)
 int hiz_reduce(GvCtx* ctx)
 {
     const bool rg16f = (ctx->config.flags & GV_CONFIG_HIZ_RG16F) != 0;

@@ -738,7 +738,16 @@ class GpuVisibility:
         return out
 
     # ---- Hi-Z ----
-    def hiz_build(self, depth):
+    def hiz_build(self, depth, mem_kind=GV_MEM_HOST):
+        """mem_kind=GV_MEM_DEVICE: `depth` is a contiguous fp32 [height, width] tensor on this context's device (anything with
+        data_ptr(), shape and is_contiguous(), e.g. a torch tensor). It is not copied: the pyramid, hiz_rebuild and the queries
+        read it where it is, so the caller keeps it alive and orders its own writes to it against the library's stream."""
+        if mem_kind == GV_MEM_DEVICE:
+            height, width = depth.shape
+            if not depth.is_contiguous() or depth.element_size() != 4 or not depth.is_floating_point():
+                raise ValueError("hiz_build(GV_MEM_DEVICE): a contiguous fp32 [height, width] device tensor is required")
+            self._check(self.lib.gv_hiz_build(self.ctx, depth.data_ptr(), width, height, GV_MEM_DEVICE))
+            return
         d = np.ascontiguousarray(depth, dtype=np.float32)
         self._check(self.lib.gv_hiz_build(self.ctx, d.ctypes.data, d.shape[1], d.shape[0], GV_MEM_HOST))
 
