@@ -722,6 +722,9 @@ void gv_destroy(GvCtx* ctx)
         ctx->upload_done = nullptr;
     }
     ctx->d_xinv.release(); ctx->sc_xf.release(); ctx->dsc_xf.release(); ctx->sc_mesh.release(); ctx->dsc_mesh.release(); ctx->dsc_a.release(); ctx->dsc_c.release(); ctx->d_pick_keys.release(); ctx->h_pick_keys.release();
+    for (auto& m : ctx->merges) {
+        m.d_records.release(); m.d_counts.release(); m.h_records.release(); m.h_counts.release();
+    }
     ctx->d_depth.release(); ctx->d_mips.release(); ctx->d_mip_offset.release(); ctx->d_tick.release(); ctx->h_done.release();
     for (int k = 0; k < 2; k++) {
         ctx->h_tick[k].release();
@@ -978,6 +981,7 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
         vs.valid = true;
         vs.published = false, vs.records_fetched = false;
         vs.sort_pending = 0;  // a sort of the previous results that nobody asked for any more
+        vs.sorted_dir = 0;
         vs.ballots_current = true;  // every cull launch but the one-launch cull + emit of a small pool writes them
         memcpy(vs.view_proj, views[v].view_proj, sizeof(vs.view_proj));
         build_view_params(views[v], &vps[v]);
@@ -985,6 +989,9 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
             GV_HIP(ctx, hipMemsetAsync(vs.draw_count.ptr, 0, 4, ctx->stream));
     }
     p.instances.views = 0;  // the views' results are replaced from here on: the instance data made from the previous ones ends
+    for (auto& m : ctx->merges)  // ... and so does every merged array this pool is a member of (gv_merge_sorted)
+        if ((m.pools >> pool_id) & 1u)
+            m.valid = false;
     // gv_cull_batch_begin: an engine-sized pool whose views all want records is only RECORDED here; the first read
     // launches every recorded cull together (flush_culls)
     if (ctx->cull_batching) {

@@ -341,6 +341,8 @@ struct ViewState {
     size_t sort_set_words = 0; // size of one set as laid out in sort_hist (0: not initialised)
     DeviceBuf<uint16_t> sort_ranks;
     uint8_t sort_pending = 0;  // small pool: gv_sort asked for (1 ascending, 2 descending), not launched yet (flush_sorts)
+    uint8_t sorted_dir = 0;    // the direction of the last gv_pool_sort since this view's cull (1 ascending, 2 descending; 0: none):
+                               // what gv_merge_sorted asks of a member
     bool published = false;  // small pool: the host buffers already hold this view's results (gv_results_fetch of a sibling view)
 };
 
@@ -398,6 +400,19 @@ struct Context {
     DeviceBuf<float2> dsc_c;         // ... and of gv_debug_stream_peak (its sink)
     DeviceBuf<unsigned long long> d_pick_keys;  // gv_pick: one key per ray (its own: no cull buffer is touched)
     PinnedBuf<unsigned long long> h_pick_keys;
+
+    // gv_merge_sorted (gv_merge.cpp): one result slot per group id; buffers of their own, no member's result is touched
+    struct MergeSlot {
+        bool valid = false;             // merged since the last gv_cull of any member pool
+        uint32_t pools = 0;             // bit p: pool p is a member
+        uint32_t items = 0, stride = 0;
+        uint8_t* target = nullptr;      // d_records.ptr or the caller's device memory
+        uint32_t capacity = 0;          // records the target holds
+        DeviceBuf<uint8_t> d_records;   // the library-owned target
+        DeviceBuf<uint32_t> d_counts;   // [items + 1]
+        PinnedBuf<uint8_t> h_records;   // staging of gv_merge_fetch
+        PinnedBuf<uint32_t> h_counts;
+    } merges[GV_MAX_MERGE_GROUPS];
 
     PoolState pools[GV_MAX_POOLS];
     // results are kept per (pool, view): every mesh system's cull can be issued before the first result is read

@@ -993,6 +993,7 @@ int gv_pool_sort(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, int descendi
         return ctx->fail(GV_E_ARG, "gv_sort: pool %u view %u has no emitted records", pool_id, view_index);
     ZoneScope zone("Meshes Sort");
     ViewState& vs = *view_of(ctx, pool_id, view_index);
+    vs.sorted_dir = descending ? 2 : 1;
     if (vs.occupancy == 0)
         return GV_OK;
     // launched with the other views' sorts when the records are asked for: small pools share one launch, mid-sized ones one set of

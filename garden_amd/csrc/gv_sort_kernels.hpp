@@ -114,6 +114,39 @@ struct SortBatch {
 // max_capacity: the largest entry capacity (sizes the grid and the LDS key table)
 hipError_t launch_sort_small_batch(const SortBatch& batch, uint32_t views, uint32_t max_capacity, hipStream_t stream);
 
+// gv_merge_sorted (gv_merge.hip): the sorted lists of SEVERAL views merged into one array of record structs per GROUP, all groups
+// of a frame by ONE launch (blockIdx.y = list, blockIdx.x = 256 records of it). Stable k-way merge without atomics, waits or a
+// host read of a count: record i of list j finds its own place — i + the records of every other list of its group that go in
+// front of it (one binary search per other list on the sort's key order; ties: lists in front win).
+constexpr uint32_t kMergeBlock = 256;
+constexpr uint32_t kMaxMergeGroups = 12;      // GV_MAX_MERGE_GROUPS
+constexpr uint32_t kMaxMergeGroupLists = 16;  // GV_MAX_MERGE_ITEMS
+struct MergeList {
+    const uint32_t* count;     // device draw count
+    const uint32_t* idx;       // the view's records after its sort
+    const float* model;
+    const float* dist;
+    const uint32_t* slot_map;  // GV_RESULTS_MAP_RECORDS: componentOffset = slot_map[slot] * component_stride (NULL: slot itself)
+    uint32_t component_stride, buffer_index;
+};
+struct MergeGroup {
+    uint8_t* dst;
+    uint32_t* counts;          // [lists + 1]: every list's count, then the total (written by the group's first workgroup)
+    uint32_t capacity;         // records dst holds: those at or beyond it are not written
+    uint32_t first, lists;     // the group's lists: MergeLaunch::list[first .. first + lists)
+    uint32_t descending;
+    uint32_t stride, component_offset, baked_model, distance_sq, buffer_index;  // GvRecordLayout (buffer_index 0xFFFFFFFF: none)
+    uint32_t pad_;
+};
+struct MergeLaunch {
+    MergeList list[kMaxSortViews];
+    MergeGroup group[kMaxMergeGroups];
+    uint8_t group_of[kMaxSortViews];
+    uint32_t lists;
+};
+// widest: the largest occupancy of a list (sizes the grid; the device-side counts decide which workgroups have work)
+hipError_t launch_merge_sorted(const MergeLaunch& launch, uint32_t widest, hipStream_t stream);
+
 // The end of a tick's device chain without a stream synchronisation: a one-lane kernel behind everything queued so far
 // writes `value` into pinned host memory (kernels of one stream run in order, and a kernel's stores have landed when the
 // next one starts), the host polls that word. hipStreamSynchronize returns 6-11 us after the last store is visible on this

@@ -93,6 +93,7 @@ public:
     // host wall time of the prepare phase, accumulated over ticks ("Meshes Prepare" zone of the reference, by step)
     struct TickSeconds {
         double total = 0, cull = 0, sort = 0, fetch = 0, records = 0, share = 0, gather = 0;  // records: filling combinedMeshes from the fetch; share / gather: several ranks
+        double sortedDelivery = 0;  // assembling the shared sorted arrays: append's copies + the bufferIndex fix-up + mergeRuns, or (mergeOnDevice) the gv_merge_fetch calls
     } tickSeconds;
     struct RankCounters {  // several ranks: what keeping the shares current took since the system was made
         uint64_t frames = 0, deals = 0, exchanges = 0, movedTrees = 0, movedTransforms = 0, editedMeshes = 0, copiedTransforms = 0;
@@ -126,6 +127,10 @@ public:
     // true: sortMeshes (mesh.cpp:265-328) runs on the device too: unsorted buffers ascending distanceSq
     // (front to back), so the engine's std::sort over combinedMeshes can be dropped
     bool sortOnDevice = true;
+    // true (with emitRecords and sortOnDevice; one context): the shared sorted arrays — transSortedMeshes, uiSortedMeshes, every
+    // shadow pass's translucent array — are merged on the device (gv_merge_sorted: one launch for all of them behind the frame's
+    // sorts) and arrive by one gv_merge_fetch each, instead of being appended run by run and merged here. Same bytes.
+    bool mergeOnDevice = false;
     // true: every frame also leaves the world matrices of all transforms on the device (gv_get_world): the sweep
     // rides on the first pool's cull (GV_SWEEP_WITH_CULL), fused into one pass when that pool is exactly paired
     bool sweepWorldMatrices = false;
@@ -405,11 +410,72 @@ private:
         }
         if (!emitRecords)
             return 0;
+        Stopwatch delivery(tickSeconds.sortedDelivery);
         if (combined.size() < (size_t)drawIndex + r.draw_count)
             combined.resize((size_t)drawIndex + r.draw_count);
         copyRecords(combined.data() + drawIndex, r, meshSystem, pool, viewIndex, bufferIndex);
         drawIndex += r.draw_count;
         return r.draw_count;
+    }
+
+    // mergeOnDevice: a sorted system's fetch for its counters and isVisible only — its records arrive with the merged array
+    void fetchCounters(MeshBuffer* counters, IMeshRenderSystem* meshSystem, uint32_t pool, uint32_t viewIndex, bool writeBack)
+    {
+        GvResult r{};
+        Stopwatch watch(tickSeconds.fetch);
+        check(gv_pool_results_fetch(ctx, pool, viewIndex, writeBack ? 1 : 0, &r), "gv_pool_results_fetch");
+        counters->meshSystem = meshSystem;
+        counters->drawCount = r.draw_count;
+        counters->instanceCount = r.instance_count;
+    }
+
+    // mergeOnDevice: the frame's shared sorted arrays as merge groups — 0 transSortedMeshes, 1 uiSortedMeshes, 2 + s the translucent
+    // array of shadow pass s; members in ascending pool order (the order append takes them in), tagged with the index the pass
+    // gives them (mesh.cpp:252). false: the frame does not fit one gv_merge_sorted call — the host merge is kept for it.
+    struct MergePlan {
+        std::vector<std::vector<GvMergeItem>> items;  // [group id]
+        std::vector<uint64_t> occupancy;              // [group id]: sum over the members
+        std::vector<GvMergeGroup> groups;             // those with members
+    };
+    bool planDeviceMerge(MergePlan& m, uint32_t passCount) const
+    {
+        GvRecordLayout layout;
+        if (!recordLayoutOf<SortedMesh>(layout, 1, (uint32_t)offsetof(SortedMesh, bufferIndex), 0) || 2 + passCount > GV_MAX_MERGE_GROUPS)
+            return false;
+        m.items.assign(2 + passCount, {});
+        m.occupancy.assign(2 + passCount, 0);
+        uint32_t total = 0;
+        for (uint32_t p = 0; p < plan.size(); p++) {
+            const SystemPlan& sp = plan[p];
+            if (!sp.sorted)
+                continue;
+            for (uint32_t v = 0; v < sp.passes.size(); v++, total++) {
+                const uint32_t g = sp.passes[v] >= 0 ? 2u + (uint32_t)sp.passes[v] : (sp.type == MeshRenderType::UI ? 1u : 0u);
+                m.items[g].push_back(GvMergeItem{p, v, sp.passes[v] >= 0 ? sp.shadowIndex : sp.bufferIndex,
+                                                 (uint32_t)sp.meshSystem->getMeshComponentSize()});
+                m.occupancy[g] += sp.occupancy;
+            }
+        }
+        if (total > 32)
+            return false;
+        for (uint32_t g = 0; g < m.items.size(); g++) {
+            if (m.items[g].size() > GV_MAX_MERGE_ITEMS)
+                return false;
+            if (m.items[g].empty())
+                continue;
+            GvMergeGroup group{};
+            group.group_id = g;
+            group.item_count = (uint32_t)m.items[g].size();
+            group.items = m.items[g].data();
+            group.descending = 1;  // back to front (SortedMesh::operator<, mesh.hpp:204)
+            group.stride = layout.stride;
+            group.component_offset = layout.component_offset;
+            group.baked_model = layout.baked_model;
+            group.distance_sq = layout.distance_sq;
+            group.buffer_index = layout.buffer_index;
+            m.groups.push_back(group);
+        }
+        return true;
     }
 
     // sortMeshes for a shared array (mesh.cpp:296-326): every system's run arrives back-to-front from gv_sort, so a
@@ -667,6 +733,13 @@ private:
         }
         if (sweepWorldMatrices && !sweepRequested)  // no system is drawn this frame: the cache is kept current all the same
             check(gv_sweep(ctx, sweepIncremental ? GV_SWEEP_INCREMENTAL : GV_SWEEP_VALU), "gv_sweep");
+        // ... and ONE merge launch for all the frame's shared sorted arrays behind the sorts (the frame's first read)
+        MergePlan merge;
+        const bool deviceMerge = mergeOnDevice && emitRecords && sortOnDevice && planDeviceMerge(merge, passCount);
+        if (deviceMerge && !merge.groups.empty()) {
+            Stopwatch watch(tickSeconds.sort);
+            check(gv_merge_sorted(ctx, merge.groups.data(), (uint32_t)merge.groups.size()), "gv_merge_sorted");
+        }
 
         // Phase 2 — read the results (the first fetch publishes every small pool's views at once).
         for (uint32_t p = 0; p < meshSystems.size(); p++) {
@@ -676,13 +749,20 @@ private:
             if (sp.sorted) {
                 const uint32_t bufferIndex = sp.bufferIndex, shadowIndex = sp.shadowIndex;
                 for (uint32_t v = 0; v < passes.size(); v++) {
-                    if (passes[v] >= 0) {
+                    if (deviceMerge) {  // counters and isVisible; the records come with the merged arrays below
+                        if (passes[v] >= 0)
+                            fetchCounters(shadowSortedBuffers[(uint32_t)passes[v]][shadowIndex], meshSystem, p, v, false);
+                        else
+                            fetchCounters(sortedBuffers[bufferIndex], meshSystem, p, v, true);
+                    } else if (passes[v] >= 0) {
                         const uint32_t s = (uint32_t)passes[v], first = shadowTransDrawIndex[s];
                         const uint32_t added = append(shadowTransMeshes[s], shadowTransDrawIndex[s], shadowSortedBuffers[s][shadowIndex], meshSystem, p, v,
                                                       false, shadowIndex);
-                        if (shadowIndex != bufferIndex)  // (records built on the device carry the light pass's index)
+                        if (shadowIndex != bufferIndex) {  // (records built on the device carry the light pass's index)
+                            Stopwatch delivery(tickSeconds.sortedDelivery);
                             for (uint32_t k = 0; k < added; k++)
                                 shadowTransMeshes[s][first + k].bufferIndex = shadowIndex;
+                        }
                         shadowTransRuns[s].push_back(shadowTransDrawIndex[s]);
                     } else if (sp.type == MeshRenderType::UI) {
                         append(uiSortedMeshes, uiDrawIndex, sortedBuffers[bufferIndex], meshSystem, p, v, true, bufferIndex);
@@ -702,7 +782,22 @@ private:
                         fill(unsortedBuffers[sp.bufferIndex], meshSystem, p, v, true);
             }
         }
-        if (emitRecords && sortOnDevice) {
+        if (deviceMerge) {  // every shared array: grown to what its members could deliver, filled by one fetch
+            Stopwatch delivery(tickSeconds.sortedDelivery);
+            for (const GvMergeGroup& group : merge.groups) {
+                std::vector<SortedMesh>& combined = group.group_id == 0 ? transSortedMeshes
+                                                    : group.group_id == 1 ? uiSortedMeshes : shadowTransMeshes[group.group_id - 2];
+                uint32_t& drawIndex = group.group_id == 0 ? transDrawIndex
+                                      : group.group_id == 1 ? uiDrawIndex : shadowTransDrawIndex[group.group_id - 2];
+                if (combined.size() < merge.occupancy[group.group_id])
+                    combined.resize(merge.occupancy[group.group_id]);  // grown, never shrunk
+                uint32_t counts[GV_MAX_MERGE_ITEMS + 1];
+                check(gv_merge_fetch(ctx, group.group_id, combined.data(), combined.size() * sizeof(SortedMesh), counts, GV_MAX_MERGE_ITEMS + 1),
+                      "gv_merge_fetch");
+                drawIndex = counts[group.item_count];
+            }
+        } else if (emitRecords && sortOnDevice) {
+            Stopwatch delivery(tickSeconds.sortedDelivery);
             mergeRuns(transSortedMeshes, transRuns);
             mergeRuns(uiSortedMeshes, uiRuns);
             for (uint32_t s = 0; s < passCount; s++)

@@ -107,6 +107,20 @@ class GvInstanceLayout(C.Structure):
     _fields_ = [("stride", C.c_uint32), ("mvp", C.c_uint32), ("model", C.c_uint32), ("slot", C.c_uint32), ("distance_sq", C.c_uint32)]
 
 
+GV_MAX_MERGE_GROUPS = 12
+GV_MAX_MERGE_ITEMS = 16
+
+
+class GvMergeItem(C.Structure):
+    _fields_ = [("pool_id", C.c_uint32), ("view_index", C.c_uint32), ("buffer_index", C.c_uint32), ("component_stride", C.c_uint32)]
+
+
+class GvMergeGroup(C.Structure):
+    _fields_ = [("group_id", C.c_uint32), ("item_count", C.c_uint32), ("items", C.POINTER(GvMergeItem)), ("descending", C.c_uint32),
+                ("stride", C.c_uint32), ("component_offset", C.c_uint32), ("baked_model", C.c_uint32), ("distance_sq", C.c_uint32),
+                ("buffer_index", C.c_uint32), ("dst_device", C.c_void_p), ("capacity_bytes", C.c_size_t)]
+
+
 class GvColumn(C.Structure):
     _fields_ = [("data", C.c_void_p), ("stride", C.c_uint32)]
 
@@ -162,6 +176,7 @@ EXPORTS = [
     "gv_pool_results_instance_bases", "gv_profile_sampling", "gv_profile_samples", "gv_profile_kernels", "gv_pick",
     "gv_pool_set_instance_layout", "gv_pool_emit_instances", "gv_pool_instances_device", "gv_pool_instances_info", "gv_pool_instances_fetch",
     "gv_pool_bind_payload", "gv_pool_set_payload_layout",
+    "gv_merge_sorted", "gv_merge_device", "gv_merge_fetch",
 ]
 
 _lib = None
@@ -279,6 +294,9 @@ def load():
     lib.gv_pool_instances_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
     lib.gv_pool_bind_payload.argtypes = [P, u32, C.POINTER(GvPayloadField), u32, u32]
     lib.gv_pool_set_payload_layout.argtypes = [P, u32, C.POINTER(u32), u32]
+    lib.gv_merge_sorted.argtypes = [P, C.POINTER(GvMergeGroup), u32]
+    lib.gv_merge_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_merge_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -727,6 +745,60 @@ class GpuVisibility:
         if dtype is not None:
             out = out.reshape(-1).view(np.uint8)[:total * stride].view(np.dtype(dtype))
         return out, starts
+
+    # ---- the shared sorted arrays ----
+    @staticmethod
+    def merge_groups(groups):
+        """The GvMergeGroup array of `groups`: dicts with group_id, items — (pool_id, view_index, buffer_index, component_stride)
+        each —, descending, dtype (a numpy structured record type with componentOffset, bakedModel, distanceSq and optionally
+        bufferIndex; or the keys stride / component_offset / baked_model / distance_sq / buffer_index) and optionally device =
+        (device pointer, capacity in bytes). Returns (array, the item arrays it points into)."""
+        arr, keep = (GvMergeGroup * max(len(groups), 1))(), []
+        for g, d in zip(arr, groups):
+            items = (GvMergeItem * max(len(d["items"]), 1))(*[GvMergeItem(*[int(x) for x in it]) for it in d["items"]])
+            keep.append(items)
+            g.group_id, g.item_count, g.items, g.descending = int(d["group_id"]), len(d["items"]), items, 1 if d.get("descending") else 0
+            if d.get("dtype") is not None:
+                dtype = np.dtype(d["dtype"])
+                at = {name: dtype.fields[name][1] for name in dtype.names}
+                g.stride, g.component_offset, g.baked_model, g.distance_sq = dtype.itemsize, at["componentOffset"], at["bakedModel"], at["distanceSq"]
+                g.buffer_index = at.get("bufferIndex", GV_NONE)
+            else:
+                g.stride, g.component_offset, g.baked_model, g.distance_sq = (int(d[k]) for k in ("stride", "component_offset", "baked_model", "distance_sq"))
+                g.buffer_index = GV_NONE if d.get("buffer_index") is None else int(d["buffer_index"])
+            if d.get("device") is not None:
+                g.dst_device, g.capacity_bytes = int(d["device"][0]), int(d["device"][1])
+        return arr, keep
+
+    def merge_sorted(self, groups):
+        """gv_merge_sorted: the sorted lists of each group's (pool, view) members merged into one record array per group, all groups
+        by one launch on the context's stream (groups: see merge_groups)."""
+        arr, keep = self.merge_groups(groups)
+        self._check(self.lib.gv_merge_sorted(self.ctx, arr, len(groups)))
+        del keep
+        if not hasattr(self, "_merge_items"):
+            self._merge_items = {}
+        for d in groups:
+            self._merge_items[int(d["group_id"])] = len(d["items"])
+
+    def merge_device(self, group_id):
+        """(device pointer of the merged records, device pointer of uint32 counts[items + 1]) of the group's last merge"""
+        rec, counts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_merge_device(self.ctx, group_id, C.byref(rec), C.byref(counts)))
+        return rec.value, counts.value
+
+    def merged(self, group_id, dtype):
+        """gv_merge_fetch: waits for the group's merge; returns (the records [0, total) viewed as the structured `dtype`, and
+        counts[items + 1]: every member's draw count, then the total)."""
+        dtype = np.dtype(dtype)
+        counts = np.zeros(GV_MAX_MERGE_ITEMS + 1, np.uint32)
+        cp = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self.lib.gv_merge_fetch(self.ctx, group_id, None, 0, cp, len(counts)))
+        item_count = getattr(self, "_merge_items", {}).get(group_id, 0)
+        total = int(counts[item_count])
+        out = np.zeros(total * dtype.itemsize, np.uint8)
+        self._check(self.lib.gv_merge_fetch(self.ctx, group_id, out.ctypes.data, out.nbytes, cp, len(counts)))
+        return out.view(dtype), counts[:item_count + 1].copy()
 
     # ---- world matrices ----
     def sweep(self, mode=GV_SWEEP_VALU):

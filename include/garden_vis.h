@@ -458,6 +458,56 @@ int gv_pool_result_count(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint
 int gv_pool_results_device(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, GvDeviceResult* out);
 int gv_pool_sort(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, int descending);
 
+/* ---- the shared sorted arrays: the sorted lists of several mesh systems merged into ONE array, on the device ----
+ * The reference keeps one array per sorted kind — transSortedMeshes, uiSortedMeshes, one translucent array per shadow pass — into
+ * which every sorted system appends SortedMesh records tagged with its bufferIndex (mesh.cpp:247-261); one std::sort orders the
+ * whole array (mesh.cpp:296-326) and renderSorted switches system whenever bufferIndex changes (mesh.cpp:659-760).
+ * gv_merge_sorted merges the already sorted lists of up to GV_MAX_MERGE_ITEMS (pool, view) members per GROUP into one array of
+ * records, in ONE kernel launch for all groups of the call (translucent, UI, one group per shadow pass).
+ * Order: the sort's own key order on the float's bits, T(u) = u ^ ((u >> 31) ? 0xFFFFFFFF : 0x80000000) — negative distance_2d
+ * keys and -0.0 < +0.0 exactly as gv_pool_sort orders them. Ties go to the member listed first (then to the member's own order):
+ * byte for byte what std::inplace_merge of the runs, taken in list order, gives.
+ * A record is written as a fetch of a pool with a record layout writes one: component_offset (uint64 = slot * the ITEM's
+ * component_stride, through the pool's index map when it has GV_RESULTS_MAP_RECORDS), baked_model (12 floats), distance_sq (the
+ * key), buffer_index (uint32 = the ITEM's buffer_index; GV_NONE as the group's offset: the struct has none), every other byte of
+ * the stride zero. stride: a multiple of 16, 16 ... 128; fields 4-byte aligned, inside the stride, disjoint.
+ * dst_device NULL: a library-owned device buffer sized for the sum of the members' OCCUPANCIES times the stride (grown, never
+ * shrunk). dst_device non-NULL: caller-owned device memory of capacity_bytes, 16-byte aligned; records whose position is at or
+ * beyond capacity_bytes / stride are not written, the true total is still reported.
+ * Asynchronous on gv_stream(ctx); counts as a read (culls recorded since gv_cull_batch_begin and deferred sorts are launched
+ * first, as gv_pool_emit_instances documents); one launch, counted under GvStats::launches[GV_K_SORT]. No result of any member
+ * changes. A group's result is valid until the next gv_cull of any member pool.
+ * GV_E_ARG: group_count 0 or more than 32 items in all; a group_id of GV_MAX_MERGE_GROUPS or more, or listed twice; item_count 0
+ * or above GV_MAX_MERGE_ITEMS; an unbound pool or a view index beyond the pool's last cull; the same (pool, view) twice in a
+ * group; a bad stride, fields that overlap or leave the stride, a component_stride of 0; a misaligned dst_device.
+ * GV_E_STATE: a count-only member or one with no results; a member that gv_pool_sort has not sorted in the group's direction
+ * since its cull; an index map that does not cover a pool delivering GV_RESULTS_MAP_RECORDS. */
+#define GV_MAX_MERGE_GROUPS 12u
+#define GV_MAX_MERGE_ITEMS 16u /* per group; 32 per call */
+typedef struct GvMergeItem {
+    uint32_t pool_id, view_index;
+    uint32_t buffer_index;     /* SortedMesh::bufferIndex of this member's records */
+    uint32_t component_stride; /* getMeshComponentSize() of the member's system */
+} GvMergeItem;
+typedef struct GvMergeGroup {
+    uint32_t group_id;         /* < GV_MAX_MERGE_GROUPS: which result slot of the context */
+    uint32_t item_count;
+    const GvMergeItem* items;  /* merge order == tie order */
+    uint32_t descending;
+    uint32_t stride, component_offset, baked_model, distance_sq, buffer_index; /* as GvRecordLayout; buffer_index may be GV_NONE */
+    void* dst_device;          /* NULL: library-owned */
+    size_t capacity_bytes;
+} GvMergeGroup;
+int gv_merge_sorted(GvCtx* ctx, const GvMergeGroup* groups, uint32_t group_count);
+/* Device pointers of a group's last merge: the records, and uint32 counts[item_count + 1] (counts[i] = member i's draw count,
+ * counts[item_count] = the total), both written in stream order on gv_stream(ctx). GV_E_STATE: no valid result. */
+int gv_merge_device(GvCtx* ctx, uint32_t group_id, const void** records, const void** counts);
+/* Waits for the group's merge and delivers counts[0 .. item_count] (counts_capacity >= item_count + 1) and — dst_host non-NULL —
+ * the records [0, total) into the caller's array through the library's pinned staging; the caller's memory is never page-locked
+ * (the rule of gv_pool_set_record_target). GV_E_ARG when bytes < total * stride or counts_capacity is too small (nothing is
+ * written); records a caller-owned device target could not hold are not delivered either. GV_E_STATE: no valid result. */
+int gv_merge_fetch(GvCtx* ctx, uint32_t group_id, void* dst_host, size_t bytes, uint32_t* counts, uint32_t counts_capacity);
+
 /* ---- multi-GPU exchange (one process per GPU): the all-gatherv of the compacted visible lists over RCCL.
  * Replaces what the reference does inside one address space — every worker appends its range's records to the shared
  * array with `drawCount.fetch_add` + memcpy into combinedMeshes (source/system/render/mesh.cpp:177-183).
