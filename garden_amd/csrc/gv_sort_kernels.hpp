@@ -94,7 +94,7 @@ hipError_t launch_reorder_meshes(const uint32_t* order, uint32_t n, const uint32
 constexpr uint32_t kSmallSortMaxSlots = 32768;
 constexpr uint32_t kBatchSortMaxSlots = 16384;
 constexpr uint32_t kRankSortMaxRecords = 12288;
-inline bool sort_is_rank_only(uint32_t capacity, uint32_t mode) { return mode == 1u && capacity > kBatchSortMaxSlots && capacity <= 65536u; }
+inline bool sort_is_rank_only(uint32_t capacity, uint32_t mode) { return mode == 1u && capacity > kBatchSortMaxSlots && capacity <= kRankOnlyMaxSlots; }
 struct SmallSortEntry {  // one view of one small pool
     const uint32_t* count;  // device draw_count
     const uint32_t* idx_in;
