@@ -15,14 +15,38 @@ using namespace gv;
 
 namespace gv {
 
-// Buffers and launch arguments of a large sort of `vs`: inputs = the view's current records, outputs = its alternate set.
-static int sort_buffers_of(GvCtx* ctx, ViewState& vs, SortBuffers& b)
+// The records of a sort of `vs`: inputs = the view's current records, outputs = its alternate set (reserved here), which
+// swap_in_sorted makes the view's records once the sort is enqueued.
+static int sort_records_of(GvCtx* ctx, ViewState& vs, SortRecords& r)
 {
     const size_t n = vs.occupancy;  // upper bound of draw_count, known without a readback
-    const size_t nblocks = sort_tile_count((uint32_t)n);
     GV_HIP(ctx, vs.alt_idx.reserve(n));
     GV_HIP(ctx, vs.alt_model.reserve(n * 12));
     GV_HIP(ctx, vs.alt_dist.reserve(n));
+    r.count = vs.draw_count.ptr;
+    r.idx_in = vs.visible_idx.ptr;
+    r.model_in = vs.baked_model.ptr;
+    r.dist_in = vs.distance_sq.ptr;
+    r.idx_out = vs.alt_idx.ptr;
+    r.model_out = vs.alt_model.ptr;
+    r.dist_out = vs.alt_dist.ptr;
+    return GV_OK;
+}
+static void swap_in_sorted(ViewState& vs)
+{
+    std::swap(vs.visible_idx, vs.alt_idx);
+    std::swap(vs.baked_model, vs.alt_model);
+    std::swap(vs.distance_sq, vs.alt_dist);
+}
+
+// Buffers and launch arguments of a large sort of `vs`.
+static int sort_buffers_of(GvCtx* ctx, ViewState& vs, SortBuffers& b)
+{
+    const size_t n = vs.occupancy;
+    const size_t nblocks = sort_tile_count((uint32_t)n);
+    b = SortBuffers{};
+    if (int rc = sort_records_of(ctx, vs, b))
+        return rc;
     for (int k = 0; k < 2; k++) {
         GV_HIP(ctx, vs.sort_keys[k].reserve(n));
         GV_HIP(ctx, vs.sort_vals[k].reserve(n));
@@ -41,14 +65,6 @@ static int sort_buffers_of(GvCtx* ctx, ViewState& vs, SortBuffers& b)
         vs.sort_parity = 0;
     }
     GV_HIP(ctx, vs.sort_ranks.reserve(n));
-    b = SortBuffers{};
-    b.count = vs.draw_count.ptr;
-    b.idx_in = vs.visible_idx.ptr;
-    b.model_in = vs.baked_model.ptr;
-    b.dist_in = vs.distance_sq.ptr;
-    b.idx_out = vs.alt_idx.ptr;
-    b.model_out = vs.alt_model.ptr;
-    b.dist_out = vs.alt_dist.ptr;
     b.ranks = vs.sort_ranks.ptr;
     for (int k = 0; k < 2; k++) {
         b.keys[k] = vs.sort_keys[k].ptr;
@@ -68,10 +84,7 @@ static int sort_large_prepare(GvCtx* ctx, ViewState& vs, bool descending, SortBa
     const size_t n = vs.occupancy;
     if (int rc = sort_buffers_of(ctx, vs, e.b))
         return rc;
-    // the previous frame's count says what to enqueue for a mid-sized pool: a short list gets the rank sort alone
-    e.mode = vs.count_hint == 0xFFFFFFFFu ? kSortBoth
-             : vs.count_hint <= kRankOnlyHintRecords ? kSortRankOnly
-             : vs.count_hint > 2 * kRankSortMaxRecords ? kSortRadixOnly : kSortBoth;
+    e.mode = sort_mode_for_hint(vs.count_hint);
     e.capacity = (uint32_t)n;
     e.descending = descending ? 1u : 0u;
     if (!sort_is_rank_only((uint32_t)n, e.mode))
@@ -81,10 +94,7 @@ static int sort_large_prepare(GvCtx* ctx, ViewState& vs, bool descending, SortBa
 static void sort_large_done(ViewState& vs)
 {
     vs.published = false, vs.records_fetched = false;
-    // the sorted records now live in the alternate set: swap it in
-    std::swap(vs.visible_idx, vs.alt_idx);
-    std::swap(vs.baked_model, vs.alt_model);
-    std::swap(vs.distance_sq, vs.alt_dist);
+    swap_in_sorted(vs);  // the sorted records now live in the alternate set
 }
 static int sort_large(GvCtx* ctx, ViewState& vs, bool descending)
 {
@@ -296,18 +306,9 @@ static int flush_small_sorts(GvCtx* ctx)
                 ViewState& vs = ctx->views[pool][v];
                 if (!vs.valid || !vs.sort_pending)
                     continue;
-                const size_t n = vs.occupancy;
-                GV_HIP(ctx, vs.alt_idx.reserve(n));
-                GV_HIP(ctx, vs.alt_model.reserve(n * 12));
-                GV_HIP(ctx, vs.alt_dist.reserve(n));
                 SmallSortEntry& b = batch.view[views];
-                b.count = vs.draw_count.ptr;
-                b.idx_in = vs.visible_idx.ptr;
-                b.model_in = vs.baked_model.ptr;
-                b.dist_in = vs.distance_sq.ptr;
-                b.idx_out = vs.alt_idx.ptr;
-                b.model_out = vs.alt_model.ptr;
-                b.dist_out = vs.alt_dist.ptr;
+                if (int rc = sort_records_of(ctx, vs, b))
+                    return rc;
                 b.capacity = vs.occupancy;
                 b.descending = vs.sort_pending == 2 ? 1u : 0u;
                 b.fused_publish = fuse_publish ? 1u : 0u;
@@ -327,9 +328,7 @@ static int flush_small_sorts(GvCtx* ctx)
         }
         for (uint32_t k = 0; k < views; k++) {  // the sorted records now live in the alternate set: swap it in
             ViewState& vs = *taken[k];
-            std::swap(vs.visible_idx, vs.alt_idx);
-            std::swap(vs.baked_model, vs.alt_model);
-            std::swap(vs.distance_sq, vs.alt_dist);
+            swap_in_sorted(vs);
             vs.sort_pending = 0;
             if (fuse_publish) {
                 vs.published = true;  // ... once the stream has been synchronised

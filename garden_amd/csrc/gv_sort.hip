@@ -10,10 +10,10 @@ namespace gv {
 // (std::sort in the reference is unstable, so any tie order is within its contract).
 // ------------------------------------------------------------------------------------------------
 // Large pools: two launches per digit, nothing between them but the kernel boundary.
-//   sort_rank_kernel     a workgroup ranks its tile of 4096 keys (stable; wave-private LDS counters), stores every key's
+//   sort_rank_*kernel    a workgroup ranks its tile of 4096 keys (stable; wave-private LDS counters), stores every key's
 //                        rank among the tile's keys of the same digit (16 bits), the tile's 256 digit counts, and adds
 //                        them into the counts of its GROUP of 32 tiles. Pass 0 builds the keys from distanceSq.
-//   sort_scatter_kernel  reloads the tile's keys and ranks, gets the number of same-digit keys in all tiles before it
+//   sort_scatter_*kernel reloads the tile's keys and ranks, gets the number of same-digit keys in all tiles before it
 //                        as (group counts before its group) + (tile counts before it inside the group), and the digit's
 //                        total as the sum over all groups — a few dozen INDEPENDENT loads, one or two memory round trips,
 //                        no separate global histogram — reorders the tile by digit in LDS and writes
@@ -238,23 +238,20 @@ __device__ __forceinline__ void sort_rank_body(const SortPassArgs& a)
         sort_rank_tile<FIRST, kSortTile>(a, n, wcount);
 }
 
-template <bool FIRST>
-__global__ __launch_bounds__(kSortThreads) void sort_rank_kernel(const SortPassArgs a)
-{
-    sort_rank_body<FIRST>(a);
-}
-
-// Several lists per launch (launch_sort_batch): blockIdx.y picks the list, everything else is the single-list kernel — every list
-// has its own buffers, counters and device-side count; a list shorter than the grid's widest leaves its surplus workgroups at once.
+// Several lists per launch (launch_sort_lists): blockIdx.y picks the list — every list has its own buffers, counters and
+// device-side count; a list shorter than the grid's widest leaves its surplus workgroups at once. A single list is a batch of one.
 // N: entries in the argument (a launch pays for the size of its arguments).
 template <uint32_t N>
 struct SortPassBatch {
     SortPassArgs list[N];
 };
+static_assert(sizeof(SortPassBatch<1>) == sizeof(SortPassArgs), "a single list's launch carries one list's arguments");
+template <uint32_t N>
+__device__ __forceinline__ uint32_t batch_list() { return N == 1 ? 0u : blockIdx.y; }  // (a batch of one needs no workgroup id y: same registers as a kernel of one list)
 template <bool FIRST, uint32_t N>
 __global__ __launch_bounds__(kSortThreads) void sort_rank_batch_kernel(const SortPassBatch<N> batch)
 {
-    sort_rank_body<FIRST>(batch.list[blockIdx.y]);
+    sort_rank_body<FIRST>(batch.list[batch_list<N>()]);
 }
 
 struct SortScatterLds {
@@ -414,25 +411,18 @@ __device__ __forceinline__ void sort_scatter_body(const SortPassArgs& a)
         sort_scatter_tile<FIRST, LAST, kSortTile>(a, n, lds);
 }
 
-template <bool FIRST, bool LAST>
-__global__ __launch_bounds__(kSortThreads) void sort_scatter_kernel(const SortPassArgs a)
-{
-    sort_scatter_body<FIRST, LAST>(a);
-}
 template <bool FIRST, bool LAST, uint32_t N>
 __global__ __launch_bounds__(kSortThreads) void sort_scatter_batch_kernel(const SortPassBatch<N> batch)
 {
-    sort_scatter_body<FIRST, LAST>(batch.list[blockIdx.y]);
+    sort_scatter_body<FIRST, LAST>(batch.list[batch_list<N>()]);
 }
 
-// Small pools (up to kSmallSort records possible): ONE launch instead of fourteen — a tick of an engine-sized scene
+// Small pools (up to kBatchSortMaxSlots records possible): ONE launch instead of fourteen — a tick of an engine-sized scene
 // (10^4 entities) is launch-bound. Rank sort: the position of record i is the number of records that order before
 // it, (key, emission index) compared as a pair, so the result is the stable order the radix passes produce. A
 // workgroup owns 64 records; its four waves each count over a quarter of the keys (staged in LDS, read as uniform
 // 16-byte broadcasts) and the partial counts meet in LDS. n^2 / 4 comparisons per wave, all CUs busy, no
 // inter-workgroup step: ~6 us at 2 k records where a one-workgroup bitonic network took 42 us.
-constexpr uint32_t kSmallSort = kBatchSortMaxSlots;
-constexpr uint32_t kMidSortSlots = 1u << 20;  // pools up to this size also get the rank-sort launch (see launch_sort)
 
 // records of [jlo, jhi) (multiples of 4) that order before record i with key ki. WHERE: 0 = every j is below the
 // workgroup's records (ties count), 2 = every j is above them (ties do not), 1 = overlapping (compare the pair)
@@ -557,8 +547,7 @@ __device__ __forceinline__ uint32_t count_before_global(const float* __restrict_
 
 // max_records: a live count above it leaves the records to the radix kernels behind; table: the key table's capacity (LDS) —
 // counts between the two take the from-memory form above
-template <class Entry>
-__device__ __forceinline__ void sort_small_block(const Entry& b, uint32_t capacity, uint32_t descending, uint32_t block,
+__device__ __forceinline__ void sort_small_block(const SortRecords& b, uint32_t capacity, uint32_t descending, uint32_t block,
                                                  uint32_t max_records = 0xFFFFFFFFu, const PublishArgs* pub = nullptr, uint32_t table = 0xFFFFFFFFu)
 {
     extern __shared__ uint32_t key[];  // order-preserving keys of all n records, padded to a multiple of 4
@@ -628,12 +617,6 @@ __device__ __forceinline__ void sort_small_block(const Entry& b, uint32_t capaci
     }
 }
 
-__global__ __launch_bounds__(256) void sort_small_kernel(const SortBuffers b, uint32_t capacity, uint32_t descending, uint32_t max_records,
-                                                         uint32_t table)
-{
-    sort_small_block(b, capacity, descending, blockIdx.x, max_records, nullptr, table);
-}
-
 // several views of one small pool (main camera + shadow passes) in one launch: blockIdx.y picks the view. N: entries in the
 // argument — a launch pays for the size of its arguments (2.4 us with a small one, 5.8 us at 20 KB), and the 32-entry batch is
 // 6.4 KB where a tick of one mesh system uses 200 bytes of it
@@ -648,7 +631,7 @@ __global__ __launch_bounds__(256) void sort_small_batch_kernel(const SortBatchN<
     sort_small_block(e, e.capacity, e.descending, blockIdx.x, 0xFFFFFFFFu, e.fused_publish ? &e.publish : nullptr);
 }
 
-// the rank-sort launch of launch_sort for several mid-sized lists at once (launch_sort_batch): blockIdx.y picks the list
+// the rank-sort launch of the lists of launch_sort_lists: blockIdx.y picks the list
 struct MidRankEntry {
     SortBuffers b;
     uint32_t capacity, descending, max_records, table;
@@ -657,42 +640,27 @@ template <uint32_t N>
 struct MidRankBatch {
     MidRankEntry list[N];
 };
+static_assert(sizeof(MidRankBatch<1>) == 160, "the argument bytes of a single list's rank sort: 144 of buffers and four words");
 template <uint32_t N>
 __global__ __launch_bounds__(256) void sort_mid_rank_batch_kernel(const MidRankBatch<N> batch)
 {
-    const MidRankEntry& e = batch.list[blockIdx.y];
+    const MidRankEntry& e = batch.list[batch_list<N>()];
     sort_small_block(e.b, e.capacity, e.descending, blockIdx.x, e.max_records, nullptr, e.table);
 }
 
-// what launch_sort decides on the host for one list: whether it gets the rank-sort launch (and with which key table), whether the
-// radix launches, and what the device-side count leaves to which of the two
-struct SortPlan {
-    bool rank_only, rank_sort;
-    uint32_t rank_records;  // the rank-sort launch's key table (LDS words)
-    uint32_t rank_blocks;   // its workgroups
-};
-static SortPlan sort_plan(uint32_t capacity, SortMode mode)
+static void sort_pass_args(const SortBatchEntry& e, const SortPlan& plan, SortPassArgs& a)
 {
-    SortPlan p{};
-    p.rank_only = sort_is_rank_only(capacity, mode);
-    p.rank_sort = capacity <= kMidSortSlots && (mode != kSortRadixOnly || capacity <= kSmallSort);
-    p.rank_records = capacity <= kSmallSort ? capacity : (p.rank_only ? kRankOnlyTableRecords : kRankSortMaxRecords);
-    p.rank_blocks = ((p.rank_only ? capacity : p.rank_records) + 63) / 64;
-    return p;
-}
-
-static void sort_pass_args(const SortBuffers& b, uint32_t capacity, bool descending, bool rank_sort, SortPassArgs& a)
-{
+    const SortBuffers& b = e.b;
     a = SortPassArgs{};
-    a.st.groups = sort_group_count(capacity);
-    a.st.set_words = sort_set_words(capacity);
+    a.st.groups = sort_group_count(e.capacity);
+    a.st.set_words = sort_set_words(e.capacity);
     a.st.group_hist = b.counters[b.parity];
     a.st.next_set = b.counters[b.parity ^ 1u];
     a.st.tile_hist = b.tile_hist;
     a.count = b.count;
-    a.capacity = capacity;
-    a.descending = descending ? 1u : 0u;
-    a.min_records = rank_sort ? kRankSortMaxRecords : 0u;
+    a.capacity = e.capacity;
+    a.descending = e.descending;
+    a.min_records = plan.radix_min_records;
     a.dist_in = b.dist_in;
     a.idx_in = b.idx_in;
     a.model_in = b.model_in;
@@ -713,50 +681,67 @@ static void sort_pass_buffers(const SortBuffers& b, uint32_t pass, SortPassArgs&
     a.slots_out = b.slots[dst];
 }
 
+// the two launches of one digit: pass 0 builds the keys (FIRST), pass 3 writes the records (LAST)
 template <uint32_t N>
-static hipError_t launch_sort_batch_n(const SortBatchEntry* lists, uint32_t count, hipStream_t stream)
+static void launch_radix_pass(uint32_t pass, dim3 grid, hipStream_t stream, const SortPassBatch<N>& passes)
 {
-    // the rank-sort launch for every list that gets one (a list that does not: max_records 0 — its workgroups leave after one load)
+    const dim3 block(kSortThreads);
+    if (pass == 0) {
+        hipLaunchKernelGGL((sort_rank_batch_kernel<true, N>), grid, block, 0, stream, passes);
+        hipLaunchKernelGGL((sort_scatter_batch_kernel<true, false, N>), grid, block, 0, stream, passes);
+    } else {
+        hipLaunchKernelGGL((sort_rank_batch_kernel<false, N>), grid, block, 0, stream, passes);
+        if (pass == 3)
+            hipLaunchKernelGGL((sort_scatter_batch_kernel<false, true, N>), grid, block, 0, stream, passes);
+        else
+            hipLaunchKernelGGL((sort_scatter_batch_kernel<false, false, N>), grid, block, 0, stream, passes);
+    }
+}
+
+// Every sort beyond the one-launch batch of small pools: `count` <= N lists (sort_plan of each) by ONE rank-sort launch and ONE
+// set of eight radix launches.
+// Short lists sort in one launch whatever the pool's size: a pool of up to kMidSortMaxSlots slots (where only the device
+// knows how short the visible list is) gets the rank-sort launch AND the radix launches, and the live count decides on
+// the device which of the two does the work — the other leaves after one load, ~2 us per launch, against 70 us for
+// the eight radix launches on a few thousand records. Measured crossover: ~12 k records (rank 11 us at 2 k, 75 us at
+// 16 k, 160 us at 32 k).
+// kSortRankOnly (the caller expects a short list: the previous frame's count): a mid-sized pool gets the rank-sort launch
+// alone — the eight radix launches that would leave after one load each are ~16 us of an engine-sized tick — and a
+// list that outgrew the key table after all is still sorted by it, from memory (count_before_global).
+// Lists that sit out a launch others of the batch want: no rank sort — its row has max_records 0, the workgroups leave after
+// one load; no radix passes — min_records 0xFFFFFFFF, the radix launches leave this list at once (behind sort_rank_body<FIRST>'s
+// zeroing of next_set: the set is zero already and stays so, the caller keeps its parity). A launch nobody wants is not issued.
+template <uint32_t N>
+static hipError_t launch_sort_lists(const SortBatchEntry* lists, uint32_t count, hipStream_t stream)
+{
     MidRankBatch<N> ranks{};
-    uint32_t rank_blocks = 0, rank_lds = 0, radix_tiles = 0;
     SortPassBatch<N> passes{};
+    uint32_t rank_blocks = 0, rank_lds = 0, radix_tiles = 0;
+    if (count > N)  // (the arguments hold N lists, and a batch of one ignores blockIdx.y: batch_list)
+        return hipErrorInvalidValue;
     for (uint32_t k = 0; k < count; k++) {
         const SortBatchEntry& e = lists[k];
         const SortPlan p = sort_plan(e.capacity, e.mode);
-        ranks.list[k] = MidRankEntry{e.b, e.capacity, e.descending, p.rank_sort ? (p.rank_only ? 0xFFFFFFFFu : p.rank_records) : 0u, p.rank_records};
+        ranks.list[k] = MidRankEntry{e.b, e.capacity, e.descending, p.rank_max_records, p.rank_records};
         if (p.rank_sort) {
             rank_blocks = std::max(rank_blocks, p.rank_blocks);
-            rank_lds = std::max(rank_lds, ((p.rank_records + 3u) & ~3u) * 4u);
+            rank_lds = std::max(rank_lds, ((p.rank_records + 3u) & ~3u) * 4u);  // the key table, beside the 1 KB of partial counts
         }
-        sort_pass_args(e.b, e.capacity, e.descending != 0, p.rank_sort, passes.list[k]);
-        if (p.rank_only)
-            passes.list[k].min_records = 0xFFFFFFFFu;  // the rank-sort launch alone: the radix launches leave this list at once
-        else
+        sort_pass_args(e, p, passes.list[k]);
+        if (p.radix)  // at full capacity (long or short tiles); the live count is on the device
             radix_tiles = std::max(radix_tiles, sort_tile_count(e.capacity));
     }
     if (rank_blocks) {
         static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(sort_mid_rank_batch_kernel<N>),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, kSmallSort * 4);
+                                                             hipFuncAttributeMaxDynamicSharedMemorySize, kBatchSortMaxSlots * 4);
         if (raised != hipSuccess)
             return raised;
         hipLaunchKernelGGL(sort_mid_rank_batch_kernel<N>, dim3(rank_blocks, count), dim3(256), rank_lds, stream, ranks);
     }
-    if (!radix_tiles)
-        return hipGetLastError();
-    const dim3 grid(radix_tiles, count), block(kSortThreads);
-    for (uint32_t pass = 0; pass < 4; pass++) {
+    for (uint32_t pass = 0; radix_tiles && pass < 4; pass++) {
         for (uint32_t k = 0; k < count; k++)
             sort_pass_buffers(lists[k].b, pass, passes.list[k]);
-        if (pass == 0) {
-            hipLaunchKernelGGL((sort_rank_batch_kernel<true, N>), grid, block, 0, stream, passes);
-            hipLaunchKernelGGL((sort_scatter_batch_kernel<true, false, N>), grid, block, 0, stream, passes);
-        } else {
-            hipLaunchKernelGGL((sort_rank_batch_kernel<false, N>), grid, block, 0, stream, passes);
-            if (pass == 3)
-                hipLaunchKernelGGL((sort_scatter_batch_kernel<false, true, N>), grid, block, 0, stream, passes);
-            else
-                hipLaunchKernelGGL((sort_scatter_batch_kernel<false, false, N>), grid, block, 0, stream, passes);
-        }
+        launch_radix_pass<N>(pass, dim3(radix_tiles, count), stream, passes);
     }
     return hipGetLastError();
 }
@@ -766,51 +751,16 @@ hipError_t launch_sort_batch(const SortBatchEntry* lists, uint32_t count, hipStr
     if (count == 0)
         return hipSuccess;
     if (count == 1)
-        return launch_sort(lists[0].b, lists[0].capacity, lists[0].descending != 0, stream, lists[0].mode);
-    return count <= 8 ? launch_sort_batch_n<8>(lists, count, stream) : launch_sort_batch_n<kMaxSortBatch>(lists, count, stream);
+        return launch_sort_lists<1>(lists, count, stream);
+    return count <= 8 ? launch_sort_lists<8>(lists, count, stream) : launch_sort_lists<kMaxSortBatch>(lists, count, stream);
 }
 
 hipError_t launch_sort(const SortBuffers& b, uint32_t capacity, bool descending, hipStream_t stream, SortMode mode)
 {
     if (capacity == 0)
         return hipSuccess;
-    // kSortRankOnly (the caller expects a short list: the previous frame's count): a mid-sized pool gets the rank-sort launch
-    // alone — the eight radix launches that would leave after one load each are ~16 us of an engine-sized tick — and a
-    // list that outgrew the key table after all is still sorted by it, from memory (count_before_global).
-    // Short lists sort in one launch whatever the pool's size: a pool of up to kMidSortSlots slots (where only the device
-    // knows how short the visible list is) gets the rank-sort launch AND the radix launches, and the live count decides on
-    // the device which of the two does the work — the other leaves after one load, ~2 us per launch, against 70 us for
-    // the eight radix launches on a few thousand records. Measured crossover: ~12 k records (rank 11 us at 2 k, 75 us at
-    // 16 k, 160 us at 32 k).
-    const SortPlan plan = sort_plan(capacity, mode);
-    if (plan.rank_sort) {
-        const uint32_t lds = ((plan.rank_records + 3u) & ~3u) * 4;  // the key table, beside the 1 KB of partial counts
-        static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(sort_small_kernel),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, kSmallSort * 4);
-        if (raised != hipSuccess)
-            return raised;
-        hipLaunchKernelGGL(sort_small_kernel, dim3(plan.rank_blocks), dim3(256), lds, stream, b, capacity, descending ? 1u : 0u,
-                           plan.rank_only ? 0xFFFFFFFFu : plan.rank_records, plan.rank_records);
-        if (capacity <= kSmallSort || plan.rank_only)
-            return hipGetLastError();
-    }
-    const uint32_t tiles = sort_tile_count(capacity);  // at full capacity (long or short tiles); the live count is on the device
-    SortPassArgs a;
-    sort_pass_args(b, capacity, descending, plan.rank_sort, a);
-    for (uint32_t pass = 0; pass < 4; pass++) {
-        sort_pass_buffers(b, pass, a);
-        if (pass == 0) {
-            hipLaunchKernelGGL(sort_rank_kernel<true>, dim3(tiles), dim3(kSortThreads), 0, stream, a);
-            hipLaunchKernelGGL((sort_scatter_kernel<true, false>), dim3(tiles), dim3(kSortThreads), 0, stream, a);
-        } else {
-            hipLaunchKernelGGL(sort_rank_kernel<false>, dim3(tiles), dim3(kSortThreads), 0, stream, a);
-            if (pass == 3)
-                hipLaunchKernelGGL((sort_scatter_kernel<false, true>), dim3(tiles), dim3(kSortThreads), 0, stream, a);
-            else
-                hipLaunchKernelGGL((sort_scatter_kernel<false, false>), dim3(tiles), dim3(kSortThreads), 0, stream, a);
-        }
-    }
-    return hipGetLastError();
+    const SortBatchEntry one{b, capacity, descending ? 1u : 0u, mode};
+    return launch_sort_lists<1>(&one, 1, stream);
 }
 
 __global__ void done_flag_kernel(uint32_t* host_flag, uint32_t value)
@@ -828,14 +778,14 @@ hipError_t launch_sort_small_batch(const SortBatch& batch, uint32_t views, uint3
 {
     if (capacity == 0 || views == 0)
         return hipSuccess;
-    if (capacity > kSmallSort)
+    if (capacity > kBatchSortMaxSlots)
         return hipErrorInvalidValue;
     const uint32_t lds = ((capacity + 3u) & ~3u) * 4;
     static_assert(sizeof(SortBatchN<kMaxSortViews>) == sizeof(SortBatch), "the full batch is the 32-entry form");
     static const hipError_t raised4 = hipFuncSetAttribute(reinterpret_cast<const void*>(sort_small_batch_kernel<4>),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, kSmallSort * 4);
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, kBatchSortMaxSlots * 4);
     static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(sort_small_batch_kernel<kMaxSortViews>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, kSmallSort * 4);
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, kBatchSortMaxSlots * 4);
     if (raised != hipSuccess || raised4 != hipSuccess)
         return raised != hipSuccess ? raised : raised4;
     const dim3 grid((capacity + 63) / 64, views);

@@ -3,14 +3,29 @@
 // enter into that).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace gv {
 
 constexpr uint32_t kMaxSortViews = 32;  // views of SEVERAL pools per batch launch (== kMaxPublishViews, checked in gv_kernels.hpp)
 
+// The sizes at which the sort changes form (sort_plan below; slots of the pool or records of the list).
+// Small pools: gv_sort only records the request, so that the views of one tick share launches when their results are first
+// asked for (and a cull recorded by gv_cull_batch_begin has run by then). Up to kBatchSortMaxSlots slots they sort in ONE
+// launch for all views (rank sort, launch_sort_small_batch: O(n^2 / lanes), 11 us at 2 k records, 75 us at 16 k — where the
+// eight radix launches take 70 us whatever the count); larger deferred pools go through launch_sort, where the device's own
+// record count picks the rank sort (up to kRankSortMaxRecords) or the radix sort.
+constexpr uint32_t kSmallSortMaxSlots = 32768;
+constexpr uint32_t kBatchSortMaxSlots = 16384;
+constexpr uint32_t kRankSortMaxRecords = 12288;
+constexpr uint32_t kMidSortMaxSlots = 1u << 20;   // pools up to this size also get the rank-sort launch, and wait for the frame's batch
+constexpr uint32_t kRankOnlyMaxSlots = 65536;     // bounds the one slow frame after a count that jumps (~2 ms at 64 k records)
+constexpr uint32_t kRankOnlyHintRecords = 10240;  // (the rank-only launch's key table holds 16384: 60 % headroom before the slow form)
+constexpr uint32_t kRankOnlyTableRecords = 16384;
+
 // sortMeshes (mesh.cpp:265-328): stable LSD radix sort of the compact records by distanceSq.
-struct SortBuffers {
+struct SortRecords {  // one list: the view's records and where they go in sorted order
     const uint32_t* count;  // device draw_count
     const uint32_t* idx_in;
     const float* model_in;
@@ -18,6 +33,8 @@ struct SortBuffers {
     uint32_t* idx_out;
     float* model_out;
     float* dist_out;
+};
+struct SortBuffers : SortRecords {
     // large pools (radix sort, gv_sort.hip):
     uint32_t* keys[2];       // (key, record index) pairs, ping-pong
     uint32_t* vals[2];
@@ -49,16 +66,42 @@ inline uint32_t sort_set_words(uint32_t capacity) { return 4u * sort_group_count
 // kBatchSortMaxSlots < slots <= kRankOnlyMaxSlots get the rank-sort launch alone (it sorts any count, slowly beyond its
 // key table: 0.74 ms for 38 k records where the radix passes take 0.17 ms — once, the next frame's hint is the new count); the counters of the radix passes are not touched (sort_is_rank_only: the caller keeps its parity).
 enum SortMode : uint32_t { kSortBoth = 0, kSortRankOnly = 1, kSortRadixOnly = 2 };  // kSortRadixOnly: a long list is expected, the rank-sort launch is left out
-constexpr uint32_t kRankOnlyMaxSlots = 65536;  // bounds the one slow frame after a count that jumps (~2 ms at 64 k records)
-constexpr uint32_t kRankOnlyHintRecords = 10240;  // (the rank-only launch's key table holds 16384: 60 % headroom before the slow form)
-constexpr uint32_t kRankOnlyTableRecords = 16384;
+inline bool sort_is_rank_only(uint32_t capacity, uint32_t mode) { return mode == 1u && capacity > kBatchSortMaxSlots && capacity <= kRankOnlyMaxSlots; }
+// the previous frame's count (0xFFFFFFFF: none yet) says what to enqueue for a mid-sized pool: a short list gets the rank sort alone
+inline SortMode sort_mode_for_hint(uint32_t count_hint)
+{
+    if (count_hint == 0xFFFFFFFFu)
+        return kSortBoth;
+    return count_hint <= kRankOnlyHintRecords ? kSortRankOnly : count_hint > 2 * kRankSortMaxRecords ? kSortRadixOnly : kSortBoth;
+}
+// What the host decides for one list: whether it gets the rank-sort launch (and with which key table), whether the radix
+// launches, and what the device-side count leaves to which of the two.
+struct SortPlan {
+    bool rank_only, rank_sort;
+    bool radix;                  // the list takes part in the eight radix launches
+    uint32_t rank_records;       // the rank-sort launch's key table (LDS words)
+    uint32_t rank_blocks;        // its workgroups
+    uint32_t rank_max_records;   // a live count above this leaves the rank-sort launch at once (0: every count does)
+    uint32_t radix_min_records;  // a live count of at most this leaves the radix launches at once (the rank sort took it)
+};
+inline SortPlan sort_plan(uint32_t capacity, SortMode mode)
+{
+    SortPlan p{};
+    p.rank_only = sort_is_rank_only(capacity, mode);
+    p.rank_sort = capacity <= kMidSortMaxSlots && (mode != kSortRadixOnly || capacity <= kBatchSortMaxSlots);
+    p.radix = !(p.rank_sort && (capacity <= kBatchSortMaxSlots || p.rank_only));
+    p.rank_records = capacity <= kBatchSortMaxSlots ? capacity : (p.rank_only ? kRankOnlyTableRecords : kRankSortMaxRecords);
+    p.rank_blocks = ((p.rank_only ? capacity : p.rank_records) + 63) / 64;
+    p.rank_max_records = !p.rank_sort ? 0u : p.rank_only ? 0xFFFFFFFFu : p.rank_records;
+    p.radix_min_records = !p.radix ? 0xFFFFFFFFu : p.rank_sort ? kRankSortMaxRecords : 0u;
+    return p;
+}
 hipError_t launch_sort(const SortBuffers& b, uint32_t capacity, bool descending, hipStream_t stream, SortMode mode = kSortBoth);
 // SEVERAL lists by ONE set of launches — a frame of many mid-sized mesh systems (10^5 slots each: too large for the one-launch batch
 // of small pools, too small to fill the device) is bound by its 9 launches per list, not by bytes: the rank-sort launch and the
 // eight radix launches of launch_sort with blockIdx.y = list (each list keeps its own buffers, counters, parity and device-side
 // count; same results). Lists of kBatchSortMaxSlots < capacity <= kMidSortMaxSlots, at most kMaxSortBatch per call.
 constexpr uint32_t kMaxSortBatch = 32;
-constexpr uint32_t kMidSortMaxSlots = 1u << 20;
 struct SortBatchEntry {
     SortBuffers b;
     uint32_t capacity, descending;
@@ -86,23 +129,7 @@ hipError_t launch_reorder_mesh_keys(const uint32_t* link, uint32_t n, const uint
 hipError_t launch_reorder_meshes(const uint32_t* order, uint32_t n, const uint32_t* xnewpos, uint32_t xn, const float4* a_in, const float2* b_in,
                                  const uint32_t* link_in, const uint32_t* orig_in, float4* a_out, float2* b_out, uint32_t* link_out,
                                  uint32_t* orig_out, uint32_t* inv_out, uint32_t* unpaired, hipStream_t stream);
-// Small pools: gv_sort only records the request, so that the views of one tick share launches when their results are first
-// asked for (and a cull recorded by gv_cull_batch_begin has run by then). Up to kBatchSortMaxSlots slots they sort in ONE
-// launch for all views (rank sort, launch_sort_small_batch: O(n^2 / lanes), 11 us at 2 k records, 75 us at 16 k — where the
-// eight radix launches take 70 us whatever the count); larger deferred pools go through launch_sort, where the device's own
-// record count picks the rank sort (up to kRankSortMaxRecords) or the radix sort.
-constexpr uint32_t kSmallSortMaxSlots = 32768;
-constexpr uint32_t kBatchSortMaxSlots = 16384;
-constexpr uint32_t kRankSortMaxRecords = 12288;
-inline bool sort_is_rank_only(uint32_t capacity, uint32_t mode) { return mode == 1u && capacity > kBatchSortMaxSlots && capacity <= kRankOnlyMaxSlots; }
-struct SmallSortEntry {  // one view of one small pool
-    const uint32_t* count;  // device draw_count
-    const uint32_t* idx_in;
-    const float* model_in;
-    const float* dist_in;
-    uint32_t* idx_out;
-    float* model_out;
-    float* dist_out;
+struct SmallSortEntry : SortRecords {  // one view of one small pool
     uint32_t capacity;      // the pool's slot count (upper bound of *count)
     uint32_t descending;
     uint32_t fused_publish; // the launch also delivers the view to the host (what publish_kernel would do afterwards):
@@ -113,6 +140,13 @@ struct SortBatch {
 };
 // max_capacity: the largest entry capacity (sizes the grid and the LDS key table)
 hipError_t launch_sort_small_batch(const SortBatch& batch, uint32_t views, uint32_t max_capacity, hipStream_t stream);
+// (kernel arguments and what the mirror's KeySorter fills: the shared base must not move a byte of them)
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(SortBuffers) == 144, "SortBuffers as before SortRecords");
+static_assert(offsetof(SmallSortEntry, capacity) == 56, "SmallSortEntry's words directly behind the seven pointers, as before SortRecords");
+static_assert(sizeof(SortBatch) == 6912, "SortBatch as before SortRecords");
+#pragma GCC diagnostic pop
 
 // gv_merge_sorted (gv_merge.hip): the sorted lists of SEVERAL views merged into one array of record structs per GROUP, all groups
 // of a frame by ONE launch (blockIdx.y = list, blockIdx.x = 256 records of it). Stable k-way merge without atomics, waits or a

@@ -1360,6 +1360,7 @@ static void replay_schedule(const std::string& path)
 // must come back with an error CODE (GV_E_OOM / GV_E_HIP) — no crash, no leak (ASan), no use of a half-made buffer — and the
 // context must still be usable: with the injection off, the same sequence runs through on the same context, and gv_destroy is clean.
 #include <hip/hip_runtime.h>
+#include "gv_kernels.hpp"  // (sort_plan_table below: the sort dispatch's plan is a pure header function)
 static int frame_sequence(GvCtx* ctx, World& w, const std::vector<float>& depth, bool tolerate)
 {
     const GvTransformLayout tl = transform_layout();
@@ -1821,6 +1822,62 @@ static void record_targets_on_both_delivery_paths()
     std::printf("record targets on both delivery paths: ok\n");
 }
 
+// The sort dispatch's plan as a table (gv_sort_kernels.hpp: sort_plan, sort_mode_for_hint): every capacity at which the form
+// changes, one below and one above, in all three modes, against literals worked out by hand from the rules — up to 16 384 slots
+// the rank sort alone whatever the mode; beyond, the rank sort (12 288-record table) beside the radix passes up to 2^20 slots,
+// the rank sort alone (16 384-record table, a workgroup per 64 SLOTS) for an expected short list up to 65 536 slots, the radix
+// passes alone for an expected long list and beyond 2^20 slots. The sentinels: what the rank launch takes (0: nothing,
+// 0xFFFFFFFF: any count) and what the radix launches leave alone (0xFFFFFFFF: every count).
+static void sort_plan_table()
+{
+    constexpr uint32_t ANY = 0xFFFFFFFFu, X = 0xDEADu;  // X: not looked at (there is no rank-sort launch)
+    struct Row {
+        uint32_t capacity, mode, rank_sort, rank_only, radix, rank_records, rank_blocks, rank_max, radix_min;
+    };
+    const Row rows[] = {
+        // capacity, mode              rank_sort rank_only radix  table  blocks  rank takes  radix leaves
+        {1, gv::kSortBoth,                 1, 0, 0,     1,    1,     1, ANY}, {1, gv::kSortRankOnly,         1, 0, 0,     1,    1,     1, ANY},
+        {1, gv::kSortRadixOnly,            1, 0, 0,     1,    1,     1, ANY},
+        {16383, gv::kSortBoth,             1, 0, 0, 16383,  256, 16383, ANY}, {16383, gv::kSortRankOnly,     1, 0, 0, 16383,  256, 16383, ANY},
+        {16383, gv::kSortRadixOnly,        1, 0, 0, 16383,  256, 16383, ANY},
+        {16384, gv::kSortBoth,             1, 0, 0, 16384,  256, 16384, ANY}, {16384, gv::kSortRankOnly,     1, 0, 0, 16384,  256, 16384, ANY},
+        {16384, gv::kSortRadixOnly,        1, 0, 0, 16384,  256, 16384, ANY},
+        {16385, gv::kSortBoth,             1, 0, 1, 12288,  192, 12288, 12288}, {16385, gv::kSortRankOnly,   1, 1, 0, 16384,  257,   ANY, ANY},
+        {16385, gv::kSortRadixOnly,        0, 0, 1,     X,    X,     0, 0},
+        {65535, gv::kSortBoth,             1, 0, 1, 12288,  192, 12288, 12288}, {65535, gv::kSortRankOnly,   1, 1, 0, 16384, 1024,   ANY, ANY},
+        {65535, gv::kSortRadixOnly,        0, 0, 1,     X,    X,     0, 0},
+        {65536, gv::kSortBoth,             1, 0, 1, 12288,  192, 12288, 12288}, {65536, gv::kSortRankOnly,   1, 1, 0, 16384, 1024,   ANY, ANY},
+        {65536, gv::kSortRadixOnly,        0, 0, 1,     X,    X,     0, 0},
+        {65537, gv::kSortBoth,             1, 0, 1, 12288,  192, 12288, 12288}, {65537, gv::kSortRankOnly,   1, 0, 1, 12288,  192, 12288, 12288},
+        {65537, gv::kSortRadixOnly,        0, 0, 1,     X,    X,     0, 0},
+        {1048576, gv::kSortBoth,           1, 0, 1, 12288,  192, 12288, 12288}, {1048576, gv::kSortRankOnly, 1, 0, 1, 12288,  192, 12288, 12288},
+        {1048576, gv::kSortRadixOnly,      0, 0, 1,     X,    X,     0, 0},
+        {1048577, gv::kSortBoth,           0, 0, 1,     X,    X,     0, 0}, {1048577, gv::kSortRankOnly,     0, 0, 1,     X,    X,     0, 0},
+        {1048577, gv::kSortRadixOnly,      0, 0, 1,     X,    X,     0, 0},
+    };
+    static_assert(sizeof(rows) / sizeof(rows[0]) == 9 * 3, "nine capacities, three modes");
+    for (const Row& r : rows) {
+        const gv::SortPlan p = gv::sort_plan(r.capacity, (gv::SortMode)r.mode);
+        const bool same = p.rank_sort == (r.rank_sort != 0) && p.rank_only == (r.rank_only != 0) && p.radix == (r.radix != 0) &&
+                          (!r.rank_sort || (p.rank_records == r.rank_records && p.rank_blocks == r.rank_blocks)) &&
+                          p.rank_max_records == r.rank_max && p.radix_min_records == r.radix_min &&
+                          gv::sort_is_rank_only(r.capacity, r.mode) == (r.rank_only != 0);
+        if (!same) {
+            std::fprintf(stderr, "sort_plan(%u, mode %u): rank_sort %d rank_only %d radix %d table %u blocks %u rank takes %u radix leaves %u\n", r.capacity,
+                         r.mode, p.rank_sort, p.rank_only, p.radix, p.rank_records, p.rank_blocks, p.rank_max_records, p.radix_min_records);
+            std::exit(1);
+        }
+    }
+    const uint32_t hints[6][2] = {{0xFFFFFFFFu, gv::kSortBoth},  {0, gv::kSortRankOnly},  {10240, gv::kSortRankOnly},
+                                  {10241, gv::kSortBoth},        {24576, gv::kSortBoth},  {24577, gv::kSortRadixOnly}};
+    for (const auto& h : hints)
+        if (gv::sort_mode_for_hint(h[0]) != h[1]) {
+            std::fprintf(stderr, "sort_mode_for_hint(%u) = %u, expected %u\n", h[0], (uint32_t)gv::sort_mode_for_hint(h[0]), h[1]);
+            std::exit(1);
+        }
+    std::printf("sort plan table: 27 plans and 6 hints as worked out by hand: ok\n");
+}
+
 int main(int argc, char** argv)
 {
     if (argc > 1) {  // schedule files (tests/schedules.py): replayed instead of the fixed exercise
@@ -1829,6 +1886,7 @@ int main(int argc, char** argv)
         std::printf("schedules: %d replayed ok\n", argc - 1);
         return 0;
     }
+    sort_plan_table();
     // spatially ordered mirror (default), pool-slot order, forced block bounds, linear scan; flat and 4-deep
     exercise(0, 40000, 3);
     exercise(GV_CONFIG_KEEP_SLOT_ORDER, 30000, 0);

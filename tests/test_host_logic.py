@@ -549,6 +549,7 @@ def test_host_orchestration_and_exchange_under_thread_sanitizer(tmp_path):
                          env=dict(os.environ, GV_RCCL_LIBRARY=transport, TSAN_OPTIONS="halt_on_error=0"))
     text = run.stdout + run.stderr
     assert run.returncode == 0 and "host orchestration: ok" in run.stdout and "ThreadSanitizer" not in text, text[-4000:]
+    assert "sort plan table: 27 plans and 6 hints as worked out by hand: ok" in run.stdout, run.stdout[:2000]  # (sort_plan, sort_mode_for_hint)
     assert run.stdout.count("exchange over the stub transport") == 4 + 24 and run.stdout.count("exchange driven by ONE thread") == 3 + 6
     assert run.stdout.count("exchange by peer stores (no communicator)") == 4 + 6
 
@@ -614,6 +615,7 @@ def test_host_orchestration_under_address_and_ub_sanitizers(tmp_path):
     assert tb.returncode == 0, tb.stderr[-3000:]
     run = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(os.environ, GV_RCCL_LIBRARY=transport))
     assert run.returncode == 0 and "host orchestration: ok" in run.stdout, (run.stdout + run.stderr)[-4000:]
+    assert "sort plan table: 27 plans and 6 hints as worked out by hand: ok" in run.stdout, run.stdout[:2000]  # (sort_plan, sort_mode_for_hint)
     assert "exchange over the stub transport, 8 ranks, list sequence 0: ok" in run.stdout, run.stdout[-2000:]
     # ... and 24 sequences of lists that jump at random between empty and the whole pool, 2-5 ranks
     assert run.stdout.count("exchange over the stub transport") == 4 + 24 and "list sequence 24: ok" in run.stdout, run.stdout[-2000:]
