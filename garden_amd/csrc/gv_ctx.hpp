@@ -606,7 +606,9 @@ bool release_record_target(PoolState::RecordTarget& target);            // false
 int copy_shard_of_pool(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, void* dst_device, uint32_t capacity, uint32_t index_base);
 
 // gv_mirror.cpp
-int sync_mirror(GvCtx* ctx);                 // brings the device mirror up to date with the bound pools + dirty ranges
+// brings the device mirror up to date with the bound pools + dirty marks: per side a full rebuild, or growth and the dirty
+// ranges; then the payload rows; then, when a tail is due, the re-order on the device (rules: gv_dirty_ranges.hpp)
+int sync_mirror(GvCtx* ctx);
 int upload_payload(GvCtx* ctx, PoolState& p);  // a pool's payload rows likewise (new slots + its own dirty set); sync_mirror calls it too
 TransformMirror xf_mirror(const GvCtx* ctx);  // the transform mirror as the kernels see it
 MeshMirror mesh_mirror(const PoolState& p);   // a pool's mirror likewise (hot: null; the sphere stream's upkeep in cull_launch sets it)

@@ -64,4 +64,33 @@ struct DirtyRanges {
     }
 };
 
+// ---- the rules of the mirror sync (gv_mirror.cpp: sync_mirror and its steps), each written once -----------------------------
+// Pure functions of counts, tabulated on both sides of every threshold by tests/cpp/dirty_ranges_test.cpp. The callers add
+// their own terms (need_full, spatial order, link changes, whether a pool records at all); only the shared arithmetic is here.
+
+// Too much of a pool sits in the unsorted tail (slots appended since the mirror was last in spatial order, `appended` of them
+// already mirrored and occupancy - mirrored about to be): more than 1/8 of a pool of at least 1024 slots goes back into order.
+inline bool tail_due_for_reorder(uint32_t occupancy, uint32_t mirrored, uint32_t appended)
+{
+    return occupancy > mirrored && ((uint64_t)appended + (occupancy - mirrored)) * 8 > occupancy && occupancy >= 1024;
+}
+
+// So few entries changed that flagging their blocks (of a pool of `nblocks` cull blocks) beats rebuilding the pool's block
+// bounds / emit seeds once it is at rest: 1/16 of the blocks, with 64 entries free.
+inline bool few_enough_to_patch_blocks(uint64_t total, uint64_t nblocks) { return total * 16 <= nblocks + 16 * 64; }
+
+// Most of the pool changed: one dense pass over all of it is cheaper than itemised uploads.
+inline bool most_of_pool(uint64_t total, uint32_t occupancy) { return total * 2 > occupancy; }
+
+// A dirty range of an AoS pool from this many slots up travels raw and is gathered on the device (upload_*_device).
+constexpr uint32_t kDeviceGatherMinSlots = 2048;
+
+// How the candidates of a mesh pool pair with transform entries: `own` of them sit at their transform's index. The values are
+// MeshMapping's (gv_kernels.hpp, which this header does not include; gv_mirror.cpp asserts that they agree).
+constexpr uint32_t kPairedGeneral = 0, kPairedSpeculate = 1, kPairedExact = 2;
+inline uint32_t mesh_mapping_of(size_t own, size_t candidates)
+{
+    return own == candidates ? kPairedExact : (own * 10 >= candidates * 9 ? kPairedSpeculate : kPairedGeneral);
+}
+
 }  // namespace gv

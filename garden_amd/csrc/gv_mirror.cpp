@@ -1,6 +1,7 @@
 // gv_mirror.cpp — the device mirror of the bound component pools: spatial order, host gathers (AoS or columns -> SoA
-// staging), dense / scattered / device-side uploads of dirty ranges, pool growth, and sync_mirror() which picks among
-// them. Replaces the per-entity Manager::tryGet / Manager::get lookups of the reference (mesh.cpp:149,
+// staging), dense / scattered / device-side uploads of dirty ranges, pool growth, the re-order on the device, and
+// sync_mirror(), a short sequence of named steps (rebuild_*, grow_*, remirror_dirty_*, reorder_mirror) chosen by the
+// rules of gv_dirty_ranges.hpp. Replaces the per-entity Manager::tryGet / Manager::get lookups of the reference (mesh.cpp:149,
 // transform.hpp:206) with slot indices resolved once per change.
 #include "gv_ctx.hpp"
 
@@ -402,12 +403,6 @@ bool aos_transform_layout(const TransformBinding& xf, const uint8_t** base, AosT
     return true;
 }
 
-// GV_DIRTY_TRANSFORM over slots [lo, hi) of an AoS pool, device side: the raw components of the span travel through the
-// library's own pinned chunks (the caller's memory is never page-locked, see below) and a device kernel does the
-// AoS -> SoA gather. Only the bytes between the first and the last bound field are read: (count - 1) strides + the
-// extent of one element, so a layout whose first field sits above offset 0 never reads past the caller's pool. The
-// host staging of those slots goes stale and is refreshed only if a host path needs it later. Returns GV_E_STATE when
-// the path is not applicable.
 // The world-matrix cache (gv_sweep) survives a dirty range when every re-mirrored entry is flagged for the subtree-scoped
 // sweep. True while the cache is valid and the flag array covers the mirror.
 bool track_world_dirty(GvCtx* ctx)
@@ -456,6 +451,12 @@ int stream_raw_span(GvCtx* ctx, const uint8_t* span, size_t bytes)
     return GV_OK;
 }
 
+// GV_DIRTY_TRANSFORM over slots [lo, hi) of an AoS pool, device side: the raw components of the span travel through the
+// library's own pinned chunks (the caller's memory is never page-locked, see stream_raw_span) and a device kernel does the
+// AoS -> SoA gather. Only the bytes between the first and the last bound field are read: (count - 1) strides + the
+// extent of one element, so a layout whose first field sits above offset 0 never reads past the caller's pool. The
+// host staging of those slots goes stale and is refreshed only if a host path needs it later. Returns GV_E_STATE when
+// the path is not applicable.
 int upload_transforms_device(GvCtx* ctx, uint32_t lo, uint32_t hi)
 {
     const uint8_t* base = nullptr;
@@ -505,7 +506,7 @@ bool aos_mesh_layout(const PoolState& p, const uint8_t** base, AosMeshLayout* L,
 // GV_DIRTY_MESH over slots [lo, hi) of an AoS pool, device side (round 3; the transform side has had this since round 1): the
 // raw components travel through the pinned chunks, aos_meshes_kernel resolves each mesh's transform through a device copy of
 // the entity -> slot table (refreshed here: the table is the caller's and may have changed) and writes the mirror entries.
-// Worth it when the span outweighs that table: ranges of at least 2048 slots and 1/12 of the entity capacity (48 raw bytes per
+// Worth it when the span outweighs that table: ranges of at least kDeviceGatherMinSlots slots and 1/12 of the entity capacity (48 raw bytes per
 // slot against 4 per entity). Not applicable (GV_E_STATE -> the host gather) to column binds and to pools with a ready column.
 int upload_meshes_device(GvCtx* ctx, PoolState& p, uint32_t lo, uint32_t hi)
 {
@@ -513,7 +514,7 @@ int upload_meshes_device(GvCtx* ctx, PoolState& p, uint32_t lo, uint32_t hi)
     AosMeshLayout L{};
     uint32_t extent = 0;
     const uint32_t count = hi > lo ? hi - lo : 0;
-    if (count < 2048 || (uint64_t)count * 12 < ctx->xf.entity_capacity || p.ready.ptr ||
+    if (count < kDeviceGatherMinSlots || (uint64_t)count * 12 < ctx->xf.entity_capacity || p.ready.ptr ||
         !aos_mesh_layout(p, &base, &L, &extent))
         return GV_E_STATE;
     const size_t bytes = (size_t)(count - 1) * L.stride + extent;
@@ -612,8 +613,6 @@ int record_uploads(GvCtx* ctx)
     ctx->upload_pending = true;
     return GV_OK;
 }
-
-bool track_world_dirty(GvCtx* ctx);
 
 // Dirty pool slots of a permuted mirror land on scattered entries: ALL the dirty ranges of a sync travel as one packet — one
 // copy, one launch (scatter_xf_packets_kernel: records, world-cache dirty bytes, active bits, block flags), one event.
@@ -1045,6 +1044,397 @@ int mark_dirty_blocks(GvCtx* ctx, PoolState& p, const std::vector<DirtyRanges::R
     return record_uploads(ctx);
 }
 
+// ---- the steps of sync_mirror -----------------------------------------------------------------------------------------
+// Every step brings one side of the mirror up to date in one way. The rules that choose among them are pure functions of
+// counts (gv_dirty_ranges.hpp: tail_due_for_reorder, few_enough_to_patch_blocks, most_of_pool, kDeviceGatherMinSlots,
+// mesh_mapping_of); each caller adds the terms that are its own.
+static_assert(kPairedGeneral == kMapGeneral && kPairedSpeculate == kMapSpeculate && kPairedExact == kMapExact, "mesh_mapping_of returns a MeshMapping");
+
+struct SyncPass {  // what one pass of sync_mirror hands from step to step
+    PhaseTimer phase;
+    bool staged = false;   // the pinned staging arrays were rewritten (behind a drained stream or wait_uploads): the copies queued from
+                           // them get ONE record_uploads behind them all, which the next sync waits for
+    bool spatial = true;   // the mirror is kept in spatial order (no GV_CONFIG_KEEP_SLOT_ORDER)
+};
+
+// The transform mirror from nothing: order, gather of every slot, depth / cycle check, upload. Every bound mesh pool follows.
+int rebuild_transforms(GvCtx* ctx, SyncPass& pass)
+{
+    const uint32_t n = ctx->xf.occupancy;
+    // staging is about to be rewritten: make sure earlier async uploads have drained
+    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    pass.staged = true;
+    const size_t cap = std::max<size_t>(n, 1);
+    GV_HIP(ctx, ctx->d_xab.reserve(cap));
+    GV_HIP(ctx, ctx->d_xc.reserve(cap));
+    GV_HIP(ctx, ctx->d_xflags.reserve(cap));
+    GV_HIP(ctx, ctx->d_xactive.reserve(cap / 64 + 1));
+    GV_HIP(ctx, ctx->d_xparent.reserve(cap));
+    // pinned staging and the host tables get a quarter of head-room: page-locking is what an append of created entities
+    // would otherwise wait for (76 of 188 ms when 1.25 M slots were appended to 8.75 M, tools/reorder_bench.py), and the
+    // mirror is re-ordered in place (no new allocation) by the time the tail reaches an eighth of the pool
+    const size_t hcap = cap + cap / 4;
+    GV_HIP(ctx, ctx->h_xab.reserve(hcap));
+    GV_HIP(ctx, ctx->h_xc.reserve(hcap));
+    GV_HIP(ctx, ctx->h_xflags.reserve(hcap));
+    GV_HIP(ctx, ctx->h_xparent.reserve(hcap));
+    pass.phase.lap("reserve transforms");
+    if (int rc = build_transform_order(ctx))
+        return rc;
+    pass.phase.lap("transform order");
+    if (n) {
+        gather_transforms(ctx, 0, n);
+        pass.phase.lap("gather transforms");
+        uint32_t depth = 0;
+        if (int rc = compute_max_depth(ctx, &depth))
+            return rc;
+        ctx->max_depth = depth;
+        pass.phase.lap("max depth");
+        if (int rc = upload_transforms(ctx, 0, n))
+            return rc;
+        if (!ctx->xinv.empty()) {
+            GV_HIP(ctx, ctx->d_xinv.reserve(cap));
+            GV_HIP(ctx, hipMemcpyAsync(ctx->d_xinv.ptr, ctx->xinv.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+            GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pageable source
+        }
+        GV_HIP(ctx, launch_pack_active(ctx->d_xflags.ptr, n, ctx->d_xactive.ptr, ctx->stream));
+    } else {
+        ctx->max_depth = 0;
+    }
+    ctx->xf_need_full = false;
+    ctx->xf_links_dirty = false;
+    ctx->xf_dirty.clear();
+    ctx->staging_stale.clear();  // everything was gathered afresh
+    ctx->world_valid = false;
+    ctx->world_partial = false;
+    GV_HIP(ctx, ctx->d_xdirty.reserve(cap));
+    GV_HIP(ctx, hipMemsetAsync(ctx->d_xdirty.ptr, 0, ctx->d_xdirty.cap, ctx->stream));
+    ctx->xdirty_set = false;
+    ctx->xf_epoch++;
+    ctx->xf_mirrored = n;
+    ctx->xf_appended = 0;
+    // transform entries may have moved: every mesh pool's slot column must be re-resolved
+    for (auto& p : ctx->pools)
+        if (p.bound)
+            p.need_full = true;
+    return GV_OK;
+}
+
+// Which pools keep recording changed blocks through a sync that re-mirrors `total` transform slots. Pools that keep block
+// bounds / emit seeds current across changes (flat, exactly paired: entry i of the pool is transform entry i) get the blocks
+// these transforms sit in flagged — `targets`; true when there is one — anything else falls back to "rebuilt once the pool is
+// at rest". ... while the re-mirrored entries are few: slots that are neighbours in the pool are scattered over the spatially
+// ordered mirror, so 10^5 of them touch nearly every block of a 10 M pool and the patch becomes a full rebuild (measured:
+// 426 us against 145 us for culling that frame without boxes; 1000 scattered movers: 37 us). Every bound pool's small_streak
+// counts the syncs in a row that were this small.
+bool pools_that_keep_flagging(GvCtx* ctx, uint64_t total, bool dense, BlockFlagTargets& targets)
+{
+    bool flagging = false;
+    for (uint32_t k = 0; k < GV_MAX_POOLS; k++) {
+        PoolState& q = ctx->pools[k];
+        if (!q.bound)
+            continue;
+        const bool few = !dense && !ctx->xf_links_dirty && few_enough_to_patch_blocks(total, blocks_of(q.occupancy));
+        q.small_streak = few ? std::min(q.small_streak + 1u, 1000u) : 0u;
+        if (!q.recording())
+            continue;
+        if (!few || ctx->max_depth != 0 || q.mapping != kMapExact || !q.d_blk_dirty.ptr) {
+            q.stop_recording();
+        } else {
+            targets.flags[k] = q.d_blk_dirty.ptr;
+            targets.occupancy[k] = q.occupancy;
+            flagging = true;
+        }
+    }
+    return flagging;
+}
+
+// Most of the transform pool is dirty: one pass over the covering range [lo, hi) (re-mirroring a clean slot is harmless)
+int upload_dense_transforms(GvCtx* ctx, uint32_t lo, uint32_t hi)
+{
+    int rc = GV_E_STATE;
+    if (!ctx->xf_links_dirty)
+        rc = upload_transforms_device(ctx, lo, hi);  // raw AoS span + device gather (GV_E_STATE: not applicable)
+    if (rc == GV_E_STATE) {
+        refresh_stale_staging(ctx);  // this path re-uploads every entry from the staging arrays
+        rc = regather_transforms_pipelined(ctx, lo, hi);  // dense, chunked, DMA under gather
+    }
+    return rc;
+}
+
+// Itemised: large ranges take the device-side gather, everything else travels as ONE scattered packet (or as plain ranged
+// copies when the mirror is in slot order). unflagged (out): the ranges whose upload path does not flag blocks itself;
+// bits_current (out): the active bit-plane was kept up to date entry by entry (the packet path, when it carried everything).
+int upload_itemised_transforms(GvCtx* ctx, const std::vector<DirtyRanges::R>& ranges, const BlockFlagTargets& targets,
+                               std::vector<DirtyRanges::R>& unflagged, bool& bits_current)
+{
+    std::vector<DirtyRanges::R> host;
+    for (const auto& r : ranges) {
+        int one = GV_E_STATE;
+        if (!ctx->xf_links_dirty && r.hi - r.lo >= kDeviceGatherMinSlots)
+            one = upload_transforms_device(ctx, r.lo, r.hi);
+        if (one == GV_E_STATE)
+            host.push_back(r);
+        else if (one != GV_OK)
+            return one;
+        else
+            unflagged.push_back(r);
+    }
+    for (const auto& r : host)
+        gather_transforms(ctx, r.lo, r.hi);
+    // a mirror in slot order takes plain ranged copies — five small copies and a memset per range — while the ranges
+    // are few; a frame that moved thousands of scattered entities (up to 16 384 ranges) would queue ~10^5 tiny copies
+    // that way: it travels as the one scattered packet too
+    if (!ctx->xinv.empty() || host.size() > kRangedCopyMaxRanges) {
+        const int rc = upload_transforms_scattered(ctx, host, targets);
+        bits_current = unflagged.empty();
+        return rc;
+    }
+    for (const auto& r : host) {
+        if (int rc = upload_transforms(ctx, r.lo, r.hi))
+            return rc;
+        if (track_world_dirty(ctx))
+            GV_HIP(ctx, hipMemsetAsync(ctx->d_xdirty.ptr + r.lo, 1, r.hi - r.lo, ctx->stream));
+        unflagged.push_back(r);
+    }
+    return GV_OK;
+}
+
+// What a re-mirror of dirty transforms leaves behind: the chain depth when links changed, the world-matrix cache, the epoch
+int after_transform_upload(GvCtx* ctx, bool dense)
+{
+    if (ctx->xf_links_dirty) {  // setParent (transform.cpp:130-195): chains changed length, maybe closed a cycle
+        uint32_t depth = 0;
+        if (int rc = compute_max_depth(ctx, &depth)) {
+            ctx->xf_need_full = true;  // the mirror now holds a cyclic link: rebuild once the caller has fixed it
+            return rc;
+        }
+        ctx->max_depth = depth;
+    }
+    if (track_world_dirty(ctx))
+        ctx->xdirty_set = true;  // (the upload paths flagged what they wrote)
+    if (track_world_dirty(ctx) && !dense)
+        ctx->world_partial = true;  // the cache stays, minus the chains through the flagged entries
+    else
+        ctx->world_valid = false;  // most of the pool moved: a full sweep is cheaper than walking flags
+    ctx->xf_epoch++;
+    return GV_OK;
+}
+
+// GV_DIRTY_TRANSFORM marks: the dirty slots are gathered and uploaded, dense or itemised, and the blocks they sit in flagged
+int remirror_dirty_transforms(GvCtx* ctx, SyncPass& pass)
+{
+    if (int rc = wait_uploads(ctx))  // (staging is about to be rewritten: the copies that read it have to be through)
+        return rc;
+    pass.staged = true;
+    const uint32_t n = ctx->xf.occupancy;
+    ctx->xf_dirty.normalise(n, 0);  // exact: a re-mirrored slot is a flagged slot (its whole subtree is re-swept)
+    const std::vector<DirtyRanges::R> ranges = ctx->xf_dirty.items;
+    const uint64_t total = ctx->xf_dirty.total();
+    if (total) {
+        const bool dense = most_of_pool(total, n);
+        BlockFlagTargets targets{};
+        const bool flagging = pools_that_keep_flagging(ctx, total, dense, targets);
+        std::vector<DirtyRanges::R> unflagged;
+        bool bits_current = false;
+        if (int rc = dense ? upload_dense_transforms(ctx, ranges.front().lo, ranges.back().hi)
+                           : upload_itemised_transforms(ctx, ranges, targets, unflagged, bits_current))
+            return rc;
+        if (!bits_current)
+            GV_HIP(ctx, launch_pack_active(ctx->d_xflags.ptr, n, ctx->d_xactive.ptr, ctx->stream));
+        if (flagging && !unflagged.empty())
+            for (uint32_t k = 0; k < GV_MAX_POOLS; k++)
+                if (targets.flags[k])
+                    if (int rc = mark_dirty_blocks(ctx, ctx->pools[k], unflagged, ctx->xinv.empty() ? nullptr : ctx->d_xinv.ptr, ctx->xf.occupancy))
+                        return rc;
+        if (int rc = after_transform_upload(ctx, dense))
+            return rc;
+    }
+    ctx->xf_links_dirty = false;
+    ctx->xf_dirty.clear();
+    return GV_OK;
+}
+
+// A mesh mirror from nothing: it follows the transform order; how its entries pair with transform entries is counted here
+int rebuild_meshes(GvCtx* ctx, PoolState& p, SyncPass& pass)
+{
+    if (!pass.staged) {
+        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        pass.staged = true;
+    }
+    const size_t cap = std::max<size_t>(p.occupancy, 1);
+    GV_HIP(ctx, p.d_a.reserve(cap));
+    GV_HIP(ctx, p.d_b.reserve(cap));
+    GV_HIP(ctx, p.d_link.reserve(cap));
+    GV_HIP(ctx, p.h_a.reserve(cap + cap / 4));  // (head-room: see the transform staging)
+    GV_HIP(ctx, p.h_b.reserve(cap + cap / 4));
+    GV_HIP(ctx, p.h_link.reserve(cap + cap / 4));
+    pass.phase.lap("upload transforms + reserve");
+    build_mesh_order(ctx, p);
+    pass.phase.lap("mesh order");
+    p.mapping = kMapGeneral;
+    if (p.occupancy) {
+        gather_meshes(ctx, p, 0, p.occupancy);
+        pass.phase.lap("gather meshes");
+        // how do mesh entries pair with transform entries? (speed only: every mapping is handled)
+        size_t candidates = 0, own = 0;
+        for (uint32_t i = 0; i < p.occupancy; i++) {
+            const uint32_t link = p.h_link.ptr[i];
+            if (link & kMeshCandidate) {
+                candidates++;
+                own += (link & kSlotMask) == i;
+            }
+        }
+        p.mapping = mesh_mapping_of(own, candidates);
+        if (int rc = upload_meshes(ctx, p, 0, p.occupancy))
+            return rc;
+        if (!p.perm.empty()) {
+            GV_HIP(ctx, p.d_orig.reserve(cap));
+            GV_HIP(ctx, p.d_inv.reserve(cap));
+            GV_HIP(ctx, hipMemcpyAsync(p.d_orig.ptr, p.perm.data(), (size_t)p.occupancy * 4, hipMemcpyHostToDevice, ctx->stream));
+            GV_HIP(ctx, hipMemcpyAsync(p.d_inv.ptr, p.inv.data(), (size_t)p.occupancy * 4, hipMemcpyHostToDevice, ctx->stream));
+            GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pageable source
+        }
+    }
+    pass.phase.lap("mapping + upload meshes");
+    p.need_full = false;
+    p.stop_recording();
+    p.dirty.clear();
+    p.staging_stale.clear();  // (every entry has just been gathered)
+    p.epoch++;
+    p.order_epoch++;
+    p.mirrored = p.occupancy;
+    p.appended = 0;
+    return GV_OK;
+}
+
+// What the device-side gather left of a pool's dirty ranges (`left`), through the host staging: one dense upload when that is
+// most of a permuted pool (`most`), plain ranged copies for a few ranges of a mirror in slot order, ONE scattered packet
+// otherwise. packet_flagged (out): the packet flagged the blocks of `left` itself — while the pool records and all the dirty
+// slots of the sync (`total`) are few.
+int upload_meshes_from_host(GvCtx* ctx, PoolState& p, const std::vector<DirtyRanges::R>& left, bool most, uint64_t total, bool& packet_flagged)
+{
+    if (most) {
+        refresh_stale_mesh_staging(ctx, p);  // (it re-uploads every entry from the staging arrays)
+        gather_meshes(ctx, p, left.front().lo, left.back().hi);
+        return upload_meshes(ctx, p, 0, p.occupancy);
+    }
+    for (const auto& r : left)
+        gather_meshes(ctx, p, r.lo, r.hi);
+    if (p.inv.empty() && left.size() <= kRangedCopyMaxRanges) {
+        for (const auto& r : left)
+            if (int rc = upload_meshes(ctx, p, r.lo, r.hi))
+                return rc;
+        return GV_OK;
+    }
+    packet_flagged = p.recording() && p.d_blk_dirty.ptr && few_enough_to_patch_blocks(total, blocks_of(p.occupancy));
+    return upload_meshes_scattered(ctx, p, left, packet_flagged ? p.d_blk_dirty.ptr : nullptr);
+}
+
+// A recording pool (see pools_that_keep_flagging) after its own dirty ranges went up: it goes on recording while the change
+// is small and the pairing exact, and whatever did not travel in a packet that flags blocks itself is flagged here
+int flag_dirty_mesh_blocks(GvCtx* ctx, PoolState& p, const std::vector<DirtyRanges::R>& ranges, const std::vector<DirtyRanges::R>& left,
+                           bool most, uint64_t total, bool packet_flagged)
+{
+    const bool few = few_enough_to_patch_blocks(total, blocks_of(p.occupancy));
+    if (!few)
+        p.small_streak = 0;  // (small mesh edits leave the streak to the transform side: no double count)
+    if (!p.recording())
+        return GV_OK;
+    if (most || p.mapping != kMapExact || !few) {
+        p.stop_recording();
+        return GV_OK;
+    }
+    std::vector<DirtyRanges::R> unflagged;
+    if (!packet_flagged) {
+        unflagged = ranges;
+    } else {
+        for (const auto& r : ranges)
+            if (std::find_if(left.begin(), left.end(), [&](const DirtyRanges::R& l) { return l.lo == r.lo && l.hi == r.hi; }) == left.end())
+                unflagged.push_back(r);
+    }
+    return unflagged.empty() ? GV_OK : mark_dirty_blocks(ctx, p, unflagged, p.inv.empty() ? nullptr : p.d_inv.ptr, p.occupancy);
+}
+
+// GV_DIRTY_MESH marks of one pool: large ranges of an AoS pool travel raw and are gathered on the device
+// (upload_meshes_device says when it applies), the rest goes through the host staging
+int remirror_dirty_meshes(GvCtx* ctx, PoolState& p, SyncPass& pass)
+{
+    if (int rc = wait_uploads(ctx))
+        return rc;
+    pass.staged = true;
+    p.dirty.normalise(p.occupancy, 0);
+    const std::vector<DirtyRanges::R> ranges = p.dirty.items;
+    const uint64_t total = p.dirty.total();
+    if (total) {
+        std::vector<DirtyRanges::R> left;  // what remains for the host paths
+        uint64_t left_total = 0;
+        for (const auto& r : ranges) {
+            const int one = upload_meshes_device(ctx, p, r.lo, r.hi);
+            if (one == GV_E_STATE) {
+                left.push_back(r);
+                left_total += r.hi - r.lo;
+            } else if (one != GV_OK) {
+                return one;
+            }
+        }
+        const bool most = !left.empty() && !p.inv.empty() && most_of_pool(left_total, p.occupancy);
+        bool packet_flagged = false;
+        if (!left.empty())
+            if (int rc = upload_meshes_from_host(ctx, p, left, most, total, packet_flagged))
+                return rc;
+        if (int rc = flag_dirty_mesh_blocks(ctx, p, ranges, left, most, total, packet_flagged))
+            return rc;
+    }
+    p.dirty.clear();
+    p.epoch++;
+    return GV_OK;
+}
+
+// The re-order itself, behind everything that brought the mirror up to date in its old order: the transforms when their tail
+// is due, then every pool whose own tail is due or whose transforms have just moved (its links name transform entries).
+// again (out): a pool without an order table was marked for a host rebuild — one more pass of sync_mirror does it, from the
+// new transform tables.
+int reorder_mirror(GvCtx* ctx, bool reorder_xf, const bool* reorder_pool, PhaseTimer& phase, bool& again)
+{
+    phase.lap("appended slots + dirty ranges");
+    KeySorter ks;
+    DeviceBuf<uint32_t> xnewpos;
+    struct Scratch { KeySorter& ks; DeviceBuf<uint32_t>& x; ~Scratch() { ks.release(); x.release(); } } scratch{ks, xnewpos};
+    if (reorder_xf) {
+        if (int rc = reorder_transforms_device(ctx, ks, xnewpos, phase))
+            return rc;
+        phase.lap("device re-order: transforms");
+    }
+    for (auto& p : ctx->pools) {
+        if (!p.bound || p.need_full || !(reorder_xf || reorder_pool[&p - ctx->pools]))
+            continue;
+        const int rc = p.occupancy ? reorder_meshes_device(ctx, p, ks, reorder_xf ? xnewpos.ptr : nullptr, phase) : GV_OK;
+        if (rc == GV_E_STATE) {
+            p.need_full = true;
+            again = true;
+        } else if (rc != GV_OK) {
+            if (reorder_xf) {
+                // the transform mirror is already in its new order: this pool and every pool behind it still name OLD transform
+                // entries in their links. Nothing re-fires the re-order, so they are rebuilt from the bound pools at the next
+                // sync (the next gv_cull must not run on stale links after a failed scratch allocation)
+                for (PoolState* q = &p; q != ctx->pools + GV_MAX_POOLS; q++)
+                    if (q->bound && !q->need_full) {
+                        q->need_full = true;
+                        q->order_epoch++;
+                    }
+            }
+            return rc;
+        }
+    }
+    phase.lap("device re-order: mesh pools");
+    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the old streams are freed with the scratch
+    ks.release();
+    xnewpos.release();
+    phase.lap("device re-order: scratch freed");
+    return GV_OK;
+}
+
 }  // namespace
 
 // The payload rows of a pool (gv_pool_bind_payload): slots appended since the last upload plus the pool's payload dirty set, gathered
@@ -1121,390 +1511,78 @@ int upload_payload(GvCtx* ctx, PoolState& p)
     return GV_OK;
 }
 
+// Brings the device mirror up to date with the bound pools and their dirty marks, one named step after the other (the steps
+// and the state they share: above; the rules that choose among them: gv_dirty_ranges.hpp). A re-order that is due runs last, on
+// the device, behind everything that brought the mirror up to date in its old order.
 int sync_mirror(GvCtx* ctx)
 {
-    PhaseTimer phase;
+    SyncPass pass;
     if (!ctx->xf.bound)
         return ctx->fail(GV_E_STATE, "gv_sync: no transform pool bound");
     GV_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t n = ctx->xf.occupancy;
-    bool staged = false;
-    const bool spatial = !(ctx->config.flags & GV_CONFIG_KEEP_SLOT_ORDER);
+    pass.spatial = !(ctx->config.flags & GV_CONFIG_KEEP_SLOT_ORDER);
     // Too much of a pool sits in the unsorted tail: back into spatial order — on the device (the new slots are appended first, like
-    // any growth, then the mirror is permuted where it lies: reorder_*_device)
+    // any growth, then the mirror is permuted where it lies: reorder_mirror); without an order table, by a full rebuild
     bool reorder_xf = false;
-    if (!ctx->xf_need_full && n > ctx->xf_mirrored && spatial &&
-        ((uint64_t)ctx->xf_appended + (n - ctx->xf_mirrored)) * 8 > n && n >= 1024) {
+    if (!ctx->xf_need_full && pass.spatial && tail_due_for_reorder(n, ctx->xf_mirrored, ctx->xf_appended)) {
         if (!ctx->xperm.empty())
             reorder_xf = true;
         else
             ctx->xf_need_full = true;
     }
     if (ctx->xf_need_full) {
-        // staging is about to be rewritten: make sure earlier async uploads have drained
-        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        staged = true;
-        const size_t cap = std::max<size_t>(n, 1);
-        GV_HIP(ctx, ctx->d_xab.reserve(cap));
-        GV_HIP(ctx, ctx->d_xc.reserve(cap));
-        GV_HIP(ctx, ctx->d_xflags.reserve(cap));
-        GV_HIP(ctx, ctx->d_xactive.reserve(cap / 64 + 1));
-        GV_HIP(ctx, ctx->d_xparent.reserve(cap));
-        // pinned staging and the host tables get a quarter of head-room: page-locking is what an append of created entities
-        // would otherwise wait for (76 of 188 ms when 1.25 M slots were appended to 8.75 M, tools/reorder_bench.py), and the
-        // mirror is re-ordered in place (no new allocation) by the time the tail reaches an eighth of the pool
-        const size_t hcap = cap + cap / 4;
-        GV_HIP(ctx, ctx->h_xab.reserve(hcap));
-        GV_HIP(ctx, ctx->h_xc.reserve(hcap));
-        GV_HIP(ctx, ctx->h_xflags.reserve(hcap));
-        GV_HIP(ctx, ctx->h_xparent.reserve(hcap));
-        phase.lap("reserve transforms");
-        int rc = build_transform_order(ctx);
-        if (rc != GV_OK)
+        if (int rc = rebuild_transforms(ctx, pass))
             return rc;
-        phase.lap("transform order");
-        if (n) {
-            gather_transforms(ctx, 0, n);
-            phase.lap("gather transforms");
-            uint32_t depth = 0;
-            rc = compute_max_depth(ctx, &depth);
-            if (rc != GV_OK)
-                return rc;
-            ctx->max_depth = depth;
-            phase.lap("max depth");
-            rc = upload_transforms(ctx, 0, n);
-            if (rc != GV_OK)
-                return rc;
-            if (!ctx->xinv.empty()) {
-                GV_HIP(ctx, ctx->d_xinv.reserve(cap));
-                GV_HIP(ctx, hipMemcpyAsync(ctx->d_xinv.ptr, ctx->xinv.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-                GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pageable source
-            }
-        } else {
-            ctx->max_depth = 0;
-        }
-        if (n)
-            GV_HIP(ctx, launch_pack_active(ctx->d_xflags.ptr, n, ctx->d_xactive.ptr, ctx->stream));
-        ctx->xf_need_full = false;
-        ctx->xf_links_dirty = false;
-        ctx->xf_dirty.clear();
-        ctx->staging_stale.clear();  // everything was gathered afresh
-        ctx->world_valid = false;
-        ctx->world_partial = false;
-        GV_HIP(ctx, ctx->d_xdirty.reserve(cap));
-        GV_HIP(ctx, hipMemsetAsync(ctx->d_xdirty.ptr, 0, ctx->d_xdirty.cap, ctx->stream));
-        ctx->xdirty_set = false;
-        ctx->xf_epoch++;
-        ctx->xf_mirrored = n;
-        ctx->xf_appended = 0;
-        // transform entries may have moved: every mesh pool's slot column must be re-resolved
-        for (auto& p : ctx->pools)
-            if (p.bound)
-                p.need_full = true;
     } else {
-      if (n > ctx->xf_mirrored) {
-        staged = true;
-        const int rc = grow_transforms(ctx, ctx->xf_mirrored, n, phase);
-        if (rc != GV_OK)
-            return rc;
-      }
-      if (ctx->xf_dirty.any()) {
-        if (int wrc = wait_uploads(ctx))  // (staging is about to be rewritten: the copies that read it have to be through)
-            return wrc;
-        staged = true;
-        ctx->xf_dirty.normalise(n, 0);  // exact: a re-mirrored slot is a flagged slot (its whole subtree is re-swept)
-        const std::vector<DirtyRanges::R> ranges = ctx->xf_dirty.items;
-        const uint64_t total = ctx->xf_dirty.total();
-        if (total) {
-            const uint32_t lo = ranges.front().lo, hi = ranges.back().hi;  // the covering range
-            int rc = GV_OK;
-            const bool dense = total * 2 > n;
-            // Pools that keep block bounds / emit seeds current across changes (flat, exactly paired: entry i of the pool is
-            // transform entry i) get the blocks these transforms sit in flagged; anything else falls back to "rebuilt once the pool
-            // is at rest". ... while the re-mirrored entries are few: slots that are neighbours in the pool are scattered over the
-            // spatially ordered mirror, so 10^5 of them touch nearly every block of a 10 M pool and the patch becomes a full rebuild
-            // (measured: 426 us against 145 us for culling that frame without boxes; 1000 scattered movers: 37 us).
-            BlockFlagTargets targets{};
-            bool flagging = false;
-            for (uint32_t k = 0; k < GV_MAX_POOLS; k++) {
-                PoolState& q = ctx->pools[k];
-                if (!q.bound)
-                    continue;
-                const uint64_t nblocks = (q.occupancy + kCullBlock - 1) / kCullBlock;
-                const bool few = !dense && !ctx->xf_links_dirty && total * 16 <= nblocks + 16 * 64;
-                q.small_streak = few ? std::min(q.small_streak + 1u, 1000u) : 0u;
-                if (!q.recording())
-                    continue;
-                if (!few || ctx->max_depth != 0 || q.mapping != kMapExact || !q.d_blk_dirty.ptr) {
-                    q.stop_recording();
-                } else {
-                    targets.flags[k] = q.d_blk_dirty.ptr;
-                    targets.occupancy[k] = q.occupancy;
-                    flagging = true;
-                }
-            }
-            std::vector<DirtyRanges::R> unflagged;  // ranges whose upload path does not flag blocks itself
-            bool bits_current = false;              // the active bit-plane was kept up to date entry by entry (the packet path)
-            if (dense) {
-                // most of the pool: one pass over the covering range (re-mirroring a clean slot is harmless)
-                rc = GV_E_STATE;
-                if (!ctx->xf_links_dirty)
-                    rc = upload_transforms_device(ctx, lo, hi);  // raw AoS span + device gather (GV_E_STATE: not applicable)
-                if (rc == GV_E_STATE) {
-                    refresh_stale_staging(ctx);  // this path re-uploads every entry from the staging arrays
-                    rc = regather_transforms_pipelined(ctx, lo, hi);  // dense, chunked, DMA under gather
-                }
-            } else {
-                // itemised: large ranges take the device-side gather, everything else travels as ONE scattered packet
-                // (or as plain ranged copies when the mirror is in slot order)
-                std::vector<DirtyRanges::R> host;
-                for (const auto& r : ranges) {
-                    int one = GV_E_STATE;
-                    if (!ctx->xf_links_dirty && r.hi - r.lo >= 2048)
-                        one = upload_transforms_device(ctx, r.lo, r.hi);
-                    if (one == GV_E_STATE)
-                        host.push_back(r);
-                    else if (one != GV_OK)
-                        return one;
-                    else
-                        unflagged.push_back(r);
-                }
-                for (const auto& r : host)
-                    gather_transforms(ctx, r.lo, r.hi);
-                // a mirror in slot order takes plain ranged copies — five small copies and a memset per range — while the ranges
-                // are few; a frame that moved thousands of scattered entities (up to 16 384 ranges) would queue ~10^5 tiny copies
-                // that way: it travels as the one scattered packet too
-                if (ctx->xinv.empty() && host.size() <= kRangedCopyMaxRanges) {
-                    for (const auto& r : host) {
-                        if ((rc = upload_transforms(ctx, r.lo, r.hi)) != GV_OK)
-                            break;
-                        if (track_world_dirty(ctx))
-                            GV_HIP(ctx, hipMemsetAsync(ctx->d_xdirty.ptr + r.lo, 1, r.hi - r.lo, ctx->stream));
-                        unflagged.push_back(r);
-                    }
-                } else {
-                    rc = upload_transforms_scattered(ctx, host, targets);
-                    bits_current = unflagged.empty();
-                }
-            }
-            if (rc != GV_OK)
+        if (n > ctx->xf_mirrored) {
+            pass.staged = true;
+            if (int rc = grow_transforms(ctx, ctx->xf_mirrored, n, pass.phase))
                 return rc;
-            if (!bits_current)
-                GV_HIP(ctx, launch_pack_active(ctx->d_xflags.ptr, n, ctx->d_xactive.ptr, ctx->stream));
-            if (flagging && !unflagged.empty())
-                for (uint32_t k = 0; k < GV_MAX_POOLS; k++)
-                    if (targets.flags[k])
-                        if (int mrc = mark_dirty_blocks(ctx, ctx->pools[k], unflagged, ctx->xinv.empty() ? nullptr : ctx->d_xinv.ptr, ctx->xf.occupancy))
-                            return mrc;
-            if (ctx->xf_links_dirty) {  // setParent (transform.cpp:130-195): chains changed length, maybe closed a cycle
-                uint32_t depth = 0;
-                rc = compute_max_depth(ctx, &depth);
-                if (rc != GV_OK) {
-                    ctx->xf_need_full = true;  // the mirror now holds a cyclic link: rebuild once the caller has fixed it
-                    return rc;
-                }
-                ctx->max_depth = depth;
-            }
-            if (track_world_dirty(ctx) && !dense) {
-                ctx->xdirty_set = true;     // (the upload paths above flagged what they wrote)
-                ctx->world_partial = true;  // the cache stays, minus the chains through the flagged entries
-            } else {
-                if (track_world_dirty(ctx))
-                    ctx->xdirty_set = true;
-                ctx->world_valid = false;   // most of the pool moved: a full sweep is cheaper than walking flags
-            }
-            ctx->xf_epoch++;
         }
-        ctx->xf_links_dirty = false;
-        ctx->xf_dirty.clear();
-      }
+        if (ctx->xf_dirty.any())
+            if (int rc = remirror_dirty_transforms(ctx, pass))
+                return rc;
     }
     bool reorder_pool[GV_MAX_POOLS] = {};
     for (auto& p : ctx->pools) {
         if (!p.bound)
             continue;
-        if (!p.need_full && p.occupancy > p.mirrored && spatial &&
-            ((uint64_t)p.appended + (p.occupancy - p.mirrored)) * 8 > p.occupancy && p.occupancy >= 1024) {
+        if (!p.need_full && pass.spatial && tail_due_for_reorder(p.occupancy, p.mirrored, p.appended)) {
             if (!p.perm.empty())
                 reorder_pool[&p - ctx->pools] = true;
             else
                 p.need_full = true;
         }
         if (!p.need_full && p.occupancy > p.mirrored) {
-            staged = true;
-            phase.lap("transforms up to date");
-            const int rc = grow_meshes(ctx, p, p.mirrored, p.occupancy);
-            if (rc != GV_OK)
+            pass.staged = true;
+            pass.phase.lap("transforms up to date");
+            if (int rc = grow_meshes(ctx, p, p.mirrored, p.occupancy))
                 return rc;
-            phase.lap("append meshes");
+            pass.phase.lap("append meshes");
         }
         if (p.need_full) {
-            if (!staged) {
-                GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                staged = true;
-            }
-            const size_t cap = std::max<size_t>(p.occupancy, 1);
-            GV_HIP(ctx, p.d_a.reserve(cap));
-            GV_HIP(ctx, p.d_b.reserve(cap));
-            GV_HIP(ctx, p.d_link.reserve(cap));
-            GV_HIP(ctx, p.h_a.reserve(cap + cap / 4));  // (head-room: see the transform staging above)
-            GV_HIP(ctx, p.h_b.reserve(cap + cap / 4));
-            GV_HIP(ctx, p.h_link.reserve(cap + cap / 4));
-            phase.lap("upload transforms + reserve");
-            build_mesh_order(ctx, p);
-            phase.lap("mesh order");
-            p.mapping = kMapGeneral;
-            if (p.occupancy) {
-                gather_meshes(ctx, p, 0, p.occupancy);
-                phase.lap("gather meshes");
-                // how do mesh entries pair with transform entries? (speed only: every mapping is handled)
-                size_t candidates = 0, own = 0;
-                for (uint32_t i = 0; i < p.occupancy; i++) {
-                    const uint32_t link = p.h_link.ptr[i];
-                    if (link & kMeshCandidate) {
-                        candidates++;
-                        own += (link & kSlotMask) == i;
-                    }
-                }
-                p.mapping = own == candidates ? kMapExact : (own * 10 >= candidates * 9 ? kMapSpeculate : kMapGeneral);
-                int rc = upload_meshes(ctx, p, 0, p.occupancy);
-                if (rc != GV_OK)
-                    return rc;
-                if (!p.perm.empty()) {
-                    GV_HIP(ctx, p.d_orig.reserve(cap));
-                    GV_HIP(ctx, p.d_inv.reserve(cap));
-                    GV_HIP(ctx, hipMemcpyAsync(p.d_orig.ptr, p.perm.data(), (size_t)p.occupancy * 4, hipMemcpyHostToDevice, ctx->stream));
-                    GV_HIP(ctx, hipMemcpyAsync(p.d_inv.ptr, p.inv.data(), (size_t)p.occupancy * 4, hipMemcpyHostToDevice, ctx->stream));
-                    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pageable source
-                }
-            }
-            phase.lap("mapping + upload meshes");
-            p.need_full = false;
-            p.stop_recording();
-            p.dirty.clear();
-            p.staging_stale.clear();  // (every entry has just been gathered)
-            p.epoch++;
-            p.order_epoch++;
-            p.mirrored = p.occupancy;
-            p.appended = 0;
+            if (int rc = rebuild_meshes(ctx, p, pass))
+                return rc;
         } else if (p.dirty.any()) {
-            if (int wrc = wait_uploads(ctx))
-                return wrc;
-            staged = true;
-            p.dirty.normalise(p.occupancy, 0);
-            const std::vector<DirtyRanges::R> ranges = p.dirty.items;
-            const uint64_t total = p.dirty.total();
-            if (total) {
-                int rc = GV_OK;
-                // large ranges of an AoS pool: raw span + device-side gather (upload_meshes_device says when it applies);
-                // `left` is what remains for the host paths
-                std::vector<DirtyRanges::R> left;
-                uint64_t left_total = 0;
-                bool packet_flagged = false;  // the scattered packet flagged the blocks of `left` itself
-                for (const auto& r : ranges) {
-                    const int one = upload_meshes_device(ctx, p, r.lo, r.hi);
-                    if (one == GV_E_STATE) {
-                        left.push_back(r);
-                        left_total += r.hi - r.lo;
-                    } else if (one != GV_OK) {
-                        return one;
-                    }
-                }
-                if (left.empty()) {
-                } else if (!p.inv.empty() && left_total * 2 > p.occupancy) {  // most of a permuted pool: one dense upload
-                    refresh_stale_mesh_staging(ctx, p);  // (it re-uploads every entry from the staging arrays)
-                    gather_meshes(ctx, p, left.front().lo, left.back().hi);
-                    rc = upload_meshes(ctx, p, 0, p.occupancy);
-                } else {
-                    for (const auto& r : left)
-                        gather_meshes(ctx, p, r.lo, r.hi);
-                    if (p.inv.empty() && left.size() <= kRangedCopyMaxRanges) {
-                        for (const auto& r : left)
-                            if ((rc = upload_meshes(ctx, p, r.lo, r.hi)) != GV_OK)
-                                break;
-                    } else {
-                        const uint64_t nb = (p.occupancy + kCullBlock - 1) / kCullBlock;
-                        const bool flag_here = p.recording() && p.d_blk_dirty.ptr && total * 16 <= nb + 16 * 64;
-                        rc = upload_meshes_scattered(ctx, p, left, flag_here ? p.d_blk_dirty.ptr : nullptr);
-                        packet_flagged = flag_here;
-                    }
-                }
-                if (rc != GV_OK)
-                    return rc;
-                const uint64_t nblocks = (p.occupancy + kCullBlock - 1) / kCullBlock;
-                if (total * 16 > nblocks + 16 * 64)
-                    p.small_streak = 0;  // (small mesh edits leave the streak to the transform side: no double count)
-                if (p.recording()) {  // (see the transform side)
-                    const bool most = !left.empty() && !p.inv.empty() && left_total * 2 > p.occupancy;
-                    if (most || p.mapping != kMapExact || total * 16 > nblocks + 16 * 64) {
-                        p.stop_recording();
-                    } else {
-                        std::vector<DirtyRanges::R> unflagged;  // what did not travel in a packet that flags blocks itself
-                        if (!packet_flagged) {
-                            unflagged = ranges;
-                        } else {
-                            for (const auto& r : ranges)
-                                if (std::find_if(left.begin(), left.end(), [&](const DirtyRanges::R& l) { return l.lo == r.lo && l.hi == r.hi; }) == left.end())
-                                    unflagged.push_back(r);
-                        }
-                        if (!unflagged.empty())
-                            if (int mrc = mark_dirty_blocks(ctx, p, unflagged, p.inv.empty() ? nullptr : p.d_inv.ptr, p.occupancy))
-                                return mrc;
-                    }
-                }
-            }
-            p.dirty.clear();
-            p.epoch++;
+            if (int rc = remirror_dirty_meshes(ctx, p, pass))
+                return rc;
         }
     }
-    if (staged)  // whatever copies this sync queued from the pinned staging arrays: the next sync waits for them before it rewrites those
-        if (int rrc = record_uploads(ctx))
-            return rrc;
+    if (pass.staged)  // whatever copies this sync queued from the pinned staging arrays: the next sync waits for them before it rewrites those
+        if (int rc = record_uploads(ctx))
+            return rc;
     for (auto& p : ctx->pools)  // (staging of their own; no cull reads them)
         if (p.bound && p.payload.count)
-            if (int prc = upload_payload(ctx, p))
-                return prc;
-    // the re-order itself, behind everything that brought the mirror up to date in its old order
+            if (int rc = upload_payload(ctx, p))
+                return rc;
     bool any_reorder = reorder_xf;
     for (bool b : reorder_pool)
         any_reorder = any_reorder || b;
     if (any_reorder) {
-        phase.lap("appended slots + dirty ranges");
-        KeySorter ks;
-        DeviceBuf<uint32_t> xnewpos;
-        struct Scratch { KeySorter& ks; DeviceBuf<uint32_t>& x; ~Scratch() { ks.release(); x.release(); } } scratch{ks, xnewpos};
         bool again = false;
-        if (reorder_xf) {
-            if (int rc = reorder_transforms_device(ctx, ks, xnewpos, phase))
-                return rc;
-            phase.lap("device re-order: transforms");
-        }
-        for (auto& p : ctx->pools) {
-            if (!p.bound || p.need_full || !(reorder_xf || reorder_pool[&p - ctx->pools]))
-                continue;  // (a pool whose transforms moved follows them: its links name transform entries)
-            const int rc = p.occupancy ? reorder_meshes_device(ctx, p, ks, reorder_xf ? xnewpos.ptr : nullptr, phase) : GV_OK;
-            if (rc == GV_E_STATE) {
-                p.need_full = true;
-                again = true;
-            } else if (rc != GV_OK) {
-                if (reorder_xf) {
-                    // the transform mirror is already in its new order: this pool and every pool behind it still name OLD transform
-                    // entries in their links. Nothing re-fires the re-order, so they are rebuilt from the bound pools at the next
-                    // sync (the next gv_cull must not run on stale links after a failed scratch allocation)
-                    for (PoolState* q = &p; q != ctx->pools + GV_MAX_POOLS; q++)
-                        if (q->bound && !q->need_full) {
-                            q->need_full = true;
-                            q->order_epoch++;
-                        }
-                }
-                return rc;
-            }
-        }
-        phase.lap("device re-order: mesh pools");
-        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the old streams are freed with the scratch
-        ks.release();
-        xnewpos.release();
-        phase.lap("device re-order: scratch freed");
+        if (int rc = reorder_mirror(ctx, reorder_xf, reorder_pool, pass.phase, again))
+            return rc;
         if (again)
             return sync_mirror(ctx);  // (pools without an order table: rebuilt on the host from the new transform tables)
     }

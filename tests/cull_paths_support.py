@@ -72,9 +72,15 @@ LITERAL_LINES = {
         "} else if (args.world) {  // uniform",
     ],
     "gv_mirror.cpp": [
-        "const bool few = !dense && !ctx->xf_links_dirty && total * 16 <= nblocks + 16 * 64;",
+        "const bool dense = most_of_pool(total, n);",
+        "const bool few = !dense && !ctx->xf_links_dirty && few_enough_to_patch_blocks(total, blocks_of(q.occupancy));",
         "if (!few || ctx->max_depth != 0 || q.mapping != kMapExact || !q.d_blk_dirty.ptr) {",
-        "p.mapping = own == candidates ? kMapExact : (own * 10 >= candidates * 9 ? kMapSpeculate : kMapGeneral);",
+        "p.mapping = mesh_mapping_of(own, candidates);",
+    ],
+    "gv_dirty_ranges.hpp": [  # the rules themselves (tabulated by tests/cpp/dirty_ranges_test.cpp)
+        "inline bool most_of_pool(uint64_t total, uint32_t occupancy) { return total * 2 > occupancy; }",
+        "inline bool few_enough_to_patch_blocks(uint64_t total, uint64_t nblocks) { return total * 16 <= nblocks + 16 * 64; }",
+        "return own == candidates ? kPairedExact : (own * 10 >= candidates * 9 ? kPairedSpeculate : kPairedGeneral);",
     ],
 }
 
@@ -121,7 +127,8 @@ class PoolModel:
         self.world = False
 
     def edit(self, occupancy, count, mapping="exact", max_depth=0):
-        """`count` transforms re-mirrored by the sync in front of the next cull (sync_mirror's itemised / dense paths)"""
+        """`count` transforms re-mirrored by the sync in front of the next cull (gv_mirror.cpp: remirror_dirty_transforms, dense or
+        itemised by most_of_pool; pools_that_keep_flagging with few_enough_to_patch_blocks — the rules of gv_dirty_ranges.hpp)"""
         dense = count * 2 > occupancy
         few = not dense and count * 16 <= blocks_of(occupancy) + 16 * 64
         self.small_streak = min(self.small_streak + 1, 1000) if few else 0
@@ -436,8 +443,9 @@ def build_scene(kind, n, transforms):
 
 
 def mirror_mapping(sc):
-    """MeshMapping of a pool whose mirror is in pool-slot order (sync_mirror's full gather): candidates = live, enabled meshes
-    with a transform; exact when each sits at its transform's slot, speculate when 90 % do"""
+    """MeshMapping of a pool whose mirror is in pool-slot order (gv_mirror.cpp: rebuild_meshes counts, mesh_mapping_of in
+    gv_dirty_ranges.hpp decides): candidates = live, enabled meshes with a transform; exact when each sits at its transform's
+    slot, speculate when 90 % do"""
     ent = sc.meshes["entity"].astype(np.int64)
     e2t = np.asarray(sc.entity_to_transform, dtype=np.int64)
     slot = np.where(ent < e2t.size, e2t[np.minimum(ent, e2t.size - 1)], int(scene.GV_NONE))

@@ -1953,6 +1953,94 @@ def test_thousands_of_scattered_dirty_marks_on_a_slot_order_mirror(gpu_slot_orde
         assert_same(got, got_vis, exp, sc.meshes["isVisible"].copy())
 
 
+def test_most_of_a_permuted_mesh_pool_in_small_ranges_goes_up_whole(gpu, oracle):
+    """GV_DIRTY_MESH ranges that are each too short for the device-side gather (under 2048 slots) but together cover most of a
+    pool whose mirror is in spatial order: the ranges are gathered on the host and the pool's mirror is uploaded whole, once
+    (28 bytes per entry), instead of as a scattered packet."""
+    n = 8_192
+    sc = scene.flat_scene(n, seed=21)
+    view = scene.main_camera_view()
+    run_both(gpu, oracle, sc, [view])
+    rng = np.random.default_rng(8)
+    up0 = gpu.stats()["upload_bytes"]
+    for lo in range(0, n, 1_024):       # 8 ranges of 1000 slots, 24 clean slots between them
+        sc.meshes["aabbMax"][lo:lo + 1_000, :3] *= rng.uniform(0.5, 3.0, (1_000, 3)).astype(np.float32)
+        sc.meshes["isEnabled"][lo:lo + 1_000] ^= (rng.random(1_000) < 0.1).astype(np.uint8)
+        gpu.mark_dirty(2, lo, 1_000, pool_id=0)
+    gpu.cull(0, [view])
+    sc.meshes["isVisible"] = 7
+    got = gpu.fetch(0, write_back=True, occupancy=n)
+    got_vis = sc.meshes["isVisible"].copy()
+    exp = oracle.prepare_meshes(sc.meshes, sc.transforms, sc.entity_to_transform, view)
+    assert_same(got, got_vis, exp, sc.meshes["isVisible"].copy())
+    assert gpu.stats()["upload_bytes"] - up0 == n * 28
+
+
+def test_one_side_of_the_mirror_is_reordered_alone(oracle):
+    """The re-order on the device when only ONE side's unsorted tail is due (gv_mirror.cpp reorder_mirror). First the transforms
+    grow past 1/8 while the only mesh pool holds a single entry: the transforms are re-ordered alone, and the pool, which has no
+    order table to permute, is rebuilt on the host by a second pass of the sync. Then a second mesh system over the same entities
+    grows past 1/8 of itself while the transforms stay: that pool alone is re-ordered. Visible set, records, isVisible and every
+    world matrix against the oracle after each step. (A context of its own: a pool id that an earlier test of a shared context left
+    bound would be taken for a pool that grew, its old slots unchanged.)"""
+    from garden_amd.lib import GpuVisibility
+    full = scene.hierarchy_scene(8_192, depth=4, fanout=5)
+    view = scene.main_camera_view()
+    seen = oracle.prepare_meshes(full.meshes[:6_000].copy(), full.transforms[:6_000].copy(), full.entity_to_transform, view)["visible_idx"]
+    lone = full.meshes[int(seen[0]):int(seen[0]) + 1].copy()  # one mesh, visible from the start
+    every_other = full.meshes[:7_000:2].copy()             # another mesh system over the same entities
+
+    gpu = GpuVisibility(device=0)
+
+    def cut(k):
+        e2t = full.entity_to_transform.copy()
+        e2t[e2t >= k] = 0xFFFFFFFF
+        return full.transforms[:k].copy(), e2t
+
+    def check(pools, tr, e2t):
+        for pool, meshes in pools:
+            gpu.cull(pool, [view])
+            got = gpu.fetch(0, write_back=False, occupancy=meshes.shape[0])
+            m2 = meshes.copy()
+            exp = oracle.prepare_meshes(m2, tr, e2t, view)
+            assert np.array_equal(got["visible_idx"], np.sort(exp["visible_idx"]))
+            o = np.argsort(exp["visible_idx"], kind="stable")
+            assert np.array_equal(got["baked_model"].view(np.uint32), exp["baked_model"][o].view(np.uint32))
+            assert np.array_equal(got["is_visible"], m2["isVisible"])
+        gpu.sweep(1)
+        assert np.array_equal(gpu.get_world(0, tr.shape[0]).view(np.uint32), oracle.world_matrices(tr, e2t).view(np.uint32))
+
+    with gpu:
+        tr, e2t = cut(6_000)
+        gpu.bind_transforms(tr, e2t)
+        gpu.bind_pool(0, lone)
+        gpu.hierarchy_rebuild()
+        check([(0, lone)], tr, e2t)
+        assert oracle.prepare_meshes(lone.copy(), tr, e2t, view)["draw_count"] == 1
+        before = gpu.stats()["mirror_reorders"]
+        tr, e2t = cut(7_000)                 # 1000 new slots * 8 > 7000: the transform tail is due, the pool's is not
+        gpu.bind_transforms(tr, e2t)
+        check([(0, lone)], tr, e2t)
+        assert gpu.stats()["mirror_reorders"] - before == 1
+        # a pool that grows alone
+        part = every_other[:3_000].copy()
+        gpu.bind_pool(1, part)
+        check([(0, lone), (1, part)], tr, e2t)
+        part = every_other[:3_500].copy()    # 500 new slots * 8 > 3500
+        gpu.bind_pool(1, part)
+        check([(0, lone), (1, part)], tr, e2t)
+        assert gpu.stats()["mirror_reorders"] - before == 1  # (counts re-orders of the transforms)
+        table = gpu.mirror_slots(1, 3_500)
+        assert np.array_equal(np.sort(table), np.arange(3_500))
+        assert not np.array_equal(table[3_000:], np.arange(3_000, 3_500))  # the appended slots no longer sit behind the others in slot order
+        # dirty marks afterwards land on the re-ordered entries of both sides
+        tr["position"][100:160, :3] += np.float32(35.0)
+        gpu.mark_dirty(0, 100, 60)
+        part["aabbMax"][3_200:3_260, :3] *= np.float32(4.0)
+        gpu.mark_dirty(2, 3_200, 60, pool_id=1)
+        check([(0, lone), (1, part)], tr, e2t)
+
+
 @pytest.mark.parametrize("case", ["grow", "replace", "early_free"])
 def test_record_target_lifetime_through_the_bare_c_abi(case):
     """gv_pool_set_record_target without the shim (tools/record_target_probe.py, its own process: the array is an anonymous

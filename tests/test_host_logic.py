@@ -513,6 +513,21 @@ def test_dirty_ranges_under_address_and_ub_sanitizers(tmp_path):
     assert run.returncode == 0 and '"ok": true' in run.stdout, run.stdout + run.stderr
 
 
+def test_mirror_sync_rules_as_a_table(tmp_path):
+    """The rules by which sync_mirror chooses its steps (garden_amd/csrc/gv_dirty_ranges.hpp: tail_due_for_reorder,
+    few_enough_to_patch_blocks, most_of_pool, kDeviceGatherMinSlots, mesh_mapping_of), each on both sides of its threshold against
+    literals worked out by hand (tests/cpp/dirty_ranges_test.cpp: mirror_rules_table), built with -fsanitize=address,undefined."""
+    import subprocess
+    root = os.path.join(os.path.dirname(__file__), "..")
+    exe = str(tmp_path / "mirror_rules_table")
+    build = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            os.path.join(root, "tests/cpp/dirty_ranges_test.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([exe, "rules"], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and '"ok": true' in run.stdout, run.stdout + run.stderr
+    assert "mirror rules table: 16 tails, 10 few, 10 most, 12 mappings as worked out by hand: ok" in run.stdout, run.stdout
+
+
 def test_host_orchestration_and_exchange_under_thread_sanitizer(tmp_path):
     """The same host build (tests/cpp/hip_stub) and the same driver under -fsanitize=thread: the exchange with one context per rank
     THREAD (1 / 2 / 3 / 8 ranks, 24 random list sequences) and with ONE thread driving 1-4 contexts over tests/cpp/rccl_stub's worker
