@@ -35,8 +35,24 @@ hipError_t launch_sort(const SortBuffers& b, uint32_t capacity, bool descending,
     return hipSuccess;
 }
 
-hipError_t launch_reorder_codes(const TransformMirror& xf, uint32_t* root, uint32_t*, float* code, hipStream_t)
+static uint32_t spread10(uint32_t v)  // 10 bits -> every third bit
 {
+    v = (v | (v << 16)) & 0x030000FFu;
+    v = (v | (v << 8)) & 0x0300F00Fu;
+    v = (v | (v << 4)) & 0x030C30C3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+
+// reorder_roots_kernel and reorder_codes_kernel as plain loops: the root of every entry and the box of the live roots' finite
+// coordinates, then the 30-bit Morton code of the ROOT's cell inside that box — the same float expression and interleave, so the
+// order the stub build gives is the order the device gives (host_orchestration_test.cpp compares it with a host rebuild). box:
+// the corners as floats, lo[3] then hi[3] (the device form keeps order-preserving integer images of them for its atomics).
+hipError_t launch_reorder_codes(const TransformMirror& xf, uint32_t* root, uint32_t* box, float* code, hipStream_t)
+{
+    if (xf.count == 0)
+        return hipSuccess;
+    float corner[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
     for (uint32_t j = 0; j < xf.count; j++) {
         uint32_t cur = j;
         for (uint32_t d = 0; xf.max_depth && d <= xf.max_depth; d++) {
@@ -46,12 +62,28 @@ hipError_t launch_reorder_codes(const TransformMirror& xf, uint32_t* root, uint3
             cur = p;
         }
         root[j] = cur;
+        if (cur == j && (xf.flags[j] & kXfLive)) {
+            const float pos[3] = {xf.ab[j].a.x, xf.ab[j].a.y, xf.ab[j].a.z};
+            for (int k = 0; k < 3; k++)
+                if (std::isfinite(pos[k])) {
+                    corner[k] = std::fmin(corner[k], pos[k]);
+                    corner[3 + k] = std::fmax(corner[3 + k], pos[k]);
+                }
+        }
     }
-    for (uint32_t j = 0; j < xf.count; j++) {  // (a coarse key is as good as a Morton code for what is checked here: any key gives a permutation)
-        uint32_t c = 0x3FFFFFFFu;
+    std::memcpy(box, corner, sizeof(corner));
+    for (uint32_t j = 0; j < xf.count; j++) {
+        uint32_t c = 0x3FFFFFFFu;  // free entries last
         if (xf.flags[j] & kXfLive) {
-            const float x = xf.ab[root[j]].a.x;
-            c = std::isfinite(x) ? (uint32_t)std::min(1023.0f, std::max(0.0f, std::fabs(x))) : 0u;
+            const float4 a = xf.ab[root[j]].a;
+            const float pos[3] = {a.x, a.y, a.z};
+            uint32_t q[3];
+            for (int k = 0; k < 3; k++) {
+                const float l = corner[k], ext = corner[3 + k] - l;
+                const float f = (ext > 0.0f && std::isfinite(pos[k])) ? (pos[k] - l) / ext : 0.0f;
+                q[k] = (uint32_t)std::fmin(1023.0f, std::fmax(0.0f, f * 1024.0f));
+            }
+            c = spread10(q[0]) | (spread10(q[1]) << 1) | (spread10(q[2]) << 2);
         }
         std::memcpy(&code[j], &c, 4);
     }

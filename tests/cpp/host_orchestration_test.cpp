@@ -6,9 +6,11 @@
 // packet, the device-side gather through the pinned chunks and the worker threads, link changes), pools that grow / shrink /
 // move, column binds, ready columns, record layouts and targets, batched ticks, sorts, Hi-Z builds of odd sizes, sweeps,
 // scene ingest and tile extraction, error paths. Kernels do nothing, so RESULTS are not checked here (the GPU tier does
-// that against the oracle) — what is checked is that every staging buffer, index table and copy the host side makes stays
+// that against the oracle; the one exception is the ORDER of a re-ordered mirror, whose code kernels the stub build states as
+// plain loops: reorder_gives_the_order_of_a_host_build) — what is checked is that every staging buffer, index table and copy the host side makes stays
 // inside what it allocated, and that the status codes are the documented ones. TEST-ONLY: the product library still
 // returns GV_E_NODEVICE without a gfx950 device.
+#include <algorithm>
 #include <cassert>
 #include <chrono>
 #include <cmath>
@@ -1822,6 +1824,163 @@ static void record_targets_on_both_delivery_paths()
     std::printf("record targets on both delivery paths: ok\n");
 }
 
+// The ORDER of a mirror re-ordered "on the device" (the stub build runs tests/cpp/hip_stub/reorder_cpu.cpp, the plain-loop form of
+// gv_reorder.hip's code kernels): a forest of three-slot trees with free slots, grown twice past 1/8 in one context. After each
+// re-order the entry -> slot table must be in ascending order of the Morton codes of the roots — worked out here, in this file's
+// own words — and a rebuild on the host must give the same table. No two trees share a cell and no live entry has the free slots'
+// code (checked; the seed moves until it holds), so the order does not depend on how the entries lay: within a tree the slots are
+// in slot order on both sides. Every coordinate is positive: a box that is not reset before the second re-order would reach to 0.
+struct OrderedWorld {
+    std::vector<Transform> xf;
+    std::vector<Mesh> meshes;
+    std::vector<uint32_t> e2t;
+
+    void build(uint32_t n, uint32_t seed)
+    {
+        std::mt19937 rng(seed);
+        std::uniform_real_distribution<float> u(0.0f, 1.0f);
+        xf.assign(n, Transform{});
+        meshes.assign(n, Mesh{});
+        e2t.assign(n + 1, GV_NONE);
+        for (uint32_t i = 0; i < n; i++) {
+            Transform& t = xf[i];
+            for (int k = 0; k < 3; k++) {
+                t.position[k] = i % 3 == 0 ? 100.0f + 6000.0f * u(rng) : 50.0f * u(rng);  // roots in the world, children beside them
+                t.scale[k] = 1.0f;
+            }
+            t.rotation[3] = 1.0f;
+            if (i % 3 == 2 && (i / 3) % 17 == 5)
+                continue;  // a free slot (a tree of two: every root is live, so no child is left a root near the origin)
+            t.entity = i + 1;
+            e2t[t.entity] = i;
+            if (i % 3 != 0)
+                t.parent = xf[i - i % 3].entity;
+            t.selfActive = t.ancestorsActive = t.modelWithAncestors = 1;
+            Mesh& m = meshes[i];
+            m.entity = t.entity;
+            m.isEnabled = 1;
+            for (int k = 0; k < 3; k++) {
+                m.aabbMin[k] = -1.0f;
+                m.aabbMax[k] = 1.0f;
+            }
+        }
+    }
+    uint32_t slot_of(uint32_t entity, uint32_t n) const
+    {
+        const uint32_t s = entity && entity < e2t.size() ? e2t[entity] : GV_NONE;
+        return s < n ? s : GV_NONE;
+    }
+    // the code of every one of the first n slots, and whether the world is free of ties among them
+    bool codes(uint32_t n, std::vector<uint32_t>& code) const
+    {
+        std::vector<uint32_t> root(n);
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (uint32_t i = 0; i < n; i++) {
+            uint32_t cur = i;
+            for (uint32_t p; (p = slot_of(xf[cur].parent, n)) != GV_NONE;)
+                cur = p;
+            root[i] = cur;
+            if (cur == i && xf[i].entity)
+                for (int k = 0; k < 3; k++) {
+                    lo[k] = std::min(lo[k], xf[i].position[k]);
+                    hi[k] = std::max(hi[k], xf[i].position[k]);
+                }
+        }
+        code.assign(n, 0x3FFFFFFFu);
+        std::vector<uint32_t> of_roots;
+        for (uint32_t i = 0; i < n; i++) {
+            if (!xf[i].entity)
+                continue;
+            uint32_t c = 0;
+            for (int k = 0; k < 3; k++) {
+                const float f = (xf[root[i]].position[k] - lo[k]) / (hi[k] - lo[k]);  // (every extent is positive here)
+                const uint32_t cell = (uint32_t)std::min(1023.0f, std::max(0.0f, f * 1024.0f));
+                for (uint32_t b = 0; b < 10; b++)
+                    c |= ((cell >> b) & 1u) << (3 * b + k);  // bit b of the x / y / z cell -> bit 3b / 3b + 1 / 3b + 2
+            }
+            code[i] = c;
+            if (root[i] == i)
+                of_roots.push_back(c);
+        }
+        std::sort(of_roots.begin(), of_roots.end());
+        return std::adjacent_find(of_roots.begin(), of_roots.end()) == of_roots.end() && of_roots.back() != 0x3FFFFFFFu;
+    }
+};
+
+static void reorder_gives_the_order_of_a_host_build()
+{
+    const uint32_t sizes[3] = {2000, 2400, 2900};  // built; + 400 (* 8 > 2400); + 500 (* 8 > 2900)
+    OrderedWorld full;
+    std::vector<uint32_t> code;
+    uint32_t seed = 77;
+    for (;; seed++) {
+        full.build(sizes[2], seed);
+        bool free_of_ties = true;
+        for (uint32_t n : sizes)
+            free_of_ties = free_of_ties && full.codes(n, code);
+        if (free_of_ties)
+            break;
+        if (seed == 77 + 16) {
+            std::fprintf(stderr, "reorder order: no world without ties among 16 seeds\n");
+            std::exit(1);
+        }
+    }
+    GvConfig cfg{(uint32_t)sizeof(GvConfig), 0, GV_HIZ_RULE_REFERENCE, 0};
+    GvCtx* ctx = nullptr;
+    CHECK(gv_create(&cfg, &ctx));
+    const GvTransformLayout tl = transform_layout();
+    const GvMeshLayout ml = mesh_layout();
+    std::vector<std::unique_ptr<OrderedWorld>> bound;  // (pools move when they grow; each stays alive while it is bound)
+    auto fetch_in_code_order = [&](uint32_t n, const char* what) {
+        std::vector<uint32_t> table(n, GV_NONE);
+        CHECK(gv_pool_mirror_slots(ctx, 0, table.data(), n));
+        check_permutation(ctx, 0, n);
+        for (uint32_t e = 1; e < n; e++) {
+            const uint32_t a = table[e - 1], b = table[e];
+            if (code[a] > code[b] || (code[a] == code[b] && a > b)) {  // (equal codes: one tree, or free slots — in slot order)
+                std::fprintf(stderr, "reorder order (%s, %u slots): entry %u holds slot %u (code %#x) before slot %u (code %#x)\n", what, n, e - 1, a,
+                             code[a], b, code[b]);
+                std::exit(1);
+            }
+        }
+        return table;
+    };
+    for (int step = 0; step < 3; step++) {
+        const uint32_t n = sizes[step];
+        auto w = std::make_unique<OrderedWorld>();
+        w->xf.assign(full.xf.begin(), full.xf.begin() + n);
+        w->meshes.assign(full.meshes.begin(), full.meshes.begin() + n);
+        w->e2t = full.e2t;  // (still names the slots beyond the pool: the library takes them for no slot)
+        full.codes(n, code);
+        GvStats before{}, after{};
+        CHECK(gv_stats(ctx, &before));
+        CHECK(gv_transform_bind(ctx, w->xf.data(), sizeof(Transform), n, &tl, w->e2t.data(), (uint32_t)w->e2t.size()));
+        CHECK(gv_pool_bind(ctx, 0, w->meshes.data(), sizeof(Mesh), n, &ml));
+        bound.push_back(std::move(w));
+        if (step == 0) {
+            CHECK(gv_hierarchy_rebuild(ctx));
+            fetch_in_code_order(n, "built on the host");
+            continue;
+        }
+        CHECK(gv_sync(ctx));  // no rebuild request: the tail is due, the mirror is re-ordered where it lies
+        CHECK(gv_stats(ctx, &after));
+        if (after.mirror_reorders != before.mirror_reorders + 1) {
+            std::fprintf(stderr, "reorder order: %llu re-orders at %u slots, expected one\n", (unsigned long long)(after.mirror_reorders - before.mirror_reorders), n);
+            std::exit(1);
+        }
+        const std::vector<uint32_t> reordered = fetch_in_code_order(n, "re-ordered where it lay");
+        CHECK(gv_hierarchy_rebuild(ctx));
+        const std::vector<uint32_t> rebuilt = fetch_in_code_order(n, "rebuilt on the host");
+        CHECK(gv_stats(ctx, &before));
+        if (reordered != rebuilt || before.mirror_reorders != after.mirror_reorders) {
+            std::fprintf(stderr, "reorder order: the re-order and the host rebuild disagree at %u slots\n", n);
+            std::exit(1);
+        }
+    }
+    gv_destroy(ctx);
+    std::printf("reorder order: 2 re-orders in code order and as a host rebuild gives it (seed %u): ok\n", seed);
+}
+
 // The sort dispatch's plan as a table (gv_sort_kernels.hpp: sort_plan, sort_mode_for_hint): every capacity at which the form
 // changes, one below and one above, in all three modes, against literals worked out by hand from the rules — up to 16 384 slots
 // the rank sort alone whatever the mode; beyond, the rank sort (12 288-record table) beside the radix passes up to 2^20 slots,
@@ -1893,6 +2052,7 @@ int main(int argc, char** argv)
     exercise(GV_CONFIG_BLOCK_BOUNDS | GV_CONFIG_PROFILE_EVENTS, 30000, 2);
     exercise(GV_CONFIG_BLOCK_BOUNDS, 20000, 0);  // flat + exactly paired: block bounds / emit seeds patched per dirty block (mark_dirty_blocks)
     exercise(GV_CONFIG_LINEAR_SCAN | GV_CONFIG_HIZ_RG16F | GV_CONFIG_KEEP_SLOT_ORDER, 300000, 3);  // (above the device-gather and auto-bounds sizes)
+    reorder_gives_the_order_of_a_host_build();
     for (int ranks : {1, 2, 3, 8})
         exchange_in_threads(ranks);
     for (int seed = 1; seed <= 24; seed++)  // lists that jump at random between empty and the whole pool

@@ -631,6 +631,8 @@ def test_host_orchestration_under_address_and_ub_sanitizers(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(os.environ, GV_RCCL_LIBRARY=transport))
     assert run.returncode == 0 and "host orchestration: ok" in run.stdout, (run.stdout + run.stderr)[-4000:]
     assert "sort plan table: 27 plans and 6 hints as worked out by hand: ok" in run.stdout, run.stdout[:2000]  # (sort_plan, sort_mode_for_hint)
+    # the mirror re-ordered where it lies (reorder_cpu.cpp states the device's rule) is in Morton order and is what a host rebuild gives
+    assert "reorder order: 2 re-orders in code order and as a host rebuild gives it" in run.stdout, run.stdout[:3000]
     assert "exchange over the stub transport, 8 ranks, list sequence 0: ok" in run.stdout, run.stdout[-2000:]
     # ... and 24 sequences of lists that jump at random between empty and the whole pool, 2-5 ranks
     assert run.stdout.count("exchange over the stub transport") == 4 + 24 and "list sequence 24: ok" in run.stdout, run.stdout[-2000:]
