@@ -698,6 +698,12 @@ void gv_destroy(GvCtx* ctx)
         p.d_a.release(); p.d_b.release(); p.d_link.release(); p.h_a.release(); p.h_b.release(); p.h_link.release(); p.d_orig.release(); p.d_inv.release(); p.d_index_map.release(); p.d_blk_lo.release(); p.d_blk_hi.release(); p.d_seed.release(); p.d_kept.release(); p.d_kept_flag.release(); p.d_blk_dirty.release(); p.d_hot.release();
         p.instances.d_data.release(); p.instances.d_starts.release(); p.instances.h_data.release(); p.instances.h_starts.release();
         p.payload.d_rows.release(); p.payload.h_stage.release(); p.payload.d_packet.release();
+        p.instances.d_first.release(); p.instances.d_draw_starts.release(); p.instances.d_local.release();
+        p.instances.d_chunk_total.release(); p.instances.h_first.release();
+        p.counts.d_counts.release(); p.counts.h_stage.release(); p.counts.d_packet.release();
+        if (p.counts.staged)
+            (void)hipEventDestroy(p.counts.staged);
+        p.counts.staged = nullptr;
     }
     for (auto& per_pool : ctx->views)
       for (auto& v : per_pool) {
@@ -869,6 +875,17 @@ int gv_pool_bind_ready(GvCtx* ctx, uint32_t pool_id, const void* data, uint32_t 
     const bool had = p.ready.ptr != nullptr;
     p.ready = Column{static_cast<const uint8_t*>(data), data ? stride : 0};
     p.ready_width = data ? width : 0;
+    p.counts.reset();  // the count mirror (gv_pool_emit_draw_instances) is uploaded anew; without a column there is none
+    if (!data && p.counts.wanted) {
+        p.counts.wanted = false;
+        GV_HIP(ctx, hipSetDevice(ctx->device));
+        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading it)
+        p.counts.staged_pending = false;
+        p.counts.d_counts.release();
+        p.counts.h_stage.release();
+        p.counts.d_packet.release();
+        std::vector<uint32_t>().swap(p.counts.held);
+    }
     if (had != (data != nullptr) && p.bound)
         p.dirty.add(0, p.occupancy);  // the candidate bits of the whole pool may change
     return GV_OK;
@@ -907,6 +924,8 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
         ctx->pools[pool].dirty.add(lo, count);
         if (ctx->pools[pool].payload.count)  // a slot filled anew has a new payload
             ctx->pools[pool].payload.dirty.add(lo, count);
+        if (ctx->pools[pool].counts.wanted)  // ... and its ready count may have changed
+            ctx->pools[pool].counts.dirty.add(lo, count);
         return GV_OK;
     }
     default:

@@ -193,8 +193,11 @@ struct PoolState {
     Column ready;              // gv_pool_bind_ready: per-slot ready count (ptr NULL: none, every slot counts 1)
     uint32_t ready_width = 0;  // 1 or 4 bytes
     uint32_t ready_count(size_t i) const { return !ready.ptr ? 1u : (ready_width == 4 ? ready.u32(i) : (uint32_t)ready.u8(i)); }
-    std::vector<uint8_t> ready_many;  // per slot: a candidate whose ready count is above 1 (kept by gather_meshes; empty without a column)
+    std::vector<uint8_t> ready_many;  // per slot, kept by gather_meshes (empty without a column): kReadyLive for a candidate, and in
+                                      // the low bits 1 when its ready count is above 1, 2 when it is above GV_MAX_DRAW_INSTANCES too
+    static constexpr uint8_t kReadyLive = 4, kReadyLevel = 3;
     uint32_t ready_many_count = 0;    // ... and how many: such draws take several instances (gv_pool_emit_instances refuses them)
+    uint32_t ready_over_count = 0;    // ... of those, above GV_MAX_DRAW_INSTANCES (flag 2 in ready_many): gv_pool_emit_draw_instances refuses them
     // gv_pool_set_instance_layout / gv_pool_emit_instances: buffers of their own, nothing a cull produced is touched
     struct Instances {
         GvInstanceLayout layout{};      // stride 0: none
@@ -209,7 +212,48 @@ struct PoolState {
         GvInstanceLayout emitted{};     // the layout it was made with
         uint32_t emitted_payload = 0;   // ... and the payload fields it wrote: (at, bytes) each
         uint32_t emitted_at[GV_MAX_PAYLOAD_FIELDS] = {}, emitted_bytes[GV_MAX_PAYLOAD_FIELDS] = {};
+        struct PayloadPlaces {          // what an emission is about to write of the payload: noted above once it has been launched
+            uint32_t count = 0;
+            uint32_t at[GV_MAX_PAYLOAD_FIELDS] = {}, bytes[GV_MAX_PAYLOAD_FIELDS] = {};
+        };
+        void note_payload(const PayloadPlaces& w)
+        {
+            emitted_payload = w.count;
+            std::copy(w.at, w.at + GV_MAX_PAYLOAD_FIELDS, emitted_at);
+            std::copy(w.bytes, w.bytes + GV_MAX_PAYLOAD_FIELDS, emitted_bytes);
+        }
+        // gv_pool_emit_draw_instances (a draw takes its ready count of instances): starts[] then holds instance starts
+        uint32_t index_at = GV_NONE;       // gv_pool_set_instance_index_field: the uint32 "index within the draw"
+        uint32_t emitted_index = GV_NONE;  // ... as the last emission wrote it (GV_NONE: it did not)
+        bool draws = false;                // the last emission was a draw emission: the buffers below describe it
+        DeviceBuf<uint32_t> d_first;       // first_instance[draw_starts[v] + k], one more word: the grand total
+        DeviceBuf<uint32_t> d_draw_starts; // [views + 1]
+        DeviceBuf<uint32_t> d_local, d_chunk_total;  // scratch between the two launches
+        PinnedBuf<uint32_t> h_first;       // staging of gv_pool_draw_bases_fetch
     } instances;
+    // The ready column on the device, one uint32 per POOL SLOT (indexed by visible_idx like the payload rows; a re-order of the
+    // mirror does not concern it): exists only once gv_pool_emit_draw_instances has been called for a pool with a ready column
+    struct Counts {
+        bool wanted = false;
+        uint32_t mirrored = 0;             // counts [0, mirrored) are on the device (0: everything is uploaded)
+        uint64_t sum = 0;                  // of the mirrored counts: the host's bound of a view's instances
+        std::vector<uint32_t> held;        // what was uploaded, slot by slot (keeps `sum` exact under partial uploads)
+        std::vector<uint32_t> over;        // the slots whose mirrored count is above GV_MAX_DRAW_INSTANCES (few, if any): a mark made
+                                           // after the last sync may have put one there, which ready_over_count has not seen
+        hipEvent_t staged = nullptr;       // behind the last copies that read h_stage: the next upload waits for THIS, not for the
+        bool staged_pending = false;       // context's upload event (which a payload upload of the same call has just recorded)
+        DirtyRanges dirty;                 // the pool's GV_DIRTY_MESH marks
+        DeviceBuf<uint32_t> d_counts;
+        PinnedBuf<uint32_t> h_stage;       // the counts (and, behind them, the packet's slots) on their way up
+        DeviceBuf<uint32_t> d_packet;
+        void reset()                       // the column was rebound: everything is uploaded again
+        {
+            mirrored = 0;
+            sum = 0;
+            dirty.clear();
+            over.clear();
+        }
+    } counts;
     // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
     // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
     // transform mirror does not concern it); read by gv_pool_emit_instances only
@@ -610,6 +654,7 @@ int copy_shard_of_pool(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, void* 
 // ranges; then the payload rows; then, when a tail is due, the re-order on the device (rules: gv_dirty_ranges.hpp)
 int sync_mirror(GvCtx* ctx);
 int upload_payload(GvCtx* ctx, PoolState& p);  // a pool's payload rows likewise (new slots + its own dirty set); sync_mirror calls it too
+int upload_counts(GvCtx* ctx, PoolState& p);   // ... and its count mirror (PoolState::Counts), once gv_pool_emit_draw_instances wants one
 TransformMirror xf_mirror(const GvCtx* ctx);  // the transform mirror as the kernels see it
 MeshMirror mesh_mirror(const PoolState& p);   // a pool's mirror likewise (hot: null; the sphere stream's upkeep in cull_launch sets it)
 

@@ -5,6 +5,9 @@
 // instances): the cull side is left as a read through gv_pool_results_device leaves it.
 // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes a plugin copies next to mvp (sprite.cpp:127-129), mirrored
 // per pool slot (gv_mirror.cpp upload_payload) and written by the same launch (instance_kernel<true>).
+// gv_pool_emit_draw_instances / gv_pool_set_instance_index_field / gv_pool_draw_bases_device / gv_pool_draw_bases_fetch: the same for
+// draws that take several instances — the ready count of the record's slot, read on the device from a mirror of the ready column
+// (gv_mirror.cpp upload_counts); two launches (draw_counts_kernel, draw_instances_kernel), the host never reads a count.
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -46,6 +49,128 @@ bool payload_fits(const GvInstanceLayout& L, const PoolState::Payload& P, const 
         f[n++] = Field{at[k], P.bytes[k], 4};
     }
     return true;
+}
+
+// the "index within the draw" word of gv_pool_set_instance_index_field against the layout and the destinations `at` (stride 0: none
+// yet — only the destinations): 4-byte aligned, inside the stride, disjoint from the layout's fields and the payload destinations
+bool index_fits(const GvInstanceLayout& L, const PoolState::Payload& P, const uint32_t* at, uint32_t index_at)
+{
+    Field f[4 + GV_MAX_PAYLOAD_FIELDS];
+    uint32_t n = L.stride ? fields_of(L, f) : 0;
+    for (uint32_t k = 0; k < P.count; k++)
+        if (at[k] != GV_NONE)
+            f[n++] = Field{at[k], P.bytes[k], 4};
+    if (index_at % 4 != 0 || index_at > kMaxInstanceStride - 4 || (L.stride && index_at > L.stride - 4))
+        return false;
+    for (uint32_t j = 0; j < n; j++)
+        if (!(index_at + 4 <= f[j].at || f[j].at + f[j].bytes <= index_at))
+            return false;
+    return true;
+}
+
+// What gv_pool_emit_instances and gv_pool_emit_draw_instances (`fn`) check alike: the arguments, the layout, the listed views
+// (results, not count-only, covered by the index map) and the payload's fit and occupancy. *with_payload: a destination is set.
+int check_emission(GvCtx* ctx, const char* fn, uint32_t pool_id, const uint32_t* view_indices, uint32_t view_count, const void* dst_device,
+                   bool* with_payload)
+{
+    if (!ctx)
+        return GV_E_ARG;
+    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
+        return ctx->fail(GV_E_ARG, "%s: pool %u is not bound", fn, pool_id);
+    PoolState& p = ctx->pools[pool_id];
+    uint32_t culled = 0;
+    while (culled < GV_MAX_VIEWS && ctx->views[pool_id][culled].valid)
+        culled++;
+    if (!view_indices || view_count == 0 || view_count > culled)
+        return ctx->fail(GV_E_ARG, "%s: %u views listed, the last gv_cull of pool %u had %u", fn, view_count, pool_id, culled);
+    if (dst_device && (uintptr_t)dst_device % 16 != 0)
+        return ctx->fail(GV_E_ARG, "%s: dst_device must be 16-byte aligned", fn);
+    uint32_t listed = 0;
+    for (uint32_t k = 0; k < view_count; k++) {
+        const uint32_t v = view_indices[k];
+        if (v >= GV_MAX_VIEWS || ((listed >> v) & 1u))
+            return ctx->fail(GV_E_ARG, "%s: view index %u is out of range or listed twice", fn, v);
+        listed |= 1u << v;
+    }
+    const GvInstanceLayout L = p.instances.layout;
+    if (!L.stride)
+        return ctx->fail(GV_E_STATE, "%s: pool %u has no instance layout (gv_pool_set_instance_layout)", fn, pool_id);
+    for (uint32_t k = 0; k < view_count; k++) {
+        const ViewState* vs = view_of(ctx, pool_id, view_indices[k]);
+        if (!vs)
+            return ctx->fail(GV_E_STATE, "%s: pool %u view %u has no results", fn, pool_id, view_indices[k]);
+        if (!vs->emitted)
+            return ctx->fail(GV_E_STATE, "%s: pool %u view %u was culled count-only (emit_records == 0)", fn, pool_id, view_indices[k]);
+        if (L.slot != GV_NONE && p.index_map_count && p.index_map_count < vs->occupancy)
+            return ctx->fail(GV_E_STATE, "%s: the index map of pool %u covers %u of its %u slots", fn, pool_id, p.index_map_count, vs->occupancy);
+    }
+    const PoolState::Payload& P = p.payload;
+    *with_payload = P.count && P.any_destination();
+    if (*with_payload) {
+        if (!payload_fits(L, P, P.at))
+            return ctx->fail(GV_E_ARG, "%s: the payload destinations of pool %u do not fit its instance layout (stride %u)", fn, pool_id, L.stride);
+        for (uint32_t k = 0; k < view_count; k++)
+            if (P.occupancy < view_of(ctx, pool_id, view_indices[k])->occupancy)
+                return ctx->fail(GV_E_STATE, "%s: the payload of pool %u covers %u of the %u slots view %u was culled with "
+                                 "(gv_pool_bind_payload)", fn, pool_id, P.occupancy, view_of(ctx, pool_id, view_indices[k])->occupancy, view_indices[k]);
+    }
+    return GV_OK;
+}
+
+// What both emissions launch with: the listed views and their workgroups, the layout, the index map, and — with_payload — where each
+// word of a payload row goes (`places`: what the fetch is to deliver, noted by the caller once the launch is made). slots: the sum of the views' occupancies. Returns the
+// bytes of an instance that the fields and the payload cover.
+uint32_t fill_launch(GvCtx* ctx, const PoolState& p, const uint32_t* view_indices, uint32_t view_count, bool with_payload, InstanceLaunch& launch,
+                     uint64_t& slots, PoolState::Instances::PayloadPlaces& places)
+{
+    const uint32_t pool_id = (uint32_t)(&p - ctx->pools);
+    const PoolState::Payload& P = p.payload;
+    const GvInstanceLayout L = p.instances.layout;
+    for (uint32_t k = 0; k < view_count; k++) {
+        const ViewState& vs = *view_of(ctx, pool_id, view_indices[k]);
+        InstanceView& w = launch.view[k];
+        w.count = vs.draw_count.ptr;
+        w.idx = vs.visible_idx.ptr;
+        w.model = vs.baked_model.ptr;
+        w.dist = vs.distance_sq.ptr;
+        memcpy(w.view_proj, vs.view_proj, sizeof(w.view_proj));
+        launch.first_block[k + 1] = launch.first_block[k] + (vs.occupancy + kInstanceBlock - 1) / kInstanceBlock;
+        slots += vs.occupancy;
+    }
+    launch.views = view_count;
+    launch.stride = L.stride;
+    launch.mvp = L.mvp;
+    launch.model = L.model;
+    launch.slot = L.slot;
+    launch.distance_sq = L.distance_sq;
+    launch.index_map = p.index_map_count ? p.d_index_map.ptr : nullptr;
+    uint32_t covered = 64;  // mvp
+    covered += (L.model != GV_NONE ? 48 : 0) + (L.slot != GV_NONE ? 4 : 0) + (L.distance_sq != GV_NONE ? 4 : 0);
+    places.count = 0;
+    if (with_payload) {
+        // where each word of a row goes; a 16-byte piece whose four words go to one 16-byte aligned place travels whole
+        launch.payload_rows = P.d_rows.ptr;
+        launch.payload_pitch = P.pitch;
+        std::fill(launch.piece_at, launch.piece_at + 4, kNoPayloadPlace);
+        std::fill(launch.word_at, launch.word_at + 16, kNoPayloadPlace);
+        for (uint32_t f = 0; f < P.count; f++) {
+            if (P.at[f] == GV_NONE)
+                continue;
+            for (uint32_t w = 0; w < P.bytes[f] / 4; w++)
+                launch.word_at[P.offset[f] / 4 + w] = (uint16_t)(P.at[f] + 4 * w);
+            covered += P.bytes[f];
+            places.at[places.count] = P.at[f];
+            places.bytes[places.count++] = P.bytes[f];
+        }
+        for (uint32_t j = 0; j < 4; j++) {
+            uint16_t* w = launch.word_at + 4 * j;
+            if (w[0] != kNoPayloadPlace && w[0] % 16 == 0 && w[1] == w[0] + 4 && w[2] == w[0] + 8 && w[3] == w[0] + 12) {
+                launch.piece_at[j] = w[0];
+                std::fill(w, w + 4, kNoPayloadPlace);
+            }
+        }
+    }
+    return covered;
 }
 
 }  // namespace
@@ -119,6 +244,9 @@ int gv_pool_set_payload_layout(GvCtx* ctx, uint32_t pool_id, const uint32_t* at,
     if (!payload_fits(p.instances.layout, p.payload, at))
         return ctx->fail(GV_E_ARG, "gv_pool_set_payload_layout: destinations must be 4-byte aligned, lie inside the instance (stride %u) and be "
                          "disjoint from each other and from mvp / model / slot / distance_sq", p.instances.layout.stride);
+    if (p.instances.index_at != GV_NONE && !index_fits(p.instances.layout, p.payload, at, p.instances.index_at))
+        return ctx->fail(GV_E_ARG, "gv_pool_set_payload_layout: the destinations overlap the index field of pool %u at %u "
+                         "(gv_pool_set_instance_index_field)", pool_id, p.instances.index_at);
     std::copy(at, at + count, p.payload.at);  // read by the next emission
     return GV_OK;
 }
@@ -150,6 +278,11 @@ int gv_pool_set_instance_layout(GvCtx* ctx, uint32_t pool_id, const GvInstanceLa
     if (layout && ctx->pools[pool_id].payload.count && !payload_fits(L, ctx->pools[pool_id].payload, ctx->pools[pool_id].payload.at))
         return ctx->fail(GV_E_ARG, "gv_pool_set_instance_layout: the payload destinations of pool %u (gv_pool_set_payload_layout) do not fit "
                          "this layout: they must lie inside the stride (%u) and be disjoint from mvp / model / slot / distance_sq", pool_id, L.stride);
+    if (layout && ctx->pools[pool_id].instances.index_at != GV_NONE &&
+        !index_fits(L, ctx->pools[pool_id].payload, ctx->pools[pool_id].payload.at, ctx->pools[pool_id].instances.index_at))
+        return ctx->fail(GV_E_ARG, "gv_pool_set_instance_layout: the index field of pool %u at %u (gv_pool_set_instance_index_field) does not fit "
+                         "this layout: it must lie inside the stride (%u) and be disjoint from mvp / model / slot / distance_sq", pool_id,
+                         ctx->pools[pool_id].instances.index_at, L.stride);
     ctx->pools[pool_id].instances.layout = L;  // read by the next emission; an emission already made keeps the layout it was made with
     return GV_OK;
 }
@@ -157,51 +290,13 @@ int gv_pool_set_instance_layout(GvCtx* ctx, uint32_t pool_id, const GvInstanceLa
 int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_indices, uint32_t view_count, void* dst_device,
                            size_t capacity_bytes)
 {
-    if (!ctx)
-        return GV_E_ARG;
-    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
-        return ctx->fail(GV_E_ARG, "gv_pool_emit_instances: pool %u is not bound", pool_id);
+    const char* const fn = "gv_pool_emit_instances";
+    bool with_payload = false;
+    if (int rc = check_emission(ctx, fn, pool_id, view_indices, view_count, dst_device, &with_payload))
+        return rc;
     PoolState& p = ctx->pools[pool_id];
     PoolState::Instances& I = p.instances;
-    uint32_t culled = 0;
-    while (culled < GV_MAX_VIEWS && ctx->views[pool_id][culled].valid)
-        culled++;
-    if (!view_indices || view_count == 0 || view_count > culled)
-        return ctx->fail(GV_E_ARG, "gv_pool_emit_instances: %u views listed, the last gv_cull of pool %u had %u", view_count, pool_id, culled);
-    if (dst_device && (uintptr_t)dst_device % 16 != 0)
-        return ctx->fail(GV_E_ARG, "gv_pool_emit_instances: dst_device must be 16-byte aligned");
-    uint32_t listed = 0;
-    for (uint32_t k = 0; k < view_count; k++) {
-        const uint32_t v = view_indices[k];
-        if (v >= GV_MAX_VIEWS || ((listed >> v) & 1u))
-            return ctx->fail(GV_E_ARG, "gv_pool_emit_instances: view index %u is out of range or listed twice", v);
-        listed |= 1u << v;
-    }
     const GvInstanceLayout L = I.layout;
-    if (!L.stride)
-        return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: pool %u has no instance layout (gv_pool_set_instance_layout)", pool_id);
-    for (uint32_t k = 0; k < view_count; k++) {
-        const ViewState* vs = view_of(ctx, pool_id, view_indices[k]);
-        if (!vs)
-            return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: pool %u view %u has no results", pool_id, view_indices[k]);
-        if (!vs->emitted)
-            return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: pool %u view %u was culled count-only (emit_records == 0)", pool_id,
-                             view_indices[k]);
-        if (L.slot != GV_NONE && p.index_map_count && p.index_map_count < vs->occupancy)
-            return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: the index map of pool %u covers %u of its %u slots", pool_id, p.index_map_count,
-                             vs->occupancy);
-    }
-    const PoolState::Payload& P = p.payload;
-    const bool with_payload = P.count && P.any_destination();
-    if (with_payload) {
-        if (!payload_fits(L, P, P.at))
-            return ctx->fail(GV_E_ARG, "gv_pool_emit_instances: the payload destinations of pool %u do not fit its instance layout (stride %u)",
-                             pool_id, L.stride);
-        for (uint32_t k = 0; k < view_count; k++)
-            if (P.occupancy < view_of(ctx, pool_id, view_indices[k])->occupancy)
-                return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: the payload of pool %u covers %u of the %u slots view %u was culled with "
-                                 "(gv_pool_bind_payload)", pool_id, P.occupancy, view_of(ctx, pool_id, view_indices[k])->occupancy, view_indices[k]);
-    }
     if (p.ready.ptr && p.ready_many_count)
         return ctx->fail(GV_E_STATE, "gv_pool_emit_instances: the ready column of pool %u holds %u live counts above 1: such a draw takes several "
                          "instances, and the instance index of draw k is k only while every draw takes one (ready counts of 0 / 1 work)",
@@ -210,29 +305,13 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
     if (int rc = flush_sorts(ctx))  // the emission is a read: recorded culls and deferred sorts first (as gv_pool_results_device)
         return rc;
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    if (P.count)  // marks made since the cull are seen by this emission (the reference reads the component at draw time, mesh.cpp:592)
+    if (p.payload.count)  // marks made since the cull are seen by this emission (the reference reads the component at draw time, mesh.cpp:592)
         if (int rc = upload_payload(ctx, p))
             return rc;
     InstanceLaunch launch{};
     uint64_t bound = 0;  // the host's upper bound of the total
-    for (uint32_t k = 0; k < view_count; k++) {
-        const ViewState& vs = *view_of(ctx, pool_id, view_indices[k]);
-        InstanceView& w = launch.view[k];
-        w.count = vs.draw_count.ptr;
-        w.idx = vs.visible_idx.ptr;
-        w.model = vs.baked_model.ptr;
-        w.dist = vs.distance_sq.ptr;
-        memcpy(w.view_proj, vs.view_proj, sizeof(w.view_proj));
-        launch.first_block[k + 1] = launch.first_block[k] + (vs.occupancy + kInstanceBlock - 1) / kInstanceBlock;
-        bound += vs.occupancy;
-    }
-    launch.views = view_count;
-    launch.stride = L.stride;
-    launch.mvp = L.mvp;
-    launch.model = L.model;
-    launch.slot = L.slot;
-    launch.distance_sq = L.distance_sq;
-    launch.index_map = p.index_map_count ? p.d_index_map.ptr : nullptr;
+    PoolState::Instances::PayloadPlaces places;
+    const uint32_t covered = fill_launch(ctx, p, view_indices, view_count, with_payload, launch, bound, places);
     if (dst_device) {
         launch.dst = static_cast<uint8_t*>(dst_device);
         launch.capacity = (uint32_t)std::min<uint64_t>(capacity_bytes / L.stride, bound);
@@ -243,39 +322,166 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
     }
     GV_HIP(ctx, I.d_starts.reserve(GV_MAX_VIEWS + 1));
     launch.starts = I.d_starts.ptr;
-    I.emitted_payload = 0;
-    if (with_payload) {
-        // where each word of a row goes; a 16-byte piece whose four words go to one 16-byte aligned place travels whole
-        launch.payload_rows = P.d_rows.ptr;
-        launch.payload_pitch = P.pitch;
-        std::fill(launch.piece_at, launch.piece_at + 4, kNoPayloadPlace);
-        std::fill(launch.word_at, launch.word_at + 16, kNoPayloadPlace);
-        uint32_t covered = 64;  // mvp
-        covered += (L.model != GV_NONE ? 48 : 0) + (L.slot != GV_NONE ? 4 : 0) + (L.distance_sq != GV_NONE ? 4 : 0);
-        for (uint32_t f = 0; f < P.count; f++) {
-            if (P.at[f] == GV_NONE)
-                continue;
-            for (uint32_t w = 0; w < P.bytes[f] / 4; w++)
-                launch.word_at[P.offset[f] / 4 + w] = (uint16_t)(P.at[f] + 4 * w);
-            covered += P.bytes[f];
-            I.emitted_at[I.emitted_payload] = P.at[f];
-            I.emitted_bytes[I.emitted_payload++] = P.bytes[f];
-        }
-        for (uint32_t j = 0; j < 4; j++) {
-            uint16_t* w = launch.word_at + 4 * j;
-            if (w[0] != kNoPayloadPlace && w[0] % 16 == 0 && w[1] == w[0] + 4 && w[2] == w[0] + 8 && w[3] == w[0] + 12) {
-                launch.piece_at[j] = w[0];
-                std::fill(w, w + 4, kNoPayloadPlace);
-            }
-        }
-        // fields and payload are disjoint and inside the stride: together as many bytes as the stride = all of it
-        launch.staged = covered == L.stride && L.stride <= kMaxStagedInstanceStride;
-    }
+    // fields and payload are disjoint and inside the stride: together as many bytes as the stride = all of it
+    launch.staged = with_payload && covered == L.stride && L.stride <= kMaxStagedInstanceStride;
     GV_HIP(ctx, launch_instances(launch, ctx->stream));
     I.target = launch.dst;
     I.capacity = launch.capacity;
     I.views = view_count;
     I.emitted = L;
+    I.note_payload(places);
+    I.emitted_index = GV_NONE;
+    I.draws = false;
+    return GV_OK;
+}
+
+int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_indices, uint32_t view_count, void* dst_device,
+                                size_t capacity_bytes)
+{
+    static_assert(kDrawChunk % kInstanceBlock == 0, "a chunk is a whole number of draw_instances_kernel workgroups");
+    const char* const fn = "gv_pool_emit_draw_instances";
+    bool with_payload = false;
+    if (int rc = check_emission(ctx, fn, pool_id, view_indices, view_count, dst_device, &with_payload))
+        return rc;
+    PoolState& p = ctx->pools[pool_id];
+    PoolState::Instances& I = p.instances;
+    PoolState::Counts& K = p.counts;
+    const GvInstanceLayout L = I.layout;
+    if (I.index_at != GV_NONE && !index_fits(L, p.payload, p.payload.at, I.index_at))
+        return ctx->fail(GV_E_ARG, "gv_pool_emit_draw_instances: the index field of pool %u (offset %u) does not fit its instance layout (stride %u) "
+                         "and payload destinations", pool_id, I.index_at, L.stride);
+    const bool counted = p.ready.ptr != nullptr;
+    if (counted && p.result_flags)
+        return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_instances: pool %u has a ready column AND a result mapping (gv_pool_set_result_mapping): "
+                         "not available together", pool_id);
+    if (counted && p.ready_over_count)
+        return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_instances: the ready column of pool %u holds %u live counts above the limit of %u "
+                         "instances per draw (GV_MAX_DRAW_INSTANCES)", pool_id, p.ready_over_count, GV_MAX_DRAW_INSTANCES);
+    if (counted)
+        for (uint32_t k = 0; k < view_count; k++)
+            if (p.occupancy < view_of(ctx, pool_id, view_indices[k])->occupancy)
+                return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_instances: the ready column of pool %u covers %u of the %u slots view %u was culled "
+                                 "with", pool_id, p.occupancy, view_of(ctx, pool_id, view_indices[k])->occupancy, view_indices[k]);
+    ZoneScope zone("Meshes Draw Instances");
+    if (int rc = flush_sorts(ctx))  // the emission is a read: recorded culls and deferred sorts first (as gv_pool_results_device)
+        return rc;
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    if (p.payload.count)  // marks made since the cull are seen by this emission (mesh.cpp:592)
+        if (int rc = upload_payload(ctx, p))
+            return rc;
+    if (counted) {  // ... and so are the counts (getInstancesAsync is read at draw time, mesh.cpp:597); the first call uploads the column
+        K.wanted = true;
+        if (int rc = upload_counts(ctx, p))
+            return rc;
+        // a mark made since the last gv_sync may have put a count above the limit into the mirror (ready_over_count has not seen it);
+        // live: a candidate as of that sync, hence possibly a draw of the cull
+        uint32_t over = 0;
+        for (uint32_t slot : K.over)
+            over += slot < p.ready_many.size() && (p.ready_many[slot] & PoolState::kReadyLive);
+        if (over)
+            return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_instances: the ready column of pool %u holds %u live counts above the limit of %u "
+                             "instances per draw (GV_MAX_DRAW_INSTANCES), marked since the last gv_sync", pool_id, over, GV_MAX_DRAW_INSTANCES);
+    }
+    DrawInstanceLaunch launch{};
+    uint64_t slots = 0;  // the sum of the listed views' occupancies: the host's upper bound of the DRAWS
+    PoolState::Instances::PayloadPlaces places;
+    uint32_t covered = fill_launch(ctx, p, view_indices, view_count, with_payload, launch.base, slots, places);
+    for (uint32_t k = 0; k < view_count; k++)
+        launch.first_chunk[k + 1] = launch.first_chunk[k] + (view_of(ctx, pool_id, view_indices[k])->occupancy + kDrawChunk - 1) / kDrawChunk;
+    // the host's upper bound of the INSTANCES: a view draws a slot at most once
+    const uint64_t bound = counted ? (uint64_t)view_count * K.sum : slots;
+    if (dst_device) {
+        launch.base.dst = static_cast<uint8_t*>(dst_device);
+        launch.base.capacity = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(capacity_bytes / L.stride, bound), UINT32_MAX);
+    } else {
+        if (bound > UINT32_MAX)
+            return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_instances: %u views of pool %u may take %llu instances, more than 32 bits hold: pass a "
+                             "caller-owned target (dst_device) sized for what is drawn", view_count, pool_id, (unsigned long long)bound);
+        GV_HIP(ctx, I.d_data.reserve(std::max<size_t>((size_t)bound * L.stride, 16)));
+        launch.base.dst = I.d_data.ptr;
+        launch.base.capacity = (uint32_t)bound;
+    }
+    GV_HIP(ctx, I.d_starts.reserve(GV_MAX_VIEWS + 1));
+    GV_HIP(ctx, I.d_draw_starts.reserve(GV_MAX_VIEWS + 1));
+    GV_HIP(ctx, I.d_first.reserve((size_t)slots + 1));
+    GV_HIP(ctx, I.d_local.reserve(std::max<size_t>((size_t)launch.base.first_block[view_count] * kInstanceBlock, 1)));
+    GV_HIP(ctx, I.d_chunk_total.reserve(std::max<size_t>(launch.first_chunk[view_count], 1)));
+    launch.base.starts = I.d_starts.ptr;
+    launch.draw_starts = I.d_draw_starts.ptr;
+    launch.first_instance = I.d_first.ptr;
+    launch.local = I.d_local.ptr;
+    launch.chunk_total = I.d_chunk_total.ptr;
+    launch.counts = counted ? K.d_counts.ptr : nullptr;
+    launch.index_at = I.index_at;
+    covered += I.index_at != GV_NONE ? 4 : 0;
+    launch.base.staged = covered == L.stride && L.stride <= kMaxStagedInstanceStride;
+    GV_HIP(ctx, launch_draw_instances(launch, ctx->stream));
+    I.target = launch.base.dst;
+    I.capacity = launch.base.capacity;
+    I.views = view_count;
+    I.emitted = L;
+    I.note_payload(places);
+    I.emitted_index = I.index_at;
+    I.draws = true;
+    return GV_OK;
+}
+
+int gv_pool_set_instance_index_field(GvCtx* ctx, uint32_t pool_id, uint32_t offset)
+{
+    if (!ctx)
+        return GV_E_ARG;
+    if (pool_id >= GV_MAX_POOLS)
+        return ctx->fail(GV_E_ARG, "gv_pool_set_instance_index_field: pool %u out of range", pool_id);
+    PoolState& p = ctx->pools[pool_id];
+    if (offset != GV_NONE && !index_fits(p.instances.layout, p.payload, p.payload.at, offset))
+        return ctx->fail(GV_E_ARG, "gv_pool_set_instance_index_field: offset %u must be 4-byte aligned, lie inside the instance (stride %u) and be "
+                         "disjoint from mvp / model / slot / distance_sq and the payload destinations", offset, p.instances.layout.stride);
+    p.instances.index_at = offset;  // read by the next draw emission
+    return GV_OK;
+}
+
+int gv_pool_draw_bases_device(GvCtx* ctx, uint32_t pool_id, const void** first_instance, const void** draw_starts)
+{
+    if (!ctx)
+        return GV_E_ARG;
+    if (pool_id >= GV_MAX_POOLS || !first_instance || !draw_starts)
+        return ctx->fail(GV_E_ARG, "gv_pool_draw_bases_device: bad argument (pool %u)", pool_id);
+    const PoolState::Instances& I = ctx->pools[pool_id].instances;
+    if (!I.views || !I.draws)
+        return ctx->fail(GV_E_STATE, "gv_pool_draw_bases_device: the last emission of pool %u since its last gv_cull is not a draw emission "
+                         "(gv_pool_emit_draw_instances)", pool_id);
+    *first_instance = I.d_first.ptr;
+    *draw_starts = I.d_draw_starts.ptr;
+    return GV_OK;
+}
+
+int gv_pool_draw_bases_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* first_instance, uint32_t capacity, uint32_t* draw_starts,
+                             uint32_t starts_capacity)
+{
+    if (!ctx)
+        return GV_E_ARG;
+    if (pool_id >= GV_MAX_POOLS || !draw_starts)
+        return ctx->fail(GV_E_ARG, "gv_pool_draw_bases_fetch: bad argument (pool %u)", pool_id);
+    PoolState::Instances& I = ctx->pools[pool_id].instances;
+    if (!I.views || !I.draws)
+        return ctx->fail(GV_E_STATE, "gv_pool_draw_bases_fetch: the last emission of pool %u since its last gv_cull is not a draw emission "
+                         "(gv_pool_emit_draw_instances)", pool_id);
+    if (starts_capacity < I.views + 1)
+        return ctx->fail(GV_E_ARG, "gv_pool_draw_bases_fetch: room for %u starts, the emission listed %u views", starts_capacity, I.views);
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    GV_HIP(ctx, I.h_starts.reserve(GV_MAX_VIEWS + 1));
+    GV_HIP(ctx, hipMemcpyAsync(I.h_starts.ptr, I.d_draw_starts.ptr, (I.views + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t draws = I.h_starts.ptr[I.views];
+    if (first_instance && capacity < (uint64_t)draws + 1)
+        return ctx->fail(GV_E_ARG, "gv_pool_draw_bases_fetch: room for %u words, %u draws and the closing total", capacity, draws);
+    if (first_instance) {
+        GV_HIP(ctx, I.h_first.reserve((size_t)draws + 1));
+        GV_HIP(ctx, hipMemcpyAsync(I.h_first.ptr, I.d_first.ptr, ((size_t)draws + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(first_instance, I.h_first.ptr, ((size_t)draws + 1) * sizeof(uint32_t));
+    }
+    memcpy(draw_starts, I.h_starts.ptr, (I.views + 1) * sizeof(uint32_t));
     return GV_OK;
 }
 
@@ -339,10 +545,12 @@ int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t
     GV_HIP(ctx, I.h_data.reserve((size_t)held * L.stride));
     GV_HIP(ctx, hipMemcpyAsync(I.h_data.ptr, I.target, (size_t)held * L.stride, hipMemcpyDeviceToHost, ctx->stream));
     GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    Field f[4 + GV_MAX_PAYLOAD_FIELDS];
+    Field f[4 + GV_MAX_PAYLOAD_FIELDS + 1];
     uint32_t n = fields_of(L, f);
     for (uint32_t k = 0; k < I.emitted_payload; k++)  // the payload fields the emission wrote
         f[n++] = Field{I.emitted_at[k], I.emitted_bytes[k], 4};
+    if (I.emitted_index != GV_NONE)  // ... and the index field of a draw emission
+        f[n++] = Field{I.emitted_index, 4, 4};
     uint8_t* const to = static_cast<uint8_t*>(dst_host);
     const uint8_t* const from = I.h_data.ptr;
     parallel_ranges(0, held, [&](uint32_t a, uint32_t b) {

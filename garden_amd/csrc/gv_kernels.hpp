@@ -222,6 +222,35 @@ struct InstanceLaunch {
 constexpr uint16_t kNoPayloadPlace = 0xFFFFu;
 constexpr uint32_t kMaxStagedInstanceStride = 128;   // 256 x 128 B = 32 KB of LDS per workgroup
 hipError_t launch_instances(const InstanceLaunch& launch, hipStream_t stream);
+// gv_pool_emit_draw_instances (gv_instance.hip): the same records, but draw k takes count[visible_idx[k]] instances (the pool's
+// mirrored ready column). TWO launches, no atomics, no host read: draw_counts_kernel scans the counts per chunk of kDrawChunk
+// records (chunk-local prefix per record + one total per chunk; a chunk beyond its view's device count stores 0, so ONE flat
+// prefix over the chunk table also carries the views in front), draw_instances_kernel adds up the totals in front of its chunk,
+// writes first_instance[] and expands every record's instance into its count consecutive instances.
+constexpr uint32_t kDrawChunk = 4096;                // records per chunk: 16 per lane of a kInstanceBlock workgroup
+constexpr uint32_t kDirectImagePieces = 12;          // the direct way's LDS image per record: mvp 4, model 3, (slot, distance_sq) 1, row 4
+struct DrawInstanceLaunch {
+    InstanceLaunch base;                             // views, layout, target, payload tables; first_block: 256-record workgroups.
+                                                     // staged: fields + payload + index field cover the whole stride (<= 128);
+                                                     // starts: INSTANCE starts [views + 1]
+    uint32_t first_chunk[kMaxInstanceViews + 1];     // chunks in front of view v
+    const uint32_t* counts;                          // one per POOL SLOT (NULL: no ready column, every count is 1)
+    uint32_t index_at;                               // offset of the uint32 "index within the draw" (kNoField: none)
+    uint32_t* local;                                 // record k of view v at first_block[v] * kInstanceBlock + k: prefix inside its chunk
+    uint32_t* chunk_total;                           // [first_chunk[views]]
+    uint32_t* first_instance;                        // [draw_starts[v] + k]; one more word behind the last draw: the grand total
+    uint32_t* draw_starts;                           // [views + 1]: prefix of the listed views' draw counts
+};
+// LDS of a draw_instances_kernel workgroup (dynamic: the bare layout's 16 KB image leaves room for 9 workgroups per CU, the direct
+// way's 48 KB for 3): the image, then the 257-entry prefix and a few words of scratch
+constexpr uint32_t kDrawLdsTail = 1088;
+inline __host__ __device__ uint32_t draw_image_bytes(uint32_t staged, uint32_t stride)
+{
+    return kInstanceBlock * (staged ? stride : kDirectImagePieces * 16u);
+}
+hipError_t launch_draw_instances(const DrawInstanceLaunch& launch, hipStream_t stream);
+// the small dirty ranges of a pool's count mirror: counts[slots[t]] = packet[t]
+hipError_t launch_scatter_counts(const uint32_t* packet, const uint32_t* slots, uint32_t count, uint32_t* counts, hipStream_t stream);
 // read-only pass over the cull kernel's input streams (65 B per entry); gv_debug_stream_peak
 hipError_t launch_stream_probe(const MeshMirror& mesh, const TransformMirror& xf, float* sink, hipStream_t stream);
 // Table-driven tick (gv_cull_batch_begin): the culls of several small pools in one launch, their emits in one launch.

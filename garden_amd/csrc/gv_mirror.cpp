@@ -292,14 +292,18 @@ void gather_meshes(GvCtx* ctx, PoolState& p, uint32_t lo, uint32_t hi)
     const bool counted = p.ready.ptr != nullptr;
     if (!counted) {
         p.ready_many.clear();
-        p.ready_many_count = 0;
+        p.ready_many_count = p.ready_over_count = 0;
     } else if (p.ready_many.size() != std::max(p.occupancy, hi)) {  // (a pool that shrank drops the flags of the slots it lost)
         p.ready_many.resize(std::max(p.occupancy, hi), 0);
-        p.ready_many_count = (uint32_t)std::count(p.ready_many.begin(), p.ready_many.end(), 1);
+        p.ready_many_count = p.ready_over_count = 0;
+        for (uint8_t flag : p.ready_many) {
+            p.ready_many_count += (flag & PoolState::kReadyLevel) != 0;
+            p.ready_over_count += (flag & PoolState::kReadyLevel) == 2;
+        }
     }
-    std::atomic<int64_t> many_delta{0};
+    std::atomic<int64_t> many_delta{0}, over_delta{0};
     parallel_ranges(lo, hi - lo, [&](uint32_t a, uint32_t b) {
-        int64_t delta = 0;
+        int64_t delta = 0, over = 0;
         for (uint32_t i = a; i < b; i++) {
             const float* mn = p.aabb_min.f32(i);
             const float* mx = p.aabb_max.f32(i);
@@ -317,14 +321,19 @@ void gather_meshes(GvCtx* ctx, PoolState& p, uint32_t lo, uint32_t hi)
             if (candidate && slot != j && p.mapping == kMapExact)
                 demoted = true;  // an edited mesh no longer pairs with its own index
             if (counted) {
-                const uint8_t many = candidate && p.ready_count(i) > 1;
-                delta += (int64_t)many - (int64_t)p.ready_many[i];
-                p.ready_many[i] = many;
+                // 1: above 1; 2: above GV_MAX_DRAW_INSTANCES too
+                const uint8_t many = !candidate || p.ready_count(i) <= 1 ? 0 : (p.ready_count(i) > GV_MAX_DRAW_INSTANCES ? 2 : 1);
+                const uint8_t was = p.ready_many[i] & PoolState::kReadyLevel;
+                delta += (int64_t)(many != 0) - (int64_t)(was != 0);
+                over += (int64_t)(many == 2) - (int64_t)(was == 2);
+                p.ready_many[i] = many | (candidate ? PoolState::kReadyLive : 0);
             }
         }
         many_delta += delta;
+        over_delta += over;
     });
     p.ready_many_count = (uint32_t)((int64_t)p.ready_many_count + many_delta.load());
+    p.ready_over_count = (uint32_t)((int64_t)p.ready_over_count + over_delta.load());
     if (demoted)
         p.mapping = kMapSpeculate;
 }
@@ -1511,6 +1520,99 @@ int upload_payload(GvCtx* ctx, PoolState& p)
     return GV_OK;
 }
 
+// The count mirror of a pool (PoolState::Counts): the ready column widened to one uint32 per pool slot — slots appended since the
+// last upload plus the dirty set the pool's GV_DIRTY_MESH marks feed, shaped like upload_payload: ranges of kDeviceGatherMinSlots
+// or more travel as contiguous copies into their place, everything smaller as ONE packet [counts | slots] and ONE scatter launch.
+int upload_counts(GvCtx* ctx, PoolState& p)
+{
+    PoolState::Counts& K = p.counts;
+    if (!K.wanted || !p.ready.ptr)
+        return GV_OK;
+    const uint32_t occupancy = p.occupancy;
+    if (K.mirrored > occupancy) {  // (the pool shrank: the sum is taken anew)
+        K.reset();
+    }
+    K.dirty.normalise(K.mirrored, 0);  // (counts at or beyond `mirrored` are uploaded as new ones below)
+    std::vector<DirtyRanges::R> ranges = K.dirty.items;
+    if (K.mirrored < occupancy)
+        ranges.push_back({K.mirrored, occupancy});
+    K.dirty.clear();
+    if (ranges.empty())
+        return GV_OK;
+    const uint32_t kept = K.mirrored;
+    K.mirrored = 0;  // (a failure below leaves the counts unknown: the next upload takes everything)
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    GV_HIP(ctx, K.d_counts.grow(occupancy, kept, ctx->stream));
+    if (!kept) {
+        K.sum = 0;
+        K.over.clear();
+    }
+    K.held.resize(occupancy, 0);
+    size_t copied = 0, packed = 0;
+    for (const auto& r : ranges)
+        (r.hi - r.lo >= kDeviceGatherMinSlots ? copied : packed) += r.hi - r.lo;
+    const size_t stage_words = copied + 2 * packed;
+    if (stage_words > K.h_stage.cap || 2 * packed > K.d_packet.cap) {  // (buffers about to be replaced: nothing queued may still use them)
+        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GV_HIP(ctx, K.h_stage.reserve(std::max<size_t>(stage_words + stage_words / 2, 1024)));
+        GV_HIP(ctx, K.d_packet.reserve(std::max<size_t>(3 * packed, 1024)));
+    }
+    if (K.staged_pending) {  // the previous upload's copies have read the staging (an event of its own: the context's upload event
+        GV_HIP(ctx, hipEventSynchronize(K.staged));  // may sit behind a payload copy this very call queued behind the frame's cull)
+        K.staged_pending = false;
+    }
+    uint32_t* const stage = K.h_stage.ptr;
+    uint32_t* const packet_counts = stage + copied;
+    uint32_t* const packet_slots = packet_counts + packed;
+    std::atomic<int64_t> change{0};
+    std::mutex over_lock;  // (taken only for a count above the limit, coming or going)
+    auto gather = [&](uint32_t* counts, uint32_t* slots, uint32_t lo, uint32_t hi) {
+        parallel_ranges(0, hi - lo, [&](uint32_t a, uint32_t b) {
+            int64_t delta = 0;
+            for (uint32_t k = a; k < b; k++) {
+                const uint32_t c = p.ready_count(lo + k);  // (a u8 column is widened here)
+                const uint32_t was = lo + k < kept ? K.held[lo + k] : 0u;
+                delta += (int64_t)c - (int64_t)was;
+                if ((c > GV_MAX_DRAW_INSTANCES) != (was > GV_MAX_DRAW_INSTANCES)) {
+                    std::lock_guard<std::mutex> hold(over_lock);
+                    if (c > GV_MAX_DRAW_INSTANCES)
+                        K.over.push_back(lo + k);
+                    else
+                        K.over.erase(std::remove(K.over.begin(), K.over.end(), lo + k), K.over.end());
+                }
+                K.held[lo + k] = counts[k] = c;
+                if (slots)
+                    slots[k] = lo + k;
+            }
+            change += delta;
+        });
+    };
+    size_t copy_at = 0, pack_at = 0;
+    for (const auto& r : ranges) {
+        const uint32_t n = r.hi - r.lo;
+        if (n >= kDeviceGatherMinSlots) {
+            gather(stage + copy_at, nullptr, r.lo, r.hi);
+            GV_HIP(ctx, hipMemcpyAsync(K.d_counts.ptr + r.lo, stage + copy_at, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+            copy_at += n;
+        } else {
+            gather(packet_counts + pack_at, packet_slots + pack_at, r.lo, r.hi);
+            pack_at += n;
+        }
+    }
+    if (packed) {
+        GV_HIP(ctx, hipMemcpyAsync(K.d_packet.ptr, packet_counts, 2 * packed * 4, hipMemcpyHostToDevice, ctx->stream));
+        GV_HIP(ctx, launch_scatter_counts(K.d_packet.ptr, K.d_packet.ptr + packed, (uint32_t)packed, K.d_counts.ptr, ctx->stream));
+    }
+    if (!K.staged)
+        GV_HIP(ctx, hipEventCreateWithFlags(&K.staged, hipEventDisableTiming));
+    GV_HIP(ctx, hipEventRecord(K.staged, ctx->stream));  // the staging is reused by the next upload: it waits for this
+    K.staged_pending = true;
+    ctx->stats.upload_bytes += stage_words * 4;
+    K.sum = (uint64_t)((int64_t)K.sum + change.load());
+    K.mirrored = occupancy;
+    return GV_OK;
+}
+
 // Brings the device mirror up to date with the bound pools and their dirty marks, one named step after the other (the steps
 // and the state they share: above; the rules that choose among them: gv_dirty_ranges.hpp). A re-order that is due runs last, on
 // the device, behind everything that brought the mirror up to date in its old order.
@@ -1575,6 +1677,10 @@ int sync_mirror(GvCtx* ctx)
     for (auto& p : ctx->pools)  // (staging of their own; no cull reads them)
         if (p.bound && p.payload.count)
             if (int rc = upload_payload(ctx, p))
+                return rc;
+    for (auto& p : ctx->pools)
+        if (p.bound && p.counts.wanted)
+            if (int rc = upload_counts(ctx, p))
                 return rc;
     bool any_reorder = reorder_xf;
     for (bool b : reorder_pool)

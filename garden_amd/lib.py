@@ -25,6 +25,7 @@ GV_CONFIG_BLOCK_BOUNDS = 8
 GV_CONFIG_HIZ_RG16F = 16
 GV_CONFIG_LINEAR_SCAN = 32
 GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH, GV_DIRTY_PAYLOAD = 0, 1, 2, 3
+GV_MAX_DRAW_INSTANCES = 65535
 GV_SWEEP_VALU, GV_SWEEP_MFMA, GV_SWEEP_WITH_CULL, GV_SWEEP_WITH_CULL_VALU, GV_SWEEP_INCREMENTAL = 0, 1, 2, 3, 4
 GV_MEM_HOST, GV_MEM_DEVICE = 0, 1
 GV_EXCHANGE_ALLGATHER, GV_EXCHANGE_P2P, GV_EXCHANGE_BROADCAST, GV_EXCHANGE_PEER = 0, 1, 2, 3
@@ -176,6 +177,7 @@ EXPORTS = [
     "gv_pool_results_instance_bases", "gv_profile_sampling", "gv_profile_samples", "gv_profile_kernels", "gv_pick",
     "gv_pool_set_instance_layout", "gv_pool_emit_instances", "gv_pool_instances_device", "gv_pool_instances_info", "gv_pool_instances_fetch",
     "gv_pool_bind_payload", "gv_pool_set_payload_layout",
+    "gv_pool_emit_draw_instances", "gv_pool_set_instance_index_field", "gv_pool_draw_bases_device", "gv_pool_draw_bases_fetch",
     "gv_merge_sorted", "gv_merge_device", "gv_merge_fetch",
 ]
 
@@ -294,6 +296,10 @@ def load():
     lib.gv_pool_instances_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
     lib.gv_pool_bind_payload.argtypes = [P, u32, C.POINTER(GvPayloadField), u32, u32]
     lib.gv_pool_set_payload_layout.argtypes = [P, u32, C.POINTER(u32), u32]
+    lib.gv_pool_emit_draw_instances.argtypes = [P, u32, C.POINTER(u32), u32, P, sz]
+    lib.gv_pool_set_instance_index_field.argtypes = [P, u32, u32]
+    lib.gv_pool_draw_bases_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_pool_draw_bases_fetch.argtypes = [P, u32, C.POINTER(u32), u32, C.POINTER(u32), u32]
     lib.gv_merge_sorted.argtypes = [P, C.POINTER(GvMergeGroup), u32]
     lib.gv_merge_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_merge_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
@@ -716,6 +722,35 @@ class GpuVisibility:
         idx = (C.c_uint32 * max(len(views), 1))(*[int(v) for v in views])
         ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
         self._check(self.lib.gv_pool_emit_instances(self.ctx, pool_id, idx, len(views), ptr, cap))
+
+    def emit_draw_instances(self, pool_id, views, device=None):
+        """gv_pool_emit_draw_instances: like emit_instances, but every draw takes its ready count (bind_ready) of instances, read from
+        the count mirror on the device; instances_info / instances_device / instances then describe this emission."""
+        idx = (C.c_uint32 * max(len(views), 1))(*[int(v) for v in views])
+        ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
+        self._check(self.lib.gv_pool_emit_draw_instances(self.ctx, pool_id, idx, len(views), ptr, cap))
+
+    def set_instance_index_field(self, pool_id, offset):
+        """gv_pool_set_instance_index_field: where a draw emission writes the uint32 index within the draw (None: nowhere)."""
+        self._check(self.lib.gv_pool_set_instance_index_field(self.ctx, pool_id, GV_NONE if offset is None else int(offset)))
+
+    def draw_bases_device(self, pool_id):
+        """(device pointer of uint32 first_instance[draws + 1], device pointer of uint32 draw_starts[views + 1]) of the pool's last
+        draw emission"""
+        first, starts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_pool_draw_bases_device(self.ctx, pool_id, C.byref(first), C.byref(starts)))
+        return first.value, starts.value
+
+    def draw_bases(self, pool_id):
+        """gv_pool_draw_bases_fetch: waits for the pool's last draw emission; returns (first_instance[draws + 1] — the first instance
+        of every draw of the listed views, back to back, and the grand total behind them — and draw_starts[views + 1])."""
+        views = self.instances_info(pool_id)[0]
+        starts = np.zeros(views + 1, np.uint32)
+        sp = starts.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self.lib.gv_pool_draw_bases_fetch(self.ctx, pool_id, None, 0, sp, len(starts)))
+        first = np.zeros(int(starts[views]) + 1, np.uint32)
+        self._check(self.lib.gv_pool_draw_bases_fetch(self.ctx, pool_id, first.ctypes.data_as(C.POINTER(C.c_uint32)), len(first), sp, len(starts)))
+        return first, starts
 
     def instances_info(self, pool_id):
         """(listed views, stride, instances the target holds) of the pool's last emission"""

@@ -397,6 +397,55 @@ int gv_pool_instances_info(GvCtx* ctx, uint32_t pool_id, uint32_t* view_count, u
  * instances the emission could not fit into a caller-owned device target are not delivered either. */
 int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* starts, uint32_t starts_capacity);
 
+/* ---- instance data for draws that take several instances (a ready count above 1, gv_pool_bind_ready) ----
+ * gv_pool_emit_draw_instances is gv_pool_emit_instances — its arguments, view ordering, "counts as a read", target rules and errors —
+ * for a pool whose draws take their ready count of instances, as `instanceCount.fetch_add(getInstancesAsync(view))` hands them out
+ * in the reference's draw loops (mesh.cpp:596-599, :624-627, :709-712, :753-756). Draw k of a listed view is record k in delivery
+ * order (after gv_pool_sort: the sorted order) and takes c_k = count[visible_idx[k]] instances, read ON THE DEVICE from a mirror of
+ * the ready column (one uint32 per pool slot; u8 columns are widened on the way up). Its first instance is
+ * first_k = starts[v] + sum of c_j over j < k, starts[v] the instance total of the views listed in front. EVERY instance
+ * first_k + j, 0 <= j < c_k, receives the layout's fields of draw k (mvp, model, slot, distance_sq: bit for bit what
+ * gv_pool_emit_instances writes for that record), the payload row of the record's pool slot at the payload destinations, and j
+ * at the index field when one is set (gv_pool_set_instance_index_field) — no system of the reference overrides getInstancesAsync
+ * (mesh.hpp:89), so what the extra instances hold is this build's rule. Only those bytes are written;
+ * instances at or beyond the target's capacity are not written, also when the cut falls inside one draw, and the true totals are
+ * still reported. A draw whose count has become 0 since the cull takes no instance (first_{k+1} == first_k). Without a ready column
+ * every count is 1 and the bytes are those of gv_pool_emit_instances. Two kernel launches on gv_stream(ctx), no host
+ * synchronisation; the host never reads a count.
+ * The count mirror exists only for a pool with a ready column that has called this function: the first call uploads the whole
+ * column; from then on the pool's GV_DIRTY_MESH marks feed a dirty set of its own, which gv_sync or the pool's next draw emission
+ * consumes, whichever comes first — a count changed and marked between the cull and the emission is what the emission uses
+ * (the reference reads getInstancesAsync at draw time, mesh.cpp:592-597), while the records stay those of the cull. Uploaded bytes
+ * count in GvStats::upload_bytes; rebinding or removing the ready column resets the mirror.
+ * The library-owned target (dst_device NULL) is sized for the listed views times the sum of the mirrored counts.
+ * GV_E_STATE in addition to gv_pool_emit_instances' errors: a ready column together with a result mapping
+ * (gv_pool_set_result_mapping); a live count above GV_MAX_DRAW_INSTANCES (in the column at the last gv_sync, or
+ * marked since); a library-owned target whose bound does not fit 32 bits of instances (pass a caller-owned target). Counts above 1
+ * are NOT refused here. "Live" means a candidate as of the last gv_sync, which is what that sync's culls could draw: a slot that
+ * was disabled then and is marked above the limit afterwards goes unnoticed until the next gv_sync. The refusal for marked counts
+ * comes after they have been uploaded (nothing is launched; the next upload corrects the mirror). Whatever a count holds, the
+ * kernels write inside the target only. */
+#define GV_MAX_DRAW_INSTANCES 65535u
+int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_indices, uint32_t view_count, void* dst_device,
+                                size_t capacity_bytes);
+/* Where gv_pool_emit_draw_instances writes a uint32 "index within the draw" (j above) into every instance: 4-byte aligned, inside
+ * the stride, disjoint from mvp / model / slot / distance_sq and from the payload destinations — checked here, in
+ * gv_pool_set_instance_layout and gv_pool_set_payload_layout against the offset in place, and at the draw emission (GV_E_ARG).
+ * GV_NONE removes it. gv_pool_emit_instances ignores it entirely. */
+int gv_pool_set_instance_index_field(GvCtx* ctx, uint32_t pool_id, uint32_t offset);
+/* Device pointers of the pool's last DRAW emission, written in stream order on gv_stream(ctx): uint32 draw_starts[view_count + 1],
+ * the prefix of the listed views' draw counts, and uint32 first_instance[], where first_instance[draw_starts[v] + k] = first_k of
+ * draw k of listed view v (an indirect draw's firstInstance); one more word behind the last draw,
+ * first_instance[draw_starts[view_count]], holds the grand total. GV_E_STATE when the pool's last emission was not a draw emission.
+ * gv_pool_instances_device / _info / _fetch serve the pool's last emission, whichever call made it: after a draw emission starts[]
+ * holds INSTANCE starts, and the fetch also delivers the index field when it was written. */
+int gv_pool_draw_bases_device(GvCtx* ctx, uint32_t pool_id, const void** first_instance, const void** draw_starts);
+/* Waits for the pool's last draw emission and delivers both arrays through the library's pinned staging: draw_starts[0 ..
+ * view_count] (starts_capacity >= view_count + 1) and — first_instance non-NULL — first_instance[0 .. draws], the closing total
+ * included (capacity >= draws + 1 words). GV_E_ARG when either array is too small: nothing is written. */
+int gv_pool_draw_bases_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* first_instance, uint32_t capacity, uint32_t* draw_starts,
+                             uint32_t starts_capacity);
+
 /* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
  * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
  * the record's componentOffset. A pool may bind those bytes (its PAYLOAD: up to GV_MAX_PAYLOAD_FIELDS fields, GV_MAX_PAYLOAD_BYTES
