@@ -704,6 +704,12 @@ void gv_destroy(GvCtx* ctx)
         if (p.counts.staged)
             (void)hipEventDestroy(p.counts.staged);
         p.counts.staged = nullptr;
+        p.geometry.release(); p.geometry.d_table.release();
+        if (p.geometry.staged)
+            (void)hipEventDestroy(p.geometry.staged);
+        p.geometry.staged = nullptr;
+        p.commands.d_data.release(); p.commands.d_counts.release(); p.commands.d_rank.release(); p.commands.d_chunk_total.release();
+        p.commands.d_draw_of.release(); p.commands.d_first_of.release(); p.commands.h_data.release(); p.commands.h_counts.release();
     }
     for (auto& per_pool : ctx->views)
       for (auto& v : per_pool) {
@@ -903,6 +909,14 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
             ctx->pools[pool].payload.dirty.add(first & kSlotMask, count);
         return GV_OK;
     }
+    if (kind == GV_DIRTY_GEOMETRY) {  // (no cull reads the geometry ids either)
+        const uint32_t pool = first >> 28;
+        if (pool >= GV_MAX_POOLS)
+            return ctx->fail(GV_E_ARG, "gv_mark_dirty: pool id %u", pool);
+        if (ctx->pools[pool].geometry.wanted)
+            ctx->pools[pool].geometry.dirty.add(first & kSlotMask, count);
+        return GV_OK;
+    }
     if (int rc = flush_recorded_culls(ctx, kind == GV_DIRTY_MESH ? std::min(first >> 28, GV_MAX_POOLS - 1u) : GV_MAX_POOLS))
         return rc;
     switch (kind) {
@@ -926,6 +940,8 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
             ctx->pools[pool].payload.dirty.add(lo, count);
         if (ctx->pools[pool].counts.wanted)  // ... and its ready count may have changed
             ctx->pools[pool].counts.dirty.add(lo, count);
+        if (ctx->pools[pool].geometry.wanted)  // ... and so may its geometry id
+            ctx->pools[pool].geometry.dirty.add(lo, count);
         return GV_OK;
     }
     default:
@@ -1008,6 +1024,7 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
             GV_HIP(ctx, hipMemsetAsync(vs.draw_count.ptr, 0, 4, ctx->stream));
     }
     p.instances.views = 0;  // the views' results are replaced from here on: the instance data made from the previous ones ends
+    p.commands.views = 0;   // ... and the commands made from that
     for (auto& m : ctx->merges)  // ... and so does every merged array this pool is a member of (gv_merge_sorted)
         if ((m.pools >> pool_id) & 1u)
             m.valid = false;

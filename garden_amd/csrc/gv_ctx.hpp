@@ -209,6 +209,7 @@ struct PoolState {
         uint8_t* target = nullptr;      // d_data.ptr or the caller's device memory
         uint32_t capacity = 0;          // instances the target holds
         uint32_t views = 0;
+        uint32_t listed[GV_MAX_VIEWS] = {};  // ... which, in the order listed (gv_pool_emit_draw_commands walks the same views)
         GvInstanceLayout emitted{};     // the layout it was made with
         uint32_t emitted_payload = 0;   // ... and the payload fields it wrote: (at, bytes) each
         uint32_t emitted_at[GV_MAX_PAYLOAD_FIELDS] = {}, emitted_bytes[GV_MAX_PAYLOAD_FIELDS] = {};
@@ -254,6 +255,59 @@ struct PoolState {
             over.clear();
         }
     } counts;
+    // gv_pool_bind_geometry: the geometry id column and the table it indexes. The ids on the device, one uint32 per POOL SLOT like
+    // the counts above (indexed by visible_idx; a re-order of the mirror does not concern them): the mirror exists only once
+    // gv_pool_emit_draw_commands has been called for a pool with an id column
+    struct Geometry {
+        bool bound = false;                // a table is bound (with or without an id column)
+        Column ids;                        // ptr NULL: none, every slot has id 0
+        uint32_t width = 0;                // 1, 2 or 4 bytes
+        uint32_t occupancy = 0;            // slots the column covers
+        uint32_t id(size_t i) const
+        {
+            if (width == 4)
+                return ids.u32(i);
+            uint16_t v = 0;
+            if (width == 2)
+                memcpy(&v, ids.at(i), 2);
+            return width == 2 ? (uint32_t)v : (uint32_t)ids.u8(i);
+        }
+        uint32_t table_count = 0;
+        DeviceBuf<GvGeometry> d_table;     // re-uploaded on every bind
+        bool wanted = false;
+        uint32_t mirrored = 0;             // ids [0, mirrored) are on the device (0: everything is uploaded)
+        hipEvent_t staged = nullptr;       // behind the last copies that read h_stage (an event of its own, as Counts::staged)
+        bool staged_pending = false;
+        DirtyRanges dirty;                 // GV_DIRTY_GEOMETRY and GV_DIRTY_MESH marks of the pool
+        DeviceBuf<uint32_t> d_ids;
+        PinnedBuf<uint32_t> h_stage;       // the ids (and, behind them, the packet's slots) on their way up
+        DeviceBuf<uint32_t> d_packet;
+        void reset()                       // rebound: everything is uploaded again
+        {
+            mirrored = 0;
+            dirty.clear();
+        }
+        void release()                     // (the caller has drained the stream)
+        {
+            d_ids.release();
+            h_stage.release();
+            d_packet.release();
+            staged_pending = false;
+        }
+    } geometry;
+    // gv_pool_set_command_layout / gv_pool_emit_draw_commands: buffers of their own, no cull result or instance data is touched
+    struct Commands {
+        GvCommandLayout layout{};          // stride 0: none
+        DeviceBuf<uint8_t> d_data;         // the library-owned target
+        DeviceBuf<uint32_t> d_counts;      // command_counts[views]
+        DeviceBuf<uint32_t> d_rank, d_chunk_total, d_draw_of, d_first_of;  // run mode's scratch
+        PinnedBuf<uint8_t> h_data;         // staging of gv_pool_draw_commands_fetch
+        PinnedBuf<uint32_t> h_counts;
+        // the last emission (views 0: none since the pool's last gv_cull or instance emission)
+        uint8_t* target = nullptr;         // d_data.ptr or the caller's device memory
+        uint32_t capacity = 0;             // command positions the target holds
+        uint32_t views = 0, stride = 0, region = 0;
+    } commands;
     // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
     // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
     // transform mirror does not concern it); read by gv_pool_emit_instances only
@@ -655,6 +709,7 @@ int copy_shard_of_pool(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, void* 
 int sync_mirror(GvCtx* ctx);
 int upload_payload(GvCtx* ctx, PoolState& p);  // a pool's payload rows likewise (new slots + its own dirty set); sync_mirror calls it too
 int upload_counts(GvCtx* ctx, PoolState& p);   // ... and its count mirror (PoolState::Counts), once gv_pool_emit_draw_instances wants one
+int upload_geometry(GvCtx* ctx, PoolState& p);  // ... and its geometry id mirror (PoolState::Geometry), once gv_pool_emit_draw_commands wants one
 TransformMirror xf_mirror(const GvCtx* ctx);  // the transform mirror as the kernels see it
 MeshMirror mesh_mirror(const PoolState& p);   // a pool's mirror likewise (hot: null; the sphere stream's upkeep in cull_launch sets it)
 

@@ -605,4 +605,43 @@ __device__ __forceinline__ void copy_rows(const float4* stage, float4* dst, uint
         dst[q] = stage[q];
 }
 
+// ---- shared by the instance and command emissions (gv_instance.hip, gv_commands.hip): 256-lane workgroups over several views ----
+// this workgroup's view: the last one whose workgroups (chunks) begin at or in front of it
+__device__ __forceinline__ uint32_t view_of_block(const uint32_t (&first)[kMaxInstanceViews + 1], uint32_t views, uint32_t block)
+{
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t k = 1; k < kMaxInstanceViews; k++)
+        if (k < views && block >= first[k])
+            v = k;
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x, uint32_t lane)
+{
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= d)
+            x += y;
+    }
+    return x;
+}
+
+// sum of t[lo, hi) by the whole workgroup (every lane gets it); scratch: one word per wave
+__device__ __forceinline__ uint32_t block_sum_of(const uint32_t* t, uint32_t lo, uint32_t hi, uint32_t* scratch)
+{
+    uint32_t x = 0;
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += kInstanceBlock)
+        x += t[i];
+#pragma unroll
+    for (uint32_t d = 32; d >= 1u; d >>= 1)
+        x += __shfl_xor(x, d, 64);
+    __syncthreads();  // (scratch may still be read from the call before)
+    if ((threadIdx.x & 63u) == 0)
+        scratch[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return scratch[0] + scratch[1] + scratch[2] + scratch[3];
+}
+
 }  // namespace gv

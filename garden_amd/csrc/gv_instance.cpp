@@ -328,6 +328,8 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
     I.target = launch.dst;
     I.capacity = launch.capacity;
     I.views = view_count;
+    std::copy(view_indices, view_indices + view_count, I.listed);
+    p.commands.views = 0;  // commands belong to the emission in front of them
     I.emitted = L;
     I.note_payload(places);
     I.emitted_index = GV_NONE;
@@ -419,6 +421,8 @@ int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* vi
     I.target = launch.base.dst;
     I.capacity = launch.base.capacity;
     I.views = view_count;
+    std::copy(view_indices, view_indices + view_count, I.listed);
+    p.commands.views = 0;  // commands belong to the emission in front of them
     I.emitted = L;
     I.note_payload(places);
     I.emitted_index = I.index_at;

@@ -222,28 +222,6 @@ hipError_t launch_instances(const InstanceLaunch& launch, hipStream_t stream)
 
 // ---- gv_pool_emit_draw_instances: draw k takes count[visible_idx[k]] instances -----------------------------------------------
 
-// this workgroup's view: the last one whose workgroups (chunks) begin at or in front of it
-__device__ __forceinline__ uint32_t view_of_block(const uint32_t (&first)[kMaxInstanceViews + 1], uint32_t views, uint32_t block)
-{
-    uint32_t v = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < kMaxInstanceViews; k++)
-        if (k < views && block >= first[k])
-            v = k;
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x, uint32_t lane)
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= d)
-            x += y;
-    }
-    return x;
-}
-
 // One workgroup per chunk of kDrawChunk records, 16 rounds of 256 consecutive records: the counts are gathered first (idx -> count,
 // the one dependent load), every round is scanned inside its wave, the 64 (round, wave) totals by wave 0: two barriers in all.
 __global__ __launch_bounds__(kInstanceBlock) void draw_counts_kernel(const DrawInstanceLaunch a)
@@ -294,22 +272,6 @@ __global__ __launch_bounds__(kInstanceBlock) void draw_counts_kernel(const DrawI
     }
     if (threadIdx.x == 0)
         a.chunk_total[blockIdx.x] = chunk_sum;
-}
-
-// sum of t[lo, hi) by the whole workgroup (every lane gets it); scratch: one word per wave
-__device__ __forceinline__ uint32_t block_sum_of(const uint32_t* t, uint32_t lo, uint32_t hi, uint32_t* scratch)
-{
-    uint32_t x = 0;
-    for (uint32_t i = lo + threadIdx.x; i < hi; i += kInstanceBlock)
-        x += t[i];
-#pragma unroll
-    for (uint32_t d = 32; d >= 1u; d >>= 1)
-        x += __shfl_xor(x, d, 64);
-    __syncthreads();  // (scratch may still be read from the call before)
-    if ((threadIdx.x & 63u) == 0)
-        scratch[threadIdx.x >> 6] = x;
-    __syncthreads();
-    return scratch[0] + scratch[1] + scratch[2] + scratch[3];
 }
 
 // the record that owns instance g: the last r of [0, 256) with pre[r] <= g (pre ascending, pre[0] <= g < pre[256]); records

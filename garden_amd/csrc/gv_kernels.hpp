@@ -251,6 +251,49 @@ inline __host__ __device__ uint32_t draw_image_bytes(uint32_t staged, uint32_t s
 hipError_t launch_draw_instances(const DrawInstanceLaunch& launch, hipStream_t stream);
 // the small dirty ranges of a pool's count mirror: counts[slots[t]] = packet[t]
 hipError_t launch_scatter_counts(const uint32_t* packet, const uint32_t* slots, uint32_t count, uint32_t* counts, hipStream_t stream);
+// gv_pool_emit_draw_commands (gv_commands.hip): one indirect command per draw of the pool's last emission E — or, merged, per run
+// of consecutive draws of one geometry id — in the caller's command struct. Per-draw mode: ONE launch
+// (command_kernel). Run mode: command_heads_kernel (head flags + chunk-local head ranks per chunk of kDrawChunk draws, one head
+// total per chunk) and command_runs_kernel (every head writes draw_of / first_of at its rank) in front of the same command_kernel.
+// No atomics, no host read, no workgroup waits for another; grids sized from the views' occupancies.
+constexpr uint32_t kCommandBlock = kInstanceBlock;  // command positions per command_kernel workgroup; draws per command_runs_kernel one
+constexpr uint32_t kMinCommandStride = 16, kMaxCommandStride = 64;  // 256 x 64 B = 16 KB of LDS per workgroup
+constexpr uint32_t kCommandHead = 0x80000000u;      // in CommandLaunch::rank: the draw opens a run
+struct CommandGeometry {                            // GvGeometry
+    uint32_t count, first;
+    int32_t vertex_offset;
+};
+struct CommandView {
+    const uint32_t* count;  // device draw count
+    const uint32_t* idx;    // records in delivery order: POOL slots
+};
+struct CommandLaunch {
+    CommandView view[kMaxInstanceViews];             // the views of E, in E's order
+    uint32_t first_block[kMaxInstanceViews + 1];     // command_kernel workgroups in front of view v (packed: of its occupancy; regions: of the region)
+    uint32_t first_draw_block[kMaxInstanceViews + 1];  // 256-draw workgroups in front of view v (command_runs_kernel; where rank[] begins)
+    uint32_t first_chunk[kMaxInstanceViews + 1];     // chunks in front of view v
+    uint32_t views;
+    uint32_t merge_runs;                             // GV_COMMANDS_MERGE_RUNS
+    uint32_t region;                                 // 0: packed
+    uint32_t stride, count, instance_count, first, first_instance, vertex_offset, draw;  // GvCommandLayout
+    const uint32_t* ids;                             // geometry id per POOL SLOT (NULL: every slot has id 0)
+    const CommandGeometry* table;
+    uint32_t table_count;
+    const uint32_t* starts;                          // E: instance starts [views + 1]
+    const uint32_t* first_instance_of;               // E, a draw emission: first_instance[draw_starts[v] + k]; NULL: first_k = starts[v] + k
+    const uint32_t* draw_starts;
+    // run mode's scratch; view v's draws at first_draw_block[v] * kCommandBlock (rank) and, one word more per view, + v (draw_of, first_of)
+    uint32_t* rank;                                  // head rank inside the draw's chunk | kCommandHead
+    uint32_t* chunk_total;                           // [first_chunk[views]] heads per chunk (0 beyond the view's count)
+    uint32_t* draw_of;                               // run r of view v -> its head draw
+    uint32_t* first_of;                              // ... and that draw's first instance
+    uint8_t* dst;
+    uint32_t capacity;                               // command positions dst holds: those at or beyond it are not written
+    uint32_t* command_counts;                        // [views], written by workgroup 0 of command_kernel
+};
+hipError_t launch_command_heads(const CommandLaunch& launch, hipStream_t stream);  // run mode only, in this order
+hipError_t launch_command_runs(const CommandLaunch& launch, hipStream_t stream);
+hipError_t launch_commands(const CommandLaunch& launch, hipStream_t stream);
 // read-only pass over the cull kernel's input streams (65 B per entry); gv_debug_stream_peak
 hipError_t launch_stream_probe(const MeshMirror& mesh, const TransformMirror& xf, float* sink, hipStream_t stream);
 // Table-driven tick (gv_cull_batch_begin): the culls of several small pools in one launch, their emits in one launch.

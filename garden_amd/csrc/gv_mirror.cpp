@@ -1613,6 +1613,78 @@ int upload_counts(GvCtx* ctx, PoolState& p)
     return GV_OK;
 }
 
+// The geometry id mirror of a pool (PoolState::Geometry): the id column widened to one uint32 per pool slot, kept like the count
+// mirror above — slots appended since the last upload plus the dirty set the pool's GV_DIRTY_GEOMETRY / GV_DIRTY_MESH marks feed;
+// ranges of kDeviceGatherMinSlots or more as contiguous copies, the rest as ONE packet [ids | slots] and ONE scatter launch.
+int upload_geometry(GvCtx* ctx, PoolState& p)
+{
+    PoolState::Geometry& G = p.geometry;
+    if (!G.wanted || !G.ids.ptr)
+        return GV_OK;
+    const uint32_t occupancy = G.occupancy;
+    if (G.mirrored > occupancy)
+        G.reset();
+    G.dirty.normalise(G.mirrored, 0);  // (ids at or beyond `mirrored` are uploaded as new ones below)
+    std::vector<DirtyRanges::R> ranges = G.dirty.items;
+    if (G.mirrored < occupancy)
+        ranges.push_back({G.mirrored, occupancy});
+    G.dirty.clear();
+    if (ranges.empty())
+        return GV_OK;
+    const uint32_t kept = G.mirrored;
+    G.mirrored = 0;  // (a failure below leaves the ids unknown: the next upload takes everything)
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    GV_HIP(ctx, G.d_ids.grow(occupancy, kept, ctx->stream));
+    size_t copied = 0, packed = 0;
+    for (const auto& r : ranges)
+        (r.hi - r.lo >= kDeviceGatherMinSlots ? copied : packed) += r.hi - r.lo;
+    const size_t stage_words = copied + 2 * packed;
+    if (stage_words > G.h_stage.cap || 2 * packed > G.d_packet.cap) {  // (buffers about to be replaced: nothing queued may still use them)
+        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GV_HIP(ctx, G.h_stage.reserve(std::max<size_t>(stage_words + stage_words / 2, 1024)));
+        GV_HIP(ctx, G.d_packet.reserve(std::max<size_t>(3 * packed, 1024)));
+    }
+    if (G.staged_pending) {  // the previous upload's copies have read the staging
+        GV_HIP(ctx, hipEventSynchronize(G.staged));
+        G.staged_pending = false;
+    }
+    uint32_t* const stage = G.h_stage.ptr;
+    uint32_t* const packet_ids = stage + copied;
+    uint32_t* const packet_slots = packet_ids + packed;
+    auto gather = [&](uint32_t* ids, uint32_t* slots, uint32_t lo, uint32_t hi) {
+        parallel_ranges(0, hi - lo, [&](uint32_t a, uint32_t b) {
+            for (uint32_t k = a; k < b; k++) {
+                ids[k] = G.id(lo + k);  // (a narrow column is widened here)
+                if (slots)
+                    slots[k] = lo + k;
+            }
+        });
+    };
+    size_t copy_at = 0, pack_at = 0;
+    for (const auto& r : ranges) {
+        const uint32_t n = r.hi - r.lo;
+        if (n >= kDeviceGatherMinSlots) {
+            gather(stage + copy_at, nullptr, r.lo, r.hi);
+            GV_HIP(ctx, hipMemcpyAsync(G.d_ids.ptr + r.lo, stage + copy_at, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+            copy_at += n;
+        } else {
+            gather(packet_ids + pack_at, packet_slots + pack_at, r.lo, r.hi);
+            pack_at += n;
+        }
+    }
+    if (packed) {
+        GV_HIP(ctx, hipMemcpyAsync(G.d_packet.ptr, packet_ids, 2 * packed * 4, hipMemcpyHostToDevice, ctx->stream));
+        GV_HIP(ctx, launch_scatter_counts(G.d_packet.ptr, G.d_packet.ptr + packed, (uint32_t)packed, G.d_ids.ptr, ctx->stream));
+    }
+    if (!G.staged)
+        GV_HIP(ctx, hipEventCreateWithFlags(&G.staged, hipEventDisableTiming));
+    GV_HIP(ctx, hipEventRecord(G.staged, ctx->stream));  // the staging is reused by the next upload: it waits for this
+    G.staged_pending = true;
+    ctx->stats.upload_bytes += stage_words * 4;
+    G.mirrored = occupancy;
+    return GV_OK;
+}
+
 // Brings the device mirror up to date with the bound pools and their dirty marks, one named step after the other (the steps
 // and the state they share: above; the rules that choose among them: gv_dirty_ranges.hpp). A re-order that is due runs last, on
 // the device, behind everything that brought the mirror up to date in its old order.
@@ -1681,6 +1753,10 @@ int sync_mirror(GvCtx* ctx)
     for (auto& p : ctx->pools)
         if (p.bound && p.counts.wanted)
             if (int rc = upload_counts(ctx, p))
+                return rc;
+    for (auto& p : ctx->pools)
+        if (p.bound && p.geometry.wanted)
+            if (int rc = upload_geometry(ctx, p))
                 return rc;
     bool any_reorder = reorder_xf;
     for (bool b : reorder_pool)

@@ -1,0 +1,128 @@
+// draw_commands.hpp — the indirect draw commands of the drop-in's mesh systems, built on the device: for a mesh system that has
+// declared its geometry (setGeometry), its command struct (setLayout) and how its commands are merged and placed (setMode),
+// GpuInstanceWriter::write() — given this object through setCommands — follows each of its two instance emissions with a command
+// emission (gv_pool_emit_draw_commands): one for the light pass behind the system's base instance array, one for the shadow passes,
+// in pass order, behind its shadow array. A command emission belongs to the instance emission in front of it: first_instance
+// indexes the array that emission filled. What the reference's draw loops would record as one drawAsync per record
+// (mesh.cpp:589-601) is then a buffer a renderer submits as one indirect draw per pass (DrawIndexedIndirectCommand with offset,
+// drawCount and stride, graphics/command-buffer.hpp:210-229), with drawCount from getBase / getShadow (packed) or the region size
+// (regions: no count has to be read back).
+//
+// The commands land in caller-owned device memory when setTargets names some (a renderer's indirect buffers), else in the
+// library's own buffer; either way they are fetched into host copies (getBase / getShadow) unless setFetch(false) — the library's
+// buffer is reused by the next emission of the pool, so without device targets the host copies are what survives a write().
+//
+// One context only, like the writer: with ranks no device holds a view's records in draw order — isSupported() is false.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "gpu_visibility_system.hpp"
+
+namespace garden {
+
+class GpuDrawCommands {
+public:
+    // what one command emission left behind
+    struct Emitted {
+        std::vector<uint8_t> commands;  // the command positions, stride bytes each (empty with setFetch(false))
+        std::vector<uint32_t> counts;   // commands per listed view: the light pass, or the culled shadow passes in pass order
+        uint32_t stride = 0, region = 0;
+    };
+
+private:
+    GpuVisibilitySystem* system;
+    struct PerSystem {
+        bool enabled = false;  // a layout is set
+        uint32_t flags = 0, region = 0;
+        void *baseDevice = nullptr, *shadowDevice = nullptr;
+        size_t baseBytes = 0, shadowBytes = 0;
+        uint32_t stride = 0;
+        Emitted base, shadow;
+    } per[GV_MAX_POOLS];
+    bool fetch = true;
+
+    void check(int rc, const char* what) const
+    {
+        if (rc != GV_OK)
+            throw GardenError(std::string(what) + " failed: " + gv_last_error(system->getContext()));
+    }
+    PerSystem& of(uint32_t p)
+    {
+        if (p >= GV_MAX_POOLS)
+            throw GardenError("GpuDrawCommands: mesh system out of range");
+        return per[p];
+    }
+
+public:
+    explicit GpuDrawCommands(GpuVisibilitySystem* system) : system(system) {}
+
+    bool isSupported() const noexcept { return system->getRankCount() == 1; }
+
+    // the geometry ids of mesh system p's components (element i at ids + i * stride, 1, 2 or 4 bytes wide; NULL: every draw takes
+    // table[0]) and the table they index (gv_pool_bind_geometry; re-issue when the pool's storage may have moved, report edits with
+    // GV_DIRTY_GEOMETRY or GV_DIRTY_MESH)
+    void setGeometry(uint32_t p, const void* ids, uint32_t stride, uint32_t width, uint32_t occupancy, const GvGeometry* table, uint32_t tableCount)
+    {
+        check(gv_pool_bind_geometry(system->getContext(), p, ids, stride, width, occupancy, table, tableCount), "gv_pool_bind_geometry");
+    }
+    // the command struct of mesh system p: see GvCommandLayout
+    void setLayout(uint32_t p, const GvCommandLayout& layout)
+    {
+        check(gv_pool_set_command_layout(system->getContext(), p, &layout), "gv_pool_set_command_layout");
+        of(p).enabled = true;
+        of(p).stride = layout.stride;
+    }
+    // flags: 0 or GV_COMMANDS_MERGE_RUNS; region: 0 packs the passes' commands, R > 0 gives every pass R positions
+    void setMode(uint32_t p, uint32_t flags, uint32_t region)
+    {
+        of(p).flags = flags;
+        of(p).region = region;
+    }
+    // caller-owned, 16-byte aligned device memory for the two command arrays of mesh system p (NULL: the library's buffer)
+    void setTargets(uint32_t p, void* baseDevice, size_t baseBytes, void* shadowDevice, size_t shadowBytes)
+    {
+        PerSystem& s = of(p);
+        s.baseDevice = baseDevice, s.baseBytes = baseBytes, s.shadowDevice = shadowDevice, s.shadowBytes = shadowBytes;
+    }
+    void setFetch(bool on) noexcept { fetch = on; }
+
+    // GpuInstanceWriter::write calls this behind each of its emissions for mesh system p (shadow: the one into the shadow array)
+    void emit(uint32_t p, bool shadow)
+    {
+        PerSystem& s = of(p);
+        if (!s.enabled)
+            return;
+        if (!isSupported())
+            throw GardenError("GpuDrawCommands: unsupported with several ranks (the merged draw order is made on the host)");
+        GvCtx* ctx = system->getContext();
+        check(gv_pool_emit_draw_commands(ctx, p, s.flags, s.region, shadow ? s.shadowDevice : s.baseDevice, shadow ? s.shadowBytes : s.baseBytes),
+              "gv_pool_emit_draw_commands");
+        Emitted& out = shadow ? s.shadow : s.base;
+        out.stride = s.stride;
+        out.region = s.region;
+        out.commands.clear();
+        if (!fetch) {
+            out.counts.clear();
+            return;
+        }
+        uint32_t views = 0, counts[GV_MAX_VIEWS];
+        check(gv_pool_instances_info(ctx, p, &views, nullptr, nullptr), "gv_pool_instances_info");
+        check(gv_pool_draw_commands_fetch(ctx, p, nullptr, 0, counts, GV_MAX_VIEWS), "gv_pool_draw_commands_fetch");
+        out.counts.assign(counts, counts + views);
+        size_t positions = (size_t)views * s.region;
+        if (!s.region)
+            for (uint32_t c : out.counts)
+                positions += c;
+        const size_t room = (shadow ? s.shadowDevice : s.baseDevice) ? (shadow ? s.shadowBytes : s.baseBytes) / s.stride : positions;
+        out.commands.resize(std::min(positions, room) * s.stride);
+        check(gv_pool_draw_commands_fetch(ctx, p, out.commands.data(), out.commands.size(), counts, GV_MAX_VIEWS), "gv_pool_draw_commands_fetch");
+    }
+
+    const Emitted& getBase(uint32_t p) { return of(p).base; }
+    const Emitted& getShadow(uint32_t p) { return of(p).shadow; }
+};
+
+}  // namespace garden

@@ -19,12 +19,14 @@
 #include <string>
 #include <vector>
 
+#include "draw_commands.hpp"
 #include "gpu_visibility_system.hpp"
 
 namespace garden {
 
 class GpuInstanceWriter {
     GpuVisibilitySystem* system;
+    GpuDrawCommands* commands = nullptr;
 
     struct PayloadAt {
         uint32_t count = 0;  // 0: no payload destinations for this system
@@ -48,6 +50,9 @@ public:
     explicit GpuInstanceWriter(GpuVisibilitySystem* system) : system(system) {}
 
     bool isSupported() const noexcept { return system->getRankCount() == 1; }
+
+    // optional: write() then follows each of its emissions with the system's indirect draw commands (draw_commands.hpp); NULL: none
+    void setCommands(GpuDrawCommands* drawCommands) noexcept { commands = drawCommands; }
 
     // the instance struct of mesh system p (pool p of the context): see GvInstanceLayout
     void setLayout(uint32_t p, const GvInstanceLayout& layout) { check(gv_pool_set_instance_layout(system->getContext(), p, &layout), "gv_pool_set_instance_layout"); }
@@ -97,6 +102,8 @@ public:
                 check(gv_pool_emit_instances(ctx, p, &v, 1, nullptr, 0), "gv_pool_emit_instances");
                 check(gv_pool_instances_fetch(ctx, p, base, baseBytes, starts, GV_MAX_VIEWS + 1), "gv_pool_instances_fetch");
                 out.baseCount = starts[1];
+                if (commands)
+                    commands->emit(p, false);
             }
         }
         if (shadow && !shadowViews.empty()) {
@@ -112,6 +119,8 @@ public:
                     k++;
             }
             out.shadowStart[shadowPassCount] = starts[shadowViews.size()];
+            if (commands)
+                commands->emit(p, true);
         }
         return out;
     }

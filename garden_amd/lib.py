@@ -24,8 +24,10 @@ GV_CONFIG_KEEP_SLOT_ORDER = 4
 GV_CONFIG_BLOCK_BOUNDS = 8
 GV_CONFIG_HIZ_RG16F = 16
 GV_CONFIG_LINEAR_SCAN = 32
-GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH, GV_DIRTY_PAYLOAD = 0, 1, 2, 3
+GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY = 0, 1, 2, 3, 4
 GV_MAX_DRAW_INSTANCES = 65535
+GV_MAX_GEOMETRIES = 65536
+GV_COMMANDS_MERGE_RUNS = 1
 GV_SWEEP_VALU, GV_SWEEP_MFMA, GV_SWEEP_WITH_CULL, GV_SWEEP_WITH_CULL_VALU, GV_SWEEP_INCREMENTAL = 0, 1, 2, 3, 4
 GV_MEM_HOST, GV_MEM_DEVICE = 0, 1
 GV_EXCHANGE_ALLGATHER, GV_EXCHANGE_P2P, GV_EXCHANGE_BROADCAST, GV_EXCHANGE_PEER = 0, 1, 2, 3
@@ -108,6 +110,18 @@ class GvInstanceLayout(C.Structure):
     _fields_ = [("stride", C.c_uint32), ("mvp", C.c_uint32), ("model", C.c_uint32), ("slot", C.c_uint32), ("distance_sq", C.c_uint32)]
 
 
+class GvGeometry(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("first", C.c_uint32), ("vertex_offset", C.c_int32)]
+
+
+GEOMETRY_DTYPE = np.dtype([("count", np.uint32), ("first", np.uint32), ("vertex_offset", np.int32)])
+
+
+class GvCommandLayout(C.Structure):
+    _fields_ = [("stride", C.c_uint32), ("count", C.c_uint32), ("instance_count", C.c_uint32), ("first", C.c_uint32),
+                ("first_instance", C.c_uint32), ("vertex_offset", C.c_uint32), ("draw", C.c_uint32)]
+
+
 GV_MAX_MERGE_GROUPS = 12
 GV_MAX_MERGE_ITEMS = 16
 
@@ -179,6 +193,8 @@ EXPORTS = [
     "gv_pool_bind_payload", "gv_pool_set_payload_layout",
     "gv_pool_emit_draw_instances", "gv_pool_set_instance_index_field", "gv_pool_draw_bases_device", "gv_pool_draw_bases_fetch",
     "gv_merge_sorted", "gv_merge_device", "gv_merge_fetch",
+    "gv_pool_bind_geometry", "gv_pool_set_command_layout", "gv_pool_emit_draw_commands", "gv_pool_draw_commands_device",
+    "gv_pool_draw_commands_fetch",
 ]
 
 _lib = None
@@ -303,6 +319,11 @@ def load():
     lib.gv_merge_sorted.argtypes = [P, C.POINTER(GvMergeGroup), u32]
     lib.gv_merge_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_merge_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
+    lib.gv_pool_bind_geometry.argtypes = [P, u32, P, u32, u32, u32, C.POINTER(GvGeometry), u32]
+    lib.gv_pool_set_command_layout.argtypes = [P, u32, C.POINTER(GvCommandLayout)]
+    lib.gv_pool_emit_draw_commands.argtypes = [P, u32, u32, u32, P, sz]
+    lib.gv_pool_draw_commands_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_pool_draw_commands_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -416,7 +437,7 @@ class GpuVisibility:
         self._check(self.lib.gv_pool_bind_ready(self.ctx, pool_id, ready.ctypes.data, ready.strides[0], ready.dtype.itemsize))
 
     def mark_dirty(self, kind, first, count, pool_id=0):
-        if kind in (GV_DIRTY_MESH, GV_DIRTY_PAYLOAD):
+        if kind in (GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY):
             first |= pool_id << 28
         self._check(self.lib.gv_mark_dirty(self.ctx, kind, first, count))
 
@@ -780,6 +801,84 @@ class GpuVisibility:
         if dtype is not None:
             out = out.reshape(-1).view(np.uint8)[:total * stride].view(np.dtype(dtype))
         return out, starts
+
+    # ---- indirect draw commands ----
+    def bind_geometry(self, pool_id, ids, table):
+        """gv_pool_bind_geometry: the pool's geometry ids (numpy u8 / u16 / u32 array, one element per slot, any element stride;
+        None: every slot draws table[0]) and the geometry table (rows of (count, first, vertex_offset); copied at the call). Both
+        None removes the binding. The caller keeps `ids` alive and unmoved, as for bind_ready."""
+        if table is None:
+            rows, tp, n = None, None, 0
+        else:
+            rows = np.asarray(table)
+            if rows.dtype.names is None:  # plain rows of three numbers
+                plain = rows.reshape(-1, 3)
+                rows = np.zeros(len(plain), GEOMETRY_DTYPE)
+                rows["count"], rows["first"], rows["vertex_offset"] = plain[:, 0], plain[:, 1], plain[:, 2]
+            rows = np.ascontiguousarray(rows)
+            assert rows.dtype.itemsize == C.sizeof(GvGeometry)
+            tp, n = C.cast(rows.ctypes.data, C.POINTER(GvGeometry)), len(rows)
+        if ids is None:
+            self._keep.pop(("geometry", pool_id), None)
+            self._check(self.lib.gv_pool_bind_geometry(self.ctx, pool_id, None, 0, 0, 0, tp, n))
+            return
+        assert ids.ndim == 1
+        self._keep[("geometry", pool_id)] = ids
+        self._check(self.lib.gv_pool_bind_geometry(self.ctx, pool_id, ids.ctypes.data, ids.strides[0], ids.dtype.itemsize, ids.shape[0], tp, n))
+
+    def set_command_layout(self, pool_id, dtype=None, offsets=None):
+        """gv_pool_set_command_layout: the caller's command struct, as a numpy structured `dtype` with the uint32 fields count,
+        instance_count, first, first_instance and optionally vertex_offset (int32) and draw — or as `offsets`, a dict of the same
+        names plus stride. Neither: the layout is removed."""
+        if dtype is not None:
+            dtype = np.dtype(dtype)
+            offsets = {name: dtype.fields[name][1] for name in dtype.names}
+            offsets["stride"] = dtype.itemsize
+        if offsets is None:
+            self._check(self.lib.gv_pool_set_command_layout(self.ctx, pool_id, None))
+            return
+        at = lambda name: GV_NONE if offsets.get(name) is None else int(offsets[name])
+        layout = GvCommandLayout(int(offsets["stride"]), int(offsets["count"]), int(offsets["instance_count"]), int(offsets["first"]),
+                                 int(offsets["first_instance"]), at("vertex_offset"), at("draw"))
+        self._check(self.lib.gv_pool_set_command_layout(self.ctx, pool_id, C.byref(layout)))
+        self._command_stride = getattr(self, "_command_stride", {})
+        self._command_stride[pool_id] = layout.stride
+
+    def emit_draw_commands(self, pool_id, merge_runs=False, region=0, device=None, flags=None):
+        """gv_pool_emit_draw_commands: one indirect command per draw (merge_runs: per run of one geometry) of the pool's last
+        instance emission, on the context's stream. region: 0 packs the views' commands, R > 0 gives every view R positions.
+        device: None for the library's own buffer, or (device pointer, capacity in bytes) of caller-owned device memory."""
+        ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
+        flags = (GV_COMMANDS_MERGE_RUNS if merge_runs else 0) if flags is None else flags
+        self._check(self.lib.gv_pool_emit_draw_commands(self.ctx, pool_id, flags, int(region), ptr, cap))
+        stride = self._command_stride[pool_id]
+        self._commands = getattr(self, "_commands", {})
+        self._commands[pool_id] = (stride, int(region), None if device is None else cap // stride)
+
+    def draw_commands_device(self, pool_id):
+        """(device pointer of the commands, device pointer of uint32 command_counts[views]) of the pool's last command emission"""
+        commands, counts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_pool_draw_commands_device(self.ctx, pool_id, C.byref(commands), C.byref(counts)))
+        return commands.value, counts.value
+
+    def draw_commands(self, pool_id, dtype=None, out=None):
+        """gv_pool_draw_commands_fetch: waits for the pool's last command emission; returns (the command positions — packed: the
+        views' commands back to back; regions: views x region — as uint8 [positions, stride] or viewed as the structured `dtype`,
+        and command_counts[views]). Positions a too small caller-owned device target does not hold stay as `out` has them
+        (default zeros)."""
+        stride, region, room = self._commands[pool_id]
+        views = self.instances_info(pool_id)[0]
+        counts = np.zeros(views, np.uint32)
+        cp = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self.lib.gv_pool_draw_commands_fetch(self.ctx, pool_id, None, 0, cp, len(counts)))
+        positions = views * region if region else int(counts.sum())
+        if out is None:
+            out = np.zeros((positions, stride), np.uint8)
+        assert out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.nbytes >= (positions if room is None else min(positions, room)) * stride
+        self._check(self.lib.gv_pool_draw_commands_fetch(self.ctx, pool_id, out.ctypes.data, out.nbytes, cp, len(counts)))
+        if dtype is not None:
+            out = out.reshape(-1).view(np.uint8)[:positions * stride].view(np.dtype(dtype))
+        return out, counts
 
     # ---- the shared sorted arrays ----
     @staticmethod

@@ -176,8 +176,10 @@ typedef enum GvDirtyKind {
                                re-validated; count == 0: entities came or went (destroy :30-73, create): rebuild and
                                re-order the whole mirror */
     GV_DIRTY_MESH = 2,      /* mesh slots changed; pool id in the top 4 bits of `first` */
-    GV_DIRTY_PAYLOAD = 3    /* the bound payload bytes (gv_pool_bind_payload) of mesh slots changed; pool id in the top 4 bits of
+    GV_DIRTY_PAYLOAD = 3,   /* the bound payload bytes (gv_pool_bind_payload) of mesh slots changed; pool id in the top 4 bits of
                                `first`, like GV_DIRTY_MESH. Read by no cull: a recorded cull of a batch is not launched by it */
+    GV_DIRTY_GEOMETRY = 4   /* the bound geometry ids (gv_pool_bind_geometry) of mesh slots changed; pool id in the top 4 bits of
+                               `first`. Read by no cull either */
 } GvDirtyKind;
 int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count);
 
@@ -445,6 +447,76 @@ int gv_pool_draw_bases_device(GvCtx* ctx, uint32_t pool_id, const void** first_i
  * included (capacity >= draws + 1 words). GV_E_ARG when either array is too small: nothing is written. */
 int gv_pool_draw_bases_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* first_instance, uint32_t capacity, uint32_t* draw_starts,
                              uint32_t starts_capacity);
+
+/* ---- indirect draw commands, built on the device ----
+ * After a cull and an instance emission the device holds every draw's instances at a known instance index, in draw order.
+ * gv_pool_emit_draw_commands writes, behind that emission, one indirect command per draw (or per run of consecutive draws of one
+ * geometry) in the caller's own command struct — the buffer a renderer hands to its indirect draw (the reference's
+ * DrawIndirectCommand / DrawIndexedIndirectCommand take such a buffer with offset, drawCount and stride,
+ * graphics/command-buffer.hpp:210-229) without the host having read a record. No system of the reference issues indirect draws, so
+ * the rule is this build's; it holds no arithmetic:
+ *   E is the pool's last emission since its last gv_cull (gv_pool_emit_instances or gv_pool_emit_draw_instances); it lists views
+ *   v = 0 .. m-1, view v has n_v draws, draw k is record k in delivery order (after gv_pool_sort: the sorted order).
+ *   s_k = visible_idx[k] is the record's POOL slot (never the index-mapped slot, never a mirror entry).
+ *   first_k, c_k: what E defines — after gv_pool_emit_instances first_k = starts[v] + k and c_k = 1; after a draw emission
+ *   first_k = first_instance[draw_starts[v] + k] and c_k = first_{k+1} - first_k, the word behind a view's last draw being starts[v+1].
+ *   g_k = id[s_k], read from the geometry id mirror as it stands when the command emission is issued (marks made after the cull
+ *   are consumed by it, as for payload and counts); without an id column g_k = 0.
+ *   G(g) = table[g] if g < table_count, else the void geometry {0, 0, 0}.
+ * Per-draw mode (flags 0): view v has C_v = n_v commands, command k = {count G(g_k).count, instance_count c_k (0 when
+ *   g_k >= table_count), first G(g_k).first, vertex_offset G(g_k).vertex_offset, first_instance first_k, draw k}.
+ * Run mode (GV_COMMANDS_MERGE_RUNS): draw k is a head iff k == 0 || g_k != g_{k-1} (raw ids; a run never crosses a view); C_v is
+ *   the number of heads; command r stands for the r-th run [h_r, h_{r+1}): geometry G(g_{h_r}), first_instance first_{h_r},
+ *   instance_count first_{h_{r+1}} - first_{h_r} (closing value starts[v+1]; 0 when the id is out of range), draw h_r. Draws whose
+ *   count is 0 take part like any other. A run's instances are contiguous in draw order, sorted views included.
+ * Placement: region_commands == 0 packs view v's commands at positions sum of C_u (u < v) + j. R = region_commands > 0 puts them
+ *   at v * R + j for j < min(C_v, R); commands with j >= R are not written and positions v * R + j, C_v <= j < R, are written as
+ *   all-zero commands, so that a host can submit drawCount = R at a host-known offset without reading anything back. A written
+ *   command has every byte of its stride defined (bytes outside the layout's fields are 0). Positions at or beyond
+ *   capacity_bytes / stride are not written, padding included. command_counts[v] = C_v is always the true count.
+ * An id at or beyond table_count is NOT an error: it yields the void command. Whatever an id holds, the kernels read inside the
+ * table only. */
+#define GV_MAX_GEOMETRIES 65536u
+typedef struct GvGeometry {
+    uint32_t count, first;   /* indexCount / firstIndex (vertexCount / firstVertex of a non-indexed draw) */
+    int32_t vertex_offset;
+} GvGeometry;
+/* The pool's geometry ids and the table they index. ids: element i at ids + i * stride, width 1, 2 or 4 bytes (widened to uint32 on
+ * the way up, like the ready column), covering `occupancy` slots; ids == NULL: every slot draws table[0] and no mirror is kept. The
+ * table (<= GV_MAX_GEOMETRIES entries) is copied at the call. ids == NULL && table == NULL removes both. Lifetime of `ids` as
+ * gv_pool_bind_ready. The id mirror — one uint32 per POOL slot — exists only once gv_pool_emit_draw_commands has been called for a
+ * pool with an id column: that call uploads the column; from then on GV_DIRTY_GEOMETRY and the pool's GV_DIRTY_MESH marks feed a
+ * dirty set of its own, consumed by gv_sync or the pool's next command emission, whichever comes first. Uploaded bytes (ids, the
+ * packet's slots, the table) count in GvStats::upload_bytes; a rebind resets the mirror.
+ * GV_E_ARG: a pool out of range, a width other than 1, 2 or 4, stride < width, a NULL table with table_count > 0, table_count 0
+ * with a table or ids, table_count above the limit, an occupancy beyond the 28-bit slot range. */
+int gv_pool_bind_geometry(GvCtx* ctx, uint32_t pool_id, const void* ids, uint32_t stride, uint32_t width, uint32_t occupancy,
+                          const GvGeometry* table, uint32_t table_count);
+typedef struct GvCommandLayout {   /* described, not assumed - like GvInstanceLayout */
+    uint32_t stride;               /* a multiple of 4, 16 ... 64 */
+    uint32_t count, instance_count, first, first_instance;   /* required uint32 fields */
+    uint32_t vertex_offset;        /* int32, or GV_NONE (non-indexed draws) */
+    uint32_t draw;                 /* uint32, or GV_NONE */
+} GvCommandLayout;                 /* fields 4-byte aligned, inside the stride, disjoint: GV_E_ARG otherwise */
+int gv_pool_set_command_layout(GvCtx* ctx, uint32_t pool_id, const GvCommandLayout* layout);   /* NULL removes it */
+#define GV_COMMANDS_MERGE_RUNS 1u
+/* The commands of the views of E, in E's order. Asynchronous on gv_stream(ctx), the host reads no count; counts as a read
+ * (recorded culls and deferred sorts are launched first, as for the emissions); changes no cull result and no instance data. The
+ * result is valid until the next gv_cull or the next instance emission of the pool. dst_device NULL: a library-owned buffer, grown
+ * and never shrunk — packed, sized for the sum of the listed views' occupancies x stride; with regions for m * R x stride. A
+ * non-NULL dst_device is caller-owned and 16-byte aligned. One launch in per-draw mode, three in run mode, counted under
+ * GvStats::launches[GV_K_EMIT].
+ * GV_E_ARG: a pool out of range, unknown flag bits, a misaligned dst_device, m * R beyond 32 bits. GV_E_STATE: no command
+ * layout, no geometry bound, no emission since the pool's last gv_cull, an id column whose occupancy is below a listed view's. */
+int gv_pool_emit_draw_commands(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device,
+                               size_t capacity_bytes);
+/* Device pointers of the pool's last command emission, written in stream order: the commands and uint32 command_counts[m]. */
+int gv_pool_draw_commands_device(GvCtx* ctx, uint32_t pool_id, const void** commands, const void** command_counts);
+/* Waits for the pool's last command emission; copies command_counts[0 .. m-1] (counts_capacity >= m) and — dst_host non-NULL — the
+ * command positions the target holds (packed: min(sum of C_v, capacity); regions: min(m * R, capacity)) through the library's
+ * pinned staging, whole commands (the library wrote every byte). GV_E_ARG when either array is too small: nothing is written. */
+int gv_pool_draw_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* command_counts,
+                                uint32_t counts_capacity);
 
 /* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
  * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
