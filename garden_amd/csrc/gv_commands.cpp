@@ -37,6 +37,7 @@ int gv_pool_bind_geometry(GvCtx* ctx, uint32_t pool_id, const void* ids, uint32_
     if (!ids) {  // no column: no mirror
         G.wanted = false;
         G.release();
+        G.staged.pending = false;
     }
     if (!table) {
         G.d_table.release();
@@ -142,7 +143,7 @@ int gv_pool_emit_draw_commands(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uin
     launch.first_instance = L.first_instance;
     launch.vertex_offset = L.vertex_offset;
     launch.draw = L.draw;
-    launch.ids = G.ids.ptr ? G.d_ids.ptr : nullptr;
+    launch.ids = G.ids.ptr ? G.d_column.ptr : nullptr;
     launch.table = reinterpret_cast<const CommandGeometry*>(G.d_table.ptr);
     launch.table_count = G.table_count;
     launch.starts = I.d_starts.ptr;

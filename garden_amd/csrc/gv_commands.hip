@@ -40,7 +40,6 @@ __global__ __launch_bounds__(kCommandBlock) void command_heads_kernel(const Comm
     static_assert(kRounds * kWaves == 64u, "wave 0 scans one (round, wave) total per lane");
     __shared__ uint32_t tail[64];  // the id of every (round, wave)'s last lane
     __shared__ uint32_t part[64];
-    __shared__ uint32_t chunk_sum;
     const uint32_t v = view_of_block(a.first_chunk, a.views, blockIdx.x);
     const CommandView& vw = a.view[v];
     const uint32_t n = *vw.count;
@@ -81,14 +80,7 @@ __global__ __launch_bounds__(kCommandBlock) void command_heads_kernel(const Comm
         if (lane == 0)
             part[q] = (uint32_t)__popcll(m);
     }
-    __syncthreads();
-    if (wave == 0) {
-        const uint32_t own = part[lane], upto = wave_inclusive_scan(own, lane);
-        part[lane] = upto - own;
-        if (lane == 63u)
-            chunk_sum = upto;
-    }
-    __syncthreads();
+    const uint32_t chunk_sum = chunk_scan_tail(part, lane, wave);
     uint32_t* const rank = a.rank + (size_t)a.first_draw_block[v] * kCommandBlock;
 #pragma unroll
     for (uint32_t r = 0; r < kRounds; r++) {

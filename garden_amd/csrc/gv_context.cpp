@@ -697,17 +697,11 @@ void gv_destroy(GvCtx* ctx)
             release_record_target(target);
         p.d_a.release(); p.d_b.release(); p.d_link.release(); p.h_a.release(); p.h_b.release(); p.h_link.release(); p.d_orig.release(); p.d_inv.release(); p.d_index_map.release(); p.d_blk_lo.release(); p.d_blk_hi.release(); p.d_seed.release(); p.d_kept.release(); p.d_kept_flag.release(); p.d_blk_dirty.release(); p.d_hot.release();
         p.instances.d_data.release(); p.instances.d_starts.release(); p.instances.h_data.release(); p.instances.h_starts.release();
-        p.payload.d_rows.release(); p.payload.h_stage.release(); p.payload.d_packet.release();
+        p.payload.release();
         p.instances.d_first.release(); p.instances.d_draw_starts.release(); p.instances.d_local.release();
         p.instances.d_chunk_total.release(); p.instances.h_first.release();
-        p.counts.d_counts.release(); p.counts.h_stage.release(); p.counts.d_packet.release();
-        if (p.counts.staged)
-            (void)hipEventDestroy(p.counts.staged);
-        p.counts.staged = nullptr;
-        p.geometry.release(); p.geometry.d_table.release();
-        if (p.geometry.staged)
-            (void)hipEventDestroy(p.geometry.staged);
-        p.geometry.staged = nullptr;
+        p.counts.release(); p.counts.staged.destroy();
+        p.geometry.release(); p.geometry.d_table.release(); p.geometry.staged.destroy();
         p.commands.d_data.release(); p.commands.d_counts.release(); p.commands.d_rank.release(); p.commands.d_chunk_total.release();
         p.commands.d_draw_of.release(); p.commands.d_first_of.release(); p.commands.h_data.release(); p.commands.h_counts.release();
     }
@@ -729,10 +723,7 @@ void gv_destroy(GvCtx* ctx)
         if (ctx->raw_done[k])
             (void)hipEventDestroy(ctx->raw_done[k]);
     }
-    if (ctx->upload_done) {
-        (void)hipEventDestroy(ctx->upload_done);
-        ctx->upload_done = nullptr;
-    }
+    ctx->uploads.destroy();
     ctx->d_xinv.release(); ctx->sc_xf.release(); ctx->dsc_xf.release(); ctx->sc_mesh.release(); ctx->dsc_mesh.release(); ctx->dsc_a.release(); ctx->dsc_c.release(); ctx->d_pick_keys.release(); ctx->h_pick_keys.release();
     for (auto& m : ctx->merges) {
         m.d_records.release(); m.d_counts.release(); m.h_records.release(); m.h_counts.release();
@@ -886,10 +877,8 @@ int gv_pool_bind_ready(GvCtx* ctx, uint32_t pool_id, const void* data, uint32_t 
         p.counts.wanted = false;
         GV_HIP(ctx, hipSetDevice(ctx->device));
         GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading it)
-        p.counts.staged_pending = false;
-        p.counts.d_counts.release();
-        p.counts.h_stage.release();
-        p.counts.d_packet.release();
+        p.counts.staged.pending = false;
+        p.counts.release();
         std::vector<uint32_t>().swap(p.counts.held);
     }
     if (had != (data != nullptr) && p.bound)

@@ -182,6 +182,66 @@ struct Stamp {
 
 inline uint32_t blocks_of(uint32_t occupancy) { return (occupancy + kCullBlock - 1) / kCullBlock; }  // cull workgroups of a pool
 
+// Behind the last copies that read a pinned staging / packet buffer: whoever rewrites the buffer next waits for THIS, not for the
+// whole stream (the previous frame's cull may still be running: a scene in which something moves every frame would otherwise run
+// host and device one after the other, 0.20 instead of 0.12 ms per frame at 10 M entities with ten movers, tools/moving_bench.py).
+// The context has one for the mirror's staging arrays, packet buffers and the payload rows; the count and the geometry id mirror
+// have one each: the context's may sit behind a payload copy that the very call which uploads them has just queued behind the
+// frame's cull.
+struct UploadFence {
+    hipEvent_t event = nullptr;
+    bool pending = false;
+    hipError_t wait()
+    {
+        if (!pending)
+            return hipSuccess;
+        const hipError_t e = hipEventSynchronize(event);
+        if (e == hipSuccess)
+            pending = false;
+        return e;
+    }
+    hipError_t record(hipStream_t stream)
+    {
+        hipError_t e = event ? hipSuccess : hipEventCreateWithFlags(&event, hipEventDisableTiming);
+        if (e == hipSuccess)
+            e = hipEventRecord(event, stream);
+        if (e == hipSuccess)
+            pending = true;
+        return e;
+    }
+    void destroy()
+    {
+        if (event)
+            (void)hipEventDestroy(event);
+        event = nullptr;
+        pending = false;
+    }
+};
+
+// A side column of a pool on the device, one element per POOL SLOT (indexed by visible_idx; a re-order of the mirror does not
+// concern it), kept by upload_slot_mirror (gv_mirror.cpp). T is the unit its buffers are counted in: bytes for the payload rows,
+// words for the counts and the geometry ids (capacities grow by halves of what they were, in that unit).
+template <typename T>
+struct SlotMirror {
+    uint32_t elem = sizeof(T);  // bytes of an element: 4 for counts and ids, the pitch for payload rows (set with it at the bind)
+    uint32_t mirrored = 0;      // elements [0, mirrored) are on the device (0: everything is uploaded)
+    DirtyRanges dirty;
+    DeviceBuf<T> d_column;
+    PinnedBuf<T> h_stage;       // the elements (and, behind them, the packet's slots) on their way up
+    DeviceBuf<T> d_packet;
+    void reset()                // rebound: everything is uploaded again
+    {
+        mirrored = 0;
+        dirty.clear();
+    }
+    void release()              // (the caller has drained the stream)
+    {
+        d_column.release();
+        h_stage.release();
+        d_packet.release();
+    }
+};
+
 struct PoolState {
     Column entity, is_enabled, aabb_min, aabb_max;
     RecordLayout record_layout{};  // gv_pool_set_record_layout (stride 0: none)
@@ -213,16 +273,6 @@ struct PoolState {
         GvInstanceLayout emitted{};     // the layout it was made with
         uint32_t emitted_payload = 0;   // ... and the payload fields it wrote: (at, bytes) each
         uint32_t emitted_at[GV_MAX_PAYLOAD_FIELDS] = {}, emitted_bytes[GV_MAX_PAYLOAD_FIELDS] = {};
-        struct PayloadPlaces {          // what an emission is about to write of the payload: noted above once it has been launched
-            uint32_t count = 0;
-            uint32_t at[GV_MAX_PAYLOAD_FIELDS] = {}, bytes[GV_MAX_PAYLOAD_FIELDS] = {};
-        };
-        void note_payload(const PayloadPlaces& w)
-        {
-            emitted_payload = w.count;
-            std::copy(w.at, w.at + GV_MAX_PAYLOAD_FIELDS, emitted_at);
-            std::copy(w.bytes, w.bytes + GV_MAX_PAYLOAD_FIELDS, emitted_bytes);
-        }
         // gv_pool_emit_draw_instances (a draw takes its ready count of instances): starts[] then holds instance starts
         uint32_t index_at = GV_NONE;       // gv_pool_set_instance_index_field: the uint32 "index within the draw"
         uint32_t emitted_index = GV_NONE;  // ... as the last emission wrote it (GV_NONE: it did not)
@@ -234,31 +284,24 @@ struct PoolState {
     } instances;
     // The ready column on the device, one uint32 per POOL SLOT (indexed by visible_idx like the payload rows; a re-order of the
     // mirror does not concern it): exists only once gv_pool_emit_draw_instances has been called for a pool with a ready column
-    struct Counts {
+    struct Counts : SlotMirror<uint32_t> {  // dirty: the pool's GV_DIRTY_MESH marks
         bool wanted = false;
-        uint32_t mirrored = 0;             // counts [0, mirrored) are on the device (0: everything is uploaded)
         uint64_t sum = 0;                  // of the mirrored counts: the host's bound of a view's instances
         std::vector<uint32_t> held;        // what was uploaded, slot by slot (keeps `sum` exact under partial uploads)
         std::vector<uint32_t> over;        // the slots whose mirrored count is above GV_MAX_DRAW_INSTANCES (few, if any): a mark made
                                            // after the last sync may have put one there, which ready_over_count has not seen
-        hipEvent_t staged = nullptr;       // behind the last copies that read h_stage: the next upload waits for THIS, not for the
-        bool staged_pending = false;       // context's upload event (which a payload upload of the same call has just recorded)
-        DirtyRanges dirty;                 // the pool's GV_DIRTY_MESH marks
-        DeviceBuf<uint32_t> d_counts;
-        PinnedBuf<uint32_t> h_stage;       // the counts (and, behind them, the packet's slots) on their way up
-        DeviceBuf<uint32_t> d_packet;
+        UploadFence staged;                // guards h_stage (its own: see UploadFence)
         void reset()                       // the column was rebound: everything is uploaded again
         {
-            mirrored = 0;
+            SlotMirror::reset();
             sum = 0;
-            dirty.clear();
             over.clear();
         }
     } counts;
     // gv_pool_bind_geometry: the geometry id column and the table it indexes. The ids on the device, one uint32 per POOL SLOT like
     // the counts above (indexed by visible_idx; a re-order of the mirror does not concern them): the mirror exists only once
     // gv_pool_emit_draw_commands has been called for a pool with an id column
-    struct Geometry {
+    struct Geometry : SlotMirror<uint32_t> {  // dirty: GV_DIRTY_GEOMETRY and GV_DIRTY_MESH marks of the pool
         bool bound = false;                // a table is bound (with or without an id column)
         Column ids;                        // ptr NULL: none, every slot has id 0
         uint32_t width = 0;                // 1, 2 or 4 bytes
@@ -275,25 +318,7 @@ struct PoolState {
         uint32_t table_count = 0;
         DeviceBuf<GvGeometry> d_table;     // re-uploaded on every bind
         bool wanted = false;
-        uint32_t mirrored = 0;             // ids [0, mirrored) are on the device (0: everything is uploaded)
-        hipEvent_t staged = nullptr;       // behind the last copies that read h_stage (an event of its own, as Counts::staged)
-        bool staged_pending = false;
-        DirtyRanges dirty;                 // GV_DIRTY_GEOMETRY and GV_DIRTY_MESH marks of the pool
-        DeviceBuf<uint32_t> d_ids;
-        PinnedBuf<uint32_t> h_stage;       // the ids (and, behind them, the packet's slots) on their way up
-        DeviceBuf<uint32_t> d_packet;
-        void reset()                       // rebound: everything is uploaded again
-        {
-            mirrored = 0;
-            dirty.clear();
-        }
-        void release()                     // (the caller has drained the stream)
-        {
-            d_ids.release();
-            h_stage.release();
-            d_packet.release();
-            staged_pending = false;
-        }
+        UploadFence staged;                // guards h_stage (its own: see UploadFence)
     } geometry;
     // gv_pool_set_command_layout / gv_pool_emit_draw_commands: buffers of their own, no cull result or instance data is touched
     struct Commands {
@@ -311,19 +336,14 @@ struct PoolState {
     // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
     // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
     // transform mirror does not concern it); read by gv_pool_emit_instances only
-    struct Payload {
+    struct Payload : SlotMirror<uint8_t> {  // dirty: GV_DIRTY_PAYLOAD and GV_DIRTY_MESH marks of the pool
         uint32_t count = 0;                        // fields (0: none bound)
         Column src[GV_MAX_PAYLOAD_FIELDS];         // read only inside upload_payload
         uint32_t bytes[GV_MAX_PAYLOAD_FIELDS] = {};
         uint32_t offset[GV_MAX_PAYLOAD_FIELDS] = {};  // of the field inside a row (fields back to back)
         uint32_t at[GV_MAX_PAYLOAD_FIELDS] = {GV_NONE, GV_NONE, GV_NONE, GV_NONE};  // destinations in the instance
-        uint32_t pitch = 0;                        // 16, 32 or 64: a row never straddles a 64-byte boundary
+        uint32_t pitch = 0;                        // 16, 32 or 64: a row never straddles a 64-byte boundary; elem while a payload is bound
         uint32_t occupancy = 0;
-        uint32_t mirrored = 0;                     // rows [0, mirrored) are on the device (0: everything is uploaded)
-        DirtyRanges dirty;                         // GV_DIRTY_PAYLOAD and GV_DIRTY_MESH marks of the pool
-        DeviceBuf<uint8_t> d_rows;
-        PinnedBuf<uint8_t> h_stage;                // the rows (and, behind them, the packet's slots) on their way up
-        DeviceBuf<uint8_t> d_packet;
         bool any_destination() const
         {
             for (uint32_t f = 0; f < count; f++)
@@ -482,8 +502,7 @@ struct Context {
     PinnedBuf<uint8_t> h_raw[2];   // the library's own pinned chunks the span travels through (double-buffered)
     hipEvent_t raw_done[2] = {nullptr, nullptr};  // chunk buffer k may be rewritten once its last copy has run
     DirtyRange staging_stale;      // slots whose host staging entries lag behind the device (written by that path)
-    hipEvent_t upload_done = nullptr;  // behind the last copies that read the pinned staging / packet buffers: the next sync waits for THIS before
-    bool upload_pending = false;       // it rewrites them, not for the whole stream (the previous frame's cull may still be running)
+    UploadFence uploads;           // guards the pinned staging arrays, the packet buffers and the payload rows' staging
     PinnedBuf<uint32_t> h_ranges;  // a sync's dirty ranges on their way to mark_dirty_blocks_kernel
     DeviceBuf<uint32_t> d_ranges;
     DeviceBuf<uint32_t> d_e2t;     // entity -> transform slot table on the device, refreshed by every device-side mesh gather

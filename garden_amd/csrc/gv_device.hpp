@@ -628,6 +628,22 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x, uint32_t lan
     return x;
 }
 
+// The tail of a chunk scan: `part` holds the 64 (round, wave) totals of a 256-lane workgroup; wave 0 scans them into the totals in
+// front of each, in place. Two barriers. Returns the chunk's sum.
+__device__ __forceinline__ uint32_t chunk_scan_tail(uint32_t* part, uint32_t lane, uint32_t wave)
+{
+    __shared__ uint32_t chunk_sum;
+    __syncthreads();
+    if (wave == 0) {
+        const uint32_t own = part[lane], upto = wave_inclusive_scan(own, lane);
+        part[lane] = upto - own;
+        if (lane == 63u)
+            chunk_sum = upto;
+    }
+    __syncthreads();
+    return chunk_sum;
+}
+
 // sum of t[lo, hi) by the whole workgroup (every lane gets it); scratch: one word per wave
 __device__ __forceinline__ uint32_t block_sum_of(const uint32_t* t, uint32_t lo, uint32_t hi, uint32_t* scratch)
 {

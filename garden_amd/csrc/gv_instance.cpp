@@ -18,36 +18,48 @@ struct Field {
     uint32_t at, bytes, align;
 };
 
-// the layout's fields in the order mvp, model, slot, distance_sq; returns how many it has
-uint32_t fields_of(const GvInstanceLayout& L, Field* f)  // (room for four)
+constexpr uint32_t kMaxFields = 4 + GV_MAX_PAYLOAD_FIELDS + 1;
+
+// The fields an instance has: the layout's in the order mvp, model, slot, distance_sq (stride 0: no layout yet, none), the payload
+// destinations `at` that are set, the index word (GV_NONE: none). Returns how many; room for kMaxFields.
+uint32_t instance_fields(const GvInstanceLayout& L, uint32_t payload, const uint32_t* at, const uint32_t* bytes, uint32_t index_at, Field* f)
 {
     uint32_t n = 0;
-    f[n++] = Field{L.mvp, 64, 16};
-    if (L.model != GV_NONE)
-        f[n++] = Field{L.model, 48, 4};
-    if (L.slot != GV_NONE)
-        f[n++] = Field{L.slot, 4, 4};
-    if (L.distance_sq != GV_NONE)
-        f[n++] = Field{L.distance_sq, 4, 4};
+    if (L.stride) {
+        f[n++] = Field{L.mvp, 64, 16};
+        for (const Field& optional : {Field{L.model, 48, 4}, Field{L.slot, 4, 4}, Field{L.distance_sq, 4, 4}})
+            if (optional.at != GV_NONE)
+                f[n++] = optional;
+    }
+    for (uint32_t k = 0; k < payload; k++)
+        if (at[k] != GV_NONE)
+            f[n++] = Field{at[k], bytes[k], 4};
+    if (index_at != GV_NONE)
+        f[n++] = Field{index_at, 4, 4};
     return n;
 }
 
+bool overlaps_any(const Field* f, uint32_t n, uint32_t at, uint32_t bytes)
+{
+    for (uint32_t j = 0; j < n; j++)
+        if (!(at + bytes <= f[j].at || f[j].at + f[j].bytes <= at))
+            return true;
+    return false;
+}
+
 // the payload destinations `at` against the instance layout (stride 0: none yet — only each other): 4-byte aligned, inside the
-// stride, disjoint from one another and from the layout's fields
+// stride, disjoint from one another and from the layout's fields (which are disjoint among themselves: gv_pool_set_instance_layout)
 bool payload_fits(const GvInstanceLayout& L, const PoolState::Payload& P, const uint32_t* at)
 {
-    Field f[4 + GV_MAX_PAYLOAD_FIELDS];
-    uint32_t n = L.stride ? fields_of(L, f) : 0;
-    for (uint32_t k = 0; k < P.count; k++) {
-        if (at[k] == GV_NONE)
-            continue;
-        if (at[k] % 4 != 0 || at[k] > kMaxInstanceStride || (L.stride && (at[k] > L.stride || P.bytes[k] > L.stride - at[k])))
+    for (uint32_t k = 0; k < P.count; k++)
+        if (at[k] != GV_NONE &&
+            (at[k] % 4 != 0 || at[k] > kMaxInstanceStride || (L.stride && (at[k] > L.stride || P.bytes[k] > L.stride - at[k]))))
             return false;
-        for (uint32_t j = 0; j < n; j++)
-            if (!(at[k] + P.bytes[k] <= f[j].at || f[j].at + f[j].bytes <= at[k]))
-                return false;
-        f[n++] = Field{at[k], P.bytes[k], 4};
-    }
+    Field f[kMaxFields];
+    const uint32_t n = instance_fields(L, P.count, at, P.bytes, GV_NONE, f);
+    for (uint32_t i = 1; i < n; i++)
+        if (overlaps_any(f, i, f[i].at, f[i].bytes))
+            return false;
     return true;
 }
 
@@ -55,17 +67,10 @@ bool payload_fits(const GvInstanceLayout& L, const PoolState::Payload& P, const 
 // yet — only the destinations): 4-byte aligned, inside the stride, disjoint from the layout's fields and the payload destinations
 bool index_fits(const GvInstanceLayout& L, const PoolState::Payload& P, const uint32_t* at, uint32_t index_at)
 {
-    Field f[4 + GV_MAX_PAYLOAD_FIELDS];
-    uint32_t n = L.stride ? fields_of(L, f) : 0;
-    for (uint32_t k = 0; k < P.count; k++)
-        if (at[k] != GV_NONE)
-            f[n++] = Field{at[k], P.bytes[k], 4};
     if (index_at % 4 != 0 || index_at > kMaxInstanceStride - 4 || (L.stride && index_at > L.stride - 4))
         return false;
-    for (uint32_t j = 0; j < n; j++)
-        if (!(index_at + 4 <= f[j].at || f[j].at + f[j].bytes <= index_at))
-            return false;
-    return true;
+    Field f[kMaxFields];
+    return !overlaps_any(f, instance_fields(L, P.count, at, P.bytes, GV_NONE, f), index_at, 4);
 }
 
 // What gv_pool_emit_instances and gv_pool_emit_draw_instances (`fn`) check alike: the arguments, the layout, the listed views
@@ -118,10 +123,10 @@ int check_emission(GvCtx* ctx, const char* fn, uint32_t pool_id, const uint32_t*
 }
 
 // What both emissions launch with: the listed views and their workgroups, the layout, the index map, and — with_payload — where each
-// word of a payload row goes (`places`: what the fetch is to deliver, noted by the caller once the launch is made). slots: the sum of the views' occupancies. Returns the
-// bytes of an instance that the fields and the payload cover.
-uint32_t fill_launch(GvCtx* ctx, const PoolState& p, const uint32_t* view_indices, uint32_t view_count, bool with_payload, InstanceLaunch& launch,
-                     uint64_t& slots, PoolState::Instances::PayloadPlaces& places)
+// word of a payload row goes. slots: the sum of the views' occupancies. Returns the bytes of an instance that the fields, the payload
+// and the index word at `index_at` (GV_NONE: none) cover.
+uint32_t fill_launch(GvCtx* ctx, const PoolState& p, const uint32_t* view_indices, uint32_t view_count, bool with_payload, uint32_t index_at,
+                     InstanceLaunch& launch, uint64_t& slots)
 {
     const uint32_t pool_id = (uint32_t)(&p - ctx->pools);
     const PoolState::Payload& P = p.payload;
@@ -144,12 +149,13 @@ uint32_t fill_launch(GvCtx* ctx, const PoolState& p, const uint32_t* view_indice
     launch.slot = L.slot;
     launch.distance_sq = L.distance_sq;
     launch.index_map = p.index_map_count ? p.d_index_map.ptr : nullptr;
-    uint32_t covered = 64;  // mvp
-    covered += (L.model != GV_NONE ? 48 : 0) + (L.slot != GV_NONE ? 4 : 0) + (L.distance_sq != GV_NONE ? 4 : 0);
-    places.count = 0;
+    Field fields[kMaxFields];
+    uint32_t covered = 0;
+    for (uint32_t i = 0, n = instance_fields(L, with_payload ? P.count : 0, P.at, P.bytes, index_at, fields); i < n; i++)
+        covered += fields[i].bytes;
     if (with_payload) {
         // where each word of a row goes; a 16-byte piece whose four words go to one 16-byte aligned place travels whole
-        launch.payload_rows = P.d_rows.ptr;
+        launch.payload_rows = P.d_column.ptr;
         launch.payload_pitch = P.pitch;
         std::fill(launch.piece_at, launch.piece_at + 4, kNoPayloadPlace);
         std::fill(launch.word_at, launch.word_at + 16, kNoPayloadPlace);
@@ -158,9 +164,6 @@ uint32_t fill_launch(GvCtx* ctx, const PoolState& p, const uint32_t* view_indice
                 continue;
             for (uint32_t w = 0; w < P.bytes[f] / 4; w++)
                 launch.word_at[P.offset[f] / 4 + w] = (uint16_t)(P.at[f] + 4 * w);
-            covered += P.bytes[f];
-            places.at[places.count] = P.at[f];
-            places.bytes[places.count++] = P.bytes[f];
         }
         for (uint32_t j = 0; j < 4; j++) {
             uint16_t* w = launch.word_at + 4 * j;
@@ -171,6 +174,37 @@ uint32_t fill_launch(GvCtx* ctx, const PoolState& p, const uint32_t* view_indice
         }
     }
     return covered;
+}
+
+// what an emission that has been launched leaves for the fetches and for gv_pool_emit_draw_commands
+void note_emission(PoolState& p, const InstanceLaunch& launch, const uint32_t* view_indices, uint32_t view_count, bool with_payload, uint32_t index,
+                   bool draws)
+{
+    PoolState::Instances& I = p.instances;
+    I.target = launch.dst;
+    I.capacity = launch.capacity;
+    I.views = view_count;
+    std::copy(view_indices, view_indices + view_count, I.listed);
+    p.commands.views = 0;  // commands belong to the emission in front of them
+    I.emitted = I.layout;
+    I.emitted_payload = 0;
+    for (uint32_t f = 0; with_payload && f < p.payload.count; f++)
+        if (p.payload.at[f] != GV_NONE) {
+            I.emitted_at[I.emitted_payload] = p.payload.at[f];
+            I.emitted_bytes[I.emitted_payload++] = p.payload.bytes[f];
+        }
+    I.emitted_index = index;
+    I.draws = draws;
+}
+
+// the first `n` words of a starts table on the device into I.h_starts, waited for
+int fetch_starts(GvCtx* ctx, PoolState::Instances& I, const uint32_t* device, uint32_t n)
+{
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    GV_HIP(ctx, I.h_starts.reserve(GV_MAX_VIEWS + 1));
+    GV_HIP(ctx, hipMemcpyAsync(I.h_starts.ptr, device, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return GV_OK;
 }
 
 }  // namespace
@@ -188,11 +222,9 @@ int gv_pool_bind_payload(GvCtx* ctx, uint32_t pool_id, const GvPayloadField* fie
     if (count == 0) {  // removed, mirror freed (the stream may still be reading it)
         GV_HIP(ctx, hipSetDevice(ctx->device));
         GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        P.d_rows.release();
-        P.h_stage.release();
-        P.d_packet.release();
-        P.dirty.clear();
-        P.count = P.occupancy = P.mirrored = P.pitch = 0;
+        P.release();
+        P.reset();
+        P.count = P.occupancy = P.pitch = 0;
         std::fill(P.at, P.at + GV_MAX_PAYLOAD_FIELDS, GV_NONE);
         return GV_OK;
     }
@@ -213,13 +245,11 @@ int gv_pool_bind_payload(GvCtx* ctx, uint32_t pool_id, const GvPayloadField* fie
     bool same = P.count == count && occupancy >= P.occupancy;
     for (uint32_t f = 0; same && f < count; f++)
         same = P.bytes[f] == fields[f].bytes;
-    if (!same) {  // another shape or a smaller occupancy: everything is uploaded
-        P.mirrored = 0;
-        P.dirty.clear();
-    }
+    if (!same)  // another shape or a smaller occupancy: everything is uploaded
+        P.reset();
     P.count = count;
     P.occupancy = occupancy;
-    P.pitch = sum <= 16 ? 16 : (sum <= 32 ? 32 : 64);
+    P.pitch = P.elem = sum <= 16 ? 16 : (sum <= 32 ? 32 : 64);  // (the mirror's element is the row)
     for (uint32_t f = 0, offset = 0; f < GV_MAX_PAYLOAD_FIELDS; f++) {
         P.src[f] = f < count ? Column{static_cast<const uint8_t*>(fields[f].data), fields[f].stride} : Column{};
         P.bytes[f] = f < count ? fields[f].bytes : 0;
@@ -262,14 +292,11 @@ int gv_pool_set_instance_layout(GvCtx* ctx, uint32_t pool_id, const GvInstanceLa
     GvInstanceLayout L{};
     if (layout) {
         L = *layout;
-        Field f[4];
-        const uint32_t n = fields_of(L, f);
+        Field f[kMaxFields];
+        const uint32_t n = instance_fields(L, 0, nullptr, nullptr, GV_NONE, f);
         bool ok = L.stride % 16 == 0 && L.stride >= kMinInstanceStride && L.stride <= kMaxInstanceStride;
-        for (uint32_t i = 0; ok && i < n; i++) {
-            ok = f[i].at % f[i].align == 0 && f[i].at <= L.stride && f[i].bytes <= L.stride - f[i].at;
-            for (uint32_t j = 0; ok && j < i; j++)
-                ok = f[i].at + f[i].bytes <= f[j].at || f[j].at + f[j].bytes <= f[i].at;
-        }
+        for (uint32_t i = 0; ok && i < n; i++)
+            ok = f[i].at % f[i].align == 0 && f[i].at <= L.stride && f[i].bytes <= L.stride - f[i].at && !overlaps_any(f, i, f[i].at, f[i].bytes);
         if (!ok)
             return ctx->fail(GV_E_ARG, "gv_pool_set_instance_layout: stride %u (a multiple of 16, %u to %u) with mvp at %u (16-byte aligned) and "
                              "model / slot / distance_sq at %u / %u / %u (4-byte aligned, 0x%x: none): fields must lie inside the instance and "
@@ -310,8 +337,7 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
             return rc;
     InstanceLaunch launch{};
     uint64_t bound = 0;  // the host's upper bound of the total
-    PoolState::Instances::PayloadPlaces places;
-    const uint32_t covered = fill_launch(ctx, p, view_indices, view_count, with_payload, launch, bound, places);
+    const uint32_t covered = fill_launch(ctx, p, view_indices, view_count, with_payload, GV_NONE, launch, bound);
     if (dst_device) {
         launch.dst = static_cast<uint8_t*>(dst_device);
         launch.capacity = (uint32_t)std::min<uint64_t>(capacity_bytes / L.stride, bound);
@@ -325,15 +351,7 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
     // fields and payload are disjoint and inside the stride: together as many bytes as the stride = all of it
     launch.staged = with_payload && covered == L.stride && L.stride <= kMaxStagedInstanceStride;
     GV_HIP(ctx, launch_instances(launch, ctx->stream));
-    I.target = launch.dst;
-    I.capacity = launch.capacity;
-    I.views = view_count;
-    std::copy(view_indices, view_indices + view_count, I.listed);
-    p.commands.views = 0;  // commands belong to the emission in front of them
-    I.emitted = L;
-    I.note_payload(places);
-    I.emitted_index = GV_NONE;
-    I.draws = false;
+    note_emission(p, launch, view_indices, view_count, with_payload, GV_NONE, false);
     return GV_OK;
 }
 
@@ -386,8 +404,7 @@ int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* vi
     }
     DrawInstanceLaunch launch{};
     uint64_t slots = 0;  // the sum of the listed views' occupancies: the host's upper bound of the DRAWS
-    PoolState::Instances::PayloadPlaces places;
-    uint32_t covered = fill_launch(ctx, p, view_indices, view_count, with_payload, launch.base, slots, places);
+    const uint32_t covered = fill_launch(ctx, p, view_indices, view_count, with_payload, I.index_at, launch.base, slots);
     for (uint32_t k = 0; k < view_count; k++)
         launch.first_chunk[k + 1] = launch.first_chunk[k] + (view_of(ctx, pool_id, view_indices[k])->occupancy + kDrawChunk - 1) / kDrawChunk;
     // the host's upper bound of the INSTANCES: a view draws a slot at most once
@@ -413,20 +430,11 @@ int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* vi
     launch.first_instance = I.d_first.ptr;
     launch.local = I.d_local.ptr;
     launch.chunk_total = I.d_chunk_total.ptr;
-    launch.counts = counted ? K.d_counts.ptr : nullptr;
+    launch.counts = counted ? K.d_column.ptr : nullptr;
     launch.index_at = I.index_at;
-    covered += I.index_at != GV_NONE ? 4 : 0;
     launch.base.staged = covered == L.stride && L.stride <= kMaxStagedInstanceStride;
     GV_HIP(ctx, launch_draw_instances(launch, ctx->stream));
-    I.target = launch.base.dst;
-    I.capacity = launch.base.capacity;
-    I.views = view_count;
-    std::copy(view_indices, view_indices + view_count, I.listed);
-    p.commands.views = 0;  // commands belong to the emission in front of them
-    I.emitted = L;
-    I.note_payload(places);
-    I.emitted_index = I.index_at;
-    I.draws = true;
+    note_emission(p, launch.base, view_indices, view_count, with_payload, I.index_at, true);
     return GV_OK;
 }
 
@@ -472,10 +480,8 @@ int gv_pool_draw_bases_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* first_insta
                          "(gv_pool_emit_draw_instances)", pool_id);
     if (starts_capacity < I.views + 1)
         return ctx->fail(GV_E_ARG, "gv_pool_draw_bases_fetch: room for %u starts, the emission listed %u views", starts_capacity, I.views);
-    GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, I.h_starts.reserve(GV_MAX_VIEWS + 1));
-    GV_HIP(ctx, hipMemcpyAsync(I.h_starts.ptr, I.d_draw_starts.ptr, (I.views + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = fetch_starts(ctx, I, I.d_draw_starts.ptr, I.views + 1))
+        return rc;
     const uint32_t draws = I.h_starts.ptr[I.views];
     if (first_instance && capacity < (uint64_t)draws + 1)
         return ctx->fail(GV_E_ARG, "gv_pool_draw_bases_fetch: room for %u words, %u draws and the closing total", capacity, draws);
@@ -532,10 +538,8 @@ int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t
         return ctx->fail(GV_E_STATE, "gv_pool_instances_fetch: pool %u has no instance data since its last gv_cull", pool_id);
     if (starts_capacity < I.views + 1)
         return ctx->fail(GV_E_ARG, "gv_pool_instances_fetch: room for %u starts, the emission listed %u views", starts_capacity, I.views);
-    GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, I.h_starts.reserve(GV_MAX_VIEWS + 1));
-    GV_HIP(ctx, hipMemcpyAsync(I.h_starts.ptr, I.d_starts.ptr, (I.views + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = fetch_starts(ctx, I, I.d_starts.ptr, I.views + 1))
+        return rc;
     const uint32_t total = I.h_starts.ptr[I.views];
     const GvInstanceLayout L = I.emitted;
     if (dst_host && bytes < (size_t)total * L.stride)
@@ -549,12 +553,8 @@ int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t
     GV_HIP(ctx, I.h_data.reserve((size_t)held * L.stride));
     GV_HIP(ctx, hipMemcpyAsync(I.h_data.ptr, I.target, (size_t)held * L.stride, hipMemcpyDeviceToHost, ctx->stream));
     GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    Field f[4 + GV_MAX_PAYLOAD_FIELDS + 1];
-    uint32_t n = fields_of(L, f);
-    for (uint32_t k = 0; k < I.emitted_payload; k++)  // the payload fields the emission wrote
-        f[n++] = Field{I.emitted_at[k], I.emitted_bytes[k], 4};
-    if (I.emitted_index != GV_NONE)  // ... and the index field of a draw emission
-        f[n++] = Field{I.emitted_index, 4, 4};
+    Field f[kMaxFields];  // the layout's, the payload fields the emission wrote, the index field of a draw emission
+    const uint32_t n = instance_fields(L, I.emitted_payload, I.emitted_at, I.emitted_bytes, I.emitted_index, f);
     uint8_t* const to = static_cast<uint8_t*>(dst_host);
     const uint8_t* const from = I.h_data.ptr;
     parallel_ranges(0, held, [&](uint32_t a, uint32_t b) {

@@ -229,7 +229,6 @@ __global__ __launch_bounds__(kInstanceBlock) void draw_counts_kernel(const DrawI
     constexpr uint32_t kRounds = kDrawChunk / kInstanceBlock;
     static_assert(kRounds * (kInstanceBlock / 64u) == 64u, "wave 0 scans one (round, wave) total per lane");
     __shared__ uint32_t part[64];
-    __shared__ uint32_t chunk_sum;
     const uint32_t v = view_of_block(a.first_chunk, a.base.views, blockIdx.x);
     const InstanceView& vw = a.base.view[v];
     const uint32_t n = *vw.count;
@@ -255,14 +254,7 @@ __global__ __launch_bounds__(kInstanceBlock) void draw_counts_kernel(const DrawI
         if (lane == 63u)
             part[r * (kInstanceBlock / 64u) + wave] = inc[r];
     }
-    __syncthreads();
-    if (wave == 0) {
-        const uint32_t own = part[lane], upto = wave_inclusive_scan(own, lane);
-        part[lane] = upto - own;
-        if (lane == 63u)
-            chunk_sum = upto;
-    }
-    __syncthreads();
+    const uint32_t chunk_sum = chunk_scan_tail(part, lane, wave);
     uint32_t* const local = a.local + (size_t)a.base.first_block[v] * kInstanceBlock;
 #pragma unroll
     for (uint32_t r = 0; r < kRounds; r++) {
@@ -520,23 +512,6 @@ hipError_t launch_draw_instances(const DrawInstanceLaunch& launch, hipStream_t s
         hipLaunchKernelGGL(draw_counts_kernel, dim3(launch.first_chunk[launch.base.views]), block, 0, stream, launch);
     hipLaunchKernelGGL(draw_instances_kernel, dim3(std::max(1u, launch.base.first_block[launch.base.views])), block,
                        draw_image_bytes(launch.base.staged, launch.base.stride) + kDrawLdsTail, stream, launch);
-    return hipGetLastError();
-}
-
-namespace {
-__global__ __launch_bounds__(256) void scatter_counts_kernel(const uint32_t* __restrict__ packet, const uint32_t* __restrict__ slots, uint32_t count,
-                                                             uint32_t* __restrict__ counts)
-{
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < count)
-        counts[slots[t]] = packet[t];
-}
-}  // namespace
-
-hipError_t launch_scatter_counts(const uint32_t* packet, const uint32_t* slots, uint32_t count, uint32_t* counts, hipStream_t stream)
-{
-    if (count)
-        hipLaunchKernelGGL(scatter_counts_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, packet, slots, count, counts);
     return hipGetLastError();
 }
 

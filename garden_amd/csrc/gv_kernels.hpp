@@ -249,8 +249,6 @@ inline __host__ __device__ uint32_t draw_image_bytes(uint32_t staged, uint32_t s
     return kInstanceBlock * (staged ? stride : kDirectImagePieces * 16u);
 }
 hipError_t launch_draw_instances(const DrawInstanceLaunch& launch, hipStream_t stream);
-// the small dirty ranges of a pool's count mirror: counts[slots[t]] = packet[t]
-hipError_t launch_scatter_counts(const uint32_t* packet, const uint32_t* slots, uint32_t count, uint32_t* counts, hipStream_t stream);
 // gv_pool_emit_draw_commands (gv_commands.hip): one indirect command per draw of the pool's last emission E — or, merged, per run
 // of consecutive draws of one geometry id — in the caller's command struct. Per-draw mode: ONE launch
 // (command_kernel). Run mode: command_heads_kernel (head flags + chunk-local head ranks per chunk of kDrawChunk draws, one head

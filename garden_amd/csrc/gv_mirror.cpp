@@ -602,27 +602,6 @@ int upload_meshes(GvCtx* ctx, PoolState& p, uint32_t lo, uint32_t hi)
     return GV_OK;
 }
 
-// The pinned staging arrays and packet buffers are read by asynchronous copies: before the host rewrites them it waits for the
-// copies of the previous sync — an event recorded behind them — not for the whole stream: the previous frame's cull and emit, queued
-// behind those copies, may still be running (a scene in which something moves every frame would otherwise run host and device one
-// after the other: 0.20 instead of 0.12 ms per frame at 10 M entities with ten movers, tools/moving_bench.py).
-int wait_uploads(GvCtx* ctx)
-{
-    if (ctx->upload_pending) {
-        GV_HIP(ctx, hipEventSynchronize(ctx->upload_done));
-        ctx->upload_pending = false;
-    }
-    return GV_OK;
-}
-int record_uploads(GvCtx* ctx)
-{
-    if (!ctx->upload_done)
-        GV_HIP(ctx, hipEventCreateWithFlags(&ctx->upload_done, hipEventDisableTiming));
-    GV_HIP(ctx, hipEventRecord(ctx->upload_done, ctx->stream));
-    ctx->upload_pending = true;
-    return GV_OK;
-}
-
 // Dirty pool slots of a permuted mirror land on scattered entries: ALL the dirty ranges of a sync travel as one packet — one
 // copy, one launch (scatter_xf_packets_kernel: records, world-cache dirty bytes, active bits, block flags), one event.
 constexpr size_t kRangedCopyMaxRanges = 32;  // dirty ranges of a slot-order mirror sent as plain copies; more go as one scattered packet
@@ -637,7 +616,8 @@ int reserve_packets(GvCtx* ctx, PinnedBuf<Packet>& host, DeviceBuf<Packet>& dev,
         GV_HIP(ctx, host.reserve(want));
         GV_HIP(ctx, dev.reserve(want));
     }
-    return wait_uploads(ctx);  // the previous packet's copy has read the pinned buffer
+    GV_HIP(ctx, ctx->uploads.wait());  // the previous packet's copy has read the pinned buffer
+    return GV_OK;
 }
 
 int upload_transforms_scattered(GvCtx* ctx, const std::vector<DirtyRanges::R>& ranges, const BlockFlagTargets& blocks)
@@ -669,8 +649,7 @@ int upload_transforms_scattered(GvCtx* ctx, const std::vector<DirtyRanges::R>& r
     GV_HIP(ctx, hipMemcpyAsync(ctx->dsc_xf.ptr, ctx->sc_xf.ptr, (size_t)n * sizeof(XfPacket), hipMemcpyHostToDevice, ctx->stream));
     GV_HIP(ctx, launch_scatter_xf_packets(ctx->dsc_xf.ptr, n, ctx->d_xab.ptr, ctx->d_xc.ptr, ctx->d_xflags.ptr, ctx->d_xparent.ptr, ctx->d_xactive.ptr,
                                           track_world_dirty(ctx) ? ctx->d_xdirty.ptr : nullptr, blocks, ctx->stream));
-    if (int rc = record_uploads(ctx))  // the packet buffer is reused by the next sync: it waits for this
-        return rc;
+    GV_HIP(ctx, ctx->uploads.record(ctx->stream));  // the packet buffer is reused by the next sync: it waits for this
     ctx->stats.upload_bytes += (size_t)n * sizeof(XfPacket);
     return GV_OK;
 }
@@ -701,8 +680,7 @@ int upload_meshes_scattered(GvCtx* ctx, PoolState& p, const std::vector<DirtyRan
     }
     GV_HIP(ctx, hipMemcpyAsync(ctx->dsc_mesh.ptr, ctx->sc_mesh.ptr, (size_t)n * sizeof(MeshPacket), hipMemcpyHostToDevice, ctx->stream));
     GV_HIP(ctx, launch_scatter_mesh_packets(ctx->dsc_mesh.ptr, n, p.d_a.ptr, p.d_b.ptr, p.d_link.ptr, block_flags, ctx->stream));
-    if (int rc = record_uploads(ctx))
-        return rc;
+    GV_HIP(ctx, ctx->uploads.record(ctx->stream));
     ctx->stats.upload_bytes += (size_t)n * sizeof(MeshPacket);
     return GV_OK;
 }
@@ -1037,8 +1015,7 @@ int mark_dirty_blocks(GvCtx* ctx, PoolState& p, const std::vector<DirtyRanges::R
         GV_HIP(ctx, ctx->h_ranges.reserve(std::max<size_t>(2 * (size_t)nr + 1, 1024)));
         GV_HIP(ctx, ctx->d_ranges.reserve(std::max<size_t>(2 * (size_t)nr + 1, 1024)));
     }
-    if (int rc = wait_uploads(ctx))  // (an earlier call's copy may still be reading the pinned words)
-        return rc;
+    GV_HIP(ctx, ctx->uploads.wait());  // (an earlier call's copy may still be reading the pinned words)
     uint32_t* start = ctx->h_ranges.ptr;
     uint32_t* first = start + nr + 1;
     uint32_t total = 0;
@@ -1050,7 +1027,8 @@ int mark_dirty_blocks(GvCtx* ctx, PoolState& p, const std::vector<DirtyRanges::R
     start[nr] = total;
     GV_HIP(ctx, hipMemcpyAsync(ctx->d_ranges.ptr, ctx->h_ranges.ptr, (2 * (size_t)nr + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     GV_HIP(ctx, launch_mark_dirty_blocks(ctx->d_ranges.ptr, ctx->d_ranges.ptr + nr + 1, nr, total, inv, slots, p.occupancy, p.d_blk_dirty.ptr, ctx->stream));
-    return record_uploads(ctx);
+    GV_HIP(ctx, ctx->uploads.record(ctx->stream));
+    return GV_OK;
 }
 
 // ---- the steps of sync_mirror -----------------------------------------------------------------------------------------
@@ -1061,8 +1039,8 @@ static_assert(kPairedGeneral == kMapGeneral && kPairedSpeculate == kMapSpeculate
 
 struct SyncPass {  // what one pass of sync_mirror hands from step to step
     PhaseTimer phase;
-    bool staged = false;   // the pinned staging arrays were rewritten (behind a drained stream or wait_uploads): the copies queued from
-                           // them get ONE record_uploads behind them all, which the next sync waits for
+    bool staged = false;   // the pinned staging arrays were rewritten (behind a drained stream or ctx->uploads.wait()): the copies queued from
+                           // them get ONE ctx->uploads.record() behind them all, which the next sync waits for
     bool spatial = true;   // the mirror is kept in spatial order (no GV_CONFIG_KEEP_SLOT_ORDER)
 };
 
@@ -1233,8 +1211,7 @@ int after_transform_upload(GvCtx* ctx, bool dense)
 // GV_DIRTY_TRANSFORM marks: the dirty slots are gathered and uploaded, dense or itemised, and the blocks they sit in flagged
 int remirror_dirty_transforms(GvCtx* ctx, SyncPass& pass)
 {
-    if (int rc = wait_uploads(ctx))  // (staging is about to be rewritten: the copies that read it have to be through)
-        return rc;
+    GV_HIP(ctx, ctx->uploads.wait());  // (staging is about to be rewritten: the copies that read it have to be through)
     pass.staged = true;
     const uint32_t n = ctx->xf.occupancy;
     ctx->xf_dirty.normalise(n, 0);  // exact: a re-mirrored slot is a flagged slot (its whole subtree is re-swept)
@@ -1369,8 +1346,7 @@ int flag_dirty_mesh_blocks(GvCtx* ctx, PoolState& p, const std::vector<DirtyRang
 // (upload_meshes_device says when it applies), the rest goes through the host staging
 int remirror_dirty_meshes(GvCtx* ctx, PoolState& p, SyncPass& pass)
 {
-    if (int rc = wait_uploads(ctx))
-        return rc;
+    GV_HIP(ctx, ctx->uploads.wait());
     pass.staged = true;
     p.dirty.normalise(p.occupancy, 0);
     const std::vector<DirtyRanges::R> ranges = p.dirty.items;
@@ -1446,42 +1422,74 @@ int reorder_mirror(GvCtx* ctx, bool reorder_xf, const bool* reorder_pool, PhaseT
 
 }  // namespace
 
-// The payload rows of a pool (gv_pool_bind_payload): slots appended since the last upload plus the pool's payload dirty set, gathered
-// from the bound fields into packed rows. Ranges of kPayloadCopyMinRows rows or more travel as contiguous copies into their place;
-// everything smaller travels the way small mirror edits do: ONE packet [rows | slots] and ONE scatter launch.
-constexpr uint32_t kPayloadCopyMinRows = 2048;
+// One upload path for the per-slot side columns (SlotMirror: payload rows, ready counts, geometry ids): the slots appended since the
+// last upload plus the mirror's dirty set. gather(dst, lo, hi) fills the hi - lo elements of slots [lo, hi). Ranges of
+// kDeviceGatherMinSlots slots or more travel as contiguous copies into their place; everything smaller travels the way small mirror
+// edits do: ONE packet [elements | slots] and ONE scatter launch. `fence` guards the staging. Sizes are counted in T, as the buffers are.
+template <typename T, typename Gather>
+int upload_slot_mirror(GvCtx* ctx, SlotMirror<T>& M, uint32_t occupancy, UploadFence& fence, Gather gather)
+{
+    M.dirty.normalise(M.mirrored, 0);  // (elements at or beyond `mirrored` are uploaded as new ones below)
+    std::vector<DirtyRanges::R> ranges = M.dirty.items;
+    if (M.mirrored < occupancy)
+        ranges.push_back({M.mirrored, occupancy});
+    M.dirty.clear();
+    if (ranges.empty())
+        return GV_OK;
+    const uint32_t kept = M.mirrored;
+    M.mirrored = 0;  // (a failure below leaves the column unknown: the next upload takes everything)
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t elem = M.elem / sizeof(T), slot = 4 / sizeof(T);  // an element and a packet's slot word, in T
+    GV_HIP(ctx, M.d_column.grow(occupancy * elem, kept * elem, ctx->stream));
+    size_t copied = 0, packed = 0;  // elements that travel as copies / in the packet
+    for (const auto& r : ranges)
+        (r.hi - r.lo >= kDeviceGatherMinSlots ? copied : packed) += r.hi - r.lo;
+    const size_t stage_size = (copied + packed) * elem + packed * slot, packet_size = packed * (elem + slot);
+    if (stage_size > M.h_stage.cap || packet_size > M.d_packet.cap) {  // (buffers about to be replaced: nothing queued may still use them)
+        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GV_HIP(ctx, M.h_stage.reserve(std::max(stage_size + stage_size / 2, 4096 / sizeof(T))));
+        GV_HIP(ctx, M.d_packet.reserve(std::max(packet_size + packet_size / 2, 4096 / sizeof(T))));
+    }
+    GV_HIP(ctx, fence.wait());  // the previous upload's copies have read the staging
+    T* const stage = M.h_stage.ptr;
+    T* const packet = stage + copied * elem;
+    uint32_t* const packet_slots = reinterpret_cast<uint32_t*>(packet + packed * elem);
+    size_t copy_at = 0, pack_at = 0;
+    for (const auto& r : ranges) {
+        const uint32_t n = r.hi - r.lo;
+        if (n >= kDeviceGatherMinSlots) {
+            gather(stage + copy_at * elem, r.lo, r.hi);
+            GV_HIP(ctx, hipMemcpyAsync(M.d_column.ptr + r.lo * elem, stage + copy_at * elem, (size_t)n * M.elem, hipMemcpyHostToDevice, ctx->stream));
+            copy_at += n;
+        } else {
+            gather(packet + pack_at * elem, r.lo, r.hi);
+            for (uint32_t k = 0; k < n; k++)
+                packet_slots[pack_at + k] = r.lo + k;
+            pack_at += n;
+        }
+    }
+    if (packed) {
+        GV_HIP(ctx, hipMemcpyAsync(M.d_packet.ptr, packet, packet_size * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        const uint32_t* const slots = reinterpret_cast<const uint32_t*>(M.d_packet.ptr + packed * elem);
+        if constexpr (sizeof(T) == 1)
+            GV_HIP(ctx, launch_scatter_payload_rows(M.d_packet.ptr, slots, (uint32_t)packed, M.elem, M.d_column.ptr, ctx->stream));
+        else
+            GV_HIP(ctx, launch_scatter_words(M.d_packet.ptr, slots, (uint32_t)packed, M.d_column.ptr, ctx->stream));
+    }
+    GV_HIP(ctx, fence.record(ctx->stream));  // the staging is reused by the next upload: it waits for this
+    ctx->stats.upload_bytes += stage_size * sizeof(T);
+    M.mirrored = occupancy;
+    return GV_OK;
+}
+
+// The payload rows of a pool (gv_pool_bind_payload), gathered from the bound fields into packed rows.
 int upload_payload(GvCtx* ctx, PoolState& p)
 {
     PoolState::Payload& P = p.payload;
     if (!P.count)
         return GV_OK;
-    P.dirty.normalise(P.mirrored, 0);  // (rows at or beyond `mirrored` are uploaded as new ones below)
-    std::vector<DirtyRanges::R> ranges = P.dirty.items;
-    if (P.mirrored < P.occupancy)
-        ranges.push_back({P.mirrored, P.occupancy});
-    P.dirty.clear();
-    if (ranges.empty())
-        return GV_OK;
-    const uint32_t kept = P.mirrored;
-    P.mirrored = 0;  // (a failure below leaves the rows unknown: the next upload takes everything)
-    GV_HIP(ctx, hipSetDevice(ctx->device));
     const size_t pitch = P.pitch;
-    GV_HIP(ctx, P.d_rows.grow((size_t)P.occupancy * pitch, (size_t)kept * pitch, ctx->stream));
-    size_t copied = 0, packed = 0;  // rows that travel as copies / in the packet
-    for (const auto& r : ranges)
-        (r.hi - r.lo >= kPayloadCopyMinRows ? copied : packed) += r.hi - r.lo;
-    const size_t stage_bytes = (copied + packed) * pitch + packed * 4, packet_bytes = packed * (pitch + 4);
-    if (stage_bytes > P.h_stage.cap || packet_bytes > P.d_packet.cap) {  // (buffers about to be replaced: nothing queued may still use them)
-        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        GV_HIP(ctx, P.h_stage.reserve(std::max<size_t>(stage_bytes + stage_bytes / 2, 4096)));
-        GV_HIP(ctx, P.d_packet.reserve(std::max<size_t>(packet_bytes + packet_bytes / 2, 4096)));
-    }
-    if (int rc = wait_uploads(ctx))  // the previous upload's copies have read the staging
-        return rc;
-    uint8_t* const stage = P.h_stage.ptr;
-    uint8_t* const packet_rows = stage + copied * pitch;
-    uint32_t* const packet_slots = reinterpret_cast<uint32_t*>(packet_rows + packed * pitch);
-    auto gather = [&](uint8_t* rows, uint32_t* slots, uint32_t lo, uint32_t hi) {
+    return upload_slot_mirror(ctx, P, P.occupancy, ctx->uploads, [&](uint8_t* rows, uint32_t lo, uint32_t hi) {
         parallel_ranges(0, hi - lo, [&](uint32_t a, uint32_t b) {
             for (uint32_t k = a; k < b; k++) {
                 uint8_t* row = rows + (size_t)k * pitch;
@@ -1491,82 +1499,29 @@ int upload_payload(GvCtx* ctx, PoolState& p)
                     end = P.offset[f] + P.bytes[f];
                 }
                 memset(row + end, 0, pitch - end);
-                if (slots)
-                    slots[k] = lo + k;
             }
         });
-    };
-    size_t copy_at = 0, pack_at = 0;
-    for (const auto& r : ranges) {
-        const uint32_t n = r.hi - r.lo;
-        if (n >= kPayloadCopyMinRows) {
-            gather(stage + copy_at * pitch, nullptr, r.lo, r.hi);
-            GV_HIP(ctx, hipMemcpyAsync(P.d_rows.ptr + (size_t)r.lo * pitch, stage + copy_at * pitch, (size_t)n * pitch, hipMemcpyHostToDevice, ctx->stream));
-            copy_at += n;
-        } else {
-            gather(packet_rows + pack_at * pitch, packet_slots + pack_at, r.lo, r.hi);
-            pack_at += n;
-        }
-    }
-    if (packed) {
-        GV_HIP(ctx, hipMemcpyAsync(P.d_packet.ptr, packet_rows, packet_bytes, hipMemcpyHostToDevice, ctx->stream));
-        GV_HIP(ctx, launch_scatter_payload_rows(P.d_packet.ptr, reinterpret_cast<const uint32_t*>(P.d_packet.ptr + packed * pitch), (uint32_t)packed,
-                                                (uint32_t)pitch, P.d_rows.ptr, ctx->stream));
-    }
-    if (int rc = record_uploads(ctx))  // the staging is reused by the next upload: it waits for this
-        return rc;
-    ctx->stats.upload_bytes += stage_bytes;
-    P.mirrored = P.occupancy;
-    return GV_OK;
+    });
 }
 
-// The count mirror of a pool (PoolState::Counts): the ready column widened to one uint32 per pool slot — slots appended since the
-// last upload plus the dirty set the pool's GV_DIRTY_MESH marks feed, shaped like upload_payload: ranges of kDeviceGatherMinSlots
-// or more travel as contiguous copies into their place, everything smaller as ONE packet [counts | slots] and ONE scatter launch.
+// The count mirror of a pool (PoolState::Counts): the ready column widened to one uint32 per pool slot, fed by the pool's
+// GV_DIRTY_MESH marks. `held` keeps `sum` exact under partial uploads; `over` lists the counts above the limit.
 int upload_counts(GvCtx* ctx, PoolState& p)
 {
     PoolState::Counts& K = p.counts;
     if (!K.wanted || !p.ready.ptr)
         return GV_OK;
-    const uint32_t occupancy = p.occupancy;
-    if (K.mirrored > occupancy) {  // (the pool shrank: the sum is taken anew)
+    if (K.mirrored > p.occupancy)  // (the pool shrank: the sum is taken anew)
         K.reset();
-    }
-    K.dirty.normalise(K.mirrored, 0);  // (counts at or beyond `mirrored` are uploaded as new ones below)
-    std::vector<DirtyRanges::R> ranges = K.dirty.items;
-    if (K.mirrored < occupancy)
-        ranges.push_back({K.mirrored, occupancy});
-    K.dirty.clear();
-    if (ranges.empty())
-        return GV_OK;
-    const uint32_t kept = K.mirrored;
-    K.mirrored = 0;  // (a failure below leaves the counts unknown: the next upload takes everything)
-    GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, K.d_counts.grow(occupancy, kept, ctx->stream));
+    const uint32_t kept = K.mirrored;  // (0 also after a failed upload: the counts are unknown, everything is taken anew)
     if (!kept) {
         K.sum = 0;
         K.over.clear();
     }
-    K.held.resize(occupancy, 0);
-    size_t copied = 0, packed = 0;
-    for (const auto& r : ranges)
-        (r.hi - r.lo >= kDeviceGatherMinSlots ? copied : packed) += r.hi - r.lo;
-    const size_t stage_words = copied + 2 * packed;
-    if (stage_words > K.h_stage.cap || 2 * packed > K.d_packet.cap) {  // (buffers about to be replaced: nothing queued may still use them)
-        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        GV_HIP(ctx, K.h_stage.reserve(std::max<size_t>(stage_words + stage_words / 2, 1024)));
-        GV_HIP(ctx, K.d_packet.reserve(std::max<size_t>(3 * packed, 1024)));
-    }
-    if (K.staged_pending) {  // the previous upload's copies have read the staging (an event of its own: the context's upload event
-        GV_HIP(ctx, hipEventSynchronize(K.staged));  // may sit behind a payload copy this very call queued behind the frame's cull)
-        K.staged_pending = false;
-    }
-    uint32_t* const stage = K.h_stage.ptr;
-    uint32_t* const packet_counts = stage + copied;
-    uint32_t* const packet_slots = packet_counts + packed;
+    K.held.resize(p.occupancy, 0);
     std::atomic<int64_t> change{0};
     std::mutex over_lock;  // (taken only for a count above the limit, coming or going)
-    auto gather = [&](uint32_t* counts, uint32_t* slots, uint32_t lo, uint32_t hi) {
+    const int rc = upload_slot_mirror(ctx, K, p.occupancy, K.staged, [&](uint32_t* counts, uint32_t lo, uint32_t hi) {
         parallel_ranges(0, hi - lo, [&](uint32_t a, uint32_t b) {
             int64_t delta = 0;
             for (uint32_t k = a; k < b; k++) {
@@ -1581,108 +1536,30 @@ int upload_counts(GvCtx* ctx, PoolState& p)
                         K.over.erase(std::remove(K.over.begin(), K.over.end(), lo + k), K.over.end());
                 }
                 K.held[lo + k] = counts[k] = c;
-                if (slots)
-                    slots[k] = lo + k;
             }
             change += delta;
         });
-    };
-    size_t copy_at = 0, pack_at = 0;
-    for (const auto& r : ranges) {
-        const uint32_t n = r.hi - r.lo;
-        if (n >= kDeviceGatherMinSlots) {
-            gather(stage + copy_at, nullptr, r.lo, r.hi);
-            GV_HIP(ctx, hipMemcpyAsync(K.d_counts.ptr + r.lo, stage + copy_at, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-            copy_at += n;
-        } else {
-            gather(packet_counts + pack_at, packet_slots + pack_at, r.lo, r.hi);
-            pack_at += n;
-        }
-    }
-    if (packed) {
-        GV_HIP(ctx, hipMemcpyAsync(K.d_packet.ptr, packet_counts, 2 * packed * 4, hipMemcpyHostToDevice, ctx->stream));
-        GV_HIP(ctx, launch_scatter_counts(K.d_packet.ptr, K.d_packet.ptr + packed, (uint32_t)packed, K.d_counts.ptr, ctx->stream));
-    }
-    if (!K.staged)
-        GV_HIP(ctx, hipEventCreateWithFlags(&K.staged, hipEventDisableTiming));
-    GV_HIP(ctx, hipEventRecord(K.staged, ctx->stream));  // the staging is reused by the next upload: it waits for this
-    K.staged_pending = true;
-    ctx->stats.upload_bytes += stage_words * 4;
-    K.sum = (uint64_t)((int64_t)K.sum + change.load());
-    K.mirrored = occupancy;
-    return GV_OK;
+    });
+    if (rc == GV_OK)
+        K.sum = (uint64_t)((int64_t)K.sum + change.load());
+    return rc;
 }
 
-// The geometry id mirror of a pool (PoolState::Geometry): the id column widened to one uint32 per pool slot, kept like the count
-// mirror above — slots appended since the last upload plus the dirty set the pool's GV_DIRTY_GEOMETRY / GV_DIRTY_MESH marks feed;
-// ranges of kDeviceGatherMinSlots or more as contiguous copies, the rest as ONE packet [ids | slots] and ONE scatter launch.
+// The geometry id mirror of a pool (PoolState::Geometry): the id column widened to one uint32 per pool slot, fed by the pool's
+// GV_DIRTY_GEOMETRY / GV_DIRTY_MESH marks.
 int upload_geometry(GvCtx* ctx, PoolState& p)
 {
     PoolState::Geometry& G = p.geometry;
     if (!G.wanted || !G.ids.ptr)
         return GV_OK;
-    const uint32_t occupancy = G.occupancy;
-    if (G.mirrored > occupancy)
+    if (G.mirrored > G.occupancy)
         G.reset();
-    G.dirty.normalise(G.mirrored, 0);  // (ids at or beyond `mirrored` are uploaded as new ones below)
-    std::vector<DirtyRanges::R> ranges = G.dirty.items;
-    if (G.mirrored < occupancy)
-        ranges.push_back({G.mirrored, occupancy});
-    G.dirty.clear();
-    if (ranges.empty())
-        return GV_OK;
-    const uint32_t kept = G.mirrored;
-    G.mirrored = 0;  // (a failure below leaves the ids unknown: the next upload takes everything)
-    GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, G.d_ids.grow(occupancy, kept, ctx->stream));
-    size_t copied = 0, packed = 0;
-    for (const auto& r : ranges)
-        (r.hi - r.lo >= kDeviceGatherMinSlots ? copied : packed) += r.hi - r.lo;
-    const size_t stage_words = copied + 2 * packed;
-    if (stage_words > G.h_stage.cap || 2 * packed > G.d_packet.cap) {  // (buffers about to be replaced: nothing queued may still use them)
-        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        GV_HIP(ctx, G.h_stage.reserve(std::max<size_t>(stage_words + stage_words / 2, 1024)));
-        GV_HIP(ctx, G.d_packet.reserve(std::max<size_t>(3 * packed, 1024)));
-    }
-    if (G.staged_pending) {  // the previous upload's copies have read the staging
-        GV_HIP(ctx, hipEventSynchronize(G.staged));
-        G.staged_pending = false;
-    }
-    uint32_t* const stage = G.h_stage.ptr;
-    uint32_t* const packet_ids = stage + copied;
-    uint32_t* const packet_slots = packet_ids + packed;
-    auto gather = [&](uint32_t* ids, uint32_t* slots, uint32_t lo, uint32_t hi) {
+    return upload_slot_mirror(ctx, G, G.occupancy, G.staged, [&](uint32_t* ids, uint32_t lo, uint32_t hi) {
         parallel_ranges(0, hi - lo, [&](uint32_t a, uint32_t b) {
-            for (uint32_t k = a; k < b; k++) {
+            for (uint32_t k = a; k < b; k++)
                 ids[k] = G.id(lo + k);  // (a narrow column is widened here)
-                if (slots)
-                    slots[k] = lo + k;
-            }
         });
-    };
-    size_t copy_at = 0, pack_at = 0;
-    for (const auto& r : ranges) {
-        const uint32_t n = r.hi - r.lo;
-        if (n >= kDeviceGatherMinSlots) {
-            gather(stage + copy_at, nullptr, r.lo, r.hi);
-            GV_HIP(ctx, hipMemcpyAsync(G.d_ids.ptr + r.lo, stage + copy_at, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-            copy_at += n;
-        } else {
-            gather(packet_ids + pack_at, packet_slots + pack_at, r.lo, r.hi);
-            pack_at += n;
-        }
-    }
-    if (packed) {
-        GV_HIP(ctx, hipMemcpyAsync(G.d_packet.ptr, packet_ids, 2 * packed * 4, hipMemcpyHostToDevice, ctx->stream));
-        GV_HIP(ctx, launch_scatter_counts(G.d_packet.ptr, G.d_packet.ptr + packed, (uint32_t)packed, G.d_ids.ptr, ctx->stream));
-    }
-    if (!G.staged)
-        GV_HIP(ctx, hipEventCreateWithFlags(&G.staged, hipEventDisableTiming));
-    GV_HIP(ctx, hipEventRecord(G.staged, ctx->stream));  // the staging is reused by the next upload: it waits for this
-    G.staged_pending = true;
-    ctx->stats.upload_bytes += stage_words * 4;
-    G.mirrored = occupancy;
-    return GV_OK;
+    });
 }
 
 // Brings the device mirror up to date with the bound pools and their dirty marks, one named step after the other (the steps
@@ -1744,8 +1621,7 @@ int sync_mirror(GvCtx* ctx)
         }
     }
     if (pass.staged)  // whatever copies this sync queued from the pinned staging arrays: the next sync waits for them before it rewrites those
-        if (int rc = record_uploads(ctx))
-            return rc;
+        GV_HIP(ctx, ctx->uploads.record(ctx->stream));
     for (auto& p : ctx->pools)  // (staging of their own; no cull reads them)
         if (p.bound && p.payload.count)
             if (int rc = upload_payload(ctx, p))

@@ -248,7 +248,22 @@ __global__ __launch_bounds__(kThreads) void scatter_payload_rows_kernel(const fl
     rows[((size_t)slots[t >> shift] << shift) + (t & ((1u << shift) - 1u))] = packet[t];
 }
 
+__global__ __launch_bounds__(kThreads) void scatter_words_kernel(const uint32_t* __restrict__ packet, const uint32_t* __restrict__ slots, uint32_t count,
+                                                                 uint32_t* __restrict__ column)
+{
+    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
+    if (t < count)
+        column[slots[t]] = packet[t];
+}
+
 }  // namespace
+
+hipError_t launch_scatter_words(const uint32_t* packet, const uint32_t* slots, uint32_t count, uint32_t* column, hipStream_t stream)
+{
+    if (count)
+        hipLaunchKernelGGL(scatter_words_kernel, grid_for(count), dim3(kThreads), 0, stream, packet, slots, count, column);
+    return hipGetLastError();
+}
 
 hipError_t launch_scatter_payload_rows(const uint8_t* packet, const uint32_t* slots, uint32_t count, uint32_t pitch, uint8_t* rows,
                                        hipStream_t stream)

@@ -218,6 +218,8 @@ hipError_t launch_scatter_mesh_packets(const MeshPacket* packets, uint32_t count
 // 64 — back to back) is written to rows + slots[k] * pitch, one lane per 16-byte piece
 hipError_t launch_scatter_payload_rows(const uint8_t* packet, const uint32_t* slots, uint32_t count, uint32_t pitch, uint8_t* rows,
                                        hipStream_t stream);
+// ... and the 4-byte elements of a per-slot column (ready counts, geometry ids): column[slots[k]] = packet[k]
+hipError_t launch_scatter_words(const uint32_t* packet, const uint32_t* slots, uint32_t count, uint32_t* column, hipStream_t stream);
 
 // gv_shard.hip: the visible list of a view as [draw_count | one bit per MIRROR entry]: a copy of the cull kernel's ballot words
 // (or, when `ballots` is NULL, built from the isVisible bytes in mirror order); words >= ceil(entries / 32), the rest is zeroed
