@@ -115,7 +115,10 @@ int gv_pool_emit_draw_commands(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uin
     if (int rc = flush_sorts(ctx))  // the emission is a read: recorded culls and deferred sorts first (as the instance emissions)
         return rc;
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    if (G.ids.ptr) {  // marks made since the cull are seen by this emission; the first call uploads the column
+    // behind a LOD selection (gv_pool_select_lods) the ids are the selected ones, per draw: the id mirror is not read, and marks made
+    // after the selection wait for the next selection, emission without one, or gv_sync
+    const bool selected = p.lod.views != 0;
+    if (G.ids.ptr && !selected) {  // marks made since the cull are seen by this emission; the first call uploads the column
         G.wanted = true;
         if (int rc = upload_geometry(ctx, p))
             return rc;
@@ -143,7 +146,8 @@ int gv_pool_emit_draw_commands(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uin
     launch.first_instance = L.first_instance;
     launch.vertex_offset = L.vertex_offset;
     launch.draw = L.draw;
-    launch.ids = G.ids.ptr ? G.d_column.ptr : nullptr;
+    launch.ids = G.ids.ptr && !selected ? G.d_column.ptr : nullptr;
+    launch.draw_ids = selected ? p.lod.d_draw_geometry.ptr : nullptr;
     launch.table = reinterpret_cast<const CommandGeometry*>(G.d_table.ptr);
     launch.table_count = G.table_count;
     launch.starts = I.d_starts.ptr;

@@ -18,6 +18,10 @@
 //   command_runs_kernel   run mode. One workgroup per 256 draws: adds up its view's chunk totals in front of its chunk; every head
 //                         writes draw_of[rank] = k and first_of[rank] = first_k.
 //
+// Behind a LOD selection (gv_pool_select_lods, CommandLaunch::draw_ids) command_kernel<true> and command_heads_kernel<true> take the
+// id of draw k of view v from draw_ids[D_v + k] (D_v: at most 7 count loads) instead of the slot gather — a coalesced stream; the
+// <false> instantiations are the kernels as they were (same registers, same occupancy: DESIGN.md §5.14).
+//
 // No atomics, no workgroup waits for another, no host read; grids sized from the views' occupancies, workgroups beyond a view's
 // device count leave after one wave-uniform load. Whatever an id holds, the table is read inside [0, table_count) only.
 #include "gv_device.hpp"
@@ -28,12 +32,22 @@ namespace {
 
 __device__ __forceinline__ uint32_t geometry_id(const CommandLaunch& a, uint32_t slot) { return a.ids ? a.ids[slot] : 0u; }
 
+// behind a LOD selection (the kLod instantiations): where the selected ids of view v begin, D_v draws into draw_ids
+__device__ __forceinline__ const uint32_t* draw_ids_of(const CommandLaunch& a, uint32_t v)
+{
+    uint32_t at = 0;
+    for (uint32_t u = 0; u < v; u++)
+        at += *a.view[u].count;
+    return a.draw_ids + at;
+}
+
 // draw k of view v: the first instance the emission gave it
 __device__ __forceinline__ uint32_t first_of_draw(const CommandLaunch& a, uint32_t v, uint32_t k)
 {
     return a.first_instance_of ? a.first_instance_of[a.draw_starts[v] + k] : a.starts[v] + k;
 }
 
+template <bool kLod>
 __global__ __launch_bounds__(kCommandBlock) void command_heads_kernel(const CommandLaunch a)
 {
     constexpr uint32_t kRounds = kDrawChunk / kCommandBlock, kWaves = kCommandBlock / 64u;
@@ -51,17 +65,29 @@ __global__ __launch_bounds__(kCommandBlock) void command_heads_kernel(const Comm
     }
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t id[kRounds];
-#pragma unroll
-    for (uint32_t r = 0; r < kRounds; r++) {
-        const uint32_t k = first + r * kCommandBlock + threadIdx.x;
-        id[r] = k < n ? stream_load(vw.idx + k) : kNoField;  // (the slot, for now)
-    }
     uint32_t before = 0;  // the id of the draw in front of the chunk
-    if (threadIdx.x == 0 && first > 0)
-        before = geometry_id(a, vw.idx[first - 1]);
+    if constexpr (kLod) {  // the selected ids, draw-indexed: no gather
+        const uint32_t* const ids = draw_ids_of(a, v);
+#pragma unroll
+        for (uint32_t r = 0; r < kRounds; r++) {
+            const uint32_t k = first + r * kCommandBlock + threadIdx.x;
+            id[r] = k < n ? stream_load(ids + k) : 0u;
+        }
+        if (threadIdx.x == 0 && first > 0)
+            before = ids[first - 1];
+    } else {
+#pragma unroll
+        for (uint32_t r = 0; r < kRounds; r++) {
+            const uint32_t k = first + r * kCommandBlock + threadIdx.x;
+            id[r] = k < n ? stream_load(vw.idx + k) : kNoField;  // (the slot, for now)
+        }
+        if (threadIdx.x == 0 && first > 0)
+            before = geometry_id(a, vw.idx[first - 1]);
+    }
 #pragma unroll
     for (uint32_t r = 0; r < kRounds; r++) {
-        id[r] = id[r] == kNoField ? 0u : geometry_id(a, id[r]);
+        if constexpr (!kLod)
+            id[r] = id[r] == kNoField ? 0u : geometry_id(a, id[r]);
         if (lane == 63u)
             tail[r * kWaves + wave] = id[r];
     }
@@ -113,6 +139,7 @@ __global__ __launch_bounds__(kCommandBlock) void command_runs_kernel(const Comma
     }
 }
 
+template <bool kLod>
 __global__ __launch_bounds__(kCommandBlock) void command_kernel(const CommandLaunch a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t image[kCommandBlock * kMaxCommandStride / 4u];
@@ -150,6 +177,9 @@ __global__ __launch_bounds__(kCommandBlock) void command_kernel(const CommandLau
         return;  // (nothing of it fits)
     const uint32_t here = min(min(kCommandBlock, (region ? region : commands) - first), a.capacity - at);
     const uint32_t words = a.stride / 4u;
+    [[maybe_unused]] const uint32_t* ids_of_view = nullptr;
+    if constexpr (kLod)
+        ids_of_view = draw_ids_of(a, v);
     if (threadIdx.x < here) {
         uint32_t* const mine = image + threadIdx.x * words;
         for (uint32_t w = 0; w < words; w++)
@@ -166,7 +196,11 @@ __global__ __launch_bounds__(kCommandBlock) void command_kernel(const CommandLau
                 from = first_of_draw(a, v, k);
                 next = k + 1u < n ? first_of_draw(a, v, k + 1u) : a.starts[v + 1];
             }
-            const uint32_t id = geometry_id(a, a.view[v].idx[k]);
+            uint32_t id;
+            if constexpr (kLod)
+                id = ids_of_view[k];
+            else
+                id = geometry_id(a, a.view[v].idx[k]);
             const bool known = id < a.table_count;
             CommandGeometry g{0u, 0u, 0};
             if (known)
@@ -202,7 +236,10 @@ __global__ __launch_bounds__(kCommandBlock) void command_kernel(const CommandLau
 
 hipError_t launch_command_heads(const CommandLaunch& launch, hipStream_t stream)
 {
-    hipLaunchKernelGGL(command_heads_kernel, dim3(launch.first_chunk[launch.views]), dim3(kCommandBlock), 0, stream, launch);
+    if (launch.draw_ids)
+        hipLaunchKernelGGL(command_heads_kernel<true>, dim3(launch.first_chunk[launch.views]), dim3(kCommandBlock), 0, stream, launch);
+    else
+        hipLaunchKernelGGL(command_heads_kernel<false>, dim3(launch.first_chunk[launch.views]), dim3(kCommandBlock), 0, stream, launch);
     return hipGetLastError();
 }
 
@@ -214,7 +251,11 @@ hipError_t launch_command_runs(const CommandLaunch& launch, hipStream_t stream)
 
 hipError_t launch_commands(const CommandLaunch& launch, hipStream_t stream)
 {
-    hipLaunchKernelGGL(command_kernel, dim3(std::max(1u, launch.first_block[launch.views])), dim3(kCommandBlock), 0, stream, launch);
+    const dim3 grid(std::max(1u, launch.first_block[launch.views]));
+    if (launch.draw_ids)
+        hipLaunchKernelGGL(command_kernel<true>, grid, dim3(kCommandBlock), 0, stream, launch);
+    else
+        hipLaunchKernelGGL(command_kernel<false>, grid, dim3(kCommandBlock), 0, stream, launch);
     return hipGetLastError();
 }
 

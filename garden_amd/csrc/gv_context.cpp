@@ -704,6 +704,8 @@ void gv_destroy(GvCtx* ctx)
         p.geometry.release(); p.geometry.d_table.release(); p.geometry.staged.destroy();
         p.commands.d_data.release(); p.commands.d_counts.release(); p.commands.d_rank.release(); p.commands.d_chunk_total.release();
         p.commands.d_draw_of.release(); p.commands.d_first_of.release(); p.commands.h_data.release(); p.commands.h_counts.release();
+        p.lod.release(); p.lod.d_table.release(); p.lod.staged.destroy(); p.lod.d_draw_geometry.release(); p.lod.d_level_counts.release();
+        p.lod.h_draw_geometry.release(); p.lod.h_level_counts.release();
     }
     for (auto& per_pool : ctx->views)
       for (auto& v : per_pool) {
@@ -906,6 +908,14 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
             ctx->pools[pool].geometry.dirty.add(first & kSlotMask, count);
         return GV_OK;
     }
+    if (kind == GV_DIRTY_LOD) {  // (... nor the sizes)
+        const uint32_t pool = first >> 28;
+        if (pool >= GV_MAX_POOLS)
+            return ctx->fail(GV_E_ARG, "gv_mark_dirty: pool id %u", pool);
+        if (ctx->pools[pool].lod.wanted)
+            ctx->pools[pool].lod.dirty.add(first & kSlotMask, count);
+        return GV_OK;
+    }
     if (int rc = flush_recorded_culls(ctx, kind == GV_DIRTY_MESH ? std::min(first >> 28, GV_MAX_POOLS - 1u) : GV_MAX_POOLS))
         return rc;
     switch (kind) {
@@ -931,6 +941,8 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
             ctx->pools[pool].counts.dirty.add(lo, count);
         if (ctx->pools[pool].geometry.wanted)  // ... and so may its geometry id
             ctx->pools[pool].geometry.dirty.add(lo, count);
+        if (ctx->pools[pool].lod.wanted)  // ... and its size
+            ctx->pools[pool].lod.dirty.add(lo, count);
         return GV_OK;
     }
     default:
@@ -1014,6 +1026,7 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
     }
     p.instances.views = 0;  // the views' results are replaced from here on: the instance data made from the previous ones ends
     p.commands.views = 0;   // ... and the commands made from that
+    p.lod.views = 0;        // ... and the levels selected for its draws
     for (auto& m : ctx->merges)  // ... and so does every merged array this pool is a member of (gv_merge_sorted)
         if ((m.pools >> pool_id) & 1u)
             m.valid = false;

@@ -220,7 +220,7 @@ struct UploadFence {
 
 // A side column of a pool on the device, one element per POOL SLOT (indexed by visible_idx; a re-order of the mirror does not
 // concern it), kept by upload_slot_mirror (gv_mirror.cpp). T is the unit its buffers are counted in: bytes for the payload rows,
-// words for the counts and the geometry ids (capacities grow by halves of what they were, in that unit).
+// words for the counts, the geometry ids and the LOD sizes (capacities grow by halves of what they were, in that unit).
 template <typename T>
 struct SlotMirror {
     uint32_t elem = sizeof(T);  // bytes of an element: 4 for counts and ids, the pitch for payload rows (set with it at the bind)
@@ -333,6 +333,23 @@ struct PoolState {
         uint32_t capacity = 0;             // command positions the target holds
         uint32_t views = 0, stride = 0, region = 0;
     } commands;
+    // gv_pool_bind_lod / gv_pool_select_lods: the size column as bit patterns, one word per POOL SLOT like the ids above (the mirror
+    // exists only once gv_pool_select_lods has been called for a pool with a size column), the table the base ids index, and the
+    // selection made behind the pool's last instance emission
+    struct Lod : SlotMirror<uint32_t> {  // dirty: GV_DIRTY_LOD and GV_DIRTY_MESH marks of the pool
+        bool bound = false;                // a table is bound (with or without a size column)
+        Column sizes;                      // ptr NULL: none, every slot has size 1
+        uint32_t occupancy = 0;            // slots the column covers
+        uint32_t table_count = 0;
+        DeviceBuf<GvLodGeometry> d_table;  // re-uploaded on every bind
+        bool wanted = false;
+        UploadFence staged;                // guards h_stage (its own: see UploadFence)
+        // the selection (views 0: none since the pool's last gv_cull or instance emission)
+        uint32_t views = 0;
+        DeviceBuf<uint32_t> d_draw_geometry;  // g_k of the listed views' draws, back to back
+        DeviceBuf<uint32_t> d_level_counts;   // [GV_MAX_VIEWS * GV_MAX_LOD_LEVELS]
+        PinnedBuf<uint32_t> h_draw_geometry, h_level_counts;  // staging of gv_pool_lods_fetch
+    } lod;
     // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
     // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
     // transform mirror does not concern it); read by gv_pool_emit_instances only
@@ -729,6 +746,7 @@ int sync_mirror(GvCtx* ctx);
 int upload_payload(GvCtx* ctx, PoolState& p);  // a pool's payload rows likewise (new slots + its own dirty set); sync_mirror calls it too
 int upload_counts(GvCtx* ctx, PoolState& p);   // ... and its count mirror (PoolState::Counts), once gv_pool_emit_draw_instances wants one
 int upload_geometry(GvCtx* ctx, PoolState& p);  // ... and its geometry id mirror (PoolState::Geometry), once gv_pool_emit_draw_commands wants one
+int upload_lod(GvCtx* ctx, PoolState& p);       // ... and its size mirror (PoolState::Lod), once gv_pool_select_lods wants one
 TransformMirror xf_mirror(const GvCtx* ctx);  // the transform mirror as the kernels see it
 MeshMirror mesh_mirror(const PoolState& p);   // a pool's mirror likewise (hot: null; the sphere stream's upkeep in cull_launch sets it)
 

@@ -260,4 +260,29 @@ __device__ __forceinline__ float4 mvp_column(const float (&a)[16], float b0, flo
     return make_float4(o[0], o[1], o[2], o[3]);
 }
 
+// ------------------------------------------------------------------------------------------------
+// level of detail of a draw (the reference carries ModelRenderComponent::lods, model.hpp:29-41, and no rule
+// that picks among them, so the rule is this build's). Test twin: tests/lod_twin.h.
+//   t          the translation of the record's bakedModel as delivered (floats 9, 10, 11): the pivot relative to camera_position
+//   d2         fmaf(tz, tz, fmaf(ty, ty, tx * tx))
+//   x          d2 * view_scale, one multiply
+//   q_i        (size * switch_at[i])^2, two multiplies, for i = 0 .. levels - 2
+//   level      the NUMBER of i with x > q_i: a count, so unsorted thresholds are defined; a comparison with a NaN is false, so a NaN
+//              size, distance or scale gives level 0; an infinite x gives levels - 1 over finite thresholds; a tie keeps the finer level
+// sw: the entry's seven switch_at words, all of them (those at or beyond levels - 1 are masked, never indexed dynamically).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float lod_distance_sq(float tx, float ty, float tz) { return fmaf(tz, tz, fmaf(ty, ty, tx * tx)); }
+
+__device__ __forceinline__ uint32_t lod_level(float x, float size, uint32_t levels, const float (&sw)[7])
+{
+    uint32_t level = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 7u; i++) {
+        const float y = size * sw[i];
+        const float q = y * y;
+        level += (i + 1u < levels && x > q) ? 1u : 0u;
+    }
+    return level;
+}
+
 }  // namespace gv

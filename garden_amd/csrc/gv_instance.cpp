@@ -186,6 +186,7 @@ void note_emission(PoolState& p, const InstanceLaunch& launch, const uint32_t* v
     I.views = view_count;
     std::copy(view_indices, view_indices + view_count, I.listed);
     p.commands.views = 0;  // commands belong to the emission in front of them
+    p.lod.views = 0;       // ... and so do the levels selected for its draws
     I.emitted = I.layout;
     I.emitted_payload = 0;
     for (uint32_t f = 0; with_payload && f < p.payload.count; f++)

@@ -288,10 +288,40 @@ struct CommandLaunch {
     uint8_t* dst;
     uint32_t capacity;                               // command positions dst holds: those at or beyond it are not written
     uint32_t* command_counts;                        // [views], written by workgroup 0 of command_kernel
+    // (last, so that every argument above keeps its offset: the <false> instantiations are the instruction streams they were)
+    const uint32_t* draw_ids;                        // the pool's LOD selection: the id of draw k of view v at D_v + k, D_v the sum of
+                                                     // the draw counts in front (the <true> instantiations read it; NULL: ids it is)
 };
 hipError_t launch_command_heads(const CommandLaunch& launch, hipStream_t stream);  // run mode only, in this order
 hipError_t launch_command_runs(const CommandLaunch& launch, hipStream_t stream);
 hipError_t launch_commands(const CommandLaunch& launch, hipStream_t stream);
+// gv_pool_select_lods (gv_lod.hip): the level of detail of every draw of the pool's last emission, all
+// listed views in ONE launch of the shape of instance_kernel: one lane per draw, grid sized from the occupancies, the counts
+// stay on the device. level_counts is zeroed in front of the launch (integer atomics: the histogram is deterministic).
+constexpr uint32_t kLodBlock = kInstanceBlock;
+constexpr uint32_t kMaxLodLevels = 8;              // GV_MAX_LOD_LEVELS
+struct LodEntry {                                  // GvLodGeometry: two 16-byte pieces
+    uint32_t levels;
+    float switch_at[kMaxLodLevels - 1];
+};
+struct LodView {
+    const uint32_t* count;  // device draw count
+    const uint32_t* idx;    // records in delivery order: POOL slots
+    const float* model;     // ... and their bakedModel, 12 floats each
+    float scale;            // view_scale[v]
+};
+struct LodLaunch {
+    LodView view[kMaxInstanceViews];               // the views of E, in E's order
+    uint32_t first_block[kMaxInstanceViews + 1];   // workgroups in front of view v
+    uint32_t views;
+    const uint32_t* ids;                           // base geometry id per POOL SLOT (NULL: every slot has id 0)
+    const uint32_t* sizes;                         // fp32 bit patterns per POOL SLOT (NULL: every slot has size 1)
+    const LodEntry* table;                         // 32-byte aligned
+    uint32_t table_count;
+    uint32_t* draw_geometry;                       // [sum of the draw counts]
+    uint32_t* level_counts;                        // [views * kMaxLodLevels]
+};
+hipError_t launch_lod(const LodLaunch& launch, hipStream_t stream);
 // read-only pass over the cull kernel's input streams (65 B per entry); gv_debug_stream_peak
 hipError_t launch_stream_probe(const MeshMirror& mesh, const TransformMirror& xf, float* sink, hipStream_t stream);
 // Table-driven tick (gv_cull_batch_begin): the culls of several small pools in one launch, their emits in one launch.

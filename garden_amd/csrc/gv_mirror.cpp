@@ -1422,7 +1422,7 @@ int reorder_mirror(GvCtx* ctx, bool reorder_xf, const bool* reorder_pool, PhaseT
 
 }  // namespace
 
-// One upload path for the per-slot side columns (SlotMirror: payload rows, ready counts, geometry ids): the slots appended since the
+// One upload path for the per-slot side columns (SlotMirror: payload rows, ready counts, geometry ids, LOD sizes): the slots appended since the
 // last upload plus the mirror's dirty set. gather(dst, lo, hi) fills the hi - lo elements of slots [lo, hi). Ranges of
 // kDeviceGatherMinSlots slots or more travel as contiguous copies into their place; everything smaller travels the way small mirror
 // edits do: ONE packet [elements | slots] and ONE scatter launch. `fence` guards the staging. Sizes are counted in T, as the buffers are.
@@ -1562,6 +1562,23 @@ int upload_geometry(GvCtx* ctx, PoolState& p)
     });
 }
 
+// The size mirror of a pool (PoolState::Lod): the fp32 size column as bit patterns, one word per pool slot, fed by the pool's
+// GV_DIRTY_LOD / GV_DIRTY_MESH marks.
+int upload_lod(GvCtx* ctx, PoolState& p)
+{
+    PoolState::Lod& S = p.lod;
+    if (!S.wanted || !S.sizes.ptr)
+        return GV_OK;
+    if (S.mirrored > S.occupancy)
+        S.reset();
+    return upload_slot_mirror(ctx, S, S.occupancy, S.staged, [&](uint32_t* sizes, uint32_t lo, uint32_t hi) {
+        parallel_ranges(0, hi - lo, [&](uint32_t a, uint32_t b) {
+            for (uint32_t k = a; k < b; k++)
+                sizes[k] = S.sizes.u32(lo + k);  // (verbatim: NaN patterns survive)
+        });
+    });
+}
+
 // Brings the device mirror up to date with the bound pools and their dirty marks, one named step after the other (the steps
 // and the state they share: above; the rules that choose among them: gv_dirty_ranges.hpp). A re-order that is due runs last, on
 // the device, behind everything that brought the mirror up to date in its old order.
@@ -1633,6 +1650,10 @@ int sync_mirror(GvCtx* ctx)
     for (auto& p : ctx->pools)
         if (p.bound && p.geometry.wanted)
             if (int rc = upload_geometry(ctx, p))
+                return rc;
+    for (auto& p : ctx->pools)
+        if (p.bound && p.lod.wanted)
+            if (int rc = upload_lod(ctx, p))
                 return rc;
     bool any_reorder = reorder_xf;
     for (bool b : reorder_pool)

@@ -12,6 +12,11 @@
 // library's own buffer; either way they are fetched into host copies (getBase / getShadow) unless setFetch(false) — the library's
 // buffer is reused by the next emission of the pool, so without device targets the host copies are what survives a write().
 //
+// Levels of detail: a system that has declared them (setLods: a size per component and, per BASE geometry, how many consecutive
+// entries of the geometry table are its levels and where they switch) gets a selection (gv_pool_select_lods) in front of each
+// command emission: every draw then takes the entry of its level, chosen per pass on the device from the record's distance
+// (DESIGN.md §4 item 11). setLodScale gives the light pass and the shadow passes their view scales.
+//
 // One context only, like the writer: with ranks no device holds a view's records in draw order — isSupported() is false.
 #pragma once
 #include <algorithm>
@@ -40,6 +45,8 @@ private:
         void *baseDevice = nullptr, *shadowDevice = nullptr;
         size_t baseBytes = 0, shadowBytes = 0;
         uint32_t stride = 0;
+        bool lods = false;     // an LOD table is bound: emit() selects in front of the commands
+        float baseScale = 1.0f, shadowScale = 1.0f;
         Emitted base, shadow;
     } per[GV_MAX_POOLS];
     bool fetch = true;
@@ -67,6 +74,20 @@ public:
     void setGeometry(uint32_t p, const void* ids, uint32_t stride, uint32_t width, uint32_t occupancy, const GvGeometry* table, uint32_t tableCount)
     {
         check(gv_pool_bind_geometry(system->getContext(), p, ids, stride, width, occupancy, table, tableCount), "gv_pool_bind_geometry");
+    }
+    // the levels of detail of mesh system p: the sizes of its components (element i at sizes + i * stride, fp32; NULL: every size is 1)
+    // and the table the BASE geometry ids index (gv_pool_bind_lod; both NULL: no LODs; report size edits with GV_DIRTY_LOD or
+    // GV_DIRTY_MESH). ModelRenderComponent::lods[L] of a model is entry base + L of the geometry table.
+    void setLods(uint32_t p, const void* sizes, uint32_t stride, uint32_t occupancy, const GvLodGeometry* table, uint32_t tableCount)
+    {
+        check(gv_pool_bind_lod(system->getContext(), p, sizes, stride, occupancy, table, tableCount), "gv_pool_bind_lod");
+        of(p).lods = table != nullptr;
+    }
+    // view_scale of the light pass and of every shadow pass (for example (tan(fov / 2) / height)^2, or a quality bias; default 1)
+    void setLodScale(uint32_t p, float baseScale, float shadowScale)
+    {
+        of(p).baseScale = baseScale;
+        of(p).shadowScale = shadowScale;
     }
     // the command struct of mesh system p: see GvCommandLayout
     void setLayout(uint32_t p, const GvCommandLayout& layout)
@@ -98,6 +119,13 @@ public:
         if (!isSupported())
             throw GardenError("GpuDrawCommands: unsupported with several ranks (the merged draw order is made on the host)");
         GvCtx* ctx = system->getContext();
+        if (s.lods) {  // the levels of this emission's draws first: the commands take the selected ids
+            uint32_t listed = 0;
+            float scales[GV_MAX_VIEWS];
+            check(gv_pool_instances_info(ctx, p, &listed, nullptr, nullptr), "gv_pool_instances_info");
+            std::fill(scales, scales + GV_MAX_VIEWS, shadow ? s.shadowScale : s.baseScale);
+            check(gv_pool_select_lods(ctx, p, scales, listed), "gv_pool_select_lods");
+        }
         check(gv_pool_emit_draw_commands(ctx, p, s.flags, s.region, shadow ? s.shadowDevice : s.baseDevice, shadow ? s.shadowBytes : s.baseBytes),
               "gv_pool_emit_draw_commands");
         Emitted& out = shadow ? s.shadow : s.base;

@@ -24,7 +24,7 @@ GV_CONFIG_KEEP_SLOT_ORDER = 4
 GV_CONFIG_BLOCK_BOUNDS = 8
 GV_CONFIG_HIZ_RG16F = 16
 GV_CONFIG_LINEAR_SCAN = 32
-GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY = 0, 1, 2, 3, 4
+GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY, GV_DIRTY_LOD = 0, 1, 2, 3, 4, 5
 GV_MAX_DRAW_INSTANCES = 65535
 GV_MAX_GEOMETRIES = 65536
 GV_COMMANDS_MERGE_RUNS = 1
@@ -117,6 +117,16 @@ class GvGeometry(C.Structure):
 GEOMETRY_DTYPE = np.dtype([("count", np.uint32), ("first", np.uint32), ("vertex_offset", np.int32)])
 
 
+GV_MAX_LOD_LEVELS = 8
+
+
+class GvLodGeometry(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("switch_at", C.c_float * (GV_MAX_LOD_LEVELS - 1))]
+
+
+LOD_DTYPE = np.dtype([("levels", np.uint32), ("switch_at", np.float32, (GV_MAX_LOD_LEVELS - 1,))])
+
+
 class GvCommandLayout(C.Structure):
     _fields_ = [("stride", C.c_uint32), ("count", C.c_uint32), ("instance_count", C.c_uint32), ("first", C.c_uint32),
                 ("first_instance", C.c_uint32), ("vertex_offset", C.c_uint32), ("draw", C.c_uint32)]
@@ -195,6 +205,7 @@ EXPORTS = [
     "gv_merge_sorted", "gv_merge_device", "gv_merge_fetch",
     "gv_pool_bind_geometry", "gv_pool_set_command_layout", "gv_pool_emit_draw_commands", "gv_pool_draw_commands_device",
     "gv_pool_draw_commands_fetch",
+    "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
 ]
 
 _lib = None
@@ -324,6 +335,10 @@ def load():
     lib.gv_pool_emit_draw_commands.argtypes = [P, u32, u32, u32, P, sz]
     lib.gv_pool_draw_commands_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_draw_commands_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
+    lib.gv_pool_bind_lod.argtypes = [P, u32, P, u32, u32, C.POINTER(GvLodGeometry), u32]
+    lib.gv_pool_select_lods.argtypes = [P, u32, C.POINTER(C.c_float), u32]
+    lib.gv_pool_lods_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_pool_lods_fetch.argtypes = [P, u32, C.POINTER(u32), u32, C.POINTER(u32), u32]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -437,7 +452,7 @@ class GpuVisibility:
         self._check(self.lib.gv_pool_bind_ready(self.ctx, pool_id, ready.ctypes.data, ready.strides[0], ready.dtype.itemsize))
 
     def mark_dirty(self, kind, first, count, pool_id=0):
-        if kind in (GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY):
+        if kind in (GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY, GV_DIRTY_LOD):
             first |= pool_id << 28
         self._check(self.lib.gv_mark_dirty(self.ctx, kind, first, count))
 
@@ -879,6 +894,59 @@ class GpuVisibility:
         if dtype is not None:
             out = out.reshape(-1).view(np.uint8)[:positions * stride].view(np.dtype(dtype))
         return out, counts
+
+    # ---- level of detail per draw ----
+    def bind_lod(self, pool_id, sizes, table):
+        """gv_pool_bind_lod: the pool's sizes (numpy float32 array, one element per slot, any element stride; None: every slot has
+        size 1) and the LOD table the BASE geometry ids index (a LOD_DTYPE array, or rows of (levels, [switch_at ...]); copied at
+        the call). Both None removes the binding. The caller keeps `sizes` alive and unmoved, as for bind_ready."""
+        if table is None:
+            rows, tp, n = None, None, 0
+        else:
+            if isinstance(table, np.ndarray) and table.dtype == LOD_DTYPE:
+                rows = np.ascontiguousarray(table)
+            else:
+                rows = np.zeros(len(table), LOD_DTYPE)
+                for k, (levels, switch_at) in enumerate(table):
+                    rows[k]["levels"] = levels
+                    rows[k]["switch_at"][:len(switch_at)] = switch_at
+            assert rows.dtype.itemsize == C.sizeof(GvLodGeometry)
+            tp, n = C.cast(rows.ctypes.data, C.POINTER(GvLodGeometry)), len(rows)
+        if sizes is None:
+            self._keep.pop(("lod", pool_id), None)
+            self._check(self.lib.gv_pool_bind_lod(self.ctx, pool_id, None, 0, 0, tp, n))
+            return
+        assert sizes.ndim == 1 and sizes.dtype == np.float32
+        self._keep[("lod", pool_id)] = sizes
+        self._check(self.lib.gv_pool_bind_lod(self.ctx, pool_id, sizes.ctypes.data, sizes.strides[0], sizes.shape[0], tp, n))
+
+    def select_lods(self, pool_id, view_scale):
+        """gv_pool_select_lods: the level of detail of every draw of the pool's last instance emission, on the context's stream;
+        view_scale: one float per listed view. None drops the selection. A command emission that follows takes the selected ids."""
+        if view_scale is None:
+            self._check(self.lib.gv_pool_select_lods(self.ctx, pool_id, None, 0))
+            return
+        scale = np.ascontiguousarray(view_scale, dtype=np.float32).reshape(-1)
+        self._check(self.lib.gv_pool_select_lods(self.ctx, pool_id, scale.ctypes.data_as(C.POINTER(C.c_float)), len(scale)))
+
+    def lods_device(self, pool_id):
+        """(device pointer of uint32 draw_geometry[draws], device pointer of uint32 level_counts[views * 8]) of the pool's selection"""
+        ids, counts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_pool_lods_device(self.ctx, pool_id, C.byref(ids), C.byref(counts)))
+        return ids.value, counts.value
+
+    def lods(self, pool_id):
+        """gv_pool_lods_fetch: waits for the pool's selection; returns (the selected geometry ids g_k as one uint32 array per listed
+        view, level_counts as uint32 [views, 8])."""
+        views = self.instances_info(pool_id)[0]
+        counts = np.zeros(views * GV_MAX_LOD_LEVELS, np.uint32)
+        cp = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self.lib.gv_pool_lods_fetch(self.ctx, pool_id, None, 0, cp, len(counts)))
+        ids = np.zeros(max(int(counts.sum()), 1), np.uint32)
+        self._check(self.lib.gv_pool_lods_fetch(self.ctx, pool_id, ids.ctypes.data_as(C.POINTER(C.c_uint32)), len(ids), cp, len(counts)))
+        counts = counts.reshape(views, GV_MAX_LOD_LEVELS)
+        ends = np.cumsum(counts.sum(axis=1, dtype=np.int64))
+        return [ids[int(e - c):int(e)].copy() for e, c in zip(ends, counts.sum(axis=1, dtype=np.int64))], counts
 
     # ---- the shared sorted arrays ----
     @staticmethod

@@ -178,8 +178,10 @@ typedef enum GvDirtyKind {
     GV_DIRTY_MESH = 2,      /* mesh slots changed; pool id in the top 4 bits of `first` */
     GV_DIRTY_PAYLOAD = 3,   /* the bound payload bytes (gv_pool_bind_payload) of mesh slots changed; pool id in the top 4 bits of
                                `first`, like GV_DIRTY_MESH. Read by no cull: a recorded cull of a batch is not launched by it */
-    GV_DIRTY_GEOMETRY = 4   /* the bound geometry ids (gv_pool_bind_geometry) of mesh slots changed; pool id in the top 4 bits of
+    GV_DIRTY_GEOMETRY = 4,  /* the bound geometry ids (gv_pool_bind_geometry) of mesh slots changed; pool id in the top 4 bits of
                                `first`. Read by no cull either */
+    GV_DIRTY_LOD = 5        /* the bound sizes (gv_pool_bind_lod) of mesh slots changed; pool id in the top 4 bits of `first`. Read
+                               by no cull either */
 } GvDirtyKind;
 int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count);
 
@@ -461,7 +463,8 @@ int gv_pool_draw_bases_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* first_insta
  *   first_k, c_k: what E defines — after gv_pool_emit_instances first_k = starts[v] + k and c_k = 1; after a draw emission
  *   first_k = first_instance[draw_starts[v] + k] and c_k = first_{k+1} - first_k, the word behind a view's last draw being starts[v+1].
  *   g_k = id[s_k], read from the geometry id mirror as it stands when the command emission is issued (marks made after the cull
- *   are consumed by it, as for payload and counts); without an id column g_k = 0.
+ *   are consumed by it, as for payload and counts); without an id column g_k = 0. While the pool holds a LOD selection made
+ *   behind E (gv_pool_select_lods, below), g_k is the selected id of the draw instead, and the id mirror is not read.
  *   G(g) = table[g] if g < table_count, else the void geometry {0, 0, 0}.
  * Per-draw mode (flags 0): view v has C_v = n_v commands, command k = {count G(g_k).count, instance_count c_k (0 when
  *   g_k >= table_count), first G(g_k).first, vertex_offset G(g_k).vertex_offset, first_instance first_k, draw k}.
@@ -517,6 +520,62 @@ int gv_pool_draw_commands_device(GvCtx* ctx, uint32_t pool_id, const void** comm
  * pinned staging, whole commands (the library wrote every byte). GV_E_ARG when either array is too small: nothing is written. */
 int gv_pool_draw_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* command_counts,
                                 uint32_t counts_capacity);
+
+/* ---- level of detail per draw, selected on the device ----
+ * The geometry id of a draw is id[s_k], one value per pool slot; with levels of detail it depends on the view too. The reference
+ * carries the data and no rule: ModelRenderComponent::lods is a vector<ModelLOD> (include/garden/system/render/model.hpp:29-41)
+ * and nothing in source/ picks among its entries, so the rule is this build's. gv_pool_select_lods applies
+ * it behind the pool's last instance emission E, in draw order, from what the device already holds; a command emission that
+ * follows takes the selected ids. With E, v, k and s_k as for the draw commands above:
+ *   b_k = id[s_k], read from the geometry id mirror as it stands when the selection is issued; without an id column b_k = 0.
+ *   r_k = size[s_k]: the bound size column, one fp32 per pool slot, copied verbatim (the engine decides what it measures, for
+ *     example a world-space bounding radius); without a column r_k = 1.0f.
+ *   t = the translation column of the record's bakedModel as delivered (floats 9, 10, 11): the pivot relative to
+ *     camera_position, WITHOUT camera_offset. d2 = fmaf(tz, tz, fmaf(ty, ty, tx * tx)).
+ *   x = d2 * view_scale[v], one fp32 multiply; view_scale[v] may hold (tan(fov / 2) / height)^2, a quality bias, or 1.
+ *   e = lod_table[b_k] if b_k < lod_table_count, otherwise one level.
+ *   For i = 0 .. e.levels - 2: y_i = r_k * e.switch_at[i], q_i = y_i * y_i.
+ *   level_k = the NUMBER of i with x > q_i. A count: unsorted thresholds are defined. A comparison with a NaN is false, so a NaN
+ *     size, distance or scale gives level 0, the finest; an infinite x gives the coarsest level over finite thresholds; an exact
+ *     tie keeps the finer level.
+ *   g_k = b_k + level_k as a uint32 add: the levels of one geometry are consecutive entries of the geometry table. An id at or
+ *     beyond the geometry table's count yields the void command, as above.
+ * Views that share camera_position select the same level for a slot given the same scale: that follows from the rule. */
+#define GV_MAX_LOD_LEVELS 8u
+typedef struct GvLodGeometry {
+    uint32_t levels;                            /* 1 .. GV_MAX_LOD_LEVELS */
+    float switch_at[GV_MAX_LOD_LEVELS - 1];     /* the first levels - 1 are read; in units of distance per size */
+} GvLodGeometry;                                /* 32 bytes */
+/* The pool's sizes and the table the BASE ids index. sizes: element i at sizes + i * stride (stride >= 4), fp32, covering
+ * `occupancy` slots; sizes == NULL with a table: every slot has size 1 and no mirror is kept. The table (<= GV_MAX_GEOMETRIES
+ * entries, levels 1 .. GV_MAX_LOD_LEVELS each) is copied at the call. sizes == NULL && table == NULL removes the binding (and a
+ * selection the pool holds). Lifetime of `sizes` as gv_pool_bind_ready. The size mirror — one word per POOL slot — exists only
+ * once gv_pool_select_lods has been called for a pool with a size column: that call uploads the column; from then on GV_DIRTY_LOD
+ * and the pool's GV_DIRTY_MESH marks feed a dirty set of its own, consumed by gv_sync or the pool's next selection, whichever
+ * comes first. No cull reads it. Uploaded bytes count in GvStats::upload_bytes; a rebind resets the mirror.
+ * GV_E_ARG: a pool out of range, stride < 4, sizes without a table, a NULL table with table_count > 0, table_count 0 with a
+ * table, table_count above the limit, levels outside 1 .. 8 in an entry, an occupancy beyond the 28-bit slot range. */
+int gv_pool_bind_lod(GvCtx* ctx, uint32_t pool_id, const void* sizes, uint32_t stride, uint32_t occupancy, const GvLodGeometry* table,
+                     uint32_t table_count);
+/* Selects the level of every draw of E: draw_geometry[D_v + k] = g_k with D_v the sum of the draw counts of the views listed in
+ * front (read on the device), and level_counts[v * GV_MAX_LOD_LEVELS + L] = the draws of view v at level L. Asynchronous on
+ * gv_stream(ctx); counts as a read (recorded culls and deferred sorts are launched first); consumes the pending id and size marks.
+ * One kernel launch (plus a memset of the histogram), counted under GvStats::launches[GV_K_EMIT]. The buffers are library-owned,
+ * sized for the sum of the listed views' occupancies, grown and never shrunk. view_scale: one float per view of E, in E's order.
+ * While the pool holds a selection made behind E, gv_pool_emit_draw_commands takes g_k from draw_geometry instead of id[s_k], in
+ * both modes (run heads compare the selected ids), and does not re-read marks made after the selection. The selection ends where
+ * E's commands end: at the pool's next gv_cull or instance emission. view_scale == NULL with view_count == 0 drops it.
+ * GV_E_ARG: a pool that is not bound, view_scale NULL with view_count > 0, view_count other than E's. GV_E_STATE: no LOD binding,
+ * no geometry bound, no emission since the pool's last gv_cull, a size or id column whose occupancy is below a listed view's. */
+int gv_pool_select_lods(GvCtx* ctx, uint32_t pool_id, const float* view_scale, uint32_t view_count);
+/* Device pointers of the pool's selection, written in stream order: uint32 draw_geometry[sum of n_v] and uint32
+ * level_counts[m * GV_MAX_LOD_LEVELS]. GV_E_STATE: the pool holds no selection. */
+int gv_pool_lods_device(GvCtx* ctx, uint32_t pool_id, const void** draw_geometry, const void** level_counts);
+/* Waits for the pool's selection; copies level_counts[0 .. m * GV_MAX_LOD_LEVELS) (counts_capacity at least that) and —
+ * draw_geometry non-NULL — the selected ids of the listed views, back to back (capacity >= the sum of the draw counts, which is
+ * the sum of level_counts). GV_E_ARG when either array is too small: nothing is written. */
+int gv_pool_lods_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* draw_geometry, uint32_t capacity, uint32_t* level_counts,
+                       uint32_t counts_capacity);
 
 /* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
  * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
