@@ -14,6 +14,8 @@ import pytest
 
 from garden_amd import scene
 from garden_amd.lib import GV_SWEEP_MFMA, GV_SWEEP_VALU
+import mirror_sync_support as ms
+from test_gpu_mirror_sync_forms import GV_SWEEP_INCREMENTAL, MAIN, block_rejected, mark, ranges_of, reaches, synced
 
 pytestmark = pytest.mark.gpu
 
@@ -100,6 +102,97 @@ def test_cfg3_10m_hiz_properties_and_oracle(gpu, oracle, flat10m):
     o = np.argsort(exp["visible_idx"], kind="stable")
     exp = {k: (v[o] if isinstance(v, np.ndarray) else v) for k, v in exp.items()}
     assert same_records(hz1, exp) and np.array_equal(hz1["is_visible"], m2["isVisible"])
+
+
+# ---- the mirror sync's one large case (tests/test_mirror_sync_census.py: the cells that exist only from 8 126 209 slots on) ----
+
+LARGE_MIN = (ms.DEVICE_GATHER_MIN * ms.FEW_SHARE - ms.FEW_FREE - 1) * ms.CULL_BLOCK + 1
+
+
+def test_marks_through_the_order_table_at_the_smallest_pool_that_has_them(oracle):
+    """('xf', 'device', 'permuted', 'aos', 'marks', 'tracked'): ONE range of kDeviceGatherMinSlots transform slots is gathered on the
+    device (aos_transforms_kernel) while the sync is still few enough to patch blocks — 16 * 2048 <= blocks + 1024 needs 31 744
+    blocks, 8 126 209 slots — so the blocks of the range are flagged by mark_dirty_blocks_kernel through d_xinv. The main-camera
+    view only. One re-mirrored entity moves to the place of a visible one from a block whose old box the view rejects whole."""
+    n = LARGE_MIN
+    assert n == 8_126_209 and ms.few_enough_to_patch_blocks(ms.DEVICE_GATHER_MIN, ms.blocks_of(n)) and not ms.few_enough_to_patch_blocks(ms.DEVICE_GATHER_MIN, ms.blocks_of(n - 1))
+    c = ms.Case("large", "spatial", n, (ms.Sync(((3_000_001, ms.DEVICE_GATHER_MIN),), claim=(("xf", "device", "marks"),)),))
+    sc = scene.flat_scene(n, seed=77)
+    T, M, e2t = sc.transforms, sc.meshes, sc.entity_to_transform
+    sT, sM = T.copy(), M.copy()
+    views = [MAIN]
+    state, _ = ms.case_start(c)
+    assert state.pools[0].patch_valid and state.xf.world_valid  # (block boxes of its own accord above kAutoBoundsMinSlots)
+    from garden_amd.lib import GpuVisibility
+    with GpuVisibility(device=0) as vis:
+        vis.bind_transforms(T, e2t)
+        vis.bind_pool(0, M)
+        vis.hierarchy_rebuild()
+        vis.cull(0, views)
+        vis.cull(0, views)
+        vis.sweep(GV_SWEEP_INCREMENTAL)
+        marks = ms.case_marks(c.syncs[0])
+        plan = ms.sync_plan(state, marks)
+        assert [(cell[0], cell[1], cell[2], cell[4], cell[5]) for cell in plan.cells] == [("xf", "device", "permuted", "marks", "tracked")]
+        (lo, hi), = ranges_of(marks.xf, n)
+        rng = np.random.default_rng(5)
+        T["position"][lo:hi, :3] += rng.normal(0, 20, (hi - lo, 3)).astype(np.float32)
+        T["rotation"][lo:hi] = T["rotation"][lo:hi][::-1].copy()
+        T["selfActive"][lo:hi] ^= (rng.random(hi - lo) < 0.05).astype(np.uint8)
+        T["selfActive"][lo] ^= 1
+        T["selfActive"][hi - 1] ^= 1
+        # the mover
+        seen = oracle.prepare_meshes(sM.copy(), sT, e2t, MAIN)["visible_idx"]
+        slots_of = vis.mirror_slots(0, n).astype(np.int64)
+        entry_of = np.empty(n, np.int64)
+        entry_of[slots_of] = np.arange(n)
+        planes = oracle.frustum(MAIN["view_proj"])
+        pos, reach = sT["position"][:, :3].astype(np.float64), reaches(sT, sM)
+        mover = None
+        for s in range(lo, hi):
+            block = entry_of[s] // ms.CULL_BLOCK
+            if M["entity"][s] == s + 1 and T["entity"][s] == s + 1 and M["isEnabled"][s] and np.all(M["aabbMax"][s, :3] > M["aabbMin"][s, :3]) and \
+                    block_rejected(planes, pos, reach, slots_of[block * ms.CULL_BLOCK:(block + 1) * ms.CULL_BLOCK]):
+                mover = s
+                break
+        assert mover is not None
+        T["position"][mover] = sT["position"][seen[len(seen) // 2]]
+        T["selfActive"][mover] = T["ancestorsActive"][mover] = 1
+        # decoys beside the range
+        T["position"][[lo - 2, hi + 1], :3] += np.float32(3.0)
+        mark(vis, marks)
+        synced(vis, plan, "large")
+        sT[lo:hi] = T[lo:hi]
+        state = ms.cull(plan.state)
+        vis.stats_reset()
+        vis.cull(0, views)
+        assert state.pools[0].boxes and vis.stats()["bounds_blocks_total"] == ms.blocks_of(n)
+
+        def check(what):
+            got = vis.fetch(0, write_back=False, occupancy=n, pool_id=0)
+            pool = sM.copy()
+            exp = oracle.prepare_meshes(pool, sT, e2t, MAIN)
+            o = np.argsort(exp["visible_idx"], kind="stable")
+            assert got["draw_count"] == exp["draw_count"] and np.array_equal(got["visible_idx"], exp["visible_idx"][o]), what
+            assert np.array_equal(got["baked_model"].view(np.uint32), exp["baked_model"][o].view(np.uint32)), what
+            assert np.array_equal(got["distance_sq"].view(np.uint32), exp["distance_sq"][o].view(np.uint32)), what
+            assert np.array_equal(got["is_visible"], pool["isVisible"]), what
+            vis.sweep(GV_SWEEP_INCREMENTAL)
+            assert np.array_equal(vis.get_world(0, n).view(np.uint32), oracle.world_matrices(sT, e2t, threads=8).view(np.uint32)), what
+            return exp
+
+        first = check("large")
+        assert mover in first["visible_idx"]
+        # the decoys, marked: the sync behind this one is few as well (two slots in the packet, which flags them itself)
+        dmarks = ms.Marks(((lo - 2, 1), (hi + 1, 1)))
+        dplan = ms.sync_plan(ms.swept(state), dmarks)
+        assert [(cell[1], cell[4]) for cell in dplan.cells] == [("packet", "packet")]
+        mark(vis, dmarks)
+        synced(vis, dplan, "large decoys")
+        sT[[lo - 2, hi + 1]] = T[[lo - 2, hi + 1]]
+        vis.cull(0, views)
+        check("large decoys")
+        assert np.array_equal(sT, T)
 
 
 @pytest.mark.parametrize("rg16f", [False, True])
