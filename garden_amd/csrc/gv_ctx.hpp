@@ -20,6 +20,7 @@
 
 #include "../../include/garden_vis.h"
 #include "gv_kernels.hpp"
+#include "gv_group_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -475,6 +476,7 @@ struct ViewState {
     uint32_t sort_parity = 0;  // which of the two counter sets in sort_hist the next large sort uses (gv_sort.hip)
     size_t sort_set_words = 0; // size of one set as laid out in sort_hist (0: not initialised)
     DeviceBuf<uint16_t> sort_ranks;
+    DeviceBuf<uint32_t> group_hist;  // gv_pool_group_draws: group and tile digit counts (gv_group_kernels.hpp; keys, pairs and ranks: the sort's scratch)
     uint8_t sort_pending = 0;  // small pool: gv_sort asked for (1 ascending, 2 descending), not launched yet (flush_sorts)
     uint8_t sorted_dir = 0;    // the direction of the last gv_pool_sort since this view's cull (1 ascending, 2 descending; 0: none):
                                // what gv_merge_sorted asks of a member
@@ -734,6 +736,10 @@ int flush_recorded_culls(GvCtx* ctx, uint32_t pool);    // ... those that read `
 ViewBuffers view_buffers(ViewState& vs);
 // gv_results.cpp (the reader side)
 int flush_sorts(GvCtx* ctx);                             // flush_culls + the sorts of small pools that were asked for and not launched yet
+// a reorder of a view's records: inputs = its current records, outputs = its alternate set (reserved here), which swap_in_sorted
+// makes the view's records once the reorder is enqueued (gv_pool_sort, gv_pool_group_draws)
+int sort_records_of(GvCtx* ctx, ViewState& vs, SortRecords& r);
+void swap_in_sorted(ViewState& vs);
 int wait_for_stream(GvCtx* ctx);                         // until the stream has drained (a polled word; hipStreamSynchronize as fallback)
 ViewState* view_of(GvCtx* ctx, uint32_t pool_id, uint32_t view_index);  // NULL: no valid results
 bool release_record_target(PoolState::RecordTarget& target);            // false: the range was found unmapped

@@ -660,4 +660,31 @@ __device__ __forceinline__ uint32_t block_sum_of(const uint32_t* t, uint32_t lo,
     return scratch[0] + scratch[1] + scratch[2] + scratch[3];
 }
 
+// ---- shared by the radix sorts (gv_sort.hip, gv_group.hip) ----
+// lanes of the wave whose `digit` equals this lane's (among `valid` lanes): 8 ballots
+__device__ __forceinline__ unsigned long long match_digit(uint32_t digit, bool valid)
+{
+    // per bit: t = 0 / ~0 from the lane's bit, m = the lanes whose bit is set; the lanes that agree with this one are
+    // ~(m ^ t) — six VALU operations per bit (sign-extending bit extract, compare, two xnor, two and) where the select form
+    // of the same thing compiled to nine
+    const unsigned long long all = __ballot(valid);
+    uint32_t lo = (uint32_t)all, hi = (uint32_t)(all >> 32);
+#pragma unroll
+    for (uint32_t b = 0; b < 8; b++) {
+        const uint32_t t = (uint32_t)((int32_t)(digit << (31u - b)) >> 31);
+        const unsigned long long m = __ballot(t != 0u);
+        lo &= ~((uint32_t)m ^ t);
+        hi &= ~((uint32_t)(m >> 32) ^ t);
+    }
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// LDS operations of one wave execute in issue order; the fences keep the compiler from reordering them
+__device__ __forceinline__ void wave_lds_order()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 }  // namespace gv

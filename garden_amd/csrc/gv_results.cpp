@@ -17,7 +17,7 @@ namespace gv {
 
 // The records of a sort of `vs`: inputs = the view's current records, outputs = its alternate set (reserved here), which
 // swap_in_sorted makes the view's records once the sort is enqueued.
-static int sort_records_of(GvCtx* ctx, ViewState& vs, SortRecords& r)
+int sort_records_of(GvCtx* ctx, ViewState& vs, SortRecords& r)
 {
     const size_t n = vs.occupancy;  // upper bound of draw_count, known without a readback
     GV_HIP(ctx, vs.alt_idx.reserve(n));
@@ -32,7 +32,7 @@ static int sort_records_of(GvCtx* ctx, ViewState& vs, SortRecords& r)
     r.dist_out = vs.alt_dist.ptr;
     return GV_OK;
 }
-static void swap_in_sorted(ViewState& vs)
+void swap_in_sorted(ViewState& vs)
 {
     std::swap(vs.visible_idx, vs.alt_idx);
     std::swap(vs.baked_model, vs.alt_model);

@@ -17,6 +17,12 @@
 // command emission: every draw then takes the entry of its level, chosen per pass on the device from the record's distance
 // (DESIGN.md §4 item 11). setLodScale gives the light pass and the shadow passes their view scales.
 //
+// Grouping: run mode merges CONSECUTIVE draws of one id, and an unsorted system's records arrive in space order. setGrouping(p, true)
+// makes GpuInstanceWriter::write() group every view it is about to emit by geometry (gv_pool_group_draws; with LODs by geometry +
+// level, GV_GROUP_BY_LOD with that pass's scale) in front of its emissions: run mode then writes one command per geometry (or
+// level) and pass. The records delivered to the host afterwards are in the grouped order too. A sorted system's order is the
+// distance order: it cannot be grouped, and asking for it throws.
+//
 // One context only, like the writer: with ranks no device holds a view's records in draw order — isSupported() is false.
 #pragma once
 #include <algorithm>
@@ -46,6 +52,7 @@ private:
         size_t baseBytes = 0, shadowBytes = 0;
         uint32_t stride = 0;
         bool lods = false;     // an LOD table is bound: emit() selects in front of the commands
+        bool grouping = false; // group() reorders the views by geometry in front of the instance emissions
         float baseScale = 1.0f, shadowScale = 1.0f;
         Emitted base, shadow;
     } per[GV_MAX_POOLS];
@@ -109,6 +116,31 @@ public:
         s.baseDevice = baseDevice, s.baseBytes = baseBytes, s.shadowDevice = shadowDevice, s.shadowBytes = shadowBytes;
     }
     void setFetch(bool on) noexcept { fetch = on; }
+    // on: the views of mesh system p are grouped by geometry in front of the writer's emissions (see above). Unsorted systems only:
+    // GardenError for a sorted one, here when the last frame already knows the system, otherwise at the write().
+    void setGrouping(uint32_t p, bool on)
+    {
+        PerSystem& s = of(p);
+        if (on && p < system->getMeshSystems().size() && system->isSystemSorted(p))
+            throw GardenError("GpuDrawCommands::setGrouping: a sorted mesh system's order is the distance order");
+        s.grouping = on;
+    }
+
+    // GpuInstanceWriter::write calls this in front of its emissions for mesh system p with the views it is about to emit (shadow: those
+    // of the shadow array). Both calls come in front of the FIRST emission: gv_pool_group_draws refuses a pool that holds one.
+    void group(uint32_t p, const uint32_t* views, uint32_t count, bool shadow)
+    {
+        PerSystem& s = of(p);
+        if (!s.grouping || !count)
+            return;
+        if (!isSupported())
+            throw GardenError("GpuDrawCommands: unsupported with several ranks (the merged draw order is made on the host)");
+        if (system->isSystemSorted(p))
+            throw GardenError("GpuDrawCommands: grouping a sorted mesh system (its order is the distance order)");
+        for (uint32_t k = 0; k < count; k++)
+            check(gv_pool_group_draws(system->getContext(), p, views[k], s.lods ? GV_GROUP_BY_LOD : 0u, shadow ? s.shadowScale : s.baseScale),
+                  "gv_pool_group_draws");
+    }
 
     // GpuInstanceWriter::write calls this behind each of its emissions for mesh system p (shadow: the one into the shadow array)
     void emit(uint32_t p, bool shadow)

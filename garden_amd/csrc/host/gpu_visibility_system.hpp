@@ -1327,6 +1327,8 @@ public:
     // the passes mesh system p was culled for in the last frame: view v of pool p stands for passes[v] — -1 the light pass, s >= 0
     // shadow pass s (instance_writer.hpp reads it)
     const std::vector<int8_t>& getSystemPasses(uint32_t p) const { return plan.at(p).passes; }
+    // mesh system p of the last frame is a sorted one (Translucent, UI): its delivery order is the distance order (draw_commands.hpp)
+    bool isSystemSorted(uint32_t p) const { return plan.at(p).sorted; }
 };
 
 }  // namespace garden

@@ -93,6 +93,16 @@ public:
         uint32_t starts[GV_MAX_VIEWS + 1];
         const PayloadAt& at = payloadAt[p < GV_MAX_POOLS ? p : 0];
         const bool payload = p < GV_MAX_POOLS && at.count != 0;
+        if (commands) {  // setGrouping: the views about to be emitted, grouped by geometry in front of the emissions (both of them
+                         // here: a pool that holds an emission is no longer grouped)
+            std::vector<uint32_t> light, cascades;
+            for (uint32_t v = 0; v < passes.size(); v++)
+                (passes[v] >= 0 ? cascades : light).push_back(v);
+            if (base)
+                commands->group(p, light.data(), (uint32_t)light.size(), false);
+            if (shadow)
+                commands->group(p, cascades.data(), (uint32_t)cascades.size(), true);
+        }
         for (uint32_t v = 0; v < passes.size(); v++) {
             if (passes[v] >= 0) {
                 shadowViews.push_back(v);

@@ -28,6 +28,7 @@ GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRT
 GV_MAX_DRAW_INSTANCES = 65535
 GV_MAX_GEOMETRIES = 65536
 GV_COMMANDS_MERGE_RUNS = 1
+GV_GROUP_BY_LOD = 1
 GV_SWEEP_VALU, GV_SWEEP_MFMA, GV_SWEEP_WITH_CULL, GV_SWEEP_WITH_CULL_VALU, GV_SWEEP_INCREMENTAL = 0, 1, 2, 3, 4
 GV_MEM_HOST, GV_MEM_DEVICE = 0, 1
 GV_EXCHANGE_ALLGATHER, GV_EXCHANGE_P2P, GV_EXCHANGE_BROADCAST, GV_EXCHANGE_PEER = 0, 1, 2, 3
@@ -206,6 +207,7 @@ EXPORTS = [
     "gv_pool_bind_geometry", "gv_pool_set_command_layout", "gv_pool_emit_draw_commands", "gv_pool_draw_commands_device",
     "gv_pool_draw_commands_fetch",
     "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
+    "gv_pool_group_draws",
 ]
 
 _lib = None
@@ -339,6 +341,7 @@ def load():
     lib.gv_pool_select_lods.argtypes = [P, u32, C.POINTER(C.c_float), u32]
     lib.gv_pool_lods_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_lods_fetch.argtypes = [P, u32, C.POINTER(u32), u32, C.POINTER(u32), u32]
+    lib.gv_pool_group_draws.argtypes = [P, u32, u32, u32, C.c_float]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -468,6 +471,7 @@ class GpuVisibility:
         re-submits the same views need not rebuild the ctypes structs every frame)."""
         arr = views if isinstance(views, C.Array) else self.views_array(views)
         self._check(self.lib.gv_cull(self.ctx, pool_id, arr, len(arr)))
+        self._culled_pool = pool_id
 
     @staticmethod
     def views_array(views):
@@ -688,6 +692,14 @@ class GpuVisibility:
             self._check(self.lib.gv_sort(self.ctx, view_index, 1 if descending else 0))
         else:
             self._check(self.lib.gv_pool_sort(self.ctx, pool_id, view_index, 1 if descending else 0))
+
+    def group_draws(self, view_index=0, pool_id=None, by_lod=False, view_scale=1.0):
+        """gv_pool_group_draws: the view's records reordered by geometry id (by_lod: by id + the level view_scale selects), stable,
+        on the context's stream; the next fetch, emission or selection sees the new order. Call it before the pool's instance
+        emission. pool_id: default, the pool of the most recent cull."""
+        if pool_id is None:
+            pool_id = getattr(self, "_culled_pool", 0)
+        self._check(self.lib.gv_pool_group_draws(self.ctx, pool_id, view_index, GV_GROUP_BY_LOD if by_lod else 0, float(view_scale)))
 
     # ---- picking ----
     def pick(self, rays, pool_ids=(0,), camera_position=(0, 0, 0), exclude=None):

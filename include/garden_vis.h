@@ -638,6 +638,36 @@ int gv_pool_result_count(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint
 int gv_pool_results_device(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, GvDeviceResult* out);
 int gv_pool_sort(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, int descending);
 
+/* ---- a view's draws grouped by geometry, on the device ----
+ * Run mode of gv_pool_emit_draw_commands merges CONSECUTIVE draws of one id, and records arrive in space or distance order: random
+ * ids give one command per draw. gv_pool_group_draws reorders the records of (pool, view) by geometry key, stable, where
+ * gv_pool_sort makes its reorder, so that every later step — the fetches, the record structs, the instance bases, both instance
+ * emissions, the LOD selection, the commands in both modes — sees draw k as record k of the new order and composes unchanged. Run
+ * mode then writes one command per geometry (or per level of one) with instance_count = the group's instance total.
+ *   Records 0 .. n-1: those of the view in the order a fetch would deliver them when the call is issued; n is the device draw
+ *     count, never read by the host. s_k = visible_idx[k], the record's POOL slot.
+ *   b_k = id[s_k], read from the geometry id mirror as it stands when the call is issued (the call uploads the column on first use
+ *     and consumes pending GV_DIRTY_GEOMETRY / GV_DIRTY_MESH marks, as gv_pool_select_lods); without an id column b_k = 0.
+ *   flags == 0: g_k = b_k, view_scale is ignored. GV_GROUP_BY_LOD: g_k = b_k + level_k, level_k exactly that of gv_pool_select_lods
+ *     above (d2 from floats 9, 10, 11 of the record's bakedModel, x = d2 * view_scale, the size mirror and the table of
+ *     gv_pool_bind_lod; size marks are uploaded and consumed as the selection does). The level depends on the record's own bytes
+ *     only: a gv_pool_select_lods issued later with the same scale selects the same g for every draw.
+ *   Key: kappa_k = min(g_k, K), K the bound geometry table's table_count: every void id shares the last bucket.
+ *   After the call record j of the view is the old record pi(j), pi the stable ascending order of kappa: within one key the previous
+ *     order is kept (behind gv_pool_sort every group is still ordered by distance). visible_idx, baked_model and distance_sq all
+ *     move; draw_count, is_visible and instance_count do not change.
+ * Asynchronous on gv_stream(ctx); counts as a read (recorded culls and deferred sorts are launched first). 2 launches per 8-bit
+ * digit of the VALUE K — one digit for K <= 255, two for K <= 65535, three for K = 65536 — counted under
+ * GvStats::launches[GV_K_SORT]: fixed by the host, never derived from a count read back. Afterwards the view counts as not
+ * distance-sorted (gv_merge_sorted refuses it with GV_E_STATE) until a later gv_pool_sort, and the next fetch delivers the new
+ * order. Without an id column and without the flag every key is 0: GV_OK, nothing is launched, nothing changes.
+ * GV_E_ARG: a NULL ctx, a pool out of range or not bound, unknown flag bits, a view without emitted records. GV_E_STATE: no
+ * geometry bound; GV_GROUP_BY_LOD without an LOD binding; an id or size column whose occupancy is below the view's; the pool holds
+ * an instance emission since its last gv_cull — group first, then emit: instance data written before the reorder would no longer
+ * match its draws. */
+#define GV_GROUP_BY_LOD 1u
+int gv_pool_group_draws(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint32_t flags, float view_scale);
+
 /* ---- the shared sorted arrays: the sorted lists of several mesh systems merged into ONE array, on the device ----
  * The reference keeps one array per sorted kind — transSortedMeshes, uiSortedMeshes, one translucent array per shadow pass — into
  * which every sorted system appends SortedMesh records tagged with its bufferIndex (mesh.cpp:247-261); one std::sort orders the
