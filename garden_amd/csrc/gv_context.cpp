@@ -414,9 +414,10 @@ static int cull_emit_one_launch(GvCtx* ctx, ViewState& vs, const MeshMirror& mes
     return GV_OK;
 }
 
-// Compaction and records of one view behind its cull (vb: its buffers as that cull saw them).
-static int emit_view(GvCtx* ctx, ViewState& vs, const MeshMirror& mesh, const TransformMirror& xf, const ViewParams& vp, const ViewBuffers& vb,
-                     bool self_prefix, const float4* emit_world, const EmitSeed* seeds)
+// Compaction and records of one view behind its cull (vb: its buffers as that cull saw them). (Shared through gv_ctx.hpp: the
+// second phase's masked cull leaves its view in the cull's format and takes the same way out, gv_second.cpp.)
+int emit_view(GvCtx* ctx, ViewState& vs, const MeshMirror& mesh, const TransformMirror& xf, const ViewParams& vp, const ViewBuffers& vb,
+              bool self_prefix, const float4* emit_world, const EmitSeed* seeds)
 {
     const uint32_t chunks = (mesh.count + kEmitChunk - 1) / kEmitChunk;
     if (vs.emitted && self_prefix) {
@@ -711,7 +712,7 @@ void gv_destroy(GvCtx* ctx)
       for (auto& v : per_pool) {
         v.mask.release(); v.chunk_count.release(); v.chunk_count2.release(); v.chunk_offset.release(); v.draw_count.release();
         v.is_visible.release(); v.vis_flags.release(); v.visible_idx.release(); v.baked_model.release(); v.distance_sq.release();
-        v.alt_idx.release(); v.alt_model.release(); v.alt_dist.release(); v.sort_hist.release(); v.sort_ranks.release(); v.group_hist.release();
+        v.alt_idx.release(); v.alt_model.release(); v.alt_dist.release(); v.sort_hist.release(); v.sort_ranks.release(); v.group_hist.release(); v.seen.release();
         for (int k = 0; k < 2; k++) { v.sort_keys[k].release(); v.sort_vals[k].release(); v.sort_slots[k].release(); }
         v.h_visible_idx.release(); v.h_draw_count.release(); v.h_baked_model.release();
         v.h_distance_sq.release(); v.h_is_visible.release(); v.is_visible_slots.release();

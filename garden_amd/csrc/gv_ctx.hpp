@@ -21,6 +21,7 @@
 #include "../../include/garden_vis.h"
 #include "gv_kernels.hpp"
 #include "gv_group_kernels.hpp"
+#include "gv_second_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -477,6 +478,7 @@ struct ViewState {
     size_t sort_set_words = 0; // size of one set as laid out in sort_hist (0: not initialised)
     DeviceBuf<uint16_t> sort_ranks;
     DeviceBuf<uint32_t> group_hist;  // gv_pool_group_draws: group and tile digit counts (gv_group_kernels.hpp; keys, pairs and ranks: the sort's scratch)
+    DeviceBuf<unsigned long long> seen;  // gv_pool_cull_second_phase, the SECOND view's: one bit per mirror entry, set for the first view's records
     uint8_t sort_pending = 0;  // small pool: gv_sort asked for (1 ascending, 2 descending), not launched yet (flush_sorts)
     uint8_t sorted_dir = 0;    // the direction of the last gv_pool_sort since this view's cull (1 ascending, 2 descending; 0: none):
                                // what gv_merge_sorted asks of a member
@@ -734,6 +736,13 @@ int exchange_drain(GvCtx* ctx);    // bounded wait for what is queued on the exc
 int flush_culls(GvCtx* ctx);                             // launches the culls recorded since gv_cull_batch_begin; ends the batch
 int flush_recorded_culls(GvCtx* ctx, uint32_t pool);    // ... those that read `pool` (GV_MAX_POOLS: any), recording goes on
 ViewBuffers view_buffers(ViewState& vs);
+// what gv_cull does per view in front of its launches, and the way out behind a cull that left ballot words and chunk totals
+// (gv_pool_cull_second_phase, gv_second.cpp, sets its view up and emits it the same way)
+void build_view_params(const GvView& v, ViewParams* out);
+int reserve_view(GvCtx* ctx, ViewState& vs, uint32_t occupancy, bool emit);
+HizDevice hiz_device(const GvCtx* ctx);
+int emit_view(GvCtx* ctx, ViewState& vs, const MeshMirror& mesh, const TransformMirror& xf, const ViewParams& vp, const ViewBuffers& vb,
+              bool self_prefix, const float4* emit_world, const EmitSeed* seeds);
 // gv_results.cpp (the reader side)
 int flush_sorts(GvCtx* ctx);                             // flush_culls + the sorts of small pools that were asked for and not launched yet
 // a reorder of a view's records: inputs = its current records, outputs = its alternate set (reserved here), which swap_in_sorted

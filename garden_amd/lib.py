@@ -208,6 +208,7 @@ EXPORTS = [
     "gv_pool_draw_commands_fetch",
     "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
     "gv_pool_group_draws",
+    "gv_pool_cull_second_phase",
 ]
 
 _lib = None
@@ -342,6 +343,7 @@ def load():
     lib.gv_pool_lods_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_lods_fetch.argtypes = [P, u32, C.POINTER(u32), u32, C.POINTER(u32), u32]
     lib.gv_pool_group_draws.argtypes = [P, u32, u32, u32, C.c_float]
+    lib.gv_pool_cull_second_phase.argtypes = [P, u32, u32, u32, C.POINTER(GvView)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -700,6 +702,16 @@ class GpuVisibility:
         if pool_id is None:
             pool_id = getattr(self, "_culled_pool", 0)
         self._check(self.lib.gv_pool_group_draws(self.ctx, pool_id, view_index, GV_GROUP_BY_LOD if by_lod else 0, float(view_scale)))
+
+    def cull_second_phase(self, first_view, second_view, view, pool_id=None):
+        """gv_pool_cull_second_phase: the second phase of two-phase occlusion culling. Culls the pool with `view` (a view dict or
+        a GvView) against the pyramid as it stands and leaves in `second_view` the records whose slot the records of `first_view`
+        do not hold: an ordinary emitted view, on the context's stream. Its is_visible (main pass) is the union of both phases.
+        pool_id: default, the pool of the most recent cull."""
+        if pool_id is None:
+            pool_id = getattr(self, "_culled_pool", 0)
+        gv = view if isinstance(view, GvView) or view is None else to_gv_view(view)
+        self._check(self.lib.gv_pool_cull_second_phase(self.ctx, pool_id, first_view, second_view, None if gv is None else C.byref(gv)))
 
     # ---- picking ----
     def pick(self, rays, pool_ids=(0,), camera_position=(0, 0, 0), exclude=None):

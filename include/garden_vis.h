@@ -668,6 +668,37 @@ int gv_pool_sort(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, int descendi
 #define GV_GROUP_BY_LOD 1u
 int gv_pool_group_draws(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint32_t flags, float view_scale);
 
+/* ---- two-phase occlusion culling: the second phase, on the device ----
+ * The pyramid a Hi-Z view queries is a frame old (it is built behind the previous frame's depth pass), so a box that has just come
+ * into view stays "occluded" for a frame. The remedy: cull against the old pyramid and draw the result (gv_cull, phase 1), rebuild
+ * the pyramid from what was drawn (gv_hiz_build), then re-test what phase 1 left out and draw the newly visible rest — this call.
+ *   S1: the pool slots in the records of (pool_id, first_view) as a fetch would deliver them when the call is issued —
+ *     visible_idx[0 .. n1), n1 the device draw count, never read by the host. POOL slots: never index-mapped, never mirror entries.
+ *     Derived from the records, so a gv_pool_sort, a gv_pool_group_draws or a re-order of the mirror between the phases changes nothing.
+ *   R: the records a gv_cull(pool_id, view, 1) issued at this moment would deliver — the mirror brought up to date as gv_cull does
+ *     it (pending gv_mark_dirty marks are consumed), against the pyramid as it stands. Every field of `view` is honoured as gv_cull
+ *     honours it (use_hiz, distance_2d, shadow_pass, camera_offset); emit_records must be 1.
+ *   Afterwards `second_view` is an ordinary emitted view of the pool, whatever it held before is replaced: its records are the
+ *     records of R whose slot is not in S1, in R's relative order (the mirror's spatial order; ascending slots with
+ *     GV_CONFIG_KEEP_SLOT_ORDER); visible_idx, baked_model and distance_sq bit for bit what R holds for them; draw_count their number;
+ *     instance_count follows from the records as for any emitted view; view_proj is kept for the instance emission. The fetches,
+ *     record structs, gv_pool_sort, gv_pool_group_draws, both instance emissions, gv_pool_select_lods and
+ *     gv_pool_emit_draw_commands take it unchanged.
+ *   is_visible (view->shadow_pass < 0; a shadow-pass view yields NULL as usual): the byte of slot s is 1 iff s is in S1 OR in the new
+ *     records. DELIBERATELY MORE THAN THE VIEW'S OWN RECORDS: it is the frame's final answer, which is what the light pass and
+ *     write_back want. gv_results_copy_mask_device of the second view carries the new entries only (bits and dst[0] match the records).
+ *   The first view is not touched: its records, count, is_visible, sort state and delivery state stay as they are.
+ * State: a read of the first view (recorded culls and deferred sorts are launched first) and, for the pool, a cull: it ends the
+ * pool's instance emission, commands and LOD selection and every merged array the pool is a member of. The pool's OTHER views stay
+ * valid; the pool's next gv_cull ends the second view like any view beyond its count. Asynchronous on gv_stream(ctx): no host
+ * synchronisation, no count read back. Launches, fixed by the host: the seen set and the masked cull under
+ * GvStats::launches[GV_K_CULL]; compaction and records as a cull's (GV_K_SCAN / GV_K_EMIT); the union of the isVisible bytes of a
+ * main-pass view under GV_K_EMIT. An empty pool, or a first view without draws, is GV_OK; with S1 empty the second view is exactly R.
+ * GV_E_ARG: a NULL ctx or view; a pool out of range or not bound; first_view == second_view; an index >= GV_MAX_VIEWS; a first
+ * view that is not valid or holds no emitted records; view->emit_records == 0. GV_E_STATE: view->use_hiz before gv_hiz_build; the
+ * pool's occupancy differs from the one the first view was culled with (cull again first). */
+int gv_pool_cull_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t first_view, uint32_t second_view, const GvView* view);
+
 /* ---- the shared sorted arrays: the sorted lists of several mesh systems merged into ONE array, on the device ----
  * The reference keeps one array per sorted kind — transSortedMeshes, uiSortedMeshes, one translucent array per shadow pass — into
  * which every sorted system appends SortedMesh records tagged with its bufferIndex (mesh.cpp:247-261); one std::sort orders the
