@@ -707,6 +707,7 @@ void gv_destroy(GvCtx* ctx)
         p.commands.d_draw_of.release(); p.commands.d_first_of.release(); p.commands.h_data.release(); p.commands.h_counts.release();
         p.lod.release(); p.lod.d_table.release(); p.lod.staged.destroy(); p.lod.d_draw_geometry.release(); p.lod.d_level_counts.release();
         p.lod.h_draw_geometry.release(); p.lod.h_level_counts.release();
+        p.bounds.d_partial.release(); p.bounds.d_out.release(); p.bounds.h_out.release();
     }
     for (auto& per_pool : ctx->views)
       for (auto& v : per_pool) {
@@ -1028,6 +1029,7 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
     p.instances.views = 0;  // the views' results are replaced from here on: the instance data made from the previous ones ends
     p.commands.views = 0;   // ... and the commands made from that
     p.lod.views = 0;        // ... and the levels selected for its draws
+    p.bounds.items = 0;     // ... and the bounds taken of them (gv_pool_view_bounds)
     for (auto& m : ctx->merges)  // ... and so does every merged array this pool is a member of (gv_merge_sorted)
         if ((m.pools >> pool_id) & 1u)
             m.valid = false;

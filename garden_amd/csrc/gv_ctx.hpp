@@ -22,6 +22,7 @@
 #include "gv_kernels.hpp"
 #include "gv_group_kernels.hpp"
 #include "gv_second_kernels.hpp"
+#include "gv_bounds_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -352,6 +353,13 @@ struct PoolState {
         DeviceBuf<uint32_t> d_level_counts;   // [GV_MAX_VIEWS * GV_MAX_LOD_LEVELS]
         PinnedBuf<uint32_t> h_draw_geometry, h_level_counts;  // staging of gv_pool_lods_fetch
     } lod;
+    // gv_pool_view_bounds: the bounds of the listed views' draws, buffers of their own (nothing a cull produced is touched)
+    struct Bounds {
+        uint32_t items = 0;                   // of the last call (0: none since the pool's last gv_cull or second phase)
+        DeviceBuf<BoundsPartial> d_partial;   // one row of keys per bounds_fold_kernel workgroup
+        DeviceBuf<BoundsResult> d_out;        // GvViewBounds[GV_MAX_BOUNDS_ITEMS]
+        PinnedBuf<BoundsResult> h_out;        // staging of gv_pool_view_bounds_fetch
+    } bounds;
     // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
     // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
     // transform mirror does not concern it); read by gv_pool_emit_instances only

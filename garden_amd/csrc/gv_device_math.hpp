@@ -285,4 +285,30 @@ __device__ __forceinline__ uint32_t lod_level(float x, float size, uint32_t leve
     return level;
 }
 
+// ------------------------------------------------------------------------------------------------
+// bounds of a view's visible draws in a caller's basis (the reference fits a cascade to its frustum slice and
+// stretches the depth range by zCoeff because it does not know where the casters are, csm.cpp:294-295). Test twin: tests/bounds_twin.h.
+//   p_c        the record's eight corners, exactly item 5's: aabb_corners over the record's own bakedModel and the box of its entry
+//   q_{c,r}    fmaf(B.c0[r], p.x, fmaf(B.c1[r], p.y, fmaf(B.c2[r], p.z, B.c3[r]))) for r = 0, 1, 2: B an affine 3x4 like bakedModel
+//   lo / hi    the minimum / maximum of q_{c,r} over all records and corners in the order of the key
+//              T(u) = u ^ ((u >> 31) ? 0xFFFFFFFF : 0x80000000) on the float's bits: -0 below +0, +-inf take part, a NaN takes no part
+//              (in that coordinate only); nothing taking part gives lo = +inf, hi = -inf
+// Minimum and maximum of unsigned keys are associative and commutative, and every q is computed from one record alone: no order of
+// evaluation — lanes, waves, workgroups, partial rows — can change any output bit. The same holds for the count of records with a NaN.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t bounds_key(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float bounds_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k); }
+
+// row r of B over the corner pairs of `c`: four packed fma chains, each element the scalar chain above
+__device__ __forceinline__ void bounds_project(const Corners& c, float b0, float b1, float b2, float b3, v2f (&q)[4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        q[j] = pk_fma(splat(b0), c.x[j], pk_fma(splat(b1), c.y[j], pk_fma(splat(b2), c.z[j], splat(b3))));
+}
+
 }  // namespace gv

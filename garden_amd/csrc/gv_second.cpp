@@ -58,6 +58,7 @@ int gv_pool_cull_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t first_view,
     p.instances.views = 0;
     p.commands.views = 0;
     p.lod.views = 0;
+    p.bounds.items = 0;
     for (auto& m : ctx->merges)
         if ((m.pools >> pool_id) & 1u)
             m.valid = false;

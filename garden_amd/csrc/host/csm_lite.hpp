@@ -7,6 +7,7 @@
 // garden_amd/scene.py); parity unpinned like the rest. Host-only, header-only, no device code.
 #pragma once
 #include "garden_host.hpp"
+#include "../../../include/garden_vis.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -157,10 +158,19 @@ struct Cascade {
     f32x4 cameraOffset;
 };
 
+// calcLightViewProj with what it computed on the way, for a caller that fits the depth range to the casters afterwards
+// (gv_pool_view_bounds; tightenedDepth below)
+struct CascadeFit {
+    Mat4 stabilized;       // the stabilised light view
+    Vec3 sliceLo, sliceHi; // the slice's box in the light view, before zCoeff
+    Vec3 lo, hi;           // ... with the depth range pulled apart by zCoeff: what the projection is built from
+    Cascade cascade;       // what calcLightViewProj returns
+};
+
 // calcLightViewProj, csm.cpp:262-305. `view` is the camera view with its translation zeroed (graphics.cpp:201), so
 // everything here is camera-relative like the rest of the path.
-inline Cascade calcLightViewProj(const f32x4x4& view, f32x4 lightDir, float fieldOfView, float aspectRatio, float nearPlane,
-                                 float farPlane, float zCoeff, uint32_t shadowMapSize)
+inline CascadeFit fit(const f32x4x4& view, f32x4 lightDir, float fieldOfView, float aspectRatio, float nearPlane, float farPlane,
+                      float zCoeff, uint32_t shadowMapSize)
 {
     const Mat4 invViewProj = inverse(mul(perspRevZ(fieldOfView, aspectRatio, nearPlane, farPlane), fromF32(view)));
     Vec3 corners[8];
@@ -185,6 +195,9 @@ inline Cascade calcLightViewProj(const f32x4x4& view, f32x4 lightDir, float fiel
         lo = {std::min(lo.x, t.x), std::min(lo.y, t.y), std::min(lo.z, t.z)};
         hi = {std::max(hi.x, t.x), std::max(hi.y, t.y), std::max(hi.z, t.z)};
     }
+    CascadeFit out;
+    out.sliceLo = lo;
+    out.sliceHi = hi;
     lo.z = lo.z < 0.0 ? lo.z * zCoeff : lo.z / zCoeff;   // :296-297: pull the light's near / far apart so casters
     hi.z = hi.z < 0.0 ? hi.z / zCoeff : hi.z * zCoeff;   // outside the slice still land in the map
     const double unitsPerTexel = (hi.x - lo.x) / (double)shadowMapSize;  // :299-304: snap to texels
@@ -193,10 +206,43 @@ inline Cascade calcLightViewProj(const f32x4x4& view, f32x4 lightDir, float fiel
     lightCameraPos.z = std::floor(lightCameraPos.z / unitsPerTexel) * unitsPerTexel;
     const Vec3 snapped = transformPoint(inverse(lightView), lightCameraPos);
     const Mat4 stabilized = lookAt(snapped - dir, snapped);
-    Cascade out;
     const Vec3 offset = (dir * lo.z + center) * -1.0;  // :306
-    out.cameraOffset = f32x4((float)offset.x, (float)offset.y, (float)offset.z, 0.0f);
-    out.viewProj = toF32(mul(orthoRevZ(lo.x, hi.x, lo.y, hi.y, lo.z, hi.z), stabilized));  // :307-309
+    out.cascade.cameraOffset = f32x4((float)offset.x, (float)offset.y, (float)offset.z, 0.0f);
+    out.cascade.viewProj = toF32(mul(orthoRevZ(lo.x, hi.x, lo.y, hi.y, lo.z, hi.z), stabilized));  // :307-309
+    out.stabilized = stabilized;
+    out.lo = lo;
+    out.hi = hi;
+    return out;
+}
+inline Cascade calcLightViewProj(const f32x4x4& view, f32x4 lightDir, float fieldOfView, float aspectRatio, float nearPlane,
+                                 float farPlane, float zCoeff, uint32_t shadowMapSize)
+{
+    return fit(view, lightDir, fieldOfView, aspectRatio, nearPlane, farPlane, zCoeff, shadowMapSize).cascade;
+}
+
+// The basis to hand to gv_pool_view_bounds for the casters of this cascade: the affine part of the stabilised light view as 12
+// fp32 floats, c0.xyz c1.xyz c2.xyz c3.xyz. The records it is applied to are camera-relative, like the light view.
+inline void casterBasis(const CascadeFit& f, float (&basis)[12])
+{
+    for (int c = 0; c < 4; c++)
+        for (int r = 0; r < 3; r++)
+            basis[3 * c + r] = (float)f.stabilized.m[4 * c + r];
+}
+
+// The cascade with its depth range fitted to the casters that survived its cull (`bounds`: gv_pool_view_bounds of the cascade's
+// view in casterBasis): near no nearer than the first caster, far no farther than the last caster or the slice's own far side —
+// receivers inside the slice stay in range — and never outside the zCoeff range. x and y stay: the texel snapping depends on them.
+// cameraOffset stays. Bounds that are empty (lo > hi) or not finite, or a range that would be empty, give the cascade as it is.
+inline Cascade tightenedDepth(const CascadeFit& f, const GvViewBounds& bounds)
+{
+    const double casterLo = bounds.lo[2], casterHi = bounds.hi[2];
+    if (!std::isfinite(casterLo) || !std::isfinite(casterHi) || casterLo > casterHi)
+        return f.cascade;
+    const double z0 = std::max(f.lo.z, casterLo), z1 = std::min(f.hi.z, std::max(casterHi, f.sliceHi.z));
+    if (!(z0 < z1))
+        return f.cascade;
+    Cascade out = f.cascade;
+    out.viewProj = toF32(mul(orthoRevZ(f.lo.x, f.hi.x, f.lo.y, f.hi.y, z0, z1), f.stabilized));
     return out;
 }
 

@@ -128,6 +128,16 @@ class GvLodGeometry(C.Structure):
 LOD_DTYPE = np.dtype([("levels", np.uint32), ("switch_at", np.float32, (GV_MAX_LOD_LEVELS - 1,))])
 
 
+GV_MAX_BOUNDS_ITEMS = 8
+
+
+class GvViewBounds(C.Structure):
+    _fields_ = [("lo", C.c_float * 3), ("draw_count", C.c_uint32), ("hi", C.c_float * 3), ("nan_records", C.c_uint32)]
+
+
+BOUNDS_DTYPE = np.dtype([("lo", np.float32, (3,)), ("draw_count", np.uint32), ("hi", np.float32, (3,)), ("nan_records", np.uint32)])
+
+
 class GvCommandLayout(C.Structure):
     _fields_ = [("stride", C.c_uint32), ("count", C.c_uint32), ("instance_count", C.c_uint32), ("first", C.c_uint32),
                 ("first_instance", C.c_uint32), ("vertex_offset", C.c_uint32), ("draw", C.c_uint32)]
@@ -209,6 +219,7 @@ EXPORTS = [
     "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
     "gv_pool_group_draws",
     "gv_pool_cull_second_phase",
+    "gv_pool_view_bounds", "gv_pool_view_bounds_device", "gv_pool_view_bounds_fetch",
 ]
 
 _lib = None
@@ -344,6 +355,9 @@ def load():
     lib.gv_pool_lods_fetch.argtypes = [P, u32, C.POINTER(u32), u32, C.POINTER(u32), u32]
     lib.gv_pool_group_draws.argtypes = [P, u32, u32, u32, C.c_float]
     lib.gv_pool_cull_second_phase.argtypes = [P, u32, u32, u32, C.POINTER(GvView)]
+    lib.gv_pool_view_bounds.argtypes = [P, u32, C.POINTER(u32), C.POINTER(C.c_float), u32]
+    lib.gv_pool_view_bounds_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(u32)]
+    lib.gv_pool_view_bounds_fetch.argtypes = [P, u32, C.POINTER(GvViewBounds), u32]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -712,6 +726,34 @@ class GpuVisibility:
             pool_id = getattr(self, "_culled_pool", 0)
         gv = view if isinstance(view, GvView) or view is None else to_gv_view(view)
         self._check(self.lib.gv_pool_cull_second_phase(self.ctx, pool_id, first_view, second_view, None if gv is None else C.byref(gv)))
+
+    def view_bounds(self, pool_id, views, bases):
+        """gv_pool_view_bounds + gv_pool_view_bounds_fetch: the bounds of the draws of each listed view in its basis (bases: 12
+        float32 per item, c0.xyz c1.xyz c2.xyz c3.xyz; shape [items, 12] or [items, 4, 3]). Waits; returns a BOUNDS_DTYPE array,
+        one element per item."""
+        self.view_bounds_issue(pool_id, views, bases)
+        return self.view_bounds_fetch(pool_id, len(np.asarray(views).reshape(-1)))
+
+    def view_bounds_issue(self, pool_id, views, bases):
+        """gv_pool_view_bounds alone: asynchronous on the context's stream"""
+        v = np.ascontiguousarray(views, dtype=np.uint32).reshape(-1)
+        b = np.ascontiguousarray(bases, dtype=np.float32).reshape(-1)
+        if len(b) != 12 * len(v):
+            raise ValueError(f"view_bounds: {len(v)} views with {len(b)} basis floats (12 per item)")
+        self._check(self.lib.gv_pool_view_bounds(self.ctx, pool_id, v.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 b.ctypes.data_as(C.POINTER(C.c_float)), len(v)))
+
+    def view_bounds_fetch(self, pool_id, capacity=GV_MAX_BOUNDS_ITEMS):
+        """gv_pool_view_bounds_fetch: waits; the items of the pool's last gv_pool_view_bounds as a BOUNDS_DTYPE array"""
+        out = np.zeros(max(int(capacity), 1), BOUNDS_DTYPE)
+        self._check(self.lib.gv_pool_view_bounds_fetch(self.ctx, pool_id, out.ctypes.data_as(C.POINTER(GvViewBounds)), int(capacity)))
+        return out[:self.view_bounds_device(pool_id)[1]]
+
+    def view_bounds_device(self, pool_id):
+        """gv_pool_view_bounds_device: (device pointer of GvViewBounds[items], items) of the pool's last gv_pool_view_bounds"""
+        ptr, items = C.c_void_p(), C.c_uint32()
+        self._check(self.lib.gv_pool_view_bounds_device(self.ctx, pool_id, C.byref(ptr), C.byref(items)))
+        return ptr.value, int(items.value)
 
     # ---- picking ----
     def pick(self, rays, pool_ids=(0,), camera_position=(0, 0, 0), exclude=None):

@@ -699,6 +699,47 @@ int gv_pool_group_draws(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint3
  * pool's occupancy differs from the one the first view was culled with (cull again first). */
 int gv_pool_cull_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t first_view, uint32_t second_view, const GvView* view);
 
+/* ---- the bounds of a view's visible draws, on the device ----
+ * The reference fits every shadow cascade to its slice of the camera frustum and then pulls the light's near and far planes apart
+ * by a constant zCoeff (source/system/render/csm.cpp:294-295), because nobody knows where the casters are. gv_pool_view_bounds
+ * answers that question from the records a cull delivered: the box, in a basis the caller names, of every corner of every draw.
+ *   Items: item i is the pair (view_indices[i], bases + 12 i). A basis B is an affine 3x4 in the layout of bakedModel — c0.xyz
+ *     c1.xyz c2.xyz c3.xyz, column-major — for example the rotation and translation of a light view. A view may be listed more
+ *     than once with different bases.
+ *   Records: those of (pool_id, view) as a fetch would deliver them when the call is issued (after a gv_pool_sort, a
+ *     gv_pool_group_draws, of a second-phase view alike), n = the device draw count, never read by the host. Per record k: the POOL
+ *     slot s = visible_idx[k] (never index-mapped, never a mirror entry); M = the record's own bakedModel (camera-relative,
+ *     camera_offset NOT included); the box = aabb_min / aabb_max of slot s as the device mirror holds them when the call is issued —
+ *     the call uploads nothing and consumes no gv_mark_dirty mark; a slot that has stopped being a candidate since holds the empty
+ *     box (min == max == 0): its eight corners coincide at the pivot.
+ *   The eight corners p = M * (x, y, z, 1) with every row r as fma(c0[r], x, fma(c1[r], y, fma(c2[r], z, c3[r]))) — the cull's
+ *     own corners — and q[r] = fma(B.c0[r], p.x, fma(B.c1[r], p.y, fma(B.c2[r], p.z, B.c3[r]))) for r = 0, 1, 2.
+ *   lo[r] / hi[r]: the minimum / maximum of q[r] over all records and corners, in the order of the key bits ^ (sign ? 0xFFFFFFFF :
+ *     0x80000000): -0 sorts below +0, +-inf take part, a NaN takes no part (in that coordinate only). draw_count = n. nan_records =
+ *     the records with a NaN among their 24 coordinates. With nothing taking part lo[r] = +inf and hi[r] = -inf: lo > hi is how a
+ *     consumer sees "empty". The order of evaluation cannot change any output bit.
+ * State: a read (recorded culls and deferred sorts are launched first); asynchronous on gv_stream(ctx), no host synchronisation;
+ * two kernel launches whatever the counts, under GvStats::launches[GV_K_EMIT]. Records, sort state, emissions, selection and
+ * commands stay as they are. The result is the pool's (one per pool: a new call replaces it) and ends with the pool's next
+ * gv_cull or gv_pool_cull_second_phase.
+ * GV_E_ARG: a NULL ctx; a pool that is not bound; item_count 0 or above GV_MAX_BOUNDS_ITEMS; NULL view_indices or bases; a view
+ * index >= GV_MAX_VIEWS; an index no cull of the pool has ever had a view at. GV_E_STATE: a view without results (a later cull
+ * of fewer views ended it); a count-only view (emit_records == 0); a mirror that no longer covers the occupancy the view was culled
+ * with. An empty pool or a view without draws: GV_OK with the empty answer. A non-finite basis is not an error. */
+#define GV_MAX_BOUNDS_ITEMS 8u
+typedef struct GvViewBounds { /* 32 bytes */
+    float lo[3];
+    uint32_t draw_count;
+    float hi[3];
+    uint32_t nan_records;
+} GvViewBounds;
+int gv_pool_view_bounds(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_indices, const float* bases, uint32_t item_count);
+/* The last call's GvViewBounds[*item_count] in device memory, as plain floats (valid behind the call on gv_stream(ctx)).
+ * GV_E_STATE: no result since the pool's last cull. */
+int gv_pool_view_bounds_device(GvCtx* ctx, uint32_t pool_id, const void** bounds, uint32_t* item_count);
+/* Waits for the result and copies 32 bytes per item. GV_E_ARG: capacity below the item count (nothing is written). GV_E_STATE as above. */
+int gv_pool_view_bounds_fetch(GvCtx* ctx, uint32_t pool_id, GvViewBounds* bounds, uint32_t capacity);
+
 /* ---- the shared sorted arrays: the sorted lists of several mesh systems merged into ONE array, on the device ----
  * The reference keeps one array per sorted kind — transSortedMeshes, uiSortedMeshes, one translucent array per shadow pass — into
  * which every sorted system appends SortedMesh records tagged with its bufferIndex (mesh.cpp:247-261); one std::sort orders the
