@@ -2,7 +2,7 @@
 // the draws a view delivered, in a basis the caller names — what fits a shadow cascade's depth range, or a
 // camera's near / far, to what is actually visible. Read on the device from the delivered records, the box mirror and the slot ->
 // entry table as they stand: nothing is uploaded, no mark is consumed, nothing any other call can observe changes. Buffers of its
-// own (PoolState::bounds). Kernels: gv_bounds.hip.
+// own (PoolState::bounds); the checks and the fetch it shares with the other derived results are gv_ctx.hpp's. Kernels: gv_bounds.hip.
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -16,8 +16,8 @@ int gv_pool_view_bounds(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_indic
     static_assert(GV_MAX_BOUNDS_ITEMS == kMaxBoundsItems, "one kernel argument per item");
     if (!ctx)
         return GV_E_ARG;
-    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
-        return ctx->fail(GV_E_ARG, "gv_pool_view_bounds: pool %u is not bound", pool_id);
+    if (!bound_pool(ctx, "gv_pool_view_bounds", pool_id))
+        return GV_E_ARG;
     if (item_count == 0 || item_count > GV_MAX_BOUNDS_ITEMS || !view_indices || !bases)
         return ctx->fail(GV_E_ARG, "gv_pool_view_bounds: %u items (1 to %u) with view_indices %p and bases %p", item_count,
                          (uint32_t)GV_MAX_BOUNDS_ITEMS, (const void*)view_indices, (const void*)bases);
@@ -47,10 +47,9 @@ int gv_pool_view_bounds(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_indic
         if (entries < vs.occupancy || slots < vs.occupancy)
             return ctx->fail(GV_E_STATE, "gv_pool_view_bounds: the mirror of pool %u covers %u entries and %u slots of the %u view %u was culled with "
                              "(cull again first)", pool_id, entries, slots, vs.occupancy, view_indices[i]);
+        const ViewRecords r = records_of(vs);
         BoundsItem& it = launch.item[i];
-        it.count = vs.draw_count.ptr;
-        it.idx = vs.visible_idx.ptr;
-        it.model = vs.baked_model.ptr;
+        it.count = r.count, it.idx = r.idx, it.model = r.model;
         it.capacity = vs.occupancy;
         memcpy(it.basis, bases + (size_t)12 * i, sizeof(it.basis));
         launch.first_block[i + 1] = launch.first_block[i] + (vs.occupancy + kBoundsRecords - 1) / kBoundsRecords;
@@ -102,11 +101,7 @@ int gv_pool_view_bounds_fetch(GvCtx* ctx, uint32_t pool_id, GvViewBounds* bounds
     if (capacity < S.items)
         return ctx->fail(GV_E_ARG, "gv_pool_view_bounds_fetch: room for %u items, the pool holds %u", capacity, S.items);
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, S.h_out.reserve(GV_MAX_BOUNDS_ITEMS));
-    GV_HIP(ctx, hipMemcpyAsync(S.h_out.ptr, S.d_out.ptr, S.items * sizeof(BoundsResult), hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(bounds, S.h_out.ptr, S.items * sizeof(GvViewBounds));
-    return GV_OK;
+    return fetch_staged(ctx, S.h_out, GV_MAX_BOUNDS_ITEMS, S.d_out.ptr, S.items, bounds);
 }
 
 }  // extern "C"

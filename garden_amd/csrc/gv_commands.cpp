@@ -2,7 +2,8 @@
 // gv_pool_draw_commands_fetch of include/garden_vis.h: one indirect command per draw (or per run of draws of one geometry) of the
 // pool's last instance emission, in the caller's command struct, built on the device from the records and the emission's instance
 // ranges. The geometry ids are mirrored per pool slot (gv_mirror.cpp upload_geometry); buffers of its own
-// (PoolState::commands): neither the cull side nor the instance data is touched. Kernels: gv_commands.hip.
+// (PoolState::commands): neither the cull side nor the instance data is touched. Shared with the other derived results (gv_ctx.hpp):
+// the reader's checks, the target choice, the staged fetch. Kernels: gv_commands.hip.
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -36,7 +37,7 @@ int gv_pool_bind_geometry(GvCtx* ctx, uint32_t pool_id, const void* ids, uint32_
     G.bound = table != nullptr;
     if (!ids) {  // no column: no mirror
         G.wanted = false;
-        G.release();
+        G.SlotMirror::release();
         G.staged.pending = false;
     }
     if (!table) {
@@ -83,8 +84,9 @@ int gv_pool_emit_draw_commands(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uin
     static_assert(kDrawChunk % kCommandBlock == 0, "a chunk is a whole number of command_runs_kernel workgroups");
     if (!ctx)
         return GV_E_ARG;
-    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
-        return ctx->fail(GV_E_ARG, "gv_pool_emit_draw_commands: pool %u is not bound", pool_id);
+    const char* const fn = "gv_pool_emit_draw_commands";
+    if (!bound_pool(ctx, fn, pool_id))
+        return GV_E_ARG;
     if (flags & ~(uint32_t)GV_COMMANDS_MERGE_RUNS)
         return ctx->fail(GV_E_ARG, "gv_pool_emit_draw_commands: unknown flags 0x%x", flags);
     if (dst_device && (uintptr_t)dst_device % 16 != 0)
@@ -107,9 +109,8 @@ int gv_pool_emit_draw_commands(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uin
         const ViewState* vs = view_of(ctx, pool_id, I.listed[k]);
         if (!vs)
             return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_commands: pool %u view %u has no results", pool_id, I.listed[k]);
-        if (G.ids.ptr && G.occupancy < vs->occupancy)
-            return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_commands: the geometry ids of pool %u cover %u of the %u slots view %u was culled with",
-                             pool_id, G.occupancy, vs->occupancy, I.listed[k]);
+        if (int rc = column_covers(ctx, fn, kGeometryIds, pool_id, G.ids, G.occupancy, *vs, I.listed[k]))
+            return rc;
     }
     ZoneScope zone("Meshes Draw Commands");
     if (int rc = flush_sorts(ctx))  // the emission is a read: recorded culls and deferred sorts first (as the instance emissions)
@@ -118,17 +119,14 @@ int gv_pool_emit_draw_commands(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uin
     // behind a LOD selection (gv_pool_select_lods) the ids are the selected ones, per draw: the id mirror is not read, and marks made
     // after the selection wait for the next selection, emission without one, or gv_sync
     const bool selected = p.lod.views != 0;
-    if (G.ids.ptr && !selected) {  // marks made since the cull are seen by this emission; the first call uploads the column
-        G.wanted = true;
-        if (int rc = upload_geometry(ctx, p))
-            return rc;
-    }
+    if (int rc = selected ? GV_OK : want_column(ctx, p, G.ids, G, upload_geometry))  // marks made since the cull are seen by this emission
+        return rc;
     CommandLaunch launch{};
     const bool merge = (flags & GV_COMMANDS_MERGE_RUNS) != 0;
     uint64_t slots = 0;  // the sum of the listed views' occupancies: the host's upper bound of the commands
     for (uint32_t k = 0; k < m; k++) {
         const ViewState& vs = *view_of(ctx, pool_id, I.listed[k]);
-        launch.view[k] = CommandView{vs.draw_count.ptr, vs.visible_idx.ptr};
+        launch.view[k] = CommandView{records_of(vs).count, records_of(vs).idx};
         const uint32_t blocks = (vs.occupancy + kCommandBlock - 1) / kCommandBlock;
         // (with regions only the positions below R are ever written: the workgroups of R cover them)
         launch.first_block[k + 1] = launch.first_block[k] + (region_commands ? (region_commands + kCommandBlock - 1) / kCommandBlock : blocks);
@@ -154,14 +152,8 @@ int gv_pool_emit_draw_commands(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uin
     launch.first_instance_of = I.draws ? I.d_first.ptr : nullptr;
     launch.draw_starts = I.draws ? I.d_draw_starts.ptr : nullptr;
     const uint64_t positions = region_commands ? (uint64_t)m * region_commands : slots;
-    if (dst_device) {
-        launch.dst = static_cast<uint8_t*>(dst_device);
-        launch.capacity = (uint32_t)std::min<uint64_t>(capacity_bytes / L.stride, positions);
-    } else {
-        GV_HIP(ctx, M.d_data.reserve(std::max<size_t>((size_t)positions * L.stride, 16)));
-        launch.dst = M.d_data.ptr;
-        launch.capacity = (uint32_t)positions;
-    }
+    if (int rc = choose_target(ctx, dst_device, capacity_bytes, L.stride, positions, M.d_data, &launch.dst, &launch.capacity))
+        return rc;
     GV_HIP(ctx, M.d_counts.reserve(GV_MAX_VIEWS));
     launch.command_counts = M.d_counts.ptr;
     const bool scan = merge && launch.first_chunk[m] != 0;
@@ -215,9 +207,8 @@ int gv_pool_draw_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, si
     if (counts_capacity < M.views)
         return ctx->fail(GV_E_ARG, "gv_pool_draw_commands_fetch: room for %u counts, the emission listed %u views", counts_capacity, M.views);
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, M.h_counts.reserve(GV_MAX_VIEWS));
-    GV_HIP(ctx, hipMemcpyAsync(M.h_counts.ptr, M.d_counts.ptr, M.views * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = fetch_staged(ctx, M.h_counts, GV_MAX_VIEWS, M.d_counts.ptr, M.views))
+        return rc;
     uint64_t positions = (uint64_t)M.views * M.region;
     if (!M.region)
         for (uint32_t k = 0; k < M.views; k++)
@@ -228,11 +219,7 @@ int gv_pool_draw_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, si
     memcpy(command_counts, M.h_counts.ptr, M.views * sizeof(uint32_t));
     if (!dst_host || !held)
         return GV_OK;
-    GV_HIP(ctx, M.h_data.reserve(held * M.stride));
-    GV_HIP(ctx, hipMemcpyAsync(M.h_data.ptr, M.target, held * M.stride, hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(dst_host, M.h_data.ptr, held * M.stride);
-    return GV_OK;
+    return fetch_staged(ctx, M.h_data, held * M.stride, M.target, held * M.stride, dst_host);
 }
 
 }  // extern "C"

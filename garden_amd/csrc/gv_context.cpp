@@ -24,7 +24,7 @@ thread_local std::string g_create_error;
 // Frustum(viewProj) (mesh.cpp:815,867,869,900,902) — host side, once per view: Gribb-Hartmann rows of
 // the column-major matrix for a [0,1] clip depth, normalised; degenerate planes (|n|^2 < 1e-12, the
 // z >= 0 plane of the infinite reversed-Z projection) are dropped. DESIGN.md §"Canonical arithmetic".
-void build_view_params(const GvView& v, ViewParams* out)
+static void build_view_params(const GvView& v, ViewParams* out)
 {
     float row[4][4];
     for (int r = 0; r < 4; r++)
@@ -59,7 +59,7 @@ void build_view_params(const GvView& v, ViewParams* out)
     out->distance_2d = v.distance_2d ? 1u : 0u;
 }
 
-int reserve_view(GvCtx* ctx, ViewState& vs, uint32_t occupancy, bool emit)
+static int reserve_view(GvCtx* ctx, ViewState& vs, uint32_t occupancy, bool emit)
 {
     const size_t n = std::max<uint32_t>(occupancy, 1);
     const size_t blocks = blocks_of((uint32_t)n);
@@ -87,6 +87,27 @@ int reserve_view(GvCtx* ctx, ViewState& vs, uint32_t occupancy, bool emit)
         GV_HIP(ctx, vs.baked_model.reserve(n * 12));
         GV_HIP(ctx, vs.distance_sq.reserve(n));
     }
+    return GV_OK;
+}
+
+// A view of `pool_id` as a cull of the pool's current occupancy is about to write it: its buffers, its state, *vp for the kernels.
+int begin_view(GvCtx* ctx, ViewState& vs, uint32_t pool_id, const GvView& view, ViewParams* vp)
+{
+    const uint32_t occupancy = ctx->pools[pool_id].occupancy;
+    const bool emit = view.emit_records != 0;
+    if (int rc = reserve_view(ctx, vs, occupancy, emit))
+        return rc;
+    vs.pool_id = pool_id;
+    vs.occupancy = occupancy;
+    vs.main_pass = view.shadow_pass < 0;
+    vs.emitted = emit;
+    vs.valid = true;
+    vs.published = false, vs.records_fetched = false;
+    vs.sort_pending = 0;  // a sort of the previous results that nobody asked for any more
+    vs.sorted_dir = 0;
+    vs.ballots_current = true;  // every cull launch but the one-launch cull + emit of a small pool writes them
+    memcpy(vs.view_proj, view.view_proj, sizeof(vs.view_proj));
+    build_view_params(view, vp);
     return GV_OK;
 }
 
@@ -696,30 +717,11 @@ void gv_destroy(GvCtx* ctx)
     for (auto& p : ctx->pools) {
         for (auto& target : p.record_target)
             release_record_target(target);
-        p.d_a.release(); p.d_b.release(); p.d_link.release(); p.h_a.release(); p.h_b.release(); p.h_link.release(); p.d_orig.release(); p.d_inv.release(); p.d_index_map.release(); p.d_blk_lo.release(); p.d_blk_hi.release(); p.d_seed.release(); p.d_kept.release(); p.d_kept_flag.release(); p.d_blk_dirty.release(); p.d_hot.release();
-        p.instances.d_data.release(); p.instances.d_starts.release(); p.instances.h_data.release(); p.instances.h_starts.release();
-        p.payload.release();
-        p.instances.d_first.release(); p.instances.d_draw_starts.release(); p.instances.d_local.release();
-        p.instances.d_chunk_total.release(); p.instances.h_first.release();
-        p.counts.release(); p.counts.staged.destroy();
-        p.geometry.release(); p.geometry.d_table.release(); p.geometry.staged.destroy();
-        p.commands.d_data.release(); p.commands.d_counts.release(); p.commands.d_rank.release(); p.commands.d_chunk_total.release();
-        p.commands.d_draw_of.release(); p.commands.d_first_of.release(); p.commands.h_data.release(); p.commands.h_counts.release();
-        p.lod.release(); p.lod.d_table.release(); p.lod.staged.destroy(); p.lod.d_draw_geometry.release(); p.lod.d_level_counts.release();
-        p.lod.h_draw_geometry.release(); p.lod.h_level_counts.release();
-        p.bounds.d_partial.release(); p.bounds.d_out.release(); p.bounds.h_out.release();
+        p.release();
     }
     for (auto& per_pool : ctx->views)
-      for (auto& v : per_pool) {
-        v.mask.release(); v.chunk_count.release(); v.chunk_count2.release(); v.chunk_offset.release(); v.draw_count.release();
-        v.is_visible.release(); v.vis_flags.release(); v.visible_idx.release(); v.baked_model.release(); v.distance_sq.release();
-        v.alt_idx.release(); v.alt_model.release(); v.alt_dist.release(); v.sort_hist.release(); v.sort_ranks.release(); v.group_hist.release(); v.seen.release();
-        for (int k = 0; k < 2; k++) { v.sort_keys[k].release(); v.sort_vals[k].release(); v.sort_slots[k].release(); }
-        v.h_visible_idx.release(); v.h_draw_count.release(); v.h_baked_model.release();
-        v.h_distance_sq.release(); v.h_is_visible.release(); v.is_visible_slots.release();
-        v.h_records.release(); v.d_records.release();
-        v.tile_status.release(); v.tile_ticket.release();
-    }
+        for (auto& v : per_pool)
+            v.release();
     ctx->d_world.release(); ctx->d_xdirty.release(); ctx->d_raw.release(); ctx->d_examined.release();
     ctx->d_e2t.release(); ctx->d_flag.release(); ctx->h_flag.release(); ctx->h_ranges.release(); ctx->d_ranges.release();
     for (int k = 0; k < 2; k++) {
@@ -729,9 +731,8 @@ void gv_destroy(GvCtx* ctx)
     }
     ctx->uploads.destroy();
     ctx->d_xinv.release(); ctx->sc_xf.release(); ctx->dsc_xf.release(); ctx->sc_mesh.release(); ctx->dsc_mesh.release(); ctx->dsc_a.release(); ctx->dsc_c.release(); ctx->d_pick_keys.release(); ctx->h_pick_keys.release();
-    for (auto& m : ctx->merges) {
-        m.d_records.release(); m.d_counts.release(); m.h_records.release(); m.h_counts.release();
-    }
+    for (auto& m : ctx->merges)
+        m.release();
     ctx->d_depth.release(); ctx->d_mips.release(); ctx->d_mip_offset.release(); ctx->d_tick.release(); ctx->h_done.release();
     for (int k = 0; k < 2; k++) {
         ctx->h_tick[k].release();
@@ -882,7 +883,7 @@ int gv_pool_bind_ready(GvCtx* ctx, uint32_t pool_id, const void* data, uint32_t 
         GV_HIP(ctx, hipSetDevice(ctx->device));
         GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading it)
         p.counts.staged.pending = false;
-        p.counts.release();
+        p.counts.SlotMirror::release();  // (the mirror alone: the fence stays)
         std::vector<uint32_t>().swap(p.counts.held);
     }
     if (had != (data != nullptr) && p.bound)
@@ -1008,31 +1009,12 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
     ViewParams vps[GV_MAX_VIEWS];
     for (uint32_t v = 0; v < view_count; v++) {
         ViewState& vs = ctx->views[pool_id][v];
-        const bool emit = views[v].emit_records != 0;
-        rc = reserve_view(ctx, vs, p.occupancy, emit);
-        if (rc != GV_OK)
+        if ((rc = begin_view(ctx, vs, pool_id, views[v], &vps[v])) != GV_OK)
             return rc;
-        vs.pool_id = pool_id;
-        vs.occupancy = p.occupancy;
-        vs.main_pass = views[v].shadow_pass < 0;
-        vs.emitted = emit;
-        vs.valid = true;
-        vs.published = false, vs.records_fetched = false;
-        vs.sort_pending = 0;  // a sort of the previous results that nobody asked for any more
-        vs.sorted_dir = 0;
-        vs.ballots_current = true;  // every cull launch but the one-launch cull + emit of a small pool writes them
-        memcpy(vs.view_proj, views[v].view_proj, sizeof(vs.view_proj));
-        build_view_params(views[v], &vps[v]);
         if (p.occupancy == 0)
             GV_HIP(ctx, hipMemsetAsync(vs.draw_count.ptr, 0, 4, ctx->stream));
     }
-    p.instances.views = 0;  // the views' results are replaced from here on: the instance data made from the previous ones ends
-    p.commands.views = 0;   // ... and the commands made from that
-    p.lod.views = 0;        // ... and the levels selected for its draws
-    p.bounds.items = 0;     // ... and the bounds taken of them (gv_pool_view_bounds)
-    for (auto& m : ctx->merges)  // ... and so does every merged array this pool is a member of (gv_merge_sorted)
-        if ((m.pools >> pool_id) & 1u)
-            m.valid = false;
+    end_derived(ctx, p, Ends::ViewsReplaced);  // from here on: whatever was made from the previous results ends
     // gv_cull_batch_begin: an engine-sized pool whose views all want records is only RECORDED here; the first read
     // launches every recorded cull together (flush_culls)
     if (ctx->cull_batching) {

@@ -284,6 +284,11 @@ struct PoolState {
         DeviceBuf<uint32_t> d_draw_starts; // [views + 1]
         DeviceBuf<uint32_t> d_local, d_chunk_total;  // scratch between the two launches
         PinnedBuf<uint32_t> h_first;       // staging of gv_pool_draw_bases_fetch
+        void release()                     // (the caller has drained the stream; so for every release() below)
+        {
+            d_data.release(), d_starts.release(), h_data.release(), h_starts.release(), d_first.release(), d_draw_starts.release();
+            d_local.release(), d_chunk_total.release(), h_first.release();
+        }
     } instances;
     // The ready column on the device, one uint32 per POOL SLOT (indexed by visible_idx like the payload rows; a re-order of the
     // mirror does not concern it): exists only once gv_pool_emit_draw_instances has been called for a pool with a ready column
@@ -299,6 +304,11 @@ struct PoolState {
             SlotMirror::reset();
             sum = 0;
             over.clear();
+        }
+        void release()                     // everything (SlotMirror::release(): the mirror alone, its fence stays)
+        {
+            SlotMirror::release();
+            staged.destroy();
         }
     } counts;
     // gv_pool_bind_geometry: the geometry id column and the table it indexes. The ids on the device, one uint32 per POOL SLOT like
@@ -322,6 +332,12 @@ struct PoolState {
         DeviceBuf<GvGeometry> d_table;     // re-uploaded on every bind
         bool wanted = false;
         UploadFence staged;                // guards h_stage (its own: see UploadFence)
+        void release()                     // everything (SlotMirror::release(): the mirror alone)
+        {
+            SlotMirror::release();
+            staged.destroy();
+            d_table.release();
+        }
     } geometry;
     // gv_pool_set_command_layout / gv_pool_emit_draw_commands: buffers of their own, no cull result or instance data is touched
     struct Commands {
@@ -335,6 +351,11 @@ struct PoolState {
         uint8_t* target = nullptr;         // d_data.ptr or the caller's device memory
         uint32_t capacity = 0;             // command positions the target holds
         uint32_t views = 0, stride = 0, region = 0;
+        void release()
+        {
+            d_data.release(), d_counts.release(), d_rank.release(), d_chunk_total.release(), d_draw_of.release(), d_first_of.release();
+            h_data.release(), h_counts.release();
+        }
     } commands;
     // gv_pool_bind_lod / gv_pool_select_lods: the size column as bit patterns, one word per POOL SLOT like the ids above (the mirror
     // exists only once gv_pool_select_lods has been called for a pool with a size column), the table the base ids index, and the
@@ -352,6 +373,12 @@ struct PoolState {
         DeviceBuf<uint32_t> d_draw_geometry;  // g_k of the listed views' draws, back to back
         DeviceBuf<uint32_t> d_level_counts;   // [GV_MAX_VIEWS * GV_MAX_LOD_LEVELS]
         PinnedBuf<uint32_t> h_draw_geometry, h_level_counts;  // staging of gv_pool_lods_fetch
+        void release()                        // everything (SlotMirror::release(): the mirror alone)
+        {
+            SlotMirror::release();
+            staged.destroy();
+            d_table.release(), d_draw_geometry.release(), d_level_counts.release(), h_draw_geometry.release(), h_level_counts.release();
+        }
     } lod;
     // gv_pool_view_bounds: the bounds of the listed views' draws, buffers of their own (nothing a cull produced is touched)
     struct Bounds {
@@ -359,6 +386,7 @@ struct PoolState {
         DeviceBuf<BoundsPartial> d_partial;   // one row of keys per bounds_fold_kernel workgroup
         DeviceBuf<BoundsResult> d_out;        // GvViewBounds[GV_MAX_BOUNDS_ITEMS]
         PinnedBuf<BoundsResult> h_out;        // staging of gv_pool_view_bounds_fetch
+        void release() { d_partial.release(), d_out.release(), h_out.release(); }
     } bounds;
     // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
     // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
@@ -431,6 +459,13 @@ struct PoolState {
     PinnedBuf<float4> h_a;
     PinnedBuf<float2> h_b;
     PinnedBuf<uint32_t> h_link;
+    void release()  // every buffer of the pool and of what is derived from it (the record targets are the caller's: gv_destroy)
+    {
+        d_a.release(), d_b.release(), d_link.release(), h_a.release(), h_b.release(), h_link.release();
+        d_orig.release(), d_inv.release(), d_index_map.release();
+        d_blk_lo.release(), d_blk_hi.release(), d_blk_dirty.release(), d_hot.release(), d_seed.release(), d_kept.release(), d_kept_flag.release();
+        instances.release(), payload.release(), counts.release(), geometry.release(), commands.release(), lod.release(), bounds.release();
+    }
 };
 
 struct ViewState {
@@ -491,6 +526,16 @@ struct ViewState {
     uint8_t sorted_dir = 0;    // the direction of the last gv_pool_sort since this view's cull (1 ascending, 2 descending; 0: none):
                                // what gv_merge_sorted asks of a member
     bool published = false;  // small pool: the host buffers already hold this view's results (gv_results_fetch of a sibling view)
+    void release()
+    {
+        mask.release(), chunk_count.release(), chunk_count2.release(), chunk_offset.release(), draw_count.release();
+        is_visible.release(), vis_flags.release(), is_visible_slots.release(), visible_idx.release(), baked_model.release(), distance_sq.release();
+        alt_idx.release(), alt_model.release(), alt_dist.release(), sort_hist.release(), sort_ranks.release(), group_hist.release(), seen.release();
+        for (int k = 0; k < 2; k++)
+            sort_keys[k].release(), sort_vals[k].release(), sort_slots[k].release();
+        h_visible_idx.release(), h_draw_count.release(), h_baked_model.release(), h_distance_sq.release(), h_is_visible.release();
+        h_records.release(), d_records.release(), tile_status.release(), tile_ticket.release();
+    }
 };
 
 struct PendingEvent {
@@ -558,6 +603,7 @@ struct Context {
         DeviceBuf<uint32_t> d_counts;   // [items + 1]
         PinnedBuf<uint8_t> h_records;   // staging of gv_merge_fetch
         PinnedBuf<uint32_t> h_counts;
+        void release() { d_records.release(), d_counts.release(), h_records.release(), h_counts.release(); }
     } merges[GV_MAX_MERGE_GROUPS];
 
     PoolState pools[GV_MAX_POOLS];
@@ -734,6 +780,107 @@ struct KernelTimer {
 
 // host worker threads for the gathers (AoS component pools -> SoA staging) and the isVisible write-back: gv_workers.hpp
 
+// ---- derived results: what is made from a view's delivered records and kept per pool (PoolState::instances, commands, lod, bounds)
+// or per group (Context::merges) ----
+
+// When a derived result ends. The table, stated once:
+//     views     -> {instances, bounds, merges the pool is a member of}
+//     instances -> {commands, selection}
+// A result ends when what it was made from is replaced. A new derived result is one more line here, under what it is made from.
+enum class Ends {
+    ViewsReplaced,     // gv_cull, gv_pool_cull_second_phase: the views' results are replaced
+    EmissionReplaced,  // gv_pool_emit_instances, gv_pool_emit_draw_instances: the instance data is replaced
+    SelectionDropped,  // gv_pool_select_lods(NULL, 0), gv_pool_bind_lod without a table
+};
+static inline void end_derived(GvCtx* ctx, PoolState& p, Ends cause)
+{
+    switch (cause) {
+    case Ends::ViewsReplaced:
+        p.instances.views = 0;
+        p.bounds.items = 0;
+        for (auto& m : ctx->merges)
+            if ((m.pools >> (uint32_t)(&p - ctx->pools)) & 1u)
+                m.valid = false;
+        [[fallthrough]];  // the instances have ended, and with them:
+    case Ends::EmissionReplaced:
+        p.commands.views = 0;
+        [[fallthrough]];
+    case Ends::SelectionDropped:
+        p.lod.views = 0;
+    }
+}
+
+// What the readers of a view's records check alike (`fn`: the entry point's name, as it appears in the message).
+// The pool, when it is bound; NULL with the message set otherwise (GV_E_ARG).
+static inline PoolState* bound_pool(GvCtx* ctx, const char* fn, uint32_t pool_id)
+{
+    if (pool_id < GV_MAX_POOLS && ctx->pools[pool_id].bound)
+        return &ctx->pools[pool_id];
+    ctx->fail(GV_E_ARG, "%s: pool %u is not bound", fn, pool_id);
+    return nullptr;
+}
+// The views of the pool's last gv_cull: its leading valid ones.
+static inline uint32_t culled_views(const GvCtx* ctx, uint32_t pool_id)
+{
+    uint32_t culled = 0;
+    while (culled < GV_MAX_VIEWS && ctx->views[pool_id][culled].valid)
+        culled++;
+    return culled;
+}
+// A side column with one element per pool slot, when one is bound, must cover the slots a view was culled with: GV_E_STATE otherwise.
+struct ColumnName { const char *subject, *verb, *hint; };
+constexpr ColumnName kGeometryIds{"the geometry ids", "cover", ""}, kLodSizes{"the sizes", "cover", ""}, kReadyColumn{"the ready column", "covers", ""},
+    kPayloadRows{"the payload", "covers", " (gv_pool_bind_payload)"};
+static inline int column_covers(GvCtx* ctx, const char* fn, const ColumnName& name, uint32_t pool_id, const Column& column, uint32_t covered,
+                                const ViewState& vs, uint32_t view_index)
+{
+    if (!column.ptr || covered >= vs.occupancy)
+        return GV_OK;
+    return ctx->fail(GV_E_STATE, "%s: %s of pool %u %s %u of the %u slots view %u was culled with%s", fn, name.subject, pool_id, name.verb, covered,
+                     vs.occupancy, view_index, name.hint);
+}
+// ... and its mirror (PoolState::counts, geometry, lod) is wanted from here on and brought up to date: the first use uploads the column,
+// later ones the marks made since (upload: upload_counts, upload_geometry, upload_lod of gv_mirror.cpp). No column: no mirror.
+template <typename Mirror>
+static int want_column(GvCtx* ctx, PoolState& p, const Column& column, Mirror& mirror, int (*upload)(GvCtx*, PoolState&))
+{
+    if (!column.ptr)
+        return GV_OK;
+    mirror.wanted = true;
+    return upload(ctx, p);
+}
+// The read pointers of a view's delivered records; the launch fillers copy what they need into their own kernel arguments.
+struct ViewRecords { const uint32_t *count, *idx; const float *model, *dist; };
+static inline ViewRecords records_of(const ViewState& vs) { return ViewRecords{vs.draw_count.ptr, vs.visible_idx.ptr, vs.baked_model.ptr, vs.distance_sq.ptr}; }
+
+// Where an emission writes: the caller's device memory, clamped to the host's bound of the total, or the library's buffer, reserved
+// for that bound (16 bytes at least). *capacity: the items of `stride` bytes the target holds.
+static inline int choose_target(GvCtx* ctx, void* dst_device, size_t capacity_bytes, uint32_t stride, uint64_t bound, DeviceBuf<uint8_t>& own, uint8_t** target,
+                         uint32_t* capacity)
+{
+    if (dst_device) {
+        *target = static_cast<uint8_t*>(dst_device);
+        *capacity = (uint32_t)std::min<uint64_t>({capacity_bytes / stride, bound, UINT32_MAX});
+        return GV_OK;
+    }
+    GV_HIP(ctx, own.reserve(std::max<size_t>((size_t)bound * stride, 16)));
+    *target = own.ptr;
+    *capacity = (uint32_t)bound;
+    return GV_OK;
+}
+// A fetch: `count` elements from the device into the result's pinned staging (reserved for `room` elements), waited for, and — `to`
+// non-NULL — on into the caller's (pageable, never page-locked) array.
+template <typename T>
+static int fetch_staged(GvCtx* ctx, PinnedBuf<T>& stage, size_t room, const void* device, size_t count, void* to = nullptr)
+{
+    GV_HIP(ctx, stage.reserve(room));
+    GV_HIP(ctx, hipMemcpyAsync(stage.ptr, device, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (to)
+        memcpy(to, stage.ptr, count * sizeof(T));
+    return GV_OK;
+}
+
 void drain_events(GvCtx* ctx);
 
 // gv_exchange.cpp
@@ -746,8 +893,7 @@ int flush_recorded_culls(GvCtx* ctx, uint32_t pool);    // ... those that read `
 ViewBuffers view_buffers(ViewState& vs);
 // what gv_cull does per view in front of its launches, and the way out behind a cull that left ballot words and chunk totals
 // (gv_pool_cull_second_phase, gv_second.cpp, sets its view up and emits it the same way)
-void build_view_params(const GvView& v, ViewParams* out);
-int reserve_view(GvCtx* ctx, ViewState& vs, uint32_t occupancy, bool emit);
+int begin_view(GvCtx* ctx, ViewState& vs, uint32_t pool_id, const GvView& view, ViewParams* vp);  // buffers, the view's state as of a new cull, *vp
 HizDevice hiz_device(const GvCtx* ctx);
 int emit_view(GvCtx* ctx, ViewState& vs, const MeshMirror& mesh, const TransformMirror& xf, const ViewParams& vp, const ViewBuffers& vb,
               bool self_prefix, const float4* emit_world, const EmitSeed* seeds);

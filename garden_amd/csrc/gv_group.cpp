@@ -2,7 +2,7 @@
 // (DESIGN.md §4 item 12). The reorder goes where gv_pool_sort's goes — into the view's alternate record set, which is then swapped in
 // (sort_records_of / swap_in_sorted of gv_results.cpp) — so that every later step that defines draw k as "record k in delivery order"
 // composes with it unchanged. Keys, pairs and ranks use the view's sort scratch; the digit counts are a buffer of their own
-// (ViewState::group_hist). Kernels: gv_group.hip.
+// (ViewState::group_hist). The reader's checks are those of the derived results (gv_ctx.hpp). Kernels: gv_group.hip.
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -13,8 +13,9 @@ int gv_pool_group_draws(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint3
 {
     if (!ctx)
         return GV_E_ARG;
-    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
-        return ctx->fail(GV_E_ARG, "gv_pool_group_draws: pool %u is not bound", pool_id);
+    const char* const fn = "gv_pool_group_draws";
+    if (!bound_pool(ctx, fn, pool_id))
+        return GV_E_ARG;
     if (flags & ~GV_GROUP_BY_LOD)
         return ctx->fail(GV_E_ARG, "gv_pool_group_draws: unknown flags 0x%x", flags);
     if (!view_of(ctx, pool_id, view_index) || !view_of(ctx, pool_id, view_index)->emitted)
@@ -28,12 +29,10 @@ int gv_pool_group_draws(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint3
         return ctx->fail(GV_E_STATE, "gv_pool_group_draws: pool %u has no geometry bound (gv_pool_bind_geometry)", pool_id);
     if (by_lod && !S.bound)
         return ctx->fail(GV_E_STATE, "gv_pool_group_draws: GV_GROUP_BY_LOD and pool %u has no LOD table bound (gv_pool_bind_lod)", pool_id);
-    if (G.ids.ptr && G.occupancy < vs.occupancy)
-        return ctx->fail(GV_E_STATE, "gv_pool_group_draws: the geometry ids of pool %u cover %u of the %u slots view %u was culled with", pool_id,
-                         G.occupancy, vs.occupancy, view_index);
-    if (by_lod && S.sizes.ptr && S.occupancy < vs.occupancy)
-        return ctx->fail(GV_E_STATE, "gv_pool_group_draws: the sizes of pool %u cover %u of the %u slots view %u was culled with", pool_id,
-                         S.occupancy, vs.occupancy, view_index);
+    if (int rc = column_covers(ctx, fn, kGeometryIds, pool_id, G.ids, G.occupancy, vs, view_index))
+        return rc;
+    if (int rc = by_lod ? column_covers(ctx, fn, kLodSizes, pool_id, S.sizes, S.occupancy, vs, view_index) : GV_OK)
+        return rc;
     if (p.instances.views)  // group first, then emit: instance data written before the reorder would no longer match its draws
         return ctx->fail(GV_E_STATE, "gv_pool_group_draws: pool %u holds an instance emission since its last gv_cull", pool_id);
     if (!G.ids.ptr && !by_lod)  // every key is 0: the stable order is the order as it stands
@@ -45,16 +44,10 @@ int gv_pool_group_draws(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint3
     if (vs.occupancy == 0)
         return GV_OK;
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    if (G.ids.ptr) {  // marks made since the cull are seen by this call; the first use uploads the column (as gv_pool_select_lods)
-        G.wanted = true;
-        if (int rc = upload_geometry(ctx, p))
-            return rc;
-    }
-    if (by_lod && S.sizes.ptr) {
-        S.wanted = true;
-        if (int rc = upload_lod(ctx, p))
-            return rc;
-    }
+    if (int rc = want_column(ctx, p, G.ids, G, upload_geometry))  // marks made since the cull are seen by this call (as gv_pool_select_lods)
+        return rc;
+    if (int rc = by_lod ? want_column(ctx, p, S.sizes, S, upload_lod) : GV_OK)
+        return rc;
     const uint32_t n = vs.occupancy;  // the host's bound of the draw count: sizes the scratch and the grids
     SortRecords r{};
     if (int rc = sort_records_of(ctx, vs, r))

@@ -8,6 +8,7 @@
 // gv_pool_emit_draw_instances / gv_pool_set_instance_index_field / gv_pool_draw_bases_device / gv_pool_draw_bases_fetch: the same for
 // draws that take several instances — the ready count of the record's slot, read on the device from a mirror of the ready column
 // (gv_mirror.cpp upload_counts); two launches (draw_counts_kernel, draw_instances_kernel), the host never reads a count.
+// The checks, the target choice and the fetch it shares with the other derived results are gv_ctx.hpp's.
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -80,12 +81,10 @@ int check_emission(GvCtx* ctx, const char* fn, uint32_t pool_id, const uint32_t*
 {
     if (!ctx)
         return GV_E_ARG;
-    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
-        return ctx->fail(GV_E_ARG, "%s: pool %u is not bound", fn, pool_id);
+    if (!bound_pool(ctx, fn, pool_id))
+        return GV_E_ARG;
     PoolState& p = ctx->pools[pool_id];
-    uint32_t culled = 0;
-    while (culled < GV_MAX_VIEWS && ctx->views[pool_id][culled].valid)
-        culled++;
+    const uint32_t culled = culled_views(ctx, pool_id);
     if (!view_indices || view_count == 0 || view_count > culled)
         return ctx->fail(GV_E_ARG, "%s: %u views listed, the last gv_cull of pool %u had %u", fn, view_count, pool_id, culled);
     if (dst_device && (uintptr_t)dst_device % 16 != 0)
@@ -115,9 +114,8 @@ int check_emission(GvCtx* ctx, const char* fn, uint32_t pool_id, const uint32_t*
         if (!payload_fits(L, P, P.at))
             return ctx->fail(GV_E_ARG, "%s: the payload destinations of pool %u do not fit its instance layout (stride %u)", fn, pool_id, L.stride);
         for (uint32_t k = 0; k < view_count; k++)
-            if (P.occupancy < view_of(ctx, pool_id, view_indices[k])->occupancy)
-                return ctx->fail(GV_E_STATE, "%s: the payload of pool %u covers %u of the %u slots view %u was culled with "
-                                 "(gv_pool_bind_payload)", fn, pool_id, P.occupancy, view_of(ctx, pool_id, view_indices[k])->occupancy, view_indices[k]);
+            if (int rc = column_covers(ctx, fn, kPayloadRows, pool_id, P.src[0], P.occupancy, *view_of(ctx, pool_id, view_indices[k]), view_indices[k]))
+                return rc;
     }
     return GV_OK;
 }
@@ -133,11 +131,9 @@ uint32_t fill_launch(GvCtx* ctx, const PoolState& p, const uint32_t* view_indice
     const GvInstanceLayout L = p.instances.layout;
     for (uint32_t k = 0; k < view_count; k++) {
         const ViewState& vs = *view_of(ctx, pool_id, view_indices[k]);
+        const ViewRecords r = records_of(vs);
         InstanceView& w = launch.view[k];
-        w.count = vs.draw_count.ptr;
-        w.idx = vs.visible_idx.ptr;
-        w.model = vs.baked_model.ptr;
-        w.dist = vs.distance_sq.ptr;
+        w.count = r.count, w.idx = r.idx, w.model = r.model, w.dist = r.dist;
         memcpy(w.view_proj, vs.view_proj, sizeof(w.view_proj));
         launch.first_block[k + 1] = launch.first_block[k] + (vs.occupancy + kInstanceBlock - 1) / kInstanceBlock;
         slots += vs.occupancy;
@@ -177,7 +173,7 @@ uint32_t fill_launch(GvCtx* ctx, const PoolState& p, const uint32_t* view_indice
 }
 
 // what an emission that has been launched leaves for the fetches and for gv_pool_emit_draw_commands
-void note_emission(PoolState& p, const InstanceLaunch& launch, const uint32_t* view_indices, uint32_t view_count, bool with_payload, uint32_t index,
+void note_emission(GvCtx* ctx, PoolState& p, const InstanceLaunch& launch, const uint32_t* view_indices, uint32_t view_count, bool with_payload, uint32_t index,
                    bool draws)
 {
     PoolState::Instances& I = p.instances;
@@ -185,8 +181,7 @@ void note_emission(PoolState& p, const InstanceLaunch& launch, const uint32_t* v
     I.capacity = launch.capacity;
     I.views = view_count;
     std::copy(view_indices, view_indices + view_count, I.listed);
-    p.commands.views = 0;  // commands belong to the emission in front of them
-    p.lod.views = 0;       // ... and so do the levels selected for its draws
+    end_derived(ctx, p, Ends::EmissionReplaced);  // commands and selected levels belong to the emission in front of them
     I.emitted = I.layout;
     I.emitted_payload = 0;
     for (uint32_t f = 0; with_payload && f < p.payload.count; f++)
@@ -196,16 +191,6 @@ void note_emission(PoolState& p, const InstanceLaunch& launch, const uint32_t* v
         }
     I.emitted_index = index;
     I.draws = draws;
-}
-
-// the first `n` words of a starts table on the device into I.h_starts, waited for
-int fetch_starts(GvCtx* ctx, PoolState::Instances& I, const uint32_t* device, uint32_t n)
-{
-    GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, I.h_starts.reserve(GV_MAX_VIEWS + 1));
-    GV_HIP(ctx, hipMemcpyAsync(I.h_starts.ptr, device, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GV_OK;
 }
 
 }  // namespace
@@ -339,20 +324,14 @@ int gv_pool_emit_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* view_in
     InstanceLaunch launch{};
     uint64_t bound = 0;  // the host's upper bound of the total
     const uint32_t covered = fill_launch(ctx, p, view_indices, view_count, with_payload, GV_NONE, launch, bound);
-    if (dst_device) {
-        launch.dst = static_cast<uint8_t*>(dst_device);
-        launch.capacity = (uint32_t)std::min<uint64_t>(capacity_bytes / L.stride, bound);
-    } else {
-        GV_HIP(ctx, I.d_data.reserve(std::max<size_t>((size_t)bound * L.stride, 16)));
-        launch.dst = I.d_data.ptr;
-        launch.capacity = (uint32_t)bound;
-    }
+    if (int rc = choose_target(ctx, dst_device, capacity_bytes, L.stride, bound, I.d_data, &launch.dst, &launch.capacity))
+        return rc;
     GV_HIP(ctx, I.d_starts.reserve(GV_MAX_VIEWS + 1));
     launch.starts = I.d_starts.ptr;
     // fields and payload are disjoint and inside the stride: together as many bytes as the stride = all of it
     launch.staged = with_payload && covered == L.stride && L.stride <= kMaxStagedInstanceStride;
     GV_HIP(ctx, launch_instances(launch, ctx->stream));
-    note_emission(p, launch, view_indices, view_count, with_payload, GV_NONE, false);
+    note_emission(ctx, p, launch, view_indices, view_count, with_payload, GV_NONE, false);
     return GV_OK;
 }
 
@@ -380,9 +359,8 @@ int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* vi
                          "instances per draw (GV_MAX_DRAW_INSTANCES)", pool_id, p.ready_over_count, GV_MAX_DRAW_INSTANCES);
     if (counted)
         for (uint32_t k = 0; k < view_count; k++)
-            if (p.occupancy < view_of(ctx, pool_id, view_indices[k])->occupancy)
-                return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_instances: the ready column of pool %u covers %u of the %u slots view %u was culled "
-                                 "with", pool_id, p.occupancy, view_of(ctx, pool_id, view_indices[k])->occupancy, view_indices[k]);
+            if (int rc = column_covers(ctx, fn, kReadyColumn, pool_id, p.ready, p.occupancy, *view_of(ctx, pool_id, view_indices[k]), view_indices[k]))
+                return rc;
     ZoneScope zone("Meshes Draw Instances");
     if (int rc = flush_sorts(ctx))  // the emission is a read: recorded culls and deferred sorts first (as gv_pool_results_device)
         return rc;
@@ -391,8 +369,7 @@ int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* vi
         if (int rc = upload_payload(ctx, p))
             return rc;
     if (counted) {  // ... and so are the counts (getInstancesAsync is read at draw time, mesh.cpp:597); the first call uploads the column
-        K.wanted = true;
-        if (int rc = upload_counts(ctx, p))
+        if (int rc = want_column(ctx, p, p.ready, K, upload_counts))
             return rc;
         // a mark made since the last gv_sync may have put a count above the limit into the mirror (ready_over_count has not seen it);
         // live: a candidate as of that sync, hence possibly a draw of the cull
@@ -410,17 +387,11 @@ int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* vi
         launch.first_chunk[k + 1] = launch.first_chunk[k] + (view_of(ctx, pool_id, view_indices[k])->occupancy + kDrawChunk - 1) / kDrawChunk;
     // the host's upper bound of the INSTANCES: a view draws a slot at most once
     const uint64_t bound = counted ? (uint64_t)view_count * K.sum : slots;
-    if (dst_device) {
-        launch.base.dst = static_cast<uint8_t*>(dst_device);
-        launch.base.capacity = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(capacity_bytes / L.stride, bound), UINT32_MAX);
-    } else {
-        if (bound > UINT32_MAX)
-            return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_instances: %u views of pool %u may take %llu instances, more than 32 bits hold: pass a "
-                             "caller-owned target (dst_device) sized for what is drawn", view_count, pool_id, (unsigned long long)bound);
-        GV_HIP(ctx, I.d_data.reserve(std::max<size_t>((size_t)bound * L.stride, 16)));
-        launch.base.dst = I.d_data.ptr;
-        launch.base.capacity = (uint32_t)bound;
-    }
+    if (!dst_device && bound > UINT32_MAX)
+        return ctx->fail(GV_E_STATE, "gv_pool_emit_draw_instances: %u views of pool %u may take %llu instances, more than 32 bits hold: pass a "
+                         "caller-owned target (dst_device) sized for what is drawn", view_count, pool_id, (unsigned long long)bound);
+    if (int rc = choose_target(ctx, dst_device, capacity_bytes, L.stride, bound, I.d_data, &launch.base.dst, &launch.base.capacity))
+        return rc;
     GV_HIP(ctx, I.d_starts.reserve(GV_MAX_VIEWS + 1));
     GV_HIP(ctx, I.d_draw_starts.reserve(GV_MAX_VIEWS + 1));
     GV_HIP(ctx, I.d_first.reserve((size_t)slots + 1));
@@ -435,7 +406,7 @@ int gv_pool_emit_draw_instances(GvCtx* ctx, uint32_t pool_id, const uint32_t* vi
     launch.index_at = I.index_at;
     launch.base.staged = covered == L.stride && L.stride <= kMaxStagedInstanceStride;
     GV_HIP(ctx, launch_draw_instances(launch, ctx->stream));
-    note_emission(p, launch.base, view_indices, view_count, with_payload, I.index_at, true);
+    note_emission(ctx, p, launch.base, view_indices, view_count, with_payload, I.index_at, true);
     return GV_OK;
 }
 
@@ -481,16 +452,15 @@ int gv_pool_draw_bases_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* first_insta
                          "(gv_pool_emit_draw_instances)", pool_id);
     if (starts_capacity < I.views + 1)
         return ctx->fail(GV_E_ARG, "gv_pool_draw_bases_fetch: room for %u starts, the emission listed %u views", starts_capacity, I.views);
-    if (int rc = fetch_starts(ctx, I, I.d_draw_starts.ptr, I.views + 1))
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = fetch_staged(ctx, I.h_starts, GV_MAX_VIEWS + 1, I.d_draw_starts.ptr, I.views + 1))
         return rc;
     const uint32_t draws = I.h_starts.ptr[I.views];
     if (first_instance && capacity < (uint64_t)draws + 1)
         return ctx->fail(GV_E_ARG, "gv_pool_draw_bases_fetch: room for %u words, %u draws and the closing total", capacity, draws);
     if (first_instance) {
-        GV_HIP(ctx, I.h_first.reserve((size_t)draws + 1));
-        GV_HIP(ctx, hipMemcpyAsync(I.h_first.ptr, I.d_first.ptr, ((size_t)draws + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        memcpy(first_instance, I.h_first.ptr, ((size_t)draws + 1) * sizeof(uint32_t));
+        if (int rc = fetch_staged(ctx, I.h_first, (size_t)draws + 1, I.d_first.ptr, (size_t)draws + 1, first_instance))
+            return rc;
     }
     memcpy(draw_starts, I.h_starts.ptr, (I.views + 1) * sizeof(uint32_t));
     return GV_OK;
@@ -539,7 +509,8 @@ int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t
         return ctx->fail(GV_E_STATE, "gv_pool_instances_fetch: pool %u has no instance data since its last gv_cull", pool_id);
     if (starts_capacity < I.views + 1)
         return ctx->fail(GV_E_ARG, "gv_pool_instances_fetch: room for %u starts, the emission listed %u views", starts_capacity, I.views);
-    if (int rc = fetch_starts(ctx, I, I.d_starts.ptr, I.views + 1))
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = fetch_staged(ctx, I.h_starts, GV_MAX_VIEWS + 1, I.d_starts.ptr, I.views + 1))
         return rc;
     const uint32_t total = I.h_starts.ptr[I.views];
     const GvInstanceLayout L = I.emitted;
@@ -551,9 +522,8 @@ int gv_pool_instances_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t
         return GV_OK;
     // whole instances into the library's pinned staging, then field by field into the caller's (pageable, never page-locked) array:
     // the bytes between the fields are the plugin's and stay as they are
-    GV_HIP(ctx, I.h_data.reserve((size_t)held * L.stride));
-    GV_HIP(ctx, hipMemcpyAsync(I.h_data.ptr, I.target, (size_t)held * L.stride, hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = fetch_staged(ctx, I.h_data, (size_t)held * L.stride, I.target, (size_t)held * L.stride))
+        return rc;
     Field f[kMaxFields];  // the layout's, the payload fields the emission wrote, the index field of a draw emission
     const uint32_t n = instance_fields(L, I.emitted_payload, I.emitted_at, I.emitted_bytes, I.emitted_index, f);
     uint8_t* const to = static_cast<uint8_t*>(dst_host);

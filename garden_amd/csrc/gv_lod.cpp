@@ -2,7 +2,8 @@
 // of detail of every draw of the pool's last instance emission, selected on the device from the delivered records, the geometry id
 // mirror and a size per pool slot. The sizes are mirrored per pool slot (gv_mirror.cpp upload_lod); buffers
 // of its own (PoolState::lod): neither the cull side nor the instance data is touched. A command emission behind the selection
-// takes its ids (gv_commands.cpp). Kernel: gv_lod.hip.
+// takes its ids (gv_commands.cpp). Shared with the other derived results (gv_ctx.hpp): the reader's checks, the staged fetch, and
+// end_derived, which says what a dropped selection ends. Kernel: gv_lod.hip.
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -38,12 +39,12 @@ int gv_pool_bind_lod(GvCtx* ctx, uint32_t pool_id, const void* sizes, uint32_t s
     S.bound = table != nullptr;
     if (!sizes) {  // no column: no mirror
         S.wanted = false;
-        S.release();
+        S.SlotMirror::release();
         S.staged.pending = false;
     }
     if (!table) {
         S.d_table.release();
-        S.views = 0;  // (a selection needs its binding: a command emission goes back to the id mirror)
+        end_derived(ctx, ctx->pools[pool_id], Ends::SelectionDropped);  // (a selection needs its binding: a command emission goes back to the id mirror)
         return GV_OK;
     }
     GV_HIP(ctx, S.d_table.reserve(table_count));
@@ -56,14 +57,15 @@ int gv_pool_select_lods(GvCtx* ctx, uint32_t pool_id, const float* view_scale, u
 {
     if (!ctx)
         return GV_E_ARG;
-    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
-        return ctx->fail(GV_E_ARG, "gv_pool_select_lods: pool %u is not bound", pool_id);
+    const char* const fn = "gv_pool_select_lods";
+    if (!bound_pool(ctx, fn, pool_id))
+        return GV_E_ARG;
     PoolState& p = ctx->pools[pool_id];
     PoolState::Instances& I = p.instances;
     PoolState::Geometry& G = p.geometry;
     PoolState::Lod& S = p.lod;
     if (!view_scale && !view_count) {  // dropped: a command emission takes the id mirror again
-        S.views = 0;
+        end_derived(ctx, p, Ends::SelectionDropped);
         return GV_OK;
     }
     if (!view_scale)
@@ -81,32 +83,25 @@ int gv_pool_select_lods(GvCtx* ctx, uint32_t pool_id, const float* view_scale, u
         const ViewState* vs = view_of(ctx, pool_id, I.listed[k]);
         if (!vs)
             return ctx->fail(GV_E_STATE, "gv_pool_select_lods: pool %u view %u has no results", pool_id, I.listed[k]);
-        if (G.ids.ptr && G.occupancy < vs->occupancy)
-            return ctx->fail(GV_E_STATE, "gv_pool_select_lods: the geometry ids of pool %u cover %u of the %u slots view %u was culled with", pool_id,
-                             G.occupancy, vs->occupancy, I.listed[k]);
-        if (S.sizes.ptr && S.occupancy < vs->occupancy)
-            return ctx->fail(GV_E_STATE, "gv_pool_select_lods: the sizes of pool %u cover %u of the %u slots view %u was culled with", pool_id,
-                             S.occupancy, vs->occupancy, I.listed[k]);
+        if (int rc = column_covers(ctx, fn, kGeometryIds, pool_id, G.ids, G.occupancy, *vs, I.listed[k]))
+            return rc;
+        if (int rc = column_covers(ctx, fn, kLodSizes, pool_id, S.sizes, S.occupancy, *vs, I.listed[k]))
+            return rc;
     }
     ZoneScope zone("Meshes LODs");
     if (int rc = flush_sorts(ctx))  // the selection is a read: recorded culls and deferred sorts first (as the emissions)
         return rc;
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    if (G.ids.ptr) {  // marks made since the cull are seen by this selection; the first call uploads the column
-        G.wanted = true;
-        if (int rc = upload_geometry(ctx, p))
-            return rc;
-    }
-    if (S.sizes.ptr) {
-        S.wanted = true;
-        if (int rc = upload_lod(ctx, p))
-            return rc;
-    }
+    if (int rc = want_column(ctx, p, G.ids, G, upload_geometry))  // marks made since the cull are seen by this selection
+        return rc;
+    if (int rc = want_column(ctx, p, S.sizes, S, upload_lod))
+        return rc;
     LodLaunch launch{};
     uint64_t slots = 0;  // the sum of the listed views' occupancies: the host's upper bound of the draws
-    for (uint32_t k = 0; k < m; k++) {  // the read pointers of the delivered records, as gv_instance.cpp fills InstanceView
+    for (uint32_t k = 0; k < m; k++) {
         const ViewState& vs = *view_of(ctx, pool_id, I.listed[k]);
-        launch.view[k] = LodView{vs.draw_count.ptr, vs.visible_idx.ptr, vs.baked_model.ptr, view_scale[k]};
+        const ViewRecords r = records_of(vs);
+        launch.view[k] = LodView{r.count, r.idx, r.model, view_scale[k]};
         launch.first_block[k + 1] = launch.first_block[k] + (vs.occupancy + kLodBlock - 1) / kLodBlock;
         slots += vs.occupancy;
     }
@@ -153,9 +148,8 @@ int gv_pool_lods_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* draw_geometry, ui
         return ctx->fail(GV_E_ARG, "gv_pool_lods_fetch: room for %u counts, the selection holds %u views of %u levels", counts_capacity, S.views,
                          GV_MAX_LOD_LEVELS);
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, S.h_level_counts.reserve(GV_MAX_VIEWS * GV_MAX_LOD_LEVELS));
-    GV_HIP(ctx, hipMemcpyAsync(S.h_level_counts.ptr, S.d_level_counts.ptr, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = fetch_staged(ctx, S.h_level_counts, GV_MAX_VIEWS * GV_MAX_LOD_LEVELS, S.d_level_counts.ptr, words))
+        return rc;
     uint64_t draws = 0;  // every draw is counted at exactly one level
     for (uint32_t w = 0; w < words; w++)
         draws += S.h_level_counts.ptr[w];
@@ -164,11 +158,7 @@ int gv_pool_lods_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* draw_geometry, ui
     memcpy(level_counts, S.h_level_counts.ptr, words * sizeof(uint32_t));
     if (!draw_geometry || !draws)
         return GV_OK;
-    GV_HIP(ctx, S.h_draw_geometry.reserve((size_t)draws));
-    GV_HIP(ctx, hipMemcpyAsync(S.h_draw_geometry.ptr, S.d_draw_geometry.ptr, (size_t)draws * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(draw_geometry, S.h_draw_geometry.ptr, (size_t)draws * sizeof(uint32_t));
-    return GV_OK;
+    return fetch_staged(ctx, S.h_draw_geometry, (size_t)draws, S.d_draw_geometry.ptr, (size_t)draws, draw_geometry);
 }
 
 }  // extern "C"

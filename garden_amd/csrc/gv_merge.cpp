@@ -2,7 +2,8 @@
 // reference (transSortedMeshes / uiSortedMeshes / the shadow passes' translucent arrays: every sorted system appends its records,
 // mesh.cpp:247-261, one sort orders the whole array, mesh.cpp:296-326, renderSorted walks it, mesh.cpp:659-760), made on the
 // device from the lists gv_pool_sort has ordered. One merge_sorted_kernel launch per call (gv_merge.hip); buffers of its own
-// (Context::merges): the members' results are left as a read through gv_pool_results_device leaves them.
+// (Context::merges): the members' results are left as a read through gv_pool_results_device leaves them. Target choice and staged
+// fetch are those of the other derived results (gv_ctx.hpp).
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -48,9 +49,7 @@ int gv_merge_sorted(GvCtx* ctx, const GvMergeGroup* groups, uint32_t group_count
             const GvMergeItem& it = G.items[i];
             if (it.pool_id >= GV_MAX_POOLS || !ctx->pools[it.pool_id].bound)
                 return ctx->fail(GV_E_ARG, "gv_merge_sorted: group %u item %u: pool %u is not bound", G.group_id, i, it.pool_id);
-            uint32_t culled = 0;
-            while (culled < GV_MAX_VIEWS && ctx->views[it.pool_id][culled].valid)
-                culled++;
+            const uint32_t culled = culled_views(ctx, it.pool_id);
             if (it.view_index >= culled)
                 return ctx->fail(GV_E_ARG, "gv_merge_sorted: group %u item %u: view %u, the last gv_cull of pool %u had %u", G.group_id, i,
                                  it.view_index, it.pool_id, culled);
@@ -102,11 +101,9 @@ int gv_merge_sorted(GvCtx* ctx, const GvMergeGroup* groups, uint32_t group_count
             const GvMergeItem& it = G.items[i];
             const ViewState& vs = ctx->views[it.pool_id][it.view_index];
             const PoolState& p = ctx->pools[it.pool_id];
+            const ViewRecords r = records_of(vs);
             MergeList& l = launch.list[launch.lists];
-            l.count = vs.draw_count.ptr;
-            l.idx = vs.visible_idx.ptr;
-            l.model = vs.baked_model.ptr;
-            l.dist = vs.distance_sq.ptr;
+            l.count = r.count, l.idx = r.idx, l.model = r.model, l.dist = r.dist;
             l.slot_map = (p.result_flags & GV_RESULTS_MAP_RECORDS) ? p.d_index_map.ptr : nullptr;
             l.component_stride = it.component_stride;
             l.buffer_index = it.buffer_index;
@@ -115,14 +112,9 @@ int gv_merge_sorted(GvCtx* ctx, const GvMergeGroup* groups, uint32_t group_count
             widest = std::max(widest, vs.occupancy);
             members |= 1u << it.pool_id;
         }
-        if (G.dst_device) {
-            g.dst = static_cast<uint8_t*>(G.dst_device);
-            g.capacity = (uint32_t)std::min<uint64_t>(G.capacity_bytes / G.stride, bound);
-        } else {
-            GV_HIP(ctx, M.d_records.reserve(std::max<size_t>((size_t)bound * G.stride, 16)));
-            g.dst = M.d_records.ptr;
-            g.capacity = (uint32_t)std::min<uint64_t>(bound, 0xFFFFFFFEu);
-        }
+        // (a bound of GV_MAX_MERGE_ITEMS occupancies of 28 bits each stays below the clamp: it changes no size)
+        if (int rc = choose_target(ctx, G.dst_device, G.capacity_bytes, G.stride, std::min<uint64_t>(bound, 0xFFFFFFFEu), M.d_records, &g.dst, &g.capacity))
+            return rc;
         GV_HIP(ctx, M.d_counts.reserve(GV_MAX_MERGE_ITEMS + 1));
         g.counts = M.d_counts.ptr;
         M.pools = members;
@@ -163,9 +155,8 @@ int gv_merge_fetch(GvCtx* ctx, uint32_t group_id, void* dst_host, size_t bytes, 
     if (counts_capacity < M.items + 1)
         return ctx->fail(GV_E_ARG, "gv_merge_fetch: room for %u counts, the group has %u items", counts_capacity, M.items);
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, M.h_counts.reserve(GV_MAX_MERGE_ITEMS + 1));
-    GV_HIP(ctx, hipMemcpyAsync(M.h_counts.ptr, M.d_counts.ptr, (M.items + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = fetch_staged(ctx, M.h_counts, GV_MAX_MERGE_ITEMS + 1, M.d_counts.ptr, M.items + 1))
+        return rc;
     const uint32_t total = M.h_counts.ptr[M.items];
     if (dst_host && bytes < (size_t)total * M.stride)
         return ctx->fail(GV_E_ARG, "gv_merge_fetch: %zu bytes for %u records of %u bytes", bytes, total, M.stride);
@@ -175,9 +166,8 @@ int gv_merge_fetch(GvCtx* ctx, uint32_t group_id, void* dst_host, size_t bytes, 
         return GV_OK;
     // into the library's pinned staging, then into the caller's (pageable, never page-locked) array
     const size_t size = (size_t)held * M.stride;
-    GV_HIP(ctx, M.h_records.reserve(size));
-    GV_HIP(ctx, hipMemcpyAsync(M.h_records.ptr, M.target, size, hipMemcpyDeviceToHost, ctx->stream));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = fetch_staged(ctx, M.h_records, size, M.target, size))
+        return rc;
     uint8_t* const to = static_cast<uint8_t*>(dst_host);
     const uint8_t* const from = M.h_records.ptr;
     constexpr size_t kPiece = (size_t)256 << 10;  // (as copy_staged_records: 256 KB pieces over the worker threads)

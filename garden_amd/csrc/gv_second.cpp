@@ -2,7 +2,8 @@
 // item 13). The first phase is gv_cull as it stands, against last frame's pyramid; once the pyramid has been rebuilt from what was
 // drawn, this call culls the pool again and leaves in `second_view` the records of that cull whose slot the first view does not
 // hold: an ordinary emitted view. Its own launches (gv_second.hip) are the seen set, the masked cull and the union of the isVisible
-// bytes; compaction and records are the cull's (emit_view of gv_context.cpp), on the second view's own ViewState.
+// bytes; compaction and records are the cull's (begin_view and emit_view of gv_context.cpp), on the second view's own ViewState; what the
+// call ends is what a cull ends (end_derived of gv_ctx.hpp).
 #include "gv_ctx.hpp"
 
 using namespace gv;
@@ -15,8 +16,8 @@ int gv_pool_cull_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t first_view,
         return GV_E_ARG;
     if (!view)
         return ctx->fail(GV_E_ARG, "gv_pool_cull_second_phase: view is NULL");
-    if (pool_id >= GV_MAX_POOLS || !ctx->pools[pool_id].bound)
-        return ctx->fail(GV_E_ARG, "gv_pool_cull_second_phase: pool %u is not bound", pool_id);
+    if (!bound_pool(ctx, "gv_pool_cull_second_phase", pool_id))
+        return GV_E_ARG;
     if (first_view >= GV_MAX_VIEWS || second_view >= GV_MAX_VIEWS || first_view == second_view)
         return ctx->fail(GV_E_ARG, "gv_pool_cull_second_phase: views %u and %u (two different indices below %u)", first_view, second_view,
                          (uint32_t)GV_MAX_VIEWS);
@@ -40,28 +41,11 @@ int gv_pool_cull_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t first_view,
     if (int rc = sync_mirror(ctx))  // ... and a cull: it sees the pools as they are
         return rc;
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = reserve_view(ctx, vs2, p.occupancy, true))
+    ViewParams vp;  // (the masked cull writes the ballot words: the mask form of this view carries the new entries only)
+    if (int rc = begin_view(ctx, vs2, pool_id, *view, &vp))
         return rc;
-    vs2.pool_id = pool_id;
-    vs2.occupancy = p.occupancy;
-    vs2.main_pass = view->shadow_pass < 0;
-    vs2.emitted = true;
-    vs2.valid = true;
-    vs2.published = false, vs2.records_fetched = false;
-    vs2.sort_pending = 0;
-    vs2.sorted_dir = 0;
-    vs2.ballots_current = true;  // the masked cull writes them: the mask form of this view carries the new entries only
-    memcpy(vs2.view_proj, view->view_proj, sizeof(vs2.view_proj));
-    ViewParams vp;
-    build_view_params(*view, &vp);
     // what a gv_cull of the pool ends, this call ends too; the pool's other views stay (invalidate_views_beyond is gv_cull's)
-    p.instances.views = 0;
-    p.commands.views = 0;
-    p.lod.views = 0;
-    p.bounds.items = 0;
-    for (auto& m : ctx->merges)
-        if ((m.pools >> pool_id) & 1u)
-            m.valid = false;
+    end_derived(ctx, p, Ends::ViewsReplaced);
     if (p.occupancy == 0) {
         GV_HIP(ctx, hipMemsetAsync(vs2.draw_count.ptr, 0, 4, ctx->stream));
         return GV_OK;
@@ -73,7 +57,7 @@ int gv_pool_cull_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t first_view,
     const size_t words = second_seen_words(p.occupancy);
     GV_HIP(ctx, vs2.seen.reserve(words));
     GV_HIP(ctx, hipMemsetAsync(vs2.seen.ptr, 0, words * sizeof(unsigned long long), ctx->stream));
-    GV_LAUNCH(ctx, GV_K_CULL, launch_second_seen(vs1.draw_count.ptr, vs1.visible_idx.ptr, vs1.occupancy, p.inv.empty() ? nullptr : p.d_inv.ptr,
+    GV_LAUNCH(ctx, GV_K_CULL, launch_second_seen(records_of(vs1).count, records_of(vs1).idx, vs1.occupancy, p.inv.empty() ? nullptr : p.d_inv.ptr,
                                                  p.occupancy, p.occupancy, vs2.seen.ptr, ctx->stream));
     const ViewBuffers vb = view_buffers(vs2);
     ViewParams cvp = vp;  // as the cull kernel sees the view: the isVisible bytes are left to the emit that follows

@@ -534,32 +534,10 @@ def test_host_orchestration_and_exchange_under_thread_sanitizer(tmp_path):
     threads, the host worker pool, the frame sequences — libgarden_vis keeps no unsynchronised state between contexts (the
     process-wide pieces are the RCCL binding, made once, and the worker pool behind its lock). Zero reports."""
     import subprocess
-    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    csrc, stub = os.path.join(root, "garden_amd", "csrc"), os.path.join(root, "tests", "cpp", "hip_stub")
-    clang = "/opt/rocm/lib/llvm/bin/clang++"
-    stubs = tmp_path / "kernel_stubs.cpp"
-    gen = subprocess.run([sys.executable, os.path.join(stub, "make_kernel_stubs.py"), csrc], capture_output=True, text=True)
-    assert gen.returncode == 0, gen.stderr
-    stubs.write_text(gen.stdout)
-    flags = ["-std=c++17", "-O1", "-g", "-fsanitize=thread", "-I" + stub, "-I" + csrc]
-    sources = [str(stubs), os.path.join(stub, "reorder_cpu.cpp"), os.path.join(stub, "exchange_cpu.cpp"),
-               os.path.join(root, "tests", "cpp", "host_orchestration_test.cpp")] + \
-              [os.path.join(csrc, f) for f in ("gv_context.cpp", "gv_results.cpp", "gv_mirror.cpp", "gv_exchange.cpp", "gv_scene.cpp", "gv_workers.cpp")]
-    builds, objects = [], []
-    for src in sources:
-        obj = str(tmp_path / (os.path.basename(src) + ".o"))
-        objects.append(obj)
-        builds.append(subprocess.Popen([clang, *flags, "-c", src, "-o", obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    for b in builds:
-        out, _ = b.communicate(timeout=900)
-        assert b.returncode == 0, out[-3000:]
-    exe = str(tmp_path / "host_orchestration_test_tsan")
-    link = subprocess.run([clang, "-fsanitize=thread", *objects, "-o", exe, "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert link.returncode == 0, link.stderr[-3000:]
-    transport = str(tmp_path / "librccl_stub_tsan.so")
-    tb = subprocess.run([clang, *flags, "-fPIC", "-shared", os.path.join(root, "tests", "cpp", "rccl_stub", "rccl_stub.cpp"), "-o", transport,
-                         "-lrt", "-lpthread"], capture_output=True, text=True)
-    assert tb.returncode == 0, tb.stderr[-3000:]
+    import host_build
+    exe, _ = host_build.build_host_program(tmp_path, "host_orchestration_test.cpp", host_build.ORCHESTRATION_SOURCES, ("-fsanitize=thread",),
+                                           "host_orchestration_test_tsan")
+    transport = host_build.build_stub_transport(tmp_path, ("-fsanitize=thread",), "librccl_stub_tsan.so")
     run = subprocess.run([exe], capture_output=True, text=True, timeout=900,
                          env=dict(os.environ, GV_RCCL_LIBRARY=transport, TSAN_OPTIONS="halt_on_error=0"))
     text = run.stdout + run.stderr
@@ -596,38 +574,13 @@ def test_host_orchestration_under_address_and_ub_sanitizers(tmp_path):
     Hi-Z builds, sweeps, scene ingest, tiles, error codes — in four context configurations. TEST-ONLY stub: the product library
     still refuses to run without a gfx950 device (test_abi.py)."""
     import subprocess
-    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    csrc, stub = os.path.join(root, "garden_amd", "csrc"), os.path.join(root, "tests", "cpp", "hip_stub")
-    clang = "/opt/rocm/lib/llvm/bin/clang++"  # (g++ 11 has no _Float16, which gv_context.cpp's RG16F read-back uses)
-    stubs = tmp_path / "kernel_stubs.cpp"
-    gen = subprocess.run([sys.executable, os.path.join(stub, "make_kernel_stubs.py"), csrc], capture_output=True, text=True)
-    assert gen.returncode == 0 and gen.stdout.count("hipError_t launch_") > 30, gen.stderr
-    stubs.write_text(gen.stdout)
-    # (-fno-sanitize=function: RCCL's entry points are called through dlsym'ed pointers whose parameter structs are declared on
-    # each side of the C boundary — same layout, different C++ types)
-    flags = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize=function", "-fno-sanitize-recover=undefined",
-             "-I" + stub, "-I" + csrc]
-    sources = [str(stubs), os.path.join(stub, "reorder_cpu.cpp"), os.path.join(stub, "exchange_cpu.cpp"),
-               os.path.join(root, "tests", "cpp", "host_orchestration_test.cpp")] + \
-              [os.path.join(csrc, f) for f in ("gv_context.cpp", "gv_results.cpp", "gv_mirror.cpp", "gv_exchange.cpp", "gv_scene.cpp", "gv_workers.cpp")]
-    objects = []
-    builds = []
-    for src in sources:  # compiled side by side
-        obj = str(tmp_path / (os.path.basename(src) + ".o"))
-        objects.append(obj)
-        builds.append(subprocess.Popen([clang, *flags, "-c", src, "-o", obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    for b in builds:
-        out, _ = b.communicate(timeout=900)
-        assert b.returncode == 0, out[-3000:]
-    exe = str(tmp_path / "host_orchestration_test")
-    link = subprocess.run([clang, "-fsanitize=address,undefined", *objects, "-o", exe, "-lpthread", "-ldl"], capture_output=True, text=True)
-    assert link.returncode == 0, link.stderr[-3000:]
+    import host_build
+    exe, launches = host_build.build_host_program(tmp_path, "host_orchestration_test.cpp", host_build.ORCHESTRATION_SOURCES, host_build.ASAN_UBSAN,
+                                                  "host_orchestration_test")
+    assert launches > 30
     # the exchange step with 1 / 2 / 3 / 8 ranks (threads): RCCL's entry points over shared memory (tests/cpp/rccl_stub), built
     # against the same stub runtime and sanitizers, named to the library with GV_RCCL_LIBRARY
-    transport = str(tmp_path / "librccl_stub_cpu.so")
-    tb = subprocess.run([clang, *flags, "-fPIC", "-shared", os.path.join(root, "tests", "cpp", "rccl_stub", "rccl_stub.cpp"), "-o", transport,
-                         "-lrt", "-lpthread"], capture_output=True, text=True)
-    assert tb.returncode == 0, tb.stderr[-3000:]
+    transport = host_build.build_stub_transport(tmp_path, host_build.ASAN_UBSAN, "librccl_stub_cpu.so")
     run = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=dict(os.environ, GV_RCCL_LIBRARY=transport))
     assert run.returncode == 0 and "host orchestration: ok" in run.stdout, (run.stdout + run.stderr)[-4000:]
     assert "sort plan table: 27 plans and 6 hints as worked out by hand: ok" in run.stdout, run.stdout[:2000]  # (sort_plan, sort_mode_for_hint)
