@@ -23,6 +23,7 @@
 #include "gv_group_kernels.hpp"
 #include "gv_second_kernels.hpp"
 #include "gv_bounds_kernels.hpp"
+#include "gv_delta_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -388,6 +389,30 @@ struct PoolState {
         PinnedBuf<BoundsResult> h_out;        // staging of gv_pool_view_bounds_fetch
         void release() { d_partial.release(), d_out.release(), h_out.release(); }
     } bounds;
+    // gv_pool_view_delta: per channel the set of POOL slots its last call saw (the baseline, one bit per slot) and that call's answer.
+    // HISTORY, not something made from the views: no cull, emission, sort, re-order or re-bind ends it (end_derived has no line for
+    // it); only the drop call, the call's own commit and gv_destroy change it. Header-only: no other host source calls gv_delta.cpp.
+    struct Delta {
+        struct Channel {
+            DeviceBuf<unsigned long long> d_set[2];  // d_set[held]: the baseline; the other one receives the next call's current set,
+            uint32_t held = 0;                       // ... and the commit is the swap (a failed call has touched the spare only)
+            uint32_t baseline_slots = 0;             // slots the baseline covers (0: empty — before the first call, after a drop)
+            bool result = false;                     // the buffers below hold an answer
+            uint32_t universe = 0;                   // U of that answer: the room of d_slots it may use
+            DeviceBuf<uint32_t> d_slots;             // appeared at [0, a), vanished at [a, a + v)
+            DeviceBuf<uint32_t> d_counts;            // {a, v, |C|, U}
+            PinnedBuf<uint32_t> h_slots, h_counts;   // staging of gv_pool_view_delta_fetch (GvViewDelta points into it)
+            void drop() { baseline_slots = 0, result = false, universe = 0; }
+            void release() { d_set[0].release(), d_set[1].release(), d_slots.release(), d_counts.release(), h_slots.release(), h_counts.release(); }
+        } channel[GV_MAX_DELTA_CHANNELS];
+        DeviceBuf<DeltaTotals> d_totals;             // scratch between the count and the place launch (stream order: shared by the channels)
+        void release()
+        {
+            for (Channel& c : channel)
+                c.release();
+            d_totals.release();
+        }
+    } delta;
     // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
     // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
     // transform mirror does not concern it); read by gv_pool_emit_instances only
@@ -465,6 +490,7 @@ struct PoolState {
         d_orig.release(), d_inv.release(), d_index_map.release();
         d_blk_lo.release(), d_blk_hi.release(), d_blk_dirty.release(), d_hot.release(), d_seed.release(), d_kept.release(), d_kept_flag.release();
         instances.release(), payload.release(), counts.release(), geometry.release(), commands.release(), lod.release(), bounds.release();
+        delta.release();
     }
 };
 
@@ -787,6 +813,9 @@ struct KernelTimer {
 //     views     -> {instances, bounds, merges the pool is a member of}
 //     instances -> {commands, selection}
 // A result ends when what it was made from is replaced. A new derived result is one more line here, under what it is made from.
+// PoolState::delta (gv_pool_view_delta) has NO line: its baseline is history — the set a channel saw at its last call, kept in pool
+// slot numbers so that neither a cull nor a re-order of the mirror concerns it — and its answer is self-contained slot numbers that
+// stay true whatever replaces the views. Both live until the channel's next call, its drop call or gv_destroy.
 enum class Ends {
     ViewsReplaced,     // gv_cull, gv_pool_cull_second_phase: the views' results are replaced
     EmissionReplaced,  // gv_pool_emit_instances, gv_pool_emit_draw_instances: the instance data is replaced

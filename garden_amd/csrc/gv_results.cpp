@@ -563,8 +563,8 @@ static int count_instances(GvCtx* ctx, const ViewState& vs, const PoolState& poo
 // The main pass's isVisible bytes arrive in pool-slot order; write_back streams them into the components themselves
 // (meshRenderView->isVisible = ...  mesh.cpp:144,152,161,166) or, with GV_RESULTS_MAP_VISIBLE, straight into the caller's WORLD pool
 // through the share's slot -> world slot table (holes and slots past the world's occupancy are skipped; ranks own disjoint world
-// slots). Every store is a cache line of its own: the workers pay from kWriteBackFloor components up (profiles/r06_write_back_ab.txt).
-constexpr uint32_t kWriteBackFloor = 49152;
+// slots). Every store is a cache line of its own: the workers pay from kWriteBackFloor (gv_workers.hpp) components up
+// (profiles/r06_write_back_ab.txt).
 static int write_back_visible(GvCtx* ctx, const ViewState& vs, const PoolState& pool, int write_back, GvResult* out)
 {
     if (!vs.main_pass || !vs.occupancy)

@@ -44,4 +44,8 @@ void parallel_ranges(uint32_t first, uint32_t count, F&& fn, uint32_t floor_item
     });
 }
 
+// The isVisible write-back (gv_results.cpp write_back_visible, gv_delta.cpp): every store is a cache line of its own, the workers
+// pay from this many stores up (profiles/r06_write_back_ab.txt)
+constexpr uint32_t kWriteBackFloor = 49152;
+
 }  // namespace gv

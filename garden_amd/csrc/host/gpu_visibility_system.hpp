@@ -753,7 +753,7 @@ private:
                         if (passes[v] >= 0)
                             fetchCounters(shadowSortedBuffers[(uint32_t)passes[v]][shadowIndex], meshSystem, p, v, false);
                         else
-                            fetchCounters(sortedBuffers[bufferIndex], meshSystem, p, v, true);
+                            fetchCounters(sortedBuffers[bufferIndex], meshSystem, p, v, writeBackVisible);
                     } else if (passes[v] >= 0) {
                         const uint32_t s = (uint32_t)passes[v], first = shadowTransDrawIndex[s];
                         const uint32_t added = append(shadowTransMeshes[s], shadowTransDrawIndex[s], shadowSortedBuffers[s][shadowIndex], meshSystem, p, v,
@@ -765,10 +765,10 @@ private:
                         }
                         shadowTransRuns[s].push_back(shadowTransDrawIndex[s]);
                     } else if (sp.type == MeshRenderType::UI) {
-                        append(uiSortedMeshes, uiDrawIndex, sortedBuffers[bufferIndex], meshSystem, p, v, true, bufferIndex);
+                        append(uiSortedMeshes, uiDrawIndex, sortedBuffers[bufferIndex], meshSystem, p, v, writeBackVisible, bufferIndex);
                         uiRuns.push_back(uiDrawIndex);
                     } else {
-                        append(transSortedMeshes, transDrawIndex, sortedBuffers[bufferIndex], meshSystem, p, v, true, bufferIndex);
+                        append(transSortedMeshes, transDrawIndex, sortedBuffers[bufferIndex], meshSystem, p, v, writeBackVisible, bufferIndex);
                         transRuns.push_back(transDrawIndex);
                     }
                 }
@@ -779,7 +779,7 @@ private:
                         fill(sb[passes[v]], meshSystem, p, v, false);
                 for (uint32_t v = 0; v < passes.size(); v++)
                     if (passes[v] < 0)
-                        fill(unsortedBuffers[sp.bufferIndex], meshSystem, p, v, true);
+                        fill(unsortedBuffers[sp.bufferIndex], meshSystem, p, v, writeBackVisible);
             }
         }
         if (deviceMerge) {  // every shared array: grown to what its members could deliver, filled by one fetch
@@ -1331,6 +1331,10 @@ public:
     bool isSystemSorted(uint32_t p) const { return plan.at(p).sorted; }
     // view v of mesh system p as the last frame culled it (second_phase.hpp re-tests the light pass with it)
     const GvView& getSystemView(uint32_t p, uint32_t v) const { return plan.at(p).views.at(v); }
+
+    // false (one context; opt-in): the light pass's fetches leave MeshRenderComponent::isVisible alone — GpuVisibleDelta::writeBack
+    // (visible_delta.hpp) stores the bytes that changed since last frame instead of the whole column
+    bool writeBackVisible = true;
 };
 
 }  // namespace garden

@@ -138,6 +138,15 @@ class GvViewBounds(C.Structure):
 BOUNDS_DTYPE = np.dtype([("lo", np.float32, (3,)), ("draw_count", np.uint32), ("hi", np.float32, (3,)), ("nan_records", np.uint32)])
 
 
+GV_MAX_DELTA_CHANNELS = 4
+GV_DELTA_RESTART = 1
+
+
+class GvViewDelta(C.Structure):
+    _fields_ = [("appeared", C.POINTER(C.c_uint32)), ("vanished", C.POINTER(C.c_uint32)), ("appeared_count", C.c_uint32),
+                ("vanished_count", C.c_uint32), ("visible_count", C.c_uint32), ("slots", C.c_uint32)]
+
+
 class GvCommandLayout(C.Structure):
     _fields_ = [("stride", C.c_uint32), ("count", C.c_uint32), ("instance_count", C.c_uint32), ("first", C.c_uint32),
                 ("first_instance", C.c_uint32), ("vertex_offset", C.c_uint32), ("draw", C.c_uint32)]
@@ -220,6 +229,7 @@ EXPORTS = [
     "gv_pool_group_draws",
     "gv_pool_cull_second_phase",
     "gv_pool_view_bounds", "gv_pool_view_bounds_device", "gv_pool_view_bounds_fetch",
+    "gv_pool_view_delta", "gv_pool_view_delta_device", "gv_pool_view_delta_fetch",
 ]
 
 _lib = None
@@ -358,6 +368,9 @@ def load():
     lib.gv_pool_view_bounds.argtypes = [P, u32, C.POINTER(u32), C.POINTER(C.c_float), u32]
     lib.gv_pool_view_bounds_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(u32)]
     lib.gv_pool_view_bounds_fetch.argtypes = [P, u32, C.POINTER(GvViewBounds), u32]
+    lib.gv_pool_view_delta.argtypes = [P, u32, u32, C.POINTER(u32), u32, u32]
+    lib.gv_pool_view_delta_device.argtypes = [P, u32, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_pool_view_delta_fetch.argtypes = [P, u32, u32, C.c_int, C.POINTER(GvViewDelta)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -754,6 +767,42 @@ class GpuVisibility:
         ptr, items = C.c_void_p(), C.c_uint32()
         self._check(self.lib.gv_pool_view_bounds_device(self.ctx, pool_id, C.byref(ptr), C.byref(items)))
         return ptr.value, int(items.value)
+
+    # ---- what came into view and what left it ----
+    def view_delta(self, pool_id, views, channel=0, restart=False, write_back=False):
+        """gv_pool_view_delta + gv_pool_view_delta_fetch: the pool slots the listed views hold now and the channel's last call did not
+        (appeared), and the other way round (vanished), ascending each. Waits; returns copies: dict(appeared, vanished,
+        visible_count, slots). write_back: 1 / 0 into the isVisible bytes of exactly those slots (the bytes must have held the
+        channel's baseline before)."""
+        self.view_delta_issue(pool_id, views, channel, restart)
+        return self.view_delta_fetch(pool_id, channel, write_back)
+
+    def view_delta_issue(self, pool_id, views, channel=0, restart=False):
+        """gv_pool_view_delta alone: asynchronous on the context's stream; commits the current set as the channel's baseline"""
+        v = np.ascontiguousarray(views, dtype=np.uint32).reshape(-1)
+        if len(v) == 0:
+            raise ValueError("view_delta: no views (view_delta_drop drops a channel)")
+        self._check(self.lib.gv_pool_view_delta(self.ctx, pool_id, channel, v.ctypes.data_as(C.POINTER(C.c_uint32)), len(v),
+                                                GV_DELTA_RESTART if restart else 0))
+
+    def view_delta_fetch(self, pool_id, channel=0, write_back=False):
+        """gv_pool_view_delta_fetch: waits; the channel's last answer as copies"""
+        d = GvViewDelta()
+        self._check(self.lib.gv_pool_view_delta_fetch(self.ctx, pool_id, channel, 1 if write_back else 0, C.byref(d)))
+        a, v = int(d.appeared_count), int(d.vanished_count)
+        return dict(appeared=np.ctypeslib.as_array(d.appeared, shape=(a,)).copy() if a else np.zeros(0, np.uint32),
+                    vanished=np.ctypeslib.as_array(d.vanished, shape=(v,)).copy() if v else np.zeros(0, np.uint32),
+                    visible_count=int(d.visible_count), slots=int(d.slots))
+
+    def view_delta_device(self, pool_id, channel=0):
+        """gv_pool_view_delta_device: (device pointer of the slot words, device pointer of the four counts) of the channel's last answer"""
+        slots, counts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_pool_view_delta_device(self.ctx, pool_id, channel, C.byref(slots), C.byref(counts)))
+        return slots.value, counts.value
+
+    def view_delta_drop(self, pool_id, channel=0):
+        """gv_pool_view_delta(NULL, 0): the channel's baseline and result are dropped; its next call behaves as a first call"""
+        self._check(self.lib.gv_pool_view_delta(self.ctx, pool_id, channel, None, 0, 0))
 
     # ---- picking ----
     def pick(self, rays, pool_ids=(0,), camera_position=(0, 0, 0), exclude=None):

@@ -740,6 +740,65 @@ int gv_pool_view_bounds_device(GvCtx* ctx, uint32_t pool_id, const void** bounds
 /* Waits for the result and copies 32 bytes per item. GV_E_ARG: capacity below the item count (nothing is written). GV_E_STATE as above. */
 int gv_pool_view_bounds_fetch(GvCtx* ctx, uint32_t pool_id, GvViewBounds* bounds, uint32_t capacity);
 
+/* ---- what came into view and what left it since the last call, on the device ----
+ * Every step above answers "what is visible now". The consumers of visibility on the host ask "what CHANGED": streaming, animation
+ * and audio want the slots that came into view and the slots that left it, and the isVisible write-back only has to touch the bytes
+ * that differ from last frame's — a few percent under a moving camera. The reference keeps no history of visibility: the rule is
+ * this build's.
+ *   Channels: a pool has GV_MAX_DELTA_CHANNELS channels that know nothing of each other (one for the light pass's write-back,
+ *     another for "visible in any cascade" ...). A channel keeps a BASELINE P, a set of POOL slots covering P.slots slots; empty
+ *     (P.slots = 0) until the channel's first call.
+ *   The current set C: the union over the listed views (1 .. GV_MAX_VIEWS, none twice) of
+ *     - a view with emitted records: the slots visible_idx[0 .. n) as a fetch would deliver them when the call is issued, n the
+ *       device draw count, never read by the host. POOL slots: never index-mapped, never mirror entries. Sorted, grouped and
+ *       second-phase views alike;
+ *     - a count-only view of the main pass (emit_records == 0, shadow_pass < 0): the slots whose is_visible byte is 1 in the bytes a
+ *       fetch would deliver at that moment.
+ *     C.slots = the largest occupancy among the listed views; a record slot at or beyond it is ignored. Listing the two views of a
+ *     two-phase frame gives the union of the phases (the set of the second view's is_visible bytes), the second view alone the
+ *     newly visible rest.
+ *   The answer: U = max(P.slots, C.slots); a set that does not cover a slot does not hold it. appeared = C \ P and vanished = P \ C,
+ *     each in ASCENDING slot order, in one device buffer of U words — appeared at [0, a), vanished at [a, a + v) — and
+ *     counts = {a, v, |C|, U} as four uint32. Every output word is defined by the two sets alone.
+ *   Commit: the same call makes C the channel's baseline, on the device, in stream order: a second call with nothing culled in
+ *     between answers two empty lists and the same |C|. GV_DELTA_RESTART takes P as empty for this call (appeared = all of C).
+ *     gv_pool_view_delta(ctx, pool, channel, NULL, 0, 0) drops the channel's baseline and result. A failed call changes nothing
+ *     (an allocation failure, GV_E_OOM, may end the channel's previous result; never its baseline).
+ *   Lifetime: the baseline is history. gv_cull, gv_pool_cull_second_phase, emissions, sorts, re-orders of the mirror and re-binds of
+ *     the pool with another occupancy leave it alone; only the drop call, the call's own commit and gv_destroy change it. The result
+ *     is slot numbers of its own and lives until the channel's next call.
+ * State: a read (recorded culls and deferred sorts are launched first); uploads nothing, consumes no mark, changes nothing any other
+ * call can observe. Asynchronous on gv_stream(ctx), no host synchronisation. Launches, fixed by the host from view_count alone and
+ * counted under GvStats::launches[GV_K_EMIT]: one per listed view, then two.
+ * GV_E_ARG: a NULL ctx; a pool that is not bound; channel >= GV_MAX_DELTA_CHANNELS; view_count > GV_MAX_VIEWS; NULL view_indices
+ * with a non-zero count; a view index >= GV_MAX_VIEWS or listed twice; an index no cull of the pool ever had a view at; unknown
+ * flag bits. GV_E_STATE: a listed view without results (a later cull of fewer views ended it); a count-only shadow view (it has
+ * neither records nor bytes). An empty pool or views without draws: GV_OK with C empty. */
+#define GV_MAX_DELTA_CHANNELS 4u
+#define GV_DELTA_RESTART 1u
+typedef struct GvViewDelta {
+    const uint32_t* appeared;  /* [appeared_count] pool slots, ascending */
+    const uint32_t* vanished;  /* [vanished_count] pool slots, ascending */
+    uint32_t appeared_count, vanished_count;
+    uint32_t visible_count;    /* |C| */
+    uint32_t slots;            /* U */
+} GvViewDelta;
+int gv_pool_view_delta(GvCtx* ctx, uint32_t pool_id, uint32_t channel, const uint32_t* view_indices, uint32_t view_count, uint32_t flags);
+/* The channel's last answer in device memory: *slots the U words, *counts the four (valid behind the call on gv_stream(ctx)).
+ * GV_E_ARG: a NULL ctx or output, a pool or channel out of range. GV_E_STATE: the channel holds no result. */
+int gv_pool_view_delta_device(GvCtx* ctx, uint32_t pool_id, uint32_t channel, const void** slots, const void** counts);
+/* Copies the four counts, waits, copies a + v words, waits. The pointers of *out go into the result's pinned staging and stay valid
+ * until the channel's next call. write_back != 0: stores 1 into the isVisible byte of every appeared slot and 0 into that of every
+ * vanished slot, and touches NO other byte — the target is the one gv_pool_results_fetch(write_back = 1) uses: the bound component
+ * column or, with GV_RESULTS_MAP_VISIBLE, visible_base + index_map[slot] * visible_stride (holes and slots beyond visible_count
+ * skipped); on the library's worker threads from the same floor up. Slots at or beyond the pool's bound occupancy are skipped: a
+ * pool that shrank has no component there any more.
+ * THE CONTRACT of the write-back: the caller's bytes are right afterwards only if they held the BASELINE before. The first frame
+ * therefore does a normal gv_pool_results_fetch(..., write_back = 1), or a GV_DELTA_RESTART call over zeroed bytes; and nobody else
+ * writes those bytes in between.
+ * GV_E_ARG: a NULL ctx or out, a pool or channel out of range. GV_E_STATE: no result; write_back without a target. */
+int gv_pool_view_delta_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t channel, int write_back, GvViewDelta* out);
+
 /* ---- the shared sorted arrays: the sorted lists of several mesh systems merged into ONE array, on the device ----
  * The reference keeps one array per sorted kind — transSortedMeshes, uiSortedMeshes, one translucent array per shadow pass — into
  * which every sorted system appends SortedMesh records tagged with its bufferIndex (mesh.cpp:247-261); one std::sort orders the
