@@ -733,6 +733,7 @@ void gv_destroy(GvCtx* ctx)
     ctx->d_xinv.release(); ctx->sc_xf.release(); ctx->dsc_xf.release(); ctx->sc_mesh.release(); ctx->dsc_mesh.release(); ctx->dsc_a.release(); ctx->dsc_c.release(); ctx->d_pick_keys.release(); ctx->h_pick_keys.release();
     for (auto& m : ctx->merges)
         m.release();
+    ctx->occluder_depth.release();
     ctx->d_depth.release(); ctx->d_mips.release(); ctx->d_mip_offset.release(); ctx->d_tick.release(); ctx->h_done.release();
     for (int k = 0; k < 2; k++) {
         ctx->h_tick[k].release();
@@ -919,6 +920,14 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
             ctx->pools[pool].lod.dirty.add(first & kSlotMask, count);
         return GV_OK;
     }
+    if (kind == GV_DIRTY_OCCLUDER) {  // (... nor the occluder boxes)
+        const uint32_t pool = first >> 28;
+        if (pool >= GV_MAX_POOLS)
+            return ctx->fail(GV_E_ARG, "gv_mark_dirty: pool id %u", pool);
+        if (ctx->pools[pool].occluders.wanted)
+            ctx->pools[pool].occluders.dirty.add(first & kSlotMask, count);
+        return GV_OK;
+    }
     if (int rc = flush_recorded_culls(ctx, kind == GV_DIRTY_MESH ? std::min(first >> 28, GV_MAX_POOLS - 1u) : GV_MAX_POOLS))
         return rc;
     switch (kind) {
@@ -946,6 +955,8 @@ int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count)
             ctx->pools[pool].geometry.dirty.add(lo, count);
         if (ctx->pools[pool].lod.wanted)  // ... and its size
             ctx->pools[pool].lod.dirty.add(lo, count);
+        if (ctx->pools[pool].occluders.wanted)  // ... and its occluder box
+            ctx->pools[pool].occluders.dirty.add(lo, count);
         return GV_OK;
     }
     default:
@@ -1156,6 +1167,10 @@ int gv_hiz_build(GvCtx* ctx, const float* depth, uint32_t width, uint32_t height
     GV_HIP(ctx, hipMemcpyAsync(ctx->d_mip_offset.ptr, ctx->mip_off, sizeof(uint64_t) * GV_MAX_MIPS, hipMemcpyHostToDevice, ctx->stream));
     if (mem_kind == GV_MEM_DEVICE) {
         ctx->depth_ptr = depth;
+        // one of the context's own occluder images, open: the pyramid reads it from here on, so it takes no further draw
+        // (gv_hiz_build_from_occluders comes through here; so does a caller who passes gv_occluder_depth_device's pointer)
+        if (depth == ctx->occluder_depth.d_image[ctx->occluder_depth.current].ptr)
+            ctx->occluder_depth.open = false;
     } else {
         GV_HIP(ctx, ctx->d_depth.reserve((size_t)width * height));
         GV_HIP(ctx, hipMemcpyAsync(ctx->d_depth.ptr, depth, (size_t)width * height * 4, hipMemcpyHostToDevice, ctx->stream));

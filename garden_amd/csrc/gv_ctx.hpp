@@ -24,6 +24,7 @@
 #include "gv_second_kernels.hpp"
 #include "gv_bounds_kernels.hpp"
 #include "gv_delta_kernels.hpp"
+#include "gv_occluder_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -413,6 +414,19 @@ struct PoolState {
             d_totals.release();
         }
     } delta;
+    // gv_pool_bind_occluders: the occluder boxes, mirrored as one 32-byte row per POOL SLOT (min in words 0-2, max in words 4-6; indexed
+    // by visible_idx like the ids above): the mirror exists only once gv_pool_draw_occluders has been called for the pool
+    struct Occluders : SlotMirror<uint8_t> {  // dirty: GV_DIRTY_OCCLUDER and GV_DIRTY_MESH marks of the pool
+        Column box_min, box_max;           // ptr NULL: no binding
+        uint32_t occupancy = 0;            // slots the columns cover
+        bool wanted = false;
+        UploadFence staged;                // guards h_stage (its own: see UploadFence)
+        void release()                     // everything (SlotMirror::release(): the mirror alone)
+        {
+            SlotMirror::release();
+            staged.destroy();
+        }
+    } occluders;
     // gv_pool_bind_payload / gv_pool_set_payload_layout: the component bytes an instance carries next to mvp, mirrored as one packed
     // row per POOL SLOT (never the mirror's order: the instance kernel indexes by the record's visible_idx, and a re-order of the
     // transform mirror does not concern it); read by gv_pool_emit_instances only
@@ -490,7 +504,7 @@ struct PoolState {
         d_orig.release(), d_inv.release(), d_index_map.release();
         d_blk_lo.release(), d_blk_hi.release(), d_blk_dirty.release(), d_hot.release(), d_seed.release(), d_kept.release(), d_kept_flag.release();
         instances.release(), payload.release(), counts.release(), geometry.release(), commands.release(), lod.release(), bounds.release();
-        delta.release();
+        delta.release(), occluders.release();
     }
 };
 
@@ -679,6 +693,26 @@ struct Context {
     bool hiz_level1_virtual = false;   // decided in gv_hiz_build: sizes whose first six levels take the fused kernel
     bool hiz_level1_stored = false;    // ... and whether gv_hiz_read_level has materialised it since the last build
 
+    // ---- occluder depth (gv_occluders.cpp): TWO images, so that the one the current pyramid reads (depth_ptr: level 0 IS the depth
+    // image) is never cleared, redrawn or reallocated under it. Accumulated state like the delta baselines: end_derived has no line for it.
+    struct OccluderDepth {
+        DeviceBuf<float> d_image[2];
+        uint32_t current = 0;              // the image of the last gv_occluder_begin
+        uint32_t width = 0, height = 0;    // ... and its size (0: no begin yet)
+        bool open = false;                 // begun and not built since: draws go into it
+        DeviceBuf<OccluderCounts> d_counts;
+        PinnedBuf<OccluderCounts> h_counts;  // staging of gv_occluder_depth_fetch
+        PinnedBuf<float> h_image;
+        // scratch of a draw, shared by all pools (stream order)
+        DeviceBuf<uint32_t> d_local;
+        DeviceBuf<unsigned long long> d_base;
+        void release()
+        {
+            d_image[0].release(), d_image[1].release(), d_counts.release(), h_counts.release(), h_image.release();
+            d_local.release(), d_base.release();
+        }
+    } occluder_depth;
+
     // ---- multi-GPU exchange (gv_exchange.cpp) ----
     void* exchange_comm = nullptr;     // ncclComm_t
     int exchange_rank = 0, exchange_world = 1;
@@ -816,6 +850,9 @@ struct KernelTimer {
 // PoolState::delta (gv_pool_view_delta) has NO line: its baseline is history — the set a channel saw at its last call, kept in pool
 // slot numbers so that neither a cull nor a re-order of the mirror concerns it — and its answer is self-contained slot numbers that
 // stay true whatever replaces the views. Both live until the channel's next call, its drop call or gv_destroy.
+// Context::occluder_depth (gv_pool_draw_occluders) has NO line either: the image is accumulated over the draws of several pools and
+// views since gv_occluder_begin, and what it holds — depths of boxes as they stood when they were drawn — is not made any less true by
+// a later cull. It lives until the begin that takes it again (never the image the current pyramid reads) or gv_destroy.
 enum class Ends {
     ViewsReplaced,     // gv_cull, gv_pool_cull_second_phase: the views' results are replaced
     EmissionReplaced,  // gv_pool_emit_instances, gv_pool_emit_draw_instances: the instance data is replaced
@@ -859,7 +896,7 @@ static inline uint32_t culled_views(const GvCtx* ctx, uint32_t pool_id)
 // A side column with one element per pool slot, when one is bound, must cover the slots a view was culled with: GV_E_STATE otherwise.
 struct ColumnName { const char *subject, *verb, *hint; };
 constexpr ColumnName kGeometryIds{"the geometry ids", "cover", ""}, kLodSizes{"the sizes", "cover", ""}, kReadyColumn{"the ready column", "covers", ""},
-    kPayloadRows{"the payload", "covers", " (gv_pool_bind_payload)"};
+    kPayloadRows{"the payload", "covers", " (gv_pool_bind_payload)"}, kOccluderBoxes{"the occluder boxes", "cover", " (gv_pool_bind_occluders)"};
 static inline int column_covers(GvCtx* ctx, const char* fn, const ColumnName& name, uint32_t pool_id, const Column& column, uint32_t covered,
                                 const ViewState& vs, uint32_t view_index)
 {
@@ -945,6 +982,7 @@ int upload_payload(GvCtx* ctx, PoolState& p);  // a pool's payload rows likewise
 int upload_counts(GvCtx* ctx, PoolState& p);   // ... and its count mirror (PoolState::Counts), once gv_pool_emit_draw_instances wants one
 int upload_geometry(GvCtx* ctx, PoolState& p);  // ... and its geometry id mirror (PoolState::Geometry), once gv_pool_emit_draw_commands wants one
 int upload_lod(GvCtx* ctx, PoolState& p);       // ... and its size mirror (PoolState::Lod), once gv_pool_select_lods wants one
+int upload_occluders(GvCtx* ctx, PoolState& p); // ... and its occluder box mirror (PoolState::Occluders), once gv_pool_draw_occluders wants one
 TransformMirror xf_mirror(const GvCtx* ctx);  // the transform mirror as the kernels see it
 MeshMirror mesh_mirror(const PoolState& p);   // a pool's mirror likewise (hot: null; the sphere stream's upkeep in cull_launch sets it)
 

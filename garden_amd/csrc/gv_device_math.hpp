@@ -311,4 +311,115 @@ __device__ __forceinline__ void bounds_project(const Corners& c, float b0, float
         q[j] = pk_fma(splat(b0), c.x[j], pk_fma(splat(b1), c.y[j], pk_fma(splat(b2), c.z[j], splat(b3))));
 }
 
+// ------------------------------------------------------------------------------------------------
+// occluder depth (the reference's Hi-Z reads its renderer's depth buffer, hiz.cpp:146, and nothing in this
+// library draws one). Test twin: tests/occluder_twin.h. Kernels: gv_occluders.hip.
+//
+// THE RULE (the same text stands in DESIGN.md §4 item 16 and tests/occluder_twin.h). For draw k of a view: slot s_k, record model M_k,
+// the slot's occluder box (omin, omax) in model space, VP = the view's view_proj, the image W x H, the call's min_pixels.
+//  1. Has a box <=> omin.x < omax.x && omin.y < omax.y && omin.z < omax.z (a NaN fails). Otherwise: not an occluder, counted no_box.
+//  2. Corners p_c = aabb_corners(M_k, omin, omax) (item 5: bit0 -> x, bit1 -> y, bit2 -> z selects max; every row
+//     fma(c0, x, fma(c1, y, fma(c2, z, c3)))). Clip: cl_r = fma(VP[r], p.x, fma(VP[4 + r], p.y, fma(VP[8 + r], p.z, VP[12 + r]))) for
+//     r = x, y, z, w; rcp = 1.0f / cl_w (IEEE); u = fma(cl_x * rcp, .5, .5), v = fma(cl_y * rcp, .5, .5), z = cl_z * rcp: the words of
+//     the Hi-Z query (hiz_occluded), restated.
+//  3. Any corner with !(cl_w > 0): skipped, counted behind.
+//  4. d = minNum(minNum over the 8 corners of z, 1.0f); !(d > 0): skipped, counted behind. (Reversed Z: d is the box's farthest depth.)
+//  5. fx = floorf(u * (float)(16 W)), fy = floorf(v * (float)(16 H)): four sub-pixel bits. Any !(|f| < 4194304.0f): skipped, counted
+//     range (a NaN or an infinity lands here). Otherwise X_c, Y_c are int32.
+//  6. Faces as corner cycles: -x (0,4,6,2), +x (1,3,7,5), -y (0,1,5,4), +y (2,6,7,3), -z (0,2,3,1), +z (4,5,7,6).
+//     A_f = sum over the cycle's edges p -> q of (X_p Y_q - X_q Y_p) in int64; a face is positive <=> A_f > 0. Each of the 12 box edges
+//     belongs to two faces: it is active <=> exactly one of them is positive, directed a -> b as in the positive face's cycle.
+//     No positive face: skipped, counted flat. (Positive faces may be the front or the back set; both bound the same silhouette.)
+//  7. Pixel (px, py) is covered <=> for every active edge and each pixel corner cx in {px, px + 1}, cy in {py, py + 1}:
+//     ex (16 cy - Y_a) - ey (16 cx - X_a) >= 2 (|ex| + |ey|), ex = X_b - X_a, ey = Y_b - Y_a, all int64. The margin 2 pays for the
+//     snapping (under one unit per axis) and the fp32 rounding in front of it (about one more).
+//  8. x0 = max(min X >> 4, 0), x1 = min(max X >> 4, W - 1) (arithmetic shifts), y likewise. An empty range, or a width or height in
+//     pixels below min_pixels: skipped, counted small. Otherwise the occluder is counted drawn (whether or not it covers a pixel).
+//  9. depth[py W + px] = max(0.0f, max over the covering occluders of d), taken on the floats' bits as uint32: every value is >= 0,
+//     so that order is the float order, and the maximum does not depend on any order of evaluation.
+// ------------------------------------------------------------------------------------------------
+// Item 2, the expressions of hiz_occluded (gv_device.hpp) restated — not shared: the hot kernels' code stays as it is. Returns item 3's
+// "every corner in front of the camera plane".
+__device__ __forceinline__ bool occluder_clip(const float (&vp)[16], const Corners& c, float (&u)[8], float (&v)[8], float (&z)[8])
+{
+    bool in_front = true;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const v2f clx = pk_fma(splat(vp[0]), c.x[j], pk_fma(splat(vp[4]), c.y[j], pk_fma(splat(vp[8]), c.z[j], splat(vp[12]))));
+        const v2f cly = pk_fma(splat(vp[1]), c.x[j], pk_fma(splat(vp[5]), c.y[j], pk_fma(splat(vp[9]), c.z[j], splat(vp[13]))));
+        const v2f clz = pk_fma(splat(vp[2]), c.x[j], pk_fma(splat(vp[6]), c.y[j], pk_fma(splat(vp[10]), c.z[j], splat(vp[14]))));
+        const v2f clw = pk_fma(splat(vp[3]), c.x[j], pk_fma(splat(vp[7]), c.y[j], pk_fma(splat(vp[11]), c.z[j], splat(vp[15]))));
+        in_front = in_front && (clw.x > 0.0f) && (clw.y > 0.0f);
+        const v2f rcp = {1.0f / clw.x, 1.0f / clw.y};  // IEEE-correct division, one per corner
+        const v2f uu = pk_fma(clx * rcp, splat(0.5f), splat(0.5f));
+        const v2f vv = pk_fma(cly * rcp, splat(0.5f), splat(0.5f));
+        const v2f zz = clz * rcp;
+        u[2 * j] = uu.x; u[2 * j + 1] = uu.y;
+        v[2 * j] = vv.x; v[2 * j + 1] = vv.y;
+        z[2 * j] = zz.x; z[2 * j + 1] = zz.y;
+    }
+    return in_front;
+}
+// Item 4 (IEEE minNum: v_min_f32, as the twin's fminf; the nesting cannot change a value that passes d > 0)
+__device__ __forceinline__ float occluder_depth(const float (&z)[8])
+{
+    return fminf(fminf(fminf(fminf(z[0], z[1]), fminf(z[2], z[3])), fminf(fminf(z[4], z[5]), fminf(z[6], z[7]))), 1.0f);
+}
+// Item 5 for one coordinate: false when it is out of range (NaN and infinities included)
+__device__ __forceinline__ bool occluder_snap(float t, float scale16, int32_t& out)
+{
+    const float f = floorf(t * scale16);
+    const bool ok = fabsf(f) < 4194304.0f;
+    out = ok ? (int32_t)f : 0;
+    return ok;
+}
+// Item 6. The 12 box edges a -> b with the face P whose cycle holds a -> b and the face Q whose cycle holds b -> a (faces numbered
+// -x +x -y +y -z +z). A cross term is shared by the edge's two faces with opposite signs, so the six areas take 12 terms.
+// Returns bits 0-11: the edge is active; bits 12-23: its direction is b -> a (Q is the positive face); 0: no positive face.
+constexpr int kOccluderEdgeA[12] = {0, 2, 4, 6, 0, 1, 4, 5, 0, 1, 2, 3};
+constexpr int kOccluderEdgeB[12] = {1, 3, 5, 7, 2, 3, 6, 7, 4, 5, 6, 7};
+constexpr int kOccluderEdgeP[12] = {2, 4, 5, 3, 4, 1, 0, 5, 0, 2, 3, 1};
+constexpr int kOccluderEdgeQ[12] = {4, 3, 2, 5, 0, 4, 5, 1, 2, 1, 0, 3};
+__device__ __forceinline__ uint32_t occluder_edges(const int32_t (&X)[8], const int32_t (&Y)[8])
+{
+    long long area[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int e = 0; e < 12; e++) {
+        const int a = kOccluderEdgeA[e], b = kOccluderEdgeB[e];
+        const long long t = (long long)X[a] * Y[b] - (long long)X[b] * Y[a];
+        area[kOccluderEdgeP[e]] += t;
+        area[kOccluderEdgeQ[e]] -= t;
+    }
+    uint32_t edges = 0;
+#pragma unroll
+    for (int e = 0; e < 12; e++) {
+        const bool p = area[kOccluderEdgeP[e]] > 0, q = area[kOccluderEdgeQ[e]] > 0;
+        edges |= (p != q ? 1u : 0u) << e;
+        edges |= (p != q && q ? 1u : 0u) << (12 + e);
+    }
+    return edges;
+}
+// Item 7 for one edge over a rectangle of pixel corners [cx0, cx1] x [cy0, cy1]: E = ex (16 cy - Ya) - ey (16 cx - Xa) - 2 (|ex| + |ey|)
+// at the corner where it is smallest / largest. E is linear, so "lo >= 0" is "every pixel corner inside passes" and "hi < 0" is
+// "none does". A pixel is the rectangle [px, px + 1] x [py, py + 1].
+struct OccluderEdge {
+    long long ex, ey, at;  // at = ex * (-Ya) + ey * Xa - margin: E = 16 (ex cy - ey cx) + at
+};
+__device__ __forceinline__ OccluderEdge occluder_edge(int32_t xa, int32_t ya, int32_t xb, int32_t yb)
+{
+    OccluderEdge g;
+    g.ex = (long long)xb - xa;
+    g.ey = (long long)yb - ya;
+    g.at = g.ey * xa - g.ex * ya - 2 * ((g.ex < 0 ? -g.ex : g.ex) + (g.ey < 0 ? -g.ey : g.ey));
+    return g;
+}
+__device__ __forceinline__ long long occluder_edge_lo(const OccluderEdge& g, long long cx0, long long cx1, long long cy0, long long cy1)
+{
+    return 16 * (g.ex * (g.ex > 0 ? cy0 : cy1) - g.ey * (g.ey > 0 ? cx1 : cx0)) + g.at;
+}
+__device__ __forceinline__ long long occluder_edge_hi(const OccluderEdge& g, long long cx0, long long cx1, long long cy0, long long cy1)
+{
+    return 16 * (g.ex * (g.ex > 0 ? cy1 : cy0) - g.ey * (g.ey > 0 ? cx0 : cx1)) + g.at;
+}
+
 }  // namespace gv

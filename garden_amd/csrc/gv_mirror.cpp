@@ -1422,7 +1422,7 @@ int reorder_mirror(GvCtx* ctx, bool reorder_xf, const bool* reorder_pool, PhaseT
 
 }  // namespace
 
-// One upload path for the per-slot side columns (SlotMirror: payload rows, ready counts, geometry ids, LOD sizes): the slots appended since the
+// One upload path for the per-slot side columns (SlotMirror: payload rows, ready counts, geometry ids, LOD sizes, occluder boxes): the slots appended since the
 // last upload plus the mirror's dirty set. gather(dst, lo, hi) fills the hi - lo elements of slots [lo, hi). Ranges of
 // kDeviceGatherMinSlots slots or more travel as contiguous copies into their place; everything smaller travels the way small mirror
 // edits do: ONE packet [elements | slots] and ONE scatter launch. `fence` guards the staging. Sizes are counted in T, as the buffers are.
@@ -1579,6 +1579,27 @@ int upload_lod(GvCtx* ctx, PoolState& p)
     });
 }
 
+// The occluder box mirror of a pool (PoolState::Occluders): one 32-byte row per pool slot — min in words 0-2, max in words 4-6, words
+// 3 and 7 zero — fed by the pool's GV_DIRTY_OCCLUDER / GV_DIRTY_MESH marks.
+int upload_occluders(GvCtx* ctx, PoolState& p)
+{
+    PoolState::Occluders& O = p.occluders;
+    if (!O.wanted || !O.box_min.ptr)
+        return GV_OK;
+    if (O.mirrored > O.occupancy)
+        O.reset();
+    return upload_slot_mirror(ctx, O, O.occupancy, O.staged, [&](uint8_t* rows, uint32_t lo, uint32_t hi) {
+        parallel_ranges(0, hi - lo, [&](uint32_t a, uint32_t b) {
+            for (uint32_t k = a; k < b; k++) {
+                uint8_t* row = rows + (size_t)k * kOccluderRowBytes;
+                memset(row, 0, kOccluderRowBytes);
+                memcpy(row, O.box_min.at(lo + k), 12);  // (verbatim: NaN patterns survive)
+                memcpy(row + 16, O.box_max.at(lo + k), 12);
+            }
+        });
+    });
+}
+
 // Brings the device mirror up to date with the bound pools and their dirty marks, one named step after the other (the steps
 // and the state they share: above; the rules that choose among them: gv_dirty_ranges.hpp). A re-order that is due runs last, on
 // the device, behind everything that brought the mirror up to date in its old order.
@@ -1654,6 +1675,10 @@ int sync_mirror(GvCtx* ctx)
     for (auto& p : ctx->pools)
         if (p.bound && p.lod.wanted)
             if (int rc = upload_lod(ctx, p))
+                return rc;
+    for (auto& p : ctx->pools)
+        if (p.bound && p.occluders.wanted)
+            if (int rc = upload_occluders(ctx, p))
                 return rc;
     bool any_reorder = reorder_xf;
     for (bool b : reorder_pool)

@@ -1329,6 +1329,9 @@ public:
     const std::vector<int8_t>& getSystemPasses(uint32_t p) const { return plan.at(p).passes; }
     // mesh system p of the last frame is a sorted one (Translucent, UI): its delivery order is the distance order (draw_commands.hpp)
     bool isSystemSorted(uint32_t p) const { return plan.at(p).sorted; }
+    // A pyramid somebody else built on the device behind this system's back (GpuOccluders::build): from the next tick on the light
+    // pass queries it, as it does after setHizDepth.
+    void adoptPyramid() noexcept { useHiz = true; }
     // view v of mesh system p as the last frame culled it (second_phase.hpp re-tests the light pass with it)
     const GvView& getSystemView(uint32_t p, uint32_t v) const { return plan.at(p).views.at(v); }
 

@@ -49,7 +49,9 @@ public:
     // Mesh system p (unsorted, its light pass culled this tick) against the pyramid as it stands now. Afterwards meshes(p)[0,
     // drawCount(p)) are the newly visible records — in the order of the system's own list: front to back when the drop-in sorts on
     // the device — and the components' isVisible bytes hold the union of both phases.
-    void run(uint32_t p)
+    // withHiz: query the pyramid even though the first phase did not — a headless frame, whose first phase had no pyramid and whose
+    // occluders were drawn from its result (GpuOccluders).
+    void run(uint32_t p, bool withHiz = false)
     {
         PerSystem& s = of(p);
         if (!isSupported())
@@ -72,7 +74,9 @@ public:
             throw GardenError("GpuSecondPhase: mesh system " + std::to_string(p) + " has no spare view");
         GvCtx* ctx = system->getContext();
         IMeshRenderSystem* meshSystem = system->getMeshSystems()[p];
-        const GvView view = system->getSystemView(p, light);
+        GvView view = system->getSystemView(p, light);
+        if (withHiz)
+            view.use_hiz = 1;
         // (a frame with more passes may have left a record target at this index: the result must not land in that pass's array)
         check(gv_pool_set_record_target(ctx, p, spare, nullptr, 0), "gv_pool_set_record_target");
         check(gv_pool_cull_second_phase(ctx, p, light, spare, &view), "gv_pool_cull_second_phase");

@@ -25,6 +25,7 @@ GV_CONFIG_BLOCK_BOUNDS = 8
 GV_CONFIG_HIZ_RG16F = 16
 GV_CONFIG_LINEAR_SCAN = 32
 GV_DIRTY_TRANSFORM, GV_DIRTY_HIERARCHY, GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY, GV_DIRTY_LOD = 0, 1, 2, 3, 4, 5
+GV_DIRTY_OCCLUDER = 6
 GV_MAX_DRAW_INSTANCES = 65535
 GV_MAX_GEOMETRIES = 65536
 GV_COMMANDS_MERGE_RUNS = 1
@@ -138,6 +139,13 @@ class GvViewBounds(C.Structure):
 BOUNDS_DTYPE = np.dtype([("lo", np.float32, (3,)), ("draw_count", np.uint32), ("hi", np.float32, (3,)), ("nan_records", np.uint32)])
 
 
+class GvOccluderCounts(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("drawn", "no_box", "behind", "range", "flat", "small")]
+
+
+OCCLUDER_COUNT_NAMES = tuple(name for name, _ in GvOccluderCounts._fields_)
+
+
 GV_MAX_DELTA_CHANNELS = 4
 GV_DELTA_RESTART = 1
 
@@ -230,6 +238,8 @@ EXPORTS = [
     "gv_pool_cull_second_phase",
     "gv_pool_view_bounds", "gv_pool_view_bounds_device", "gv_pool_view_bounds_fetch",
     "gv_pool_view_delta", "gv_pool_view_delta_device", "gv_pool_view_delta_fetch",
+    "gv_pool_bind_occluders", "gv_occluder_begin", "gv_pool_draw_occluders", "gv_occluder_depth_device", "gv_occluder_depth_fetch",
+    "gv_hiz_build_from_occluders",
 ]
 
 _lib = None
@@ -371,6 +381,12 @@ def load():
     lib.gv_pool_view_delta.argtypes = [P, u32, u32, C.POINTER(u32), u32, u32]
     lib.gv_pool_view_delta_device.argtypes = [P, u32, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_view_delta_fetch.argtypes = [P, u32, u32, C.c_int, C.POINTER(GvViewDelta)]
+    lib.gv_pool_bind_occluders.argtypes = [P, u32, P, P, u32, u32]
+    lib.gv_occluder_begin.argtypes = [P, u32, u32]
+    lib.gv_pool_draw_occluders.argtypes = [P, u32, u32, u32]
+    lib.gv_occluder_depth_device.argtypes = [P, C.POINTER(P), C.POINTER(u32), C.POINTER(u32), C.POINTER(P)]
+    lib.gv_occluder_depth_fetch.argtypes = [P, P, C.c_size_t, C.POINTER(GvOccluderCounts)]
+    lib.gv_hiz_build_from_occluders.argtypes = [P]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -484,7 +500,7 @@ class GpuVisibility:
         self._check(self.lib.gv_pool_bind_ready(self.ctx, pool_id, ready.ctypes.data, ready.strides[0], ready.dtype.itemsize))
 
     def mark_dirty(self, kind, first, count, pool_id=0):
-        if kind in (GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY, GV_DIRTY_LOD):
+        if kind in (GV_DIRTY_MESH, GV_DIRTY_PAYLOAD, GV_DIRTY_GEOMETRY, GV_DIRTY_LOD, GV_DIRTY_OCCLUDER):
             first |= pool_id << 28
         self._check(self.lib.gv_mark_dirty(self.ctx, kind, first, count))
 
@@ -1142,6 +1158,48 @@ class GpuVisibility:
 
     def hiz_rebuild(self):
         self._check(self.lib.gv_hiz_rebuild(self.ctx))
+
+    # ---- occluder depth ----
+    def bind_occluders(self, pool_id, box_min, box_max):
+        """gv_pool_bind_occluders: per-slot occluder boxes in model space (fp32 [n, 3+] each, C-contiguous rows of one common row
+        stride; None, None removes the binding). The caller keeps them alive and unmoved; edits are reported with GV_DIRTY_OCCLUDER.
+        The binder's contract: a box lies inside what the slot draws — the library does not check it."""
+        if box_min is None and box_max is None:
+            self._keep.pop(("occluders", pool_id), None)
+            self._check(self.lib.gv_pool_bind_occluders(self.ctx, pool_id, None, None, 0, 0))
+            return
+        if box_min.dtype != np.float32 or box_max.dtype != np.float32 or box_min.ndim != 2 or box_min.shape[0] != box_max.shape[0] \
+                or box_min.strides != box_max.strides or box_min.strides[1] != 4 or box_min.shape[1] < 3 or box_max.shape[1] < 3:
+            raise ValueError("bind_occluders: two fp32 [n, 3+] arrays of the same row stride")
+        self._keep[("occluders", pool_id)] = (box_min, box_max)
+        self._check(self.lib.gv_pool_bind_occluders(self.ctx, pool_id, box_min.ctypes.data, box_max.ctypes.data, box_min.strides[0],
+                                                    box_min.shape[0]))
+
+    def occluder_begin(self, width, height):
+        """gv_occluder_begin: opens (sizes, clears) the occluder image the current pyramid does not read; asynchronous"""
+        self._check(self.lib.gv_occluder_begin(self.ctx, width, height))
+
+    def draw_occluders(self, pool_id, view_index, min_pixels=1):
+        """gv_pool_draw_occluders: the occluder boxes of the view's draws into the open image; asynchronous"""
+        self._check(self.lib.gv_pool_draw_occluders(self.ctx, pool_id, view_index, min_pixels))
+
+    def occluder_depth_device(self):
+        """gv_occluder_depth_device: (device pointer of the image, width, height, device pointer of the six counts)"""
+        depth, counts, w, h = C.c_void_p(), C.c_void_p(), C.c_uint32(), C.c_uint32()
+        self._check(self.lib.gv_occluder_depth_device(self.ctx, C.byref(depth), C.byref(w), C.byref(h), C.byref(counts)))
+        return depth.value, w.value, h.value, counts.value
+
+    def occluder_depth(self):
+        """gv_occluder_depth_fetch: waits; (image fp32 [height, width], counts as a dict of the six fields)"""
+        _, w, h, _ = self.occluder_depth_device()
+        image = np.empty((h, w), np.float32)
+        counts = GvOccluderCounts()
+        self._check(self.lib.gv_occluder_depth_fetch(self.ctx, image.ctypes.data, image.nbytes, C.byref(counts)))
+        return image, {name: int(getattr(counts, name)) for name in OCCLUDER_COUNT_NAMES}
+
+    def hiz_build_from_occluders(self):
+        """gv_hiz_build_from_occluders: the pyramid of the open image (not copied), which it closes"""
+        self._check(self.lib.gv_hiz_build_from_occluders(self.ctx))
 
     def hiz_mip_count(self):
         n = C.c_uint32()

@@ -180,8 +180,10 @@ typedef enum GvDirtyKind {
                                `first`, like GV_DIRTY_MESH. Read by no cull: a recorded cull of a batch is not launched by it */
     GV_DIRTY_GEOMETRY = 4,  /* the bound geometry ids (gv_pool_bind_geometry) of mesh slots changed; pool id in the top 4 bits of
                                `first`. Read by no cull either */
-    GV_DIRTY_LOD = 5        /* the bound sizes (gv_pool_bind_lod) of mesh slots changed; pool id in the top 4 bits of `first`. Read
+    GV_DIRTY_LOD = 5,       /* the bound sizes (gv_pool_bind_lod) of mesh slots changed; pool id in the top 4 bits of `first`. Read
                                by no cull either */
+    GV_DIRTY_OCCLUDER = 6   /* the bound occluder boxes (gv_pool_bind_occluders) of mesh slots changed; pool id in the top 4 bits of
+                               `first`. Read by no cull either */
 } GvDirtyKind;
 int gv_mark_dirty(GvCtx* ctx, uint32_t kind, uint32_t first, uint32_t count);
 
@@ -798,6 +800,70 @@ int gv_pool_view_delta_device(GvCtx* ctx, uint32_t pool_id, uint32_t channel, co
  * writes those bytes in between.
  * GV_E_ARG: a NULL ctx or out, a pool or channel out of range. GV_E_STATE: no result; write_back without a target. */
 int gv_pool_view_delta_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t channel, int write_back, GvViewDelta* out);
+
+/* ---- occluder depth, drawn on the device ----
+ * The Hi-Z query (GvView::use_hiz, gv_pool_cull_second_phase) reads a depth image; the reference takes it from its renderer's depth
+ * buffer. A headless server, a shadow cascade or a pass that has not been drawn yet has none. These calls draw one: every draw of a
+ * delivered view whose slot has an OCCLUDER BOX — a box in the slot's model space, the space aabb_min / aabb_max live in — writes
+ * the farthest depth of that box into the pixels the box's projected silhouette wholly covers, shrunk by a margin that pays for the
+ * snapping of its vertices. One depth per box, conservative in area and in depth; the image then goes through gv_hiz_build.
+ *   Frame order: gv_cull (no Hi-Z) -> gv_occluder_begin -> gv_pool_draw_occluders per pool and view -> gv_hiz_build_from_occluders
+ *     -> gv_cull with use_hiz, or gv_pool_cull_second_phase.
+ *   The rule, per draw k of the view (slot s = visible_idx[k], M = the record's own bakedModel, VP = the view's view_proj as culled):
+ *     1. has a box <=> omin.x < omax.x && omin.y < omax.y && omin.z < omax.z (a NaN fails); otherwise counted no_box.
+ *     2. corners and clip coordinates exactly as the Hi-Z query computes them for an AABB (fma nesting, IEEE 1 / w, u = fma(x / w, .5,
+ *        .5), v likewise, z / w): an occluder box equal to the slot's AABB gets the query's own words.
+ *     3. any corner with !(w > 0): skipped, counted behind.   4. d = min(minNum of the 8 z, 1.0f); !(d > 0): skipped, counted behind.
+ *     5. X = floorf(u * 16 W), Y = floorf(v * 16 H) (four sub-pixel bits); any !(|.| < 2^22): skipped, counted range.
+ *     6. the silhouette: the box edges between a face of positive and a face of non-positive projected area (int64); no positive
+ *        face: skipped, counted flat. Mirrored models and mirrored projections give the same silhouette.
+ *     7. a pixel is covered <=> each of its four corners (cx, cy) passes ex (16 cy - Y_a) - ey (16 cx - X_a) >= 2 (|ex| + |ey|) for
+ *        every silhouette edge a -> b (int64).
+ *     8. pixel range x0 = max(min X >> 4, 0) .. x1 = min(max X >> 4, W - 1), y likewise; empty, or narrower or lower than
+ *        min_pixels: skipped, counted small. Otherwise counted drawn.
+ *     9. depth[py W + px] = max(0.0f, max over the covering occluders of d): order-independent, reproducible bit for bit.
+ *   THE BINDER'S CONTRACT: the library does not check that an occluder box lies inside the slot's AABB, nor inside the geometry the
+ *     slot draws. A box that sticks out of solid geometry culls what is visible. */
+typedef struct GvOccluderCounts { /* 24 bytes; summed over the draws of every gv_pool_draw_occluders since gv_occluder_begin */
+    uint32_t drawn, no_box, behind, range, flat, small;
+} GvOccluderCounts;
+/* Binds the occluder boxes of a pool's slots: 3 fp32 each at box_min + i * stride and box_max + i * stride, i < occupancy (stride >=
+ * 12). box_min == NULL && box_max == NULL removes the binding. Lifetime of the pointers as for gv_pool_bind_ready. The boxes are
+ * mirrored per POOL slot (one 32-byte row: min in words 0-2, max in words 4-6), only once gv_pool_draw_occluders has been called
+ * for the pool: that call uploads the column; from then on GV_DIRTY_OCCLUDER and the pool's GV_DIRTY_MESH marks feed a dirty set
+ * of its own, consumed by gv_sync or the pool's next draw, whichever comes first (bytes under GvStats::upload_bytes). A rebind
+ * uploads everything again.
+ * GV_E_ARG: a NULL ctx; a pool out of range; exactly one of the pointers NULL; stride < 12; occupancy beyond the 28-bit slot range. */
+int gv_pool_bind_occluders(GvCtx* ctx, uint32_t pool_id, const void* box_min, const void* box_max, uint32_t stride, uint32_t occupancy);
+/* Opens an occluder image of width x height (1 .. 32768 each): sized, cleared to 0 (reversed Z: "nothing in front of anything")
+ * and its six counts zeroed, asynchronously on gv_stream(ctx). The context owns TWO images and takes the one the current pyramid
+ * does not read: the pyramid's level 0 is the depth image, so an image a pyramid reads is never cleared, redrawn or reallocated
+ * under it (gv_hiz_rebuild keeps reproducing the old pyramid). A begin on an open image starts it over.
+ * GV_E_ARG: a NULL ctx; a size of 0 or above 32768 (nothing changes). GV_E_OOM: an open image that had to grow is gone; the pyramid's
+ * image is not touched. */
+int gv_occluder_begin(GvCtx* ctx, uint32_t width, uint32_t height);
+/* Draws the occluders of one delivered view of one pool into the open image; several pools and views may draw into one image. A
+ * read of the view, as gv_pool_view_bounds (recorded culls and deferred sorts are launched first; records of sorted, grouped and
+ * second-phase views alike, in delivery order, the device draw count never read by the host); asynchronous on gv_stream(ctx): three
+ * kernel launches whatever the counts, under GvStats::launches[GV_K_HIZ]. The image is accumulated state, like the baselines of
+ * gv_pool_view_delta: no cull, emission or sort ends it.
+ * MEMORY: the call's scratch is one word per slot of the occupancy the view was culled with and 8 bytes per 256 slots (40 MB at
+ * 10^7 slots), allocated at the first draw, shared by all pools and kept; a later view with a larger occupancy replaces it,
+ * which waits for the device once. No row is stored per occluder: the raster launch computes it again from the record.
+ * GV_E_ARG: a NULL ctx; a pool that is not bound; a view index >= GV_MAX_VIEWS, or one no cull of the pool ever had a view at.
+ * GV_E_STATE: no open image (gv_occluder_begin; gv_hiz_build_from_occluders closes it); no occluder binding; a view without results
+ * or culled count-only; boxes that cover fewer slots than the view was culled with. */
+int gv_pool_draw_occluders(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint32_t min_pixels);
+/* The image of the last gv_occluder_begin (open or built) in device memory, width * height fp32 in rows, and its six counts as
+ * uint32 (valid behind the draws on gv_stream(ctx)). GV_E_ARG: a NULL ctx or output. GV_E_STATE: no gv_occluder_begin yet. */
+int gv_occluder_depth_device(GvCtx* ctx, const void** depth, uint32_t* width, uint32_t* height, const void** counts);
+/* Waits for the draws and copies the image (depth may be NULL: counts only; `bytes` is the room at depth) and the counts (may be NULL).
+ * GV_E_ARG: a NULL ctx; both outputs NULL; bytes below width * height * 4 (nothing is written). GV_E_STATE as above. */
+int gv_occluder_depth_fetch(GvCtx* ctx, float* depth, size_t bytes, GvOccluderCounts* counts);
+/* gv_hiz_build(image, width, height, GV_MEM_DEVICE) of the open image, and closes it: further draws need a new gv_occluder_begin
+ * (which takes the other image). GV_E_STATE: no open image. Otherwise as gv_hiz_build. A caller who hands the open image's pointer
+ * (gv_occluder_depth_device) to gv_hiz_build himself closes it the same way: no image takes a draw once a pyramid reads it. */
+int gv_hiz_build_from_occluders(GvCtx* ctx);
 
 /* ---- the shared sorted arrays: the sorted lists of several mesh systems merged into ONE array, on the device ----
  * The reference keeps one array per sorted kind — transSortedMeshes, uiSortedMeshes, one translucent array per shadow pass — into
