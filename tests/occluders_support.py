@@ -1,7 +1,8 @@
 """Test helpers of gv_pool_draw_occluders: the C twin (tests/occluder_twin.h) built into a shared library, the expected image and
 counts of a draw from the records fetched in front of the call, the float64 model the conservativeness census holds the twin to,
-and the worlds of tests/test_gpu_occluders.py. The tile size and the workgroup size are read from the kernel header, so the cases
-follow the kernel. TEST INFRASTRUCTURE ONLY."""
+the worlds of tests/test_gpu_occluders.py, and — for tests/test_occluder_walk_census.py and tests/test_gpu_occluder_walks.py — the
+walk census (what the three launches do with a set of records) and the cases at working image sizes. The tile size, the workgroup
+size and the raster grid are read from the kernel header, so the cases follow the kernel. TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
 import functools
 import math
@@ -57,6 +58,35 @@ void twin_paths(const float* models, const float* boxes, uint32_t n, const float
     for (k = 0; k < n; k++)
         if (occluder_twin_setup(models + 12 * (size_t)k, boxes + 6 * (size_t)k, vp, W, H, min_pixels, &s) == OCCLUDER_TWIN_DRAWN)
             occluder_twin_tile_paths(&s, T, paths);
+}
+
+/* per record, in one call: out[5 k ..] = class, x0, x1, y0, y1 (the range of a record that is not drawn: zeros) */
+void twin_ranges(const float* models, const float* boxes, uint32_t n, const float* vp, uint32_t W, uint32_t H, uint32_t min_pixels, int32_t* out)
+{
+    OccluderTwinSetup s;
+    uint32_t k;
+    for (k = 0; k < n; k++) {
+        int32_t* o = out + 5 * (size_t)k;
+        o[0] = occluder_twin_setup(models + 12 * (size_t)k, boxes + 6 * (size_t)k, vp, W, H, min_pixels, &s);
+        o[1] = o[2] = o[3] = o[4] = 0;
+        if (o[0] == OCCLUDER_TWIN_DRAWN)
+            o[1] = s.x0, o[2] = s.x1, o[3] = s.y0, o[4] = s.y1;
+    }
+}
+
+/* per pixel, the drawn occluders that cover it: added to cover[W H] */
+void twin_overlap(const float* models, const float* boxes, uint32_t n, const float* vp, uint32_t W, uint32_t H, uint32_t min_pixels, uint32_t* cover)
+{
+    OccluderTwinSetup s;
+    uint32_t k;
+    int32_t px, py;
+    for (k = 0; k < n; k++) {
+        if (occluder_twin_setup(models + 12 * (size_t)k, boxes + 6 * (size_t)k, vp, W, H, min_pixels, &s) != OCCLUDER_TWIN_DRAWN)
+            continue;
+        for (py = s.y0; py <= s.y1; py++)
+            for (px = s.x0; px <= s.x1; px++)
+                cover[(size_t)py * W + px] += (uint32_t)occluder_twin_covered(&s, px, py, OCCLUDER_TWIN_MARGIN);
+    }
 }
 
 /* what a draw moves: out[0] pixels the drawn occluders cover (with multiplicity), out[1] of those, the ones whose stored word was
@@ -183,6 +213,10 @@ def build_twin(directory):
     lib.twin_traffic.restype = None
     lib.twin_census.argtypes = [P, P, U32, P, U32, U32, C.c_int, P]
     lib.twin_census.restype = None
+    lib.twin_ranges.argtypes = [P, P, U32, P, U32, U32, U32, P]
+    lib.twin_ranges.restype = None
+    lib.twin_overlap.argtypes = [P, P, U32, P, U32, U32, U32, P]
+    lib.twin_overlap.restype = None
     return lib
 
 
@@ -239,8 +273,38 @@ def twin_census(twin, models, boxes, vp, width, height, margin):
     return dict(zip(("drawn", "written", "violations", "unjudged", "range_pixels"), (int(x) for x in out)))
 
 
+def twin_ranges(twin, models, boxes, vp, width, height, min_pixels=1):
+    """int32 [n, 5]: per record its class and, for a drawn one, the pixel range of item 8 (x0, x1, y0, y1); one call for all n"""
+    m, b, vp = _arrays(models, boxes, vp)
+    out = np.zeros((len(m), 5), np.int32)
+    twin.twin_ranges(m.ctypes.data, b.ctypes.data, len(m), vp.ctypes.data, width, height, min_pixels, out.ctypes.data)
+    return out
+
+
+def twin_overlap(twin, models, boxes, vp, width, height, min_pixels=1):
+    """uint32 [height, width]: per pixel the number of drawn occluders that cover it"""
+    m, b, vp = _arrays(models, boxes, vp)
+    cover = np.zeros((height, width), np.uint32)
+    twin.twin_overlap(m.ctypes.data, b.ctypes.data, len(m), vp.ctypes.data, width, height, min_pixels, cover.ctypes.data)
+    return cover
+
+
 def words(image):
     return np.ascontiguousarray(image, np.float32).view(np.uint32)
+
+
+def first_difference(got, want, tile=T):
+    """None when two images agree word for word; otherwise a line about the first pixel (in row order) that differs, its tile and
+    the number of differing words — what a failing comparison of a large image reports in place of the image"""
+    a, b = words(got), words(want)
+    if a.shape != b.shape:
+        return f"shapes differ: {a.shape} and {b.shape}"
+    if np.array_equal(a, b):
+        return None
+    differs = a != b
+    py, px = (int(v) for v in np.argwhere(differs)[0])
+    return (f"{int(differs.sum())} of {a.size} words differ; the first at pixel ({px}, {py}), tile ({px // tile}, {py // tile}), "
+            f"pixel ({px % tile}, {py % tile}) of it: got 0x{int(a[py, px]):08x}, expected 0x{int(b[py, px]):08x}")
 
 
 # ---- cameras and models ---------------------------------------------------------------------------------------------------------------
@@ -415,3 +479,321 @@ def oracle_cull(n=600, width=64, height=48, min_pixels=1):
     hiz_view = parity_view(use_hiz=1)
     full = oracle_py.prepare_meshes(sc.meshes.copy(), sc.transforms, sc.entity_to_transform, hiz_view, hiz=oracle_py.Hiz(image))
     return dict(first=first, image=image, counts=counts, full=full)
+
+
+# ---- the walk census: what the three launches do with a set of records ---------------------------------------------------------------
+
+RASTER_GROUPS = header_constant("gv_occluder_kernels.hpp", "kOccluderRasterGroups")
+RASTER_WAVES = RASTER_GROUPS * (BLOCK // 64)
+SCAN_TURN_BLOCKS = 4 * BLOCK
+# The lines of the library that walk_census restates (tests/test_occluder_walk_census.py checks that it still holds them).
+WALK_LINES = {"gv_occluders.hip": [
+    "constexpr uint32_t kWaves = kOccluderBlock / 64u;",
+    "const uint32_t first = blockIdx.x * kOccluderBlock;",
+    "if (first >= n)",
+    "for (uint32_t start = 0; start < blocks; start += 4 * kOccluderBlock) {",
+    "const unsigned long long waves = (unsigned long long)gridDim.x * kWaves;",
+    "const unsigned long long share = (total + waves - 1) / waves;",
+    "const unsigned long long i0 = wave * share, i1 = min(i0 + share, total);",
+    "const uint32_t behind = lo + 1 < held ? local[lo + 1] : (uint32_t)(a.base[b + 1] - base);",
+    "const uint32_t t = (uint32_t)(i - begin);",
+    "const int32_t px0 = (int32_t)(((uint32_t)(x0 >> kTileShift) + t % tiles_x) << kTileShift);",
+    "const int32_t py0 = (int32_t)(((uint32_t)(y0 >> kTileShift) + t / tiles_x) << kTileShift);",
+    "const int32_t rx0 = max(px0, x0), rx1 = min(px0 + (int32_t)kOccluderTile - 1, x1);",
+    "const int32_t ry0 = max(py0, y0), ry1 = min(py0 + (int32_t)kOccluderTile - 1, y1);",
+    "const uint32_t s_first = (uint32_t)(ry0 - py0) >> 1, s_last = (uint32_t)(ry1 - py0) >> 1;",
+    "const uint32_t blocks = (launch.capacity + kOccluderBlock - 1) / kOccluderBlock;",
+    "hipLaunchKernelGGL(occluder_setup_kernel, dim3(std::max(1u, blocks)), dim3(kOccluderBlock), 0, stream, launch);",
+    "hipLaunchKernelGGL(occluder_raster_kernel, dim3(kOccluderRasterGroups), dim3(kOccluderBlock), 0, stream, launch);",
+]}
+
+
+def walk_census(twin, models, boxes, vp, width, height, min_pixels=1, occupancy=None):
+    """What the three launches of one gv_pool_draw_occluders do with n records in delivery order (models [n, 12] and the occluder
+    boxes of their slots [n, 6]) — a count of the FORMS the kernels take, none of it a measurement. It restates, of gv_occluders.hip
+    (the lines in WALK_LINES):
+
+      setup   a record block is kOccluderBlock records; the grid is ceil(occupancy / kOccluderBlock) workgroups (one at least), and
+              a workgroup whose first record is at or beyond n leaves: `blocks_beyond_count`. The tiles of a drawn occluder are
+              the T x T cells its pixel range touches (occluder_tiles) — the range is the twin's (twin_ranges).
+      scan    a turn takes 4 * kOccluderBlock record blocks: `scan_turns`, the drawn occluders among each turn's records.
+      raster  waves = kOccluderRasterGroups * kOccluderBlock / 64, share = ceil(total / waves), wave w walks the items
+              [w share, min((w + 1) share, total)); an item is (occluder, tile t), the occluders in delivery order, t row-major over
+              the occluder's tiles: tile column t % tiles_x, tile row t / tiles_x; the tile is clipped to the occluder's pixel range
+              (rx0, rx1, ry0, ry1), and a wave step is the two rows py0 + 2 s and py0 + 2 s + 1.
+
+    Returns a dict:
+      total, share, waves_with_items, last_walk (the items of the last wave that has some), last_walk_short
+      reuse                     items whose occluder is the previous item's in the same walk (`i >= end` is false)
+      cross                     items that follow an item of another occluder in the same walk; of those: cross_over_empty (they pass
+                                one or more records without tiles), cross_block (a record-block boundary), cross_empty_blocks (one
+                                or more whole record blocks without a tile)
+      empty_blocks_between      record blocks without a tile between blocks that have some
+      block_last_drawn, block_first_drawn   blocks whose last (`behind` from base[b + 1] - base) or first record is a drawn occluder
+      mid_starts                walks whose first item has t > 0; mid_row_starts: of those, t % tiles_x != 0
+      single_occluder_walks     walks of the full length `share` (2 or more) that stay inside one occluder
+      tiles_x_max, tile_rows_max
+      inside, mixed, outside    the three tile paths (twin_paths)
+      clip_left, clip_right, clip_top, clip_bottom   tiles whose occluder's pixel range ends inside them on that side
+      cut_right_edge, cut_bottom_edge   tiles that reach beyond the image (its width or height is no multiple of T)
+      half_last_step, half_first_step   tiles whose last wave step has only its upper row live (ry1 - py0 even), or whose first
+                                has only its lower row (ry0 - py0 odd)
+      scan_turns, drawn_per_turn (a tuple), drawn_in_last_block, last_block_records
+      setup_grid, blocks_beyond_count
+      overlap_max               the largest number of drawn occluders that cover one pixel (twin_overlap)
+      counts                    the six counts, as a dict"""
+    m, b, vp = _arrays(models, boxes, vp)
+    n = len(m)
+    occupancy = n if occupancy is None else occupancy
+    assert occupancy >= n
+    info = twin_ranges(twin, m, b, vp, width, height, min_pixels).astype(np.int64)
+    drawn = info[:, 0] == DRAWN
+    x0, x1, y0, y1 = (info[:, k] for k in range(1, 5))
+    tiles_x = np.where(drawn, x1 // T - x0 // T + 1, 0)
+    tile_rows = np.where(drawn, y1 // T - y0 // T + 1, 0)
+    tiles = tiles_x * tile_rows
+    total = int(tiles.sum())
+    share = -(-total // RASTER_WAVES)
+    c = dict(total=total, share=share, counts={name: int((info[:, 0] == k).sum()) for k, name in enumerate(COUNT_NAMES)})
+    c["waves_with_items"] = -(-total // share) if total else 0
+    c["last_walk"] = total - (c["waves_with_items"] - 1) * share if total else 0
+    c["last_walk_short"] = bool(total and c["last_walk"] < share)
+
+    # the items: occluder and tile of each, and whether a walk starts at it
+    begin = np.cumsum(tiles) - tiles
+    rec = np.repeat(np.arange(n), tiles)
+    t = np.arange(total) - begin[rec]
+    starts = np.arange(total) % max(share, 1) == 0
+    prev = np.concatenate([rec[:1], rec[:-1]])
+    follows = ~starts
+    crossing = follows & (rec != prev)
+    c["reuse"] = int((follows & (rec == prev)).sum())
+    c["cross"] = int(crossing.sum())
+    c["cross_over_empty"] = int((crossing & (rec - prev > 1)).sum())
+    c["cross_block"] = int((crossing & (rec // BLOCK != prev // BLOCK)).sum())
+    c["cross_empty_blocks"] = int((crossing & (rec // BLOCK - prev // BLOCK > 1)).sum())
+    c["mid_starts"] = int((starts & (t > 0)).sum())
+    c["mid_row_starts"] = int((starts & (t % np.maximum(tiles_x[rec], 1) != 0)).sum())
+    full = total // share if share >= 2 else 0
+    walks = rec[:full * share].reshape(full, max(share, 1))
+    c["single_occluder_walks"] = int((walks[:, 0] == walks[:, -1]).sum()) if full else 0
+    c["tiles_x_max"], c["tile_rows_max"] = int(tiles_x.max(initial=0)), int(tile_rows.max(initial=0))
+
+    # record blocks
+    blocks = -(-n // BLOCK)
+    block_tiles = np.bincount(np.arange(n) // BLOCK, weights=tiles, minlength=blocks)
+    holding = np.nonzero(block_tiles > 0)[0]
+    c["empty_blocks_between"] = int(holding[-1] - holding[0] + 1 - len(holding)) if len(holding) else 0
+    firsts = np.arange(blocks) * BLOCK
+    lasts = np.minimum(firsts + BLOCK, n) - 1
+    c["block_first_drawn"], c["block_last_drawn"] = int(drawn[firsts].sum()), int(drawn[lasts].sum())
+    c["scan_turns"] = -(-blocks // SCAN_TURN_BLOCKS)
+    turn_records = SCAN_TURN_BLOCKS * BLOCK
+    c["drawn_per_turn"] = tuple(int(drawn[k * turn_records:(k + 1) * turn_records].sum()) for k in range(c["scan_turns"]))
+    c["last_block_records"] = n - (blocks - 1) * BLOCK if n else 0
+    c["drawn_in_last_block"] = int(drawn[(blocks - 1) * BLOCK:].sum()) if n else 0
+    c["setup_grid"] = max(1, -(-occupancy // BLOCK))
+    c["blocks_beyond_count"] = c["setup_grid"] - blocks
+
+    # tiles: the paths, and the shapes of the clipped rectangle (per occluder: a side of its range clips one column or row of tiles)
+    c["inside"], c["mixed"], c["outside"] = twin_paths(twin, m, b, vp, width, height, min_pixels)
+    c["clip_left"] = int(tile_rows[drawn & (x0 % T != 0)].sum())
+    c["clip_right"] = int(tile_rows[drawn & (x1 % T != T - 1)].sum())
+    c["clip_top"] = int(tiles_x[drawn & (y0 % T != 0)].sum())
+    c["clip_bottom"] = int(tiles_x[drawn & (y1 % T != T - 1)].sum())
+    c["cut_right_edge"] = int(tile_rows[drawn & (x1 // T == (width - 1) // T)].sum()) if width % T else 0
+    c["cut_bottom_edge"] = int(tiles_x[drawn & (y1 // T == (height - 1) // T)].sum()) if height % T else 0
+    c["half_last_step"] = int(tiles_x[drawn & (y1 % T % 2 == 0)].sum())
+    c["half_first_step"] = int(tiles_x[drawn & (y0 % T % 2 == 1)].sum())
+    c["overlap_max"] = int(twin_overlap(twin, m, b, vp, width, height, min_pixels).max(initial=0))
+    assert c["inside"] + c["mixed"] + c["outside"] == total and c["reuse"] + c["cross"] + c["waves_with_items"] == total
+    return c
+
+
+def records_of(fetched, boxes):
+    """(models [n, 12], boxes [n, 6]) of fetched records in their order: the records' own models, the boxes of their POOL slots"""
+    n = int(fetched["draw_count"])
+    slots = np.asarray(fetched["visible_idx"])[:n].astype(np.int64)
+    return np.asarray(fetched["baked_model"], np.float32).reshape(-1, 12)[:n], np.asarray(boxes, np.float32)[slots]
+
+
+def census_line(census):
+    """the census on one line, for a report"""
+    return ", ".join(f"{k} {v}" for k, v in census.items() if k != "counts") + ", " + " ".join(f"{k} {v}" for k, v in census["counts"].items())
+
+
+# ---- the walk cases: the smallest shapes found that reach each form of the raster and scan launches -------------------------------
+
+def plant(sc, lo, hi, slot, scale=(4.0, 4.0, 4.0), position=None):
+    """slot becomes an upright box of the given scale (at its own pivot unless a position is given) whose occluder box is 0.9 of its
+    unit AABB: a drawn occluder under parity_view() wherever in [-20, 20]^3 it stands"""
+    t, m = sc.transforms, sc.meshes
+    if position is not None:
+        t["position"][slot, :3] = position
+    t["scale"][slot, :3] = scale
+    t["rotation"][slot] = (0.0, 0.0, 0.0, 1.0)
+    m["aabbMin"][slot, :3], m["aabbMax"][slot, :3] = -1.0, 1.0
+    lo[slot, :3], hi[slot, :3] = -0.9, 0.9
+
+
+def in_mirror_order(sc):
+    """the same entities with their slots laid in the order the mirror gives them (tests/reorder_support.py): the mirror's order
+    of the result IS its slot order, so both mirror orders deliver the records of such a world alike"""
+    import reorder_support
+    table, _ = reorder_support.built_tables(sc.transforms, sc.entity_to_transform, sc.meshes["entity"])
+    transforms, meshes = sc.transforms[table].copy(), sc.meshes[table].copy()
+    e2t = np.full(len(sc.entity_to_transform), scene.GV_NONE, np.uint32)
+    e2t[transforms["entity"]] = np.arange(len(transforms), dtype=np.uint32)
+    return scene.Scene(meshes, transforms, e2t)
+
+
+def _parity_case(n):
+    sc = parity_world(n)
+    lo, hi = occluder_boxes(sc.meshes)
+    return sc, lo, hi
+
+
+STACK_PLATES = 64
+
+
+def _stack_case(n):
+    """n coaxial, upright plates that fill the screen of parity_view(), 10 + k in front of the camera in a shuffled slot order"""
+    sc = scene.flat_scene(n, seed=scene.SEED + 0x0CC8, defects=False)
+    depth = 10.0 + np.random.Generator(np.random.PCG64(scene.SEED ^ 0x0CC8)).permutation(n)
+    t, m = sc.transforms, sc.meshes
+    t["position"][:, :3] = np.stack([np.zeros(n), np.zeros(n), depth - CAMERA_BACK], axis=1).astype(np.float32)
+    t["scale"][:, :3] = (200.0, 200.0, 0.05)
+    t["rotation"][:] = (0.0, 0.0, 0.0, 1.0)
+    m["aabbMin"][:, :3], m["aabbMax"][:, :3] = -1.0, 1.0
+    return sc, m["aabbMin"].copy(), m["aabbMax"].copy()
+
+
+SCAN_STRIDE = 509
+
+
+def _scan_case(n):
+    """a box on every SCAN_STRIDE-th slot only, and one planted on the last slot at the far corner of the pivots' range: the last
+    record in slot order and — the largest code of the mirror's order, the last slot among equals — in the mirror's. Unlike
+    parity_world alone, the pivots are spread to [-50, 50] in x and y (still inside parity_view(): every slot is a draw) and the
+    slots without a box are a hundredth of their size: at parity_world's own spread and sizes parity_view(fov=NARROW_FOV) keeps nine
+    slots in ten, and the second draw is to leave most of the setup grid beyond the count."""
+    sc, lo, hi = _parity_case(n)
+    keep = np.zeros(n, bool)
+    keep[::SCAN_STRIDE] = True
+    lo[~keep], hi[~keep] = 0.0, 0.0
+    sc.transforms["position"][:, :2] *= np.float32(2.5)
+    sc.transforms["scale"][~keep, :3] *= np.float32(0.01)
+    plant(sc, lo, hi, n - 1, position=(50.0, 50.0, 20.0))
+    return sc, lo, hi
+
+
+GAP_SLOTS = (BLOCK, 3 * BLOCK)
+
+
+def _gap_case(n):
+    """parity_world in the mirror's order, the slots of two whole record blocks in the middle without boxes, and a box that fills
+    the screen planted on either side of the gap: the last record of the block in front of it and the first of the block behind it"""
+    sc = in_mirror_order(parity_world(n))
+    lo, hi = occluder_boxes(sc.meshes)
+    lo[GAP_SLOTS[0]:GAP_SLOTS[1]], hi[GAP_SLOTS[0]:GAP_SLOTS[1]] = 0.0, 0.0
+    plant(sc, lo, hi, GAP_SLOTS[0] - 1, scale=(200.0, 200.0, 1.0))
+    plant(sc, lo, hi, GAP_SLOTS[1], scale=(200.0, 200.0, 1.0))
+    return sc, lo, hi
+
+
+class WalkCase:
+    """name, record count, image size, the world's builder, what the case exists for, and the conditions its census must meet: a
+    tuple of (text, predicate of the census). `narrow`: the conditions of a second draw into the same image, of
+    parity_view(fov=NARROW_FOV) of the same pool."""
+
+    def __init__(self, name, records, width, height, build, forms, conditions, narrow=()):
+        self.name, self.records, self.width, self.height, self.build = name, records, width, height, build
+        self.forms, self.conditions, self.narrow = forms, tuple(conditions), tuple(narrow)
+
+    def __repr__(self):
+        return self.name
+
+    def missed(self, census, conditions=None):
+        """the texts of the conditions the census does not meet"""
+        return [text for text, holds in (self.conditions if conditions is None else conditions) if not holds(census)]
+
+
+NARROW_FOV = 20.0
+# CONDITIONS, not measurements of the kernel: they keep a case from passing without reaching the form it is named for. total, share,
+# the tile paths and tiles_x_max do not depend on the order of the records; what does (reuse, crossings, where a walk starts) is asked
+# for as "at least one", or as a count that the oracle's records in slot order clear by a factor of three or more.
+WALK_CASES = (
+    WalkCase("share-2", 1025, 512, 256, _parity_case, "share >= 2; reuse; crossings; every tile path",
+             [("share >= 2", lambda c: c["share"] >= 2),
+              ("reuse >= 1000", lambda c: c["reuse"] >= 1000),
+              ("cross >= 100", lambda c: c["cross"] >= 100),
+              ("cross_over_empty >= 1", lambda c: c["cross_over_empty"] >= 1),
+              ("every tile path >= 100", lambda c: min(c["inside"], c["mixed"], c["outside"]) >= 100)]),
+    WalkCase("npot-1000x600", 1025, 1000, 600, _parity_case, "share >= 4; an image no multiple of T; tiles clipped on every side",
+             [("share >= 4", lambda c: c["share"] >= 4),
+              ("tiles cut by the right image edge", lambda c: 1000 % T != 0 and c["cut_right_edge"] >= 1),
+              ("tiles cut by the bottom image edge", lambda c: 600 % T != 0 and c["cut_bottom_edge"] >= 1),
+              ("range-clipped tiles on all four sides", lambda c: min(c["clip_left"], c["clip_right"], c["clip_top"], c["clip_bottom"]) >= 1),
+              ("a first step with only its lower row", lambda c: c["half_first_step"] >= 1)]),
+    WalkCase("wide-4099x33", 1025, 4099, 33, _parity_case, "tiles_x > 64; a second tile row one pixel high; width = 3 mod 32",
+             [("tiles_x_max > 64", lambda c: c["tiles_x_max"] > 64),
+              ("a second tile row, one pixel high", lambda c: 33 % T == 1 and c["tile_rows_max"] == 2 and c["cut_bottom_edge"] >= 1),
+              ("half-used last wave steps", lambda c: c["half_last_step"] >= c["cut_bottom_edge"] >= 1),
+              ("width = 3 mod 32", lambda c: 4099 % 32 == 3 and c["cut_right_edge"] >= 1),
+              ("mid_row_starts >= 1", lambda c: c["mid_row_starts"] >= 1)]),
+    WalkCase("full-2048x1024", 1025, 2048, 1024, _parity_case, "share >= 16; walks inside one occluder; mid-row starts; the inside path",
+             [("share >= 16", lambda c: c["share"] >= 16),
+              ("single_occluder_walks >= 1", lambda c: c["single_occluder_walks"] >= 1),
+              ("mid_row_starts >= 1", lambda c: c["mid_row_starts"] >= 1),
+              ("inside >= 10000", lambda c: c["inside"] >= 10_000),
+              ("mixed and outside in the thousands", lambda c: min(c["mixed"], c["outside"]) >= 1000),
+              ("cross_block >= 1", lambda c: c["cross_block"] >= 1)]),
+    WalkCase("stack", STACK_PLATES, 512, 256, _stack_case, "64 occluders over every pixel",
+             [("overlap_max == 64", lambda c: c["overlap_max"] == STACK_PLATES == 64),
+              ("share >= 2", lambda c: c["share"] >= 2),
+              ("every plate is drawn", lambda c: c["counts"]["drawn"] == STACK_PLATES)]),
+    WalkCase("scan-3-turns", 2 * SCAN_TURN_BLOCKS * BLOCK + 1, 64, 48, _scan_case, "three scan turns; a sparse grid",
+             [("scan_turns == 3", lambda c: c["scan_turns"] == 3),
+              ("a drawn occluder in every turn", lambda c: len(c["drawn_per_turn"]) == 3 and min(c["drawn_per_turn"]) >= 1),
+              ("a drawn occluder in the last block, one record wide", lambda c: c["last_block_records"] == 1 and c["drawn_in_last_block"] == 1),
+              ("empty_blocks_between >= 1", lambda c: c["empty_blocks_between"] >= 1)],
+             narrow=[("blocks_beyond_count >= half the grid", lambda c: 2 * c["blocks_beyond_count"] >= c["setup_grid"]),
+                     ("the narrow view draws something", lambda c: c["counts"]["drawn"] >= 1)]),
+    WalkCase("sparse-then-dense", 1025, 512, 256, _gap_case, "two empty record blocks inside a walk",
+             [("empty_blocks_between == 2", lambda c: c["empty_blocks_between"] == 2),
+              ("a crossing jumps the empty blocks", lambda c: c["cross_empty_blocks"] >= 1),
+              ("block_last_drawn >= 1 and block_first_drawn >= 1", lambda c: c["block_last_drawn"] >= 1 and c["block_first_drawn"] >= 1),
+              ("share >= 2", lambda c: c["share"] >= 2)]),
+)
+WALK_CASE = {case.name: case for case in WALK_CASES}
+
+
+@functools.lru_cache(maxsize=None)
+def walk_world(name):
+    """(scene, lo, hi, boxes by slot) of a case, built once: treat as read-only"""
+    case = WALK_CASE[name]
+    sc, lo, hi = case.build(case.records)
+    assert sc.count == case.records
+    return sc, lo, hi, boxes_by_slot(lo, hi)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_records(name, fov=90.0):
+    """the oracle's records of a case's world under parity_view(fov=fov): slot order, the device's under keep_slot_order. Read-only."""
+    from oracle import oracle_py
+    sc = walk_world(name)[0]
+    return oracle_py.prepare_meshes(sc.meshes.copy(), sc.transforms, sc.entity_to_transform, parity_view(fov=fov))
+
+
+def mirror_order(name, records):
+    """the same records in the order the mirror delivers them when it keeps its own order (tests/reorder_support.py)"""
+    import reorder_support
+    sc = walk_world(name)[0]
+    _, table = reorder_support.built_tables(sc.transforms, sc.entity_to_transform, sc.meshes["entity"])
+    n = int(records["draw_count"])
+    slots = np.asarray(records["visible_idx"])[:n]
+    place = np.full(sc.count, -1, np.int64)
+    place[slots] = np.arange(n)
+    order = place[table]
+    order = order[order >= 0]
+    return dict(draw_count=n, visible_idx=slots[order], baked_model=np.asarray(records["baked_model"]).reshape(-1, 12)[:n][order])
