@@ -734,6 +734,7 @@ void gv_destroy(GvCtx* ctx)
     for (auto& m : ctx->merges)
         m.release();
     ctx->occluder_depth.release();
+    ctx->receiver_mask.release();
     ctx->d_depth.release(); ctx->d_mips.release(); ctx->d_mip_offset.release(); ctx->d_tick.release(); ctx->h_done.release();
     for (int k = 0; k < 2; k++) {
         ctx->h_tick[k].release();
@@ -1171,6 +1172,9 @@ int gv_hiz_build(GvCtx* ctx, const float* depth, uint32_t width, uint32_t height
         // (gv_hiz_build_from_occluders comes through here; so does a caller who passes gv_occluder_depth_device's pointer)
         if (depth == ctx->occluder_depth.d_image[ctx->occluder_depth.current].ptr)
             ctx->occluder_depth.open = false;
+        // ... or one of its receiver masks (gv_hiz_build_from_receivers, or gv_receiver_mask_device's pointer): the same rule
+        if (depth == ctx->receiver_mask.d_image[ctx->receiver_mask.current].ptr)
+            ctx->receiver_mask.open = false;
     } else {
         GV_HIP(ctx, ctx->d_depth.reserve((size_t)width * height));
         GV_HIP(ctx, hipMemcpyAsync(ctx->d_depth.ptr, depth, (size_t)width * height * 4, hipMemcpyHostToDevice, ctx->stream));

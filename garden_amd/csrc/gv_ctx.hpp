@@ -25,6 +25,7 @@
 #include "gv_bounds_kernels.hpp"
 #include "gv_delta_kernels.hpp"
 #include "gv_occluder_kernels.hpp"
+#include "gv_receiver_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -713,6 +714,20 @@ struct Context {
         }
     } occluder_depth;
 
+    // ---- receiver mask (gv_receivers.cpp): TWO images of its own, by the same rule — the one the current pyramid reads is never
+    // cleared, redrawn or reallocated under it. Accumulated state like the occluder images: end_derived has no line for it. A draw's
+    // scratch is occluder_depth.d_local / d_base: every user is ordered on the one stream.
+    struct ReceiverMask {
+        DeviceBuf<float> d_image[2];
+        uint32_t current = 0;              // the image of the last gv_receiver_begin
+        uint32_t width = 0, height = 0;    // ... and its size (0: no begin yet)
+        bool open = false;                 // begun and not built since: draws go into it
+        DeviceBuf<ReceiverCounts> d_counts;
+        PinnedBuf<ReceiverCounts> h_counts;  // staging of gv_receiver_mask_fetch
+        PinnedBuf<float> h_image;
+        void release() { d_image[0].release(), d_image[1].release(), d_counts.release(), h_counts.release(), h_image.release(); }
+    } receiver_mask;
+
     // ---- multi-GPU exchange (gv_exchange.cpp) ----
     void* exchange_comm = nullptr;     // ncclComm_t
     int exchange_rank = 0, exchange_world = 1;
@@ -853,6 +868,7 @@ struct KernelTimer {
 // Context::occluder_depth (gv_pool_draw_occluders) has NO line either: the image is accumulated over the draws of several pools and
 // views since gv_occluder_begin, and what it holds — depths of boxes as they stood when they were drawn — is not made any less true by
 // a later cull. It lives until the begin that takes it again (never the image the current pyramid reads) or gv_destroy.
+// Context::receiver_mask (gv_pool_draw_receivers) likewise: accumulated since gv_receiver_begin, ended by nothing but the next begin.
 enum class Ends {
     ViewsReplaced,     // gv_cull, gv_pool_cull_second_phase: the views' results are replaced
     EmissionReplaced,  // gv_pool_emit_instances, gv_pool_emit_draw_instances: the instance data is replaced

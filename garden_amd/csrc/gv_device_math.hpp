@@ -422,4 +422,62 @@ __device__ __forceinline__ long long occluder_edge_hi(const OccluderEdge& g, lon
     return 16 * (g.ex * (g.ex > 0 ? cy1 : cy0) - g.ey * (g.ey > 0 ? cx0 : cx1)) + g.at;
 }
 
+// ------------------------------------------------------------------------------------------------
+// receiver mask (shadow-caster culling by a receiver mask, Bittner et al. 2011: the reference culls every shadow
+// pass as a plain frustum cull, mesh.cpp:795-847). The mirror image of item 16: an OUTER rasteriser that keeps the MINIMUM of the boxes'
+// farthest depths, projected with a matrix the caller names. Test twin: tests/receiver_twin.h. Kernels: gv_receivers.hip.
+//
+// THE RECEIVER RULE (the same text stands in DESIGN.md §4 item 17 and tests/receiver_twin.h). For draw k of the source view: slot s_k,
+// record model M_k, the slot's cull AABB (amin, amax) as the mesh mirror holds it, L = the call's light_view_proj, the mask W x H.
+//  1. Corners p_c = aabb_corners(M_k, amin, amax) and clip coordinates exactly as item 16 step 2 with L in place of VP: cl_r = fma(L[r],
+//     p.x, fma(L[4 + r], p.y, fma(L[8 + r], p.z, L[12 + r]))), rcp = 1.0f / cl_w (IEEE), u = fma(cl_x * rcp, .5, .5), v likewise,
+//     z = cl_z * rcp: a caster that is also a receiver gets the words its own Hi-Z query computes against L.
+//  2. Any corner with !(cl_w > 0): counted behind, and +0.0f goes into EVERY pixel of the mask (a receiver that cannot be bounded keeps
+//     every caster; it is never skipped).
+//  3. m = minNum over the 8 corners of z; d = (m > 0.0f) ? m : +0.0f (a NaN gives +0.0f; -0.0f, whose bits are the largest unsigned
+//     word, never appears). No upper clamp: a receiver in front of the near plane keeps its d > 1.
+//  4. fx = floorf(u * (float)(16 W)), fy = floorf(v * (float)(16 H)). Any !(|f| < 4194304.0f): counted range, and d goes into every
+//     pixel of the mask. Otherwise X_c, Y_c are int32.
+//  5. x0 = max((min X - 2) >> 4, 0), x1 = min((max X + 2) >> 4, W - 1) (arithmetic shifts; the 2 is item 16's margin), y likewise. An
+//     empty range: counted outside, nothing written.
+//  6. Faces, areas (int64) and active directed edges as item 16 step 6. No positive face: counted flat, and d goes into every pixel of
+//     the range (an edge-on sprite, a sub-pixel box).
+//  7. Otherwise counted drawn. Pixel (px, py) of the range is touched <=> for EVERY active edge a -> b SOME pixel corner cx in {px, px + 1},
+//     cy in {py, py + 1} passes ex (16 cy - Y_a) - ey (16 cx - X_a) >= -2 (|ex| + |ey|), ex = X_b - X_a, ey = Y_b - Y_a, all int64: item
+//     16's half-plane test at the corner that lies MOST inside, with the margin on the other side. d goes into every touched pixel.
+//  8. mask[py W + px] = min(+inf, min over the receivers that write the pixel of their word), taken on the floats' bits as uint32: every
+//     word is a non-negative float or +inf, so that order is the float order, and the result depends on no order of evaluation.
+// ------------------------------------------------------------------------------------------------
+// Steps 1, 4 and 6 are occluder_clip, occluder_snap and occluder_edges: the same words.
+// Step 3 (IEEE minNum; the nesting cannot change a value that passes m > 0, and everything else becomes +0.0f)
+__device__ __forceinline__ float receiver_depth(const float (&z)[8])
+{
+    const float m = fminf(fminf(fminf(z[0], z[1]), fminf(z[2], z[3])), fminf(fminf(z[4], z[5]), fminf(z[6], z[7])));
+    return m > 0.0f ? m : 0.0f;
+}
+// Step 7 for one edge: E = ex (16 cy - Ya) - ey (16 cx - Xa) + 2 (|ex| + |ey|) = 16 (ex cy - ey cx) + at. A pixel passes the edge when
+// E >= 0 at its best corner: occluder_edge_hi over [px, px + 1] x [py, py + 1].
+__device__ __forceinline__ OccluderEdge receiver_edge(int32_t xa, int32_t ya, int32_t xb, int32_t yb)
+{
+    OccluderEdge g;
+    g.ex = (long long)xb - xa;
+    g.ey = (long long)yb - ya;
+    g.at = g.ey * xa - g.ex * ya + 2 * ((g.ex < 0 ? -g.ex : g.ex) + (g.ey < 0 ? -g.ey : g.ey));
+    return g;
+}
+__device__ __forceinline__ long long receiver_edge_at(const OccluderEdge& g, long long px, long long py)
+{
+    return occluder_edge_hi(g, px, px + 1, py, py + 1);
+}
+// ... over the PIXELS [px0, px1] x [py0, py1]: the best corner's E of the pixel where it is smallest ("lo >= 0": every pixel passes the
+// edge) and largest ("hi < 0": none does). The best corner's E is linear in (px, py) too.
+__device__ __forceinline__ long long receiver_edge_lo(const OccluderEdge& g, long long px0, long long px1, long long py0, long long py1)
+{
+    return receiver_edge_at(g, g.ey > 0 ? px1 : px0, g.ex > 0 ? py0 : py1);
+}
+__device__ __forceinline__ long long receiver_edge_hi(const OccluderEdge& g, long long px0, long long px1, long long py0, long long py1)
+{
+    return receiver_edge_at(g, g.ey > 0 ? px0 : px1, g.ex > 0 ? py1 : py0);
+}
+
 }  // namespace gv

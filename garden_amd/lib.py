@@ -146,6 +146,13 @@ class GvOccluderCounts(C.Structure):
 OCCLUDER_COUNT_NAMES = tuple(name for name, _ in GvOccluderCounts._fields_)
 
 
+class GvReceiverCounts(C.Structure):
+    _fields_ = [(name, C.c_uint32) for name in ("drawn", "flat", "behind", "range", "outside", "reserved")]
+
+
+RECEIVER_COUNT_NAMES = tuple(name for name, _ in GvReceiverCounts._fields_)
+
+
 GV_MAX_DELTA_CHANNELS = 4
 GV_DELTA_RESTART = 1
 
@@ -240,6 +247,7 @@ EXPORTS = [
     "gv_pool_view_delta", "gv_pool_view_delta_device", "gv_pool_view_delta_fetch",
     "gv_pool_bind_occluders", "gv_occluder_begin", "gv_pool_draw_occluders", "gv_occluder_depth_device", "gv_occluder_depth_fetch",
     "gv_hiz_build_from_occluders",
+    "gv_receiver_begin", "gv_pool_draw_receivers", "gv_receiver_mask_device", "gv_receiver_mask_fetch", "gv_hiz_build_from_receivers",
 ]
 
 _lib = None
@@ -387,6 +395,11 @@ def load():
     lib.gv_occluder_depth_device.argtypes = [P, C.POINTER(P), C.POINTER(u32), C.POINTER(u32), C.POINTER(P)]
     lib.gv_occluder_depth_fetch.argtypes = [P, P, C.c_size_t, C.POINTER(GvOccluderCounts)]
     lib.gv_hiz_build_from_occluders.argtypes = [P]
+    lib.gv_receiver_begin.argtypes = [P, u32, u32]
+    lib.gv_pool_draw_receivers.argtypes = [P, u32, u32, P]
+    lib.gv_receiver_mask_device.argtypes = [P, C.POINTER(P), C.POINTER(u32), C.POINTER(u32), C.POINTER(P)]
+    lib.gv_receiver_mask_fetch.argtypes = [P, P, C.c_size_t, C.POINTER(GvReceiverCounts)]
+    lib.gv_hiz_build_from_receivers.argtypes = [P]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name not in ("gv_abi_version", "gv_destroy", "gv_last_error", "gv_stream", "gv_scene_destroy"):
@@ -1200,6 +1213,35 @@ class GpuVisibility:
     def hiz_build_from_occluders(self):
         """gv_hiz_build_from_occluders: the pyramid of the open image (not copied), which it closes"""
         self._check(self.lib.gv_hiz_build_from_occluders(self.ctx))
+
+    # ---- receiver mask ----
+    def receiver_begin(self, width, height):
+        """gv_receiver_begin: opens (sizes, clears to +inf) the receiver image the current pyramid does not read; asynchronous"""
+        self._check(self.lib.gv_receiver_begin(self.ctx, width, height))
+
+    def draw_receivers(self, pool_id, view_index, light_view_proj):
+        """gv_pool_draw_receivers: the cull AABBs of the view's draws into the open mask, projected with light_view_proj (16 fp32,
+        column-major; copied by the call); asynchronous"""
+        light = np.ascontiguousarray(light_view_proj, dtype=np.float32).reshape(16)
+        self._check(self.lib.gv_pool_draw_receivers(self.ctx, pool_id, view_index, light.ctypes.data))
+
+    def receiver_mask_device(self):
+        """gv_receiver_mask_device: (device pointer of the mask, width, height, device pointer of the counts)"""
+        mask, counts, w, h = C.c_void_p(), C.c_void_p(), C.c_uint32(), C.c_uint32()
+        self._check(self.lib.gv_receiver_mask_device(self.ctx, C.byref(mask), C.byref(w), C.byref(h), C.byref(counts)))
+        return mask.value, w.value, h.value, counts.value
+
+    def receiver_mask(self):
+        """gv_receiver_mask_fetch: waits; (mask fp32 [height, width], counts as a dict of the six fields)"""
+        _, w, h, _ = self.receiver_mask_device()
+        image = np.empty((h, w), np.float32)
+        counts = GvReceiverCounts()
+        self._check(self.lib.gv_receiver_mask_fetch(self.ctx, image.ctypes.data, image.nbytes, C.byref(counts)))
+        return image, {name: int(getattr(counts, name)) for name in RECEIVER_COUNT_NAMES}
+
+    def hiz_build_from_receivers(self):
+        """gv_hiz_build_from_receivers: the pyramid of the open mask (not copied), which it closes"""
+        self._check(self.lib.gv_hiz_build_from_receivers(self.ctx))
 
     def hiz_mip_count(self):
         n = C.c_uint32()

@@ -865,6 +865,69 @@ int gv_occluder_depth_fetch(GvCtx* ctx, float* depth, size_t bytes, GvOccluderCo
  * (gv_occluder_depth_device) to gv_hiz_build himself closes it the same way: no image takes a draw once a pyramid reads it. */
 int gv_hiz_build_from_occluders(GvCtx* ctx);
 
+/* ---- receiver mask: shadow-caster culling against what the main view sees ----
+ * A shadow cascade's box is long towards the light, so a plain frustum cull of it keeps many casters whose shadows fall on nothing the
+ * main camera sees. The remedy (Bittner et al. 2011): draw the bounds of what the main view SEES into the light's clip space, keeping
+ * per texel the farthest depth any visible receiver reaches, +inf where none does; a caster wholly behind every receiver under its
+ * footprint, or over empty texels, is dropped. No new cull: the Hi-Z query reports "occluded" iff the box's nearest depth is less than
+ * the minimum of the pyramid over its footprint, which over such an image reads "behind every visible receiver it could shadow". Every
+ * consumer of the pyramid compares and never computes, so the infinity is harmless. These calls draw the image: every draw of a
+ * delivered view writes one depth — its cull AABB's farthest, against the matrix the caller names — into every pixel the AABB's projected
+ * silhouette TOUCHES, grown by the margin the occluder raster shrinks by; each pixel keeps the minimum. The boxes are the ones the cull
+ * already mirrors: there is no binding and no binder's contract.
+ *   Frame order: 1. gv_cull of the main view (which may itself use Hi-Z against the renderer's depth). 2. For each cascade k:
+ *     gv_receiver_begin -> gv_pool_draw_receivers(pool, main view, L_k) for every pool that receives shadows ->
+ *     gv_hiz_build_from_receivers -> gv_cull of cascade k with use_hiz = 1. 3. The context has ONE pyramid: the main view's depth
+ *     pyramid is rebuilt next frame (as it is every frame anyway), and cascades culled this way go one at a time — they leave the
+ *     batched multi-view pass. A gv_cull replaces ALL views of its pool: a cull that names cascade k alone ends the main view's
+ *     records, which the next cascade's mask is drawn from — name the main view again in front of it.
+ *   The rule, per draw k of the source view (slot s = visible_idx[k], M = the record's own bakedModel, (amin, amax) = the slot's cull
+ *   AABB as mirrored, L = light_view_proj):
+ *     1. corners and clip coordinates exactly as the Hi-Z query computes them against L: a caster that is also a receiver gets its
+ *        own query's words, and is never culled by itself.
+ *     2. any corner with !(w > 0): counted behind; +0.0f into EVERY pixel (a receiver that cannot be bounded keeps every caster). A
+ *        NaN or infinite model lands here, not in step 4: every corner's w is NaN whatever L holds.
+ *     3. d = the minNum of the 8 z when that is > 0, +0.0f otherwise (never -0.0f); no upper clamp.
+ *     4. X = floorf(u * 16 W), Y = floorf(v * 16 H); any !(|.| < 2^22): counted range; d into every pixel.
+ *     5. pixel range x0 = max((min X - 2) >> 4, 0) .. x1 = min((max X + 2) >> 4, W - 1), y likewise; empty: counted outside, nothing written.
+ *     6. the silhouette edges as for occluders; no positive face: counted flat; d into every pixel of the range.
+ *     7. otherwise counted drawn; a pixel is touched <=> for every silhouette edge a -> b SOME pixel corner passes
+ *        ex (16 cy - Y_a) - ey (16 cx - X_a) >= -2 (|ex| + |ey|) (int64); d into every touched pixel.
+ *     8. mask[py W + px] = min(+inf, min of the words written there) on the floats' bits: order-independent, reproducible bit for bit. */
+typedef struct GvReceiverCounts { /* 24 bytes; summed over the draws of every gv_pool_draw_receivers since gv_receiver_begin */
+    uint32_t drawn, flat, behind, range, outside, reserved; /* every record lands in exactly one of the first five; reserved is 0 */
+} GvReceiverCounts;
+/* Opens a receiver mask of width x height (1 .. 32768 each): sized, every word cleared to +inf (0x7F800000: "no receiver here") and
+ * its counts zeroed, asynchronously on gv_stream(ctx). The context owns TWO receiver images of its own, apart from the occluder
+ * images, and takes the one the current pyramid does not read: an image a pyramid reads is never cleared, redrawn or reallocated
+ * under it. A begin on an open mask starts it over. An open occluder image and an open receiver mask may coexist.
+ * GV_E_ARG: a NULL ctx; a size of 0 or above 32768 (nothing changes). GV_E_OOM: an open mask that had to grow is gone; the pyramid's
+ * image is not touched. */
+int gv_receiver_begin(GvCtx* ctx, uint32_t width, uint32_t height);
+/* Draws the cull AABBs of the records of one delivered view of one pool into the open mask, projected with light_view_proj (16 floats,
+ * column-major like GvView::view_proj; copied by the call); several pools and views may draw into one mask. A read of the view, as
+ * gv_pool_view_bounds and gv_pool_draw_occluders (recorded culls and deferred sorts are launched first; records of sorted, grouped and
+ * second-phase views alike, in delivery order, the device draw count never read by the host); asynchronous on gv_stream(ctx): three
+ * kernel launches whatever the counts, under GvStats::launches[GV_K_HIZ]. A receiver whose range holds at most 16 pixels is written
+ * by the first launch; the tiles of the others are listed and walked by the third.
+ * MEMORY: the scratch of gv_pool_draw_occluders, shared with it (one word per slot of the occupancy the view was culled with and 8
+ * bytes per 256 slots), allocated at first use and kept.
+ * GV_E_ARG: a NULL ctx or matrix; a pool that is not bound; a view index >= GV_MAX_VIEWS, or one no cull of the pool ever had a view at.
+ * GV_E_STATE: no open mask (gv_receiver_begin; gv_hiz_build_from_receivers closes it); a view without results or culled count-only;
+ * a mesh mirror that covers fewer slots than the view was culled with — a guard only, like gv_pool_view_bounds's: a cull synchronises
+ * the mirror it reads, and no sequence of public calls is known to reach it. */
+int gv_pool_draw_receivers(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, const float light_view_proj[16]);
+/* The mask of the last gv_receiver_begin (open or built) in device memory, width * height fp32 in rows, and its counts as six
+ * uint32 (valid behind the draws on gv_stream(ctx)). GV_E_ARG: a NULL ctx or output. GV_E_STATE: no gv_receiver_begin yet. */
+int gv_receiver_mask_device(GvCtx* ctx, const void** mask, uint32_t* width, uint32_t* height, const void** counts);
+/* Waits for the draws and copies the mask (may be NULL: counts only; `bytes` is the room at mask) and the counts (may be NULL).
+ * GV_E_ARG: a NULL ctx; both outputs NULL; bytes below width * height * 4 (nothing is written). GV_E_STATE as above. */
+int gv_receiver_mask_fetch(GvCtx* ctx, float* mask, size_t bytes, GvReceiverCounts* counts);
+/* gv_hiz_build(mask, width, height, GV_MEM_DEVICE) of the open mask, and closes it: further draws need a new gv_receiver_begin
+ * (which takes the other image). GV_E_STATE: no open mask. Otherwise as gv_hiz_build. A caller who hands the open mask's pointer
+ * (gv_receiver_mask_device) to gv_hiz_build himself closes it the same way. */
+int gv_hiz_build_from_receivers(GvCtx* ctx);
+
 /* ---- the shared sorted arrays: the sorted lists of several mesh systems merged into ONE array, on the device ----
  * The reference keeps one array per sorted kind — transSortedMeshes, uiSortedMeshes, one translucent array per shadow pass — into
  * which every sorted system appends SortedMesh records tagged with its bufferIndex (mesh.cpp:247-261); one std::sort orders the
