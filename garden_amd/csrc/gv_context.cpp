@@ -107,6 +107,7 @@ int begin_view(GvCtx* ctx, ViewState& vs, uint32_t pool_id, const GvView& view, 
     vs.sorted_dir = 0;
     vs.ballots_current = true;  // every cull launch but the one-launch cull + emit of a small pool writes them
     memcpy(vs.view_proj, view.view_proj, sizeof(vs.view_proj));
+    memcpy(vs.camera_position, view.camera_position, sizeof(vs.camera_position));
     build_view_params(view, vp);
     return GV_OK;
 }

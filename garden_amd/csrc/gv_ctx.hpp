@@ -26,6 +26,7 @@
 #include "gv_delta_kernels.hpp"
 #include "gv_occluder_kernels.hpp"
 #include "gv_receiver_kernels.hpp"
+#include "gv_previous_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -415,6 +416,30 @@ struct PoolState {
             d_totals.release();
         }
     } delta;
+    // gv_pool_keep_models / gv_pool_forget_models: the models a view delivered, one 64-byte row per POOL slot (12 floats verbatim, the
+    // epoch they were kept at, three zero words). HISTORY like Delta above: no cull, emission, sort, group, re-order or re-bind ends it
+    // (end_derived has no line for it); only those two calls and gv_destroy change it. Header-only: no other host source calls gv_previous.cpp.
+    struct Models {
+        DeviceBuf<float4> d_rows;          // [4 per slot]; rows at or beyond `slots` hold nothing anybody reads
+        uint32_t epoch = 0;                // e: 0 = empty
+        uint32_t slots = 0;                // H.slots: the coverage
+        float view_proj[16] = {};          // of the view kept at epoch e, as given to its cull
+        float camera_position[3] = {};
+        void empty() { epoch = 0, slots = 0; }  // (the buffers stay)
+        void release() { d_rows.release(); }
+    } models;
+    // gv_pool_emit_previous: the last answer, made from a view (ends under Ends::ViewsReplaced), buffers of its own
+    struct Previous {
+        bool result = false;               // the buffers below hold an answer of a view of the pool's last cull
+        GvPreviousLayout emitted{};        // the layout it was made with
+        uint8_t* target = nullptr;         // d_data.ptr or the caller's device memory
+        uint32_t capacity = 0;             // items the target holds
+        DeviceBuf<uint8_t> d_data;         // the library-owned target
+        DeviceBuf<uint32_t> d_counts;      // {n, kept draws, items written, e}
+        PinnedBuf<uint8_t> h_data;         // staging of gv_pool_previous_fetch
+        PinnedBuf<uint32_t> h_counts;
+        void release() { d_data.release(), d_counts.release(), h_data.release(), h_counts.release(); }
+    } previous;
     // gv_pool_bind_occluders: the occluder boxes, mirrored as one 32-byte row per POOL SLOT (min in words 0-2, max in words 4-6; indexed
     // by visible_idx like the ids above): the mirror exists only once gv_pool_draw_occluders has been called for the pool
     struct Occluders : SlotMirror<uint8_t> {  // dirty: GV_DIRTY_OCCLUDER and GV_DIRTY_MESH marks of the pool
@@ -505,7 +530,7 @@ struct PoolState {
         d_orig.release(), d_inv.release(), d_index_map.release();
         d_blk_lo.release(), d_blk_hi.release(), d_blk_dirty.release(), d_hot.release(), d_seed.release(), d_kept.release(), d_kept_flag.release();
         instances.release(), payload.release(), counts.release(), geometry.release(), commands.release(), lod.release(), bounds.release();
-        delta.release(), occluders.release();
+        delta.release(), occluders.release(), models.release(), previous.release();
     }
 };
 
@@ -554,6 +579,7 @@ struct ViewState {
     uint32_t pool_id = 0, occupancy = 0;
     bool main_pass = false, emitted = false, valid = false;
     float view_proj[16] = {};  // GvView::view_proj of this view's cull (gv_pool_emit_instances multiplies the records' models by it)
+    float camera_position[3] = {};  // GvView::camera_position likewise (gv_pool_keep_models keeps it, gv_pool_emit_previous takes the difference)
     // fused cull + emit (launch_cull_emit): look-back words, ticket counter and their running epoch / base
     DeviceBuf<unsigned long long> tile_status;
     DeviceBuf<uint32_t> tile_ticket;
@@ -859,7 +885,7 @@ struct KernelTimer {
 // or per group (Context::merges) ----
 
 // When a derived result ends. The table, stated once:
-//     views     -> {instances, bounds, merges the pool is a member of}
+//     views     -> {instances, bounds, previous, merges the pool is a member of}
 //     instances -> {commands, selection}
 // A result ends when what it was made from is replaced. A new derived result is one more line here, under what it is made from.
 // PoolState::delta (gv_pool_view_delta) has NO line: its baseline is history — the set a channel saw at its last call, kept in pool
@@ -869,6 +895,8 @@ struct KernelTimer {
 // views since gv_occluder_begin, and what it holds — depths of boxes as they stood when they were drawn — is not made any less true by
 // a later cull. It lives until the begin that takes it again (never the image the current pyramid reads) or gv_destroy.
 // Context::receiver_mask (gv_pool_draw_receivers) likewise: accumulated since gv_receiver_begin, ended by nothing but the next begin.
+// PoolState::models (gv_pool_keep_models) has NO line: last frame's models by pool slot are history exactly as the delta baselines are.
+// PoolState::previous (gv_pool_emit_previous), the answer made from a view and that history, HAS one: it ends with the view.
 enum class Ends {
     ViewsReplaced,     // gv_cull, gv_pool_cull_second_phase: the views' results are replaced
     EmissionReplaced,  // gv_pool_emit_instances, gv_pool_emit_draw_instances: the instance data is replaced
@@ -880,6 +908,7 @@ static inline void end_derived(GvCtx* ctx, PoolState& p, Ends cause)
     case Ends::ViewsReplaced:
         p.instances.views = 0;
         p.bounds.items = 0;
+        p.previous.result = false;
         for (auto& m : ctx->merges)
             if ((m.pools >> (uint32_t)(&p - ctx->pools)) & 1u)
                 m.valid = false;

@@ -617,6 +617,11 @@ __device__ __forceinline__ uint32_t view_of_block(const uint32_t (&first)[kMaxIn
     return v;
 }
 
+// 16-byte slot of column c of the workgroup's instance i in the stage: rotated by i / 4 so that the 16 lanes of a store group
+// (4 instances x 4 columns on the way out, 16 instances x 1 column on the way in) cover the 16 slots of a bank row
+// (instance_kernel's mvp; the rows and the prev_mvp of gv_previous.hip)
+__device__ __forceinline__ uint32_t stage_slot(uint32_t i, uint32_t c) { return i * 4u + ((c + (i >> 2)) & 3u); }
+
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x, uint32_t lane)
 {
 #pragma unroll

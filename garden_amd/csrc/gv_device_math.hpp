@@ -261,6 +261,23 @@ __device__ __forceinline__ float4 mvp_column(const float (&a)[16], float b0, flo
 }
 
 // ------------------------------------------------------------------------------------------------
+// last frame's mvp per draw (the reference fills its velocity attachment from the camera alone,
+// shaders/velocity.frag, and has no per-object velocity: the rule is this build's). Test twin: tests/previous_twin.h. Kernels:
+// gv_previous.hip — the selection is two compares and three selects in front of mvp_column above, which IS step 4.
+//
+// THE PREVIOUS RULE (the same text stands in DESIGN.md §4 item 18, include/garden_vis.h and tests/previous_twin.h). For draw k of a
+// view: slot s_k, record model M_k, VP = the view's view_proj, the pool's history H (per slot 12 floats and a stamp; an epoch e, 0 =
+// empty; a coverage H.slots; the kept view's view_proj KVP and camera position KC), PVP = prev_view_proj, or KVP when it is NULL,
+// d_r = view.camera_position[r] - KC[r] (one fp32 subtraction per component, done on the host).
+//  1. Cut: GV_PREVIOUS_CUT, or e == 0: every draw is fresh, with PVP = VP and d = (0, 0, 0).
+//  2. Kept <=> no cut && s_k < H.slots && stamp[s_k] == e: P_k = the row's 12 floats.
+//  3. Fresh otherwise: the draw is taken as static in the world. P_k = M_k with c3[r] = M_k.c3[r] + d_r (one fp32 add per component);
+//     the other nine floats verbatim.
+//  4. prev_mvp_k = PVP * P_k exactly as item 9: element i of column j = fma(PVP[12 + i], b3, fma(PVP[8 + i], b2, fma(PVP[4 + i], b1,
+//     fma(PVP[i], b0, +0)))) with (b0, b1, b2) = column j of P_k and b3 = 0, or 1 for j = 3. has_history_k = 1 when kept, 0 when fresh.
+// ------------------------------------------------------------------------------------------------
+
+// ------------------------------------------------------------------------------------------------
 // level of detail of a draw (the reference carries ModelRenderComponent::lods, model.hpp:29-41, and no rule
 // that picks among them, so the rule is this build's). Test twin: tests/lod_twin.h.
 //   t          the translation of the record's bakedModel as delivered (floats 9, 10, 11): the pivot relative to camera_position

@@ -41,10 +41,6 @@
 
 namespace gv {
 
-// 16-byte slot of column c of the workgroup's instance i in the stage: rotated by i / 4 so that the 16 lanes of a store group
-// (4 instances x 4 columns on the way out, 16 instances x 1 column on the way in) cover the 16 slots of a bank row
-__device__ __forceinline__ uint32_t stage_slot(uint32_t i, uint32_t c) { return i * 4u + ((c + (i >> 2)) & 3u); }
-
 // the row's pieces and words to where the host's tables send them; put4(offset, float4) / put1(offset, float) write into the instance
 template <typename Put4, typename Put1>
 __device__ __forceinline__ void place_payload(const InstanceLaunch& a, const float4 (&row)[4], Put4 put4, Put1 put1)

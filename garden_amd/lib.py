@@ -162,6 +162,14 @@ class GvViewDelta(C.Structure):
                 ("vanished_count", C.c_uint32), ("visible_count", C.c_uint32), ("slots", C.c_uint32)]
 
 
+GV_KEEP_ADD = 1
+GV_PREVIOUS_CUT = 1
+
+
+class GvPreviousLayout(C.Structure):
+    _fields_ = [("stride", C.c_uint32), ("prev_mvp", C.c_uint32), ("has_history", C.c_uint32)]
+
+
 class GvCommandLayout(C.Structure):
     _fields_ = [("stride", C.c_uint32), ("count", C.c_uint32), ("instance_count", C.c_uint32), ("first", C.c_uint32),
                 ("first_instance", C.c_uint32), ("vertex_offset", C.c_uint32), ("draw", C.c_uint32)]
@@ -247,6 +255,7 @@ EXPORTS = [
     "gv_pool_view_delta", "gv_pool_view_delta_device", "gv_pool_view_delta_fetch",
     "gv_pool_bind_occluders", "gv_occluder_begin", "gv_pool_draw_occluders", "gv_occluder_depth_device", "gv_occluder_depth_fetch",
     "gv_hiz_build_from_occluders",
+    "gv_pool_keep_models", "gv_pool_forget_models", "gv_pool_emit_previous", "gv_pool_previous_device", "gv_pool_previous_fetch",
     "gv_receiver_begin", "gv_pool_draw_receivers", "gv_receiver_mask_device", "gv_receiver_mask_fetch", "gv_hiz_build_from_receivers",
 ]
 
@@ -395,6 +404,11 @@ def load():
     lib.gv_occluder_depth_device.argtypes = [P, C.POINTER(P), C.POINTER(u32), C.POINTER(u32), C.POINTER(P)]
     lib.gv_occluder_depth_fetch.argtypes = [P, P, C.c_size_t, C.POINTER(GvOccluderCounts)]
     lib.gv_hiz_build_from_occluders.argtypes = [P]
+    lib.gv_pool_keep_models.argtypes = [P, u32, u32, u32]
+    lib.gv_pool_forget_models.argtypes = [P, u32, u32, u32]
+    lib.gv_pool_emit_previous.argtypes = [P, u32, u32, C.POINTER(GvPreviousLayout), C.POINTER(C.c_float), u32, P, C.c_size_t]
+    lib.gv_pool_previous_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_pool_previous_fetch.argtypes = [P, u32, P, C.c_size_t, C.POINTER(u32)]
     lib.gv_receiver_begin.argtypes = [P, u32, u32]
     lib.gv_pool_draw_receivers.argtypes = [P, u32, u32, P]
     lib.gv_receiver_mask_device.argtypes = [P, C.POINTER(P), C.POINTER(u32), C.POINTER(u32), C.POINTER(P)]
@@ -1242,6 +1256,54 @@ class GpuVisibility:
     def hiz_build_from_receivers(self):
         """gv_hiz_build_from_receivers: the pyramid of the open mask (not copied), which it closes"""
         self._check(self.lib.gv_hiz_build_from_receivers(self.ctx))
+
+    # ---- last frame's mvp per draw (motion vectors) ----
+    def keep_models(self, pool_id, view_index=0, add=False):
+        """gv_pool_keep_models: the models the view delivered become the pool's history, by pool slot (add: GV_KEEP_ADD, the second
+        view of a two-phase frame joins the epoch of the first); asynchronous, call it behind emit_previous"""
+        self._check(self.lib.gv_pool_keep_models(self.ctx, pool_id, view_index, GV_KEEP_ADD if add else 0))
+
+    def forget_models(self, pool_id, first=0, count=0):
+        """gv_pool_forget_models: slots [first, first + count) are fresh at the next emission; count 0 empties the whole history"""
+        self._check(self.lib.gv_pool_forget_models(self.ctx, pool_id, first, count))
+
+    def emit_previous(self, pool_id, view_index=0, stride=64, prev_mvp=0, has_history=None, prev_view_proj=None, cut=False, device=None,
+                      layout=True):
+        """gv_pool_emit_previous: last frame's viewProj * model of every draw of the view (and whether the draw had a history), on the
+        context's stream. layout=False passes a NULL layout ({64, 0, none}); prev_view_proj None: the kept view's; device: None for
+        the library's own buffer, or (device pointer, capacity in bytes) of caller-owned device memory."""
+        L = GvPreviousLayout(int(stride), int(prev_mvp), GV_NONE if has_history is None else int(has_history))
+        pvp = None
+        if prev_view_proj is not None:
+            held = np.ascontiguousarray(prev_view_proj, dtype=np.float32).reshape(16)
+            pvp = held.ctypes.data_as(C.POINTER(C.c_float))
+        ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
+        self._check(self.lib.gv_pool_emit_previous(self.ctx, pool_id, view_index, C.byref(L) if layout else None, pvp,
+                                                   GV_PREVIOUS_CUT if cut else 0, ptr, cap))
+        self._previous_stride = int(stride) if layout else 64
+
+    def previous_device(self, pool_id):
+        """gv_pool_previous_device: (device pointer of the items, device pointer of the four counts) of the pool's last emission"""
+        items, counts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_pool_previous_device(self.ctx, pool_id, C.byref(items), C.byref(counts)))
+        return items.value, counts.value
+
+    def previous(self, pool_id, out=None, stride=None, counts_only=False):
+        """gv_pool_previous_fetch: waits for the pool's last emit_previous; returns (items [written, stride] as uint8, counts = {n,
+        kept draws, items written, e} as four uint32). out: the caller's own C-contiguous array to deliver into (only the layout's
+        fields are written: its other bytes stay); default a zero-filled one. stride: default that of this object's last emit_previous.
+        counts_only: waits and returns (None, counts)."""
+        stride = int(stride if stride is not None else getattr(self, "_previous_stride", 64))
+        counts = np.zeros(4, np.uint32)
+        cp = counts.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self.lib.gv_pool_previous_fetch(self.ctx, pool_id, None, 0, cp))
+        if counts_only:
+            return None, counts
+        if out is None:
+            out = np.zeros((int(counts[2]), stride), np.uint8)
+        assert out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        self._check(self.lib.gv_pool_previous_fetch(self.ctx, pool_id, out.ctypes.data, out.nbytes, cp))
+        return out, counts
 
     def hiz_mip_count(self):
         n = C.c_uint32()

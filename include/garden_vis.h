@@ -928,6 +928,76 @@ int gv_receiver_mask_fetch(GvCtx* ctx, float* mask, size_t bytes, GvReceiverCoun
  * (gv_receiver_mask_device) to gv_hiz_build himself closes it the same way. */
 int gv_hiz_build_from_receivers(GvCtx* ctx);
 
+/* ---- last frame's mvp per draw, for motion vectors ----
+ * A velocity attachment filled from the camera alone (reprojecting depth with last frame's viewProj) gives every object that MOVES the
+ * wrong motion vector. The cure is a second matrix per instance: last frame's viewProj * model of the same object; the vertex stage
+ * then emits curr - prev. Last frame's models exist only in last frame's records on the device, in another order and for another
+ * visible set: these calls keep them per POOL slot (never index-mapped, never mirror entries: a re-order of the mirror does not
+ * concern them) and join them to this frame's draws on the device. The reference has no per-object velocity: the rule is this build's.
+ *
+ * THE PREVIOUS RULE (the same text stands in DESIGN.md §4 item 18, gv_device_math.hpp and tests/previous_twin.h). For draw k of a
+ * view: slot s_k, record model M_k, VP = the view's view_proj, the pool's history H (per slot 12 floats and a stamp; an epoch e, 0 =
+ * empty; a coverage H.slots; the kept view's view_proj KVP and camera position KC), PVP = prev_view_proj, or KVP when it is NULL,
+ * d_r = view.camera_position[r] - KC[r] (one fp32 subtraction per component, done on the host).
+ *  1. Cut: GV_PREVIOUS_CUT, or e == 0: every draw is fresh, with PVP = VP and d = (0, 0, 0).
+ *  2. Kept <=> no cut && s_k < H.slots && stamp[s_k] == e: P_k = the row's 12 floats.
+ *  3. Fresh otherwise: the draw is taken as static in the world. P_k = M_k with c3[r] = M_k.c3[r] + d_r (one fp32 add per component);
+ *     the other nine floats verbatim.
+ *  4. prev_mvp_k = PVP * P_k exactly as item 9: element i of column j = fma(PVP[12 + i], b3, fma(PVP[8 + i], b2, fma(PVP[4 + i], b1,
+ *     fma(PVP[i], b0, +0)))) with (b0, b1, b2) = column j of P_k and b3 = 0, or 1 for j = 3. has_history_k = 1 when kept, 0 when fresh.
+ * Under a cut the 64 bytes are bit for bit what gv_pool_emit_instances writes as mvp. Non-finite matrices are not an error.
+ *
+ * The frame a caller runs: cull -> (sort / group) -> gv_pool_emit_instances -> gv_pool_emit_previous -> gv_pool_keep_models.
+ * Everything is in stream order, so the emission reads last frame's rows before the keep replaces them.
+ * MEMORY: the history takes 64 bytes per pool slot of the largest occupancy kept (640 MB at 10^7 slots), allocated by the first keep.
+ * Lifetime: the history is HISTORY like the baselines of gv_pool_view_delta: no cull, emission, sort, group, re-order or re-bind ends
+ * it; only gv_pool_keep_models, gv_pool_forget_models and gv_destroy change it. It is deliberately NOT fed by GV_DIRTY_MESH marks: a
+ * caller that refills a slot forgets it. One history per pool: one camera. The emission's result is made from a view and ends with
+ * the pool's next gv_cull or gv_pool_cull_second_phase. */
+#define GV_KEEP_ADD 1u         /* gv_pool_keep_models: the second view of a two-phase frame, kept into the same epoch */
+#define GV_PREVIOUS_CUT 1u     /* gv_pool_emit_previous: a camera cut, every draw is fresh against the view's own view_proj */
+typedef struct GvPreviousLayout { /* stride: a multiple of 16, 64 ... 256; the fields inside it and disjoint */
+    uint32_t stride;
+    uint32_t prev_mvp;         /* 64 bytes, 16-byte aligned */
+    uint32_t has_history;      /* uint32 1 / 0, 4-byte aligned; GV_NONE: not written */
+} GvPreviousLayout;
+/* Keeps records 0 .. n-1 of (pool, view) as a fetch would deliver them when the call is issued (sorted, grouped and second-phase views
+ * alike; n the device draw count, never read by the host). flags == 0: e advances by one (should it wrap to 0, every stamp is cleared
+ * first and e becomes 1), the view's view_proj and camera_position are kept as given to its cull, and row[s_k] = {M_k verbatim, stamp
+ * e} for every record; rows of other slots are not touched, their older stamp makes them stale. GV_KEEP_ADD does the same without
+ * advancing e. The coverage grows to the view's occupancy: old rows survive (a device copy in stream order), new rows have stamp 0.
+ * A read of the view (recorded culls and deferred sorts are launched first) that changes nothing any other call can observe;
+ * asynchronous on gv_stream(ctx): one kernel launch under GvStats::launches[GV_K_EMIT] (one more should e wrap).
+ * GV_E_ARG: a NULL ctx; a pool that is not bound; a view index >= GV_MAX_VIEWS, or one no cull of the pool ever had a view at; unknown
+ * flag bits. GV_E_STATE: a view without results or culled count-only; GV_KEEP_ADD with an empty history (e == 0) or for a view whose
+ * view_proj and camera_position do not equal the kept ones bit for bit. A failed call changes nothing. */
+int gv_pool_keep_models(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, uint32_t flags);
+/* The stamps of slots [first, first + count) that the coverage holds become 0: those slots are fresh at the next emission (a
+ * teleported entity, a slot filled anew). count == 0 empties the whole history: e = 0, coverage 0, buffers kept. One kernel launch
+ * under GV_K_EMIT, or none. GV_E_ARG: a NULL ctx; a pool that is not bound. */
+int gv_pool_forget_models(GvCtx* ctx, uint32_t pool_id, uint32_t first, uint32_t count);
+/* Writes, for every draw k of (pool, view) in delivery order at the time of the call, prev_mvp_k and has_history_k by the rule above:
+ * item k at dst + k * layout->stride, only the layout's bytes. layout NULL: {64, 0, GV_NONE}. prev_view_proj (16 floats, column-major,
+ * copied by the call) NULL: the kept view_proj. dst_device NULL: a library-owned buffer sized for the view's occupancy (grown, never
+ * shrunk). dst_device non-NULL: caller-owned device memory of capacity_bytes, 16-byte aligned; items at or beyond capacity_bytes /
+ * stride are not written. It may be the instance buffer of the pool's emission at the first listed view — a plain emission puts draw k
+ * at instance k, so a plugin struct {mvp, prevMvp} is filled by the two calls; keeping the fields apart from the instance layout's is
+ * the caller's business. counts = {n, kept draws (of all n), items written, e} as four uint32 on the device.
+ * A read of the view, asynchronous on gv_stream(ctx), no host synchronisation, no count read back: one memset and one kernel launch
+ * under GvStats::launches[GV_K_EMIT]. One result per pool, valid until the pool's next cull.
+ * GV_E_ARG: a NULL ctx; a pool that is not bound; a view index >= GV_MAX_VIEWS, or one no cull of the pool ever had a view at; unknown
+ * flag bits; a bad layout; a misaligned dst_device. GV_E_STATE: a view without results or culled count-only. An empty pool or a view
+ * without draws: GV_OK, counts = {0, 0, 0, e}. A failed call changes neither the history nor the previous result. */
+int gv_pool_emit_previous(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, const GvPreviousLayout* layout, const float* prev_view_proj,
+                          uint32_t flags, void* dst_device, size_t capacity_bytes);
+/* The last emission in device memory: *items the target, *counts the four words (valid behind the call on gv_stream(ctx)).
+ * GV_E_ARG: a NULL ctx or output; a pool that is not bound. GV_E_STATE: no result since the pool's last cull. */
+int gv_pool_previous_device(GvCtx* ctx, uint32_t pool_id, const void** items, const void** counts);
+/* Waits for the emission, delivers counts4[0 .. 3] and — dst_host non-NULL — the items written, field by field through the library's
+ * pinned staging (the caller's memory is never page-locked; bytes between the fields stay as they are).
+ * GV_E_ARG: a NULL ctx or counts4; a pool that is not bound; bytes below items written * stride (nothing is written). GV_E_STATE as above. */
+int gv_pool_previous_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* counts4);
+
 /* ---- the shared sorted arrays: the sorted lists of several mesh systems merged into ONE array, on the device ----
  * The reference keeps one array per sorted kind — transSortedMeshes, uiSortedMeshes, one translucent array per shadow pass — into
  * which every sorted system appends SortedMesh records tagged with its bufferIndex (mesh.cpp:247-261); one std::sort orders the
