@@ -56,6 +56,7 @@ static void build_view_params(const GvView& v, ViewParams* out)
     memcpy(out->vp, v.view_proj, sizeof(out->vp));
     out->write_is_visible = v.shadow_pass < 0 ? 1u : 0u;  // isNotShadowPass  mesh.cpp:121
     out->use_hiz = v.use_hiz ? 1u : 0u;
+    out->hiz_index = Context::pyramid_of(v.use_hiz);
     out->distance_2d = v.distance_2d ? 1u : 0u;
 }
 
@@ -238,22 +239,25 @@ int hiz_reduce(GvCtx* ctx)
     return GV_OK;
 }
 
-HizDevice hiz_device(const GvCtx* ctx)
+// what the kernels see of slot `k`'s pyramid (not built: all zero)
+static HizDevice hiz_device_of(const GvCtx* ctx, const Context::HizParked& k)
 {
     HizDevice hz{};
-    if (ctx->hiz_valid) {
-        hz.depth = ctx->depth_ptr;
-        hz.mips = ctx->d_mips.ptr;
-        hz.mip_offset = ctx->d_mip_offset.ptr;
-        hz.width = ctx->hiz_w;
-        hz.height = ctx->hiz_h;
-        hz.mip_count = ctx->hiz_mips;
-        hz.nested = ctx->hiz_nested ? 1u : 0u;
+    if (k.hiz_valid) {
+        hz.depth = k.depth_ptr;
+        hz.mips = k.d_mips.ptr;
+        hz.mip_offset = k.d_mip_offset.ptr;
+        hz.width = k.hiz_w;
+        hz.height = k.hiz_h;
+        hz.mip_count = k.hiz_mips;
+        hz.nested = k.hiz_nested ? 1u : 0u;
         hz.rg16f = (ctx->config.flags & GV_CONFIG_HIZ_RG16F) ? 1u : 0u;
-        hz.level1_virtual = ctx->hiz_level1_virtual ? 1u : 0u;
+        hz.level1_virtual = k.hiz_level1_virtual ? 1u : 0u;
     }
     return hz;
 }
+HizDevice hiz_device(const GvCtx* ctx) { return hiz_device_of(ctx, ctx->hiz_live()); }                         // the selected pyramid
+HizDevice hiz_device(const GvCtx* ctx, uint32_t pyramid) { return hiz_device_of(ctx, ctx->hiz_slot(pyramid)); }  // ... any, selected or parked
 
 // ---- the launches of one gv_cull: sweep, decide, upkeep of what is derived from the pool, cull, emit (cull_launch at the end) ----
 
@@ -462,16 +466,17 @@ int emit_view(GvCtx* ctx, ViewState& vs, const MeshMirror& mesh, const Transform
 // The launches of one gv_cull (views already reserved and marked valid by gv_cull): the sweep riding on it, block
 // bounds, the cull itself in the form that fits (fused sweep + cull, cull + emit in one launch, batched views, ...),
 // compaction and emission.
-int cull_launch(GvCtx* ctx, uint32_t pool_id, const ViewParams* vps, uint32_t view_count, bool batched)
+int cull_launch(GvCtx* ctx, uint32_t pool_id, const ViewParams* vps, uint32_t view_count, bool batched, bool multi_hiz)
 {
     PoolState& p = ctx->pools[pool_id];
     ViewState* views = ctx->views[pool_id];
     MeshMirror mesh = mesh_mirror(p);
     const TransformMirror xf = xf_mirror(ctx);
-    const HizDevice hz = hiz_device(ctx);
+    HizDevice hzs[GV_MAX_VIEWS];    // every view's own pyramid (GvView::use_hiz names it; pyramid 0 for a view that does not query)
     ViewBuffers vbs[GV_MAX_VIEWS];
     ViewParams cvps[GV_MAX_VIEWS];  // as the cull kernels see the views: isVisible bytes are left to the emit that follows
     for (uint32_t v = 0; v < view_count; v++) {
+        hzs[v] = hiz_device(ctx, vps[v].hiz_index);
         vbs[v] = view_buffers(views[v]);
         cvps[v] = vps[v];
         if (views[v].emitted)
@@ -512,8 +517,10 @@ int cull_launch(GvCtx* ctx, uint32_t pool_id, const ViewParams* vps, uint32_t vi
     const BlockBounds bounds{p.d_blk_lo.ptr, p.d_blk_hi.ptr, ctx->d_examined.ptr};  // (handed on only under use_bounds)
     if (use_bounds)
         ctx->bounds_blocks_total = blocks_of(p.occupancy);
-    if (plan.batched)
-        GV_LAUNCH(ctx, GV_K_CULL, launch_cull_multi(mesh, xf, hz, cvps, vbs, view_count, ctx->stream, use_bounds ? &bounds : nullptr));
+    if (plan.batched && multi_hiz)  // every view against its own pyramid, still ONE pass over the streams
+        GV_LAUNCH(ctx, GV_K_CULL, launch_cull_multi_hiz(mesh, xf, hzs, cvps, vbs, view_count, ctx->stream, use_bounds ? &bounds : nullptr));
+    else if (plan.batched)
+        GV_LAUNCH(ctx, GV_K_CULL, launch_cull_multi(mesh, xf, hzs[0], cvps, vbs, view_count, ctx->stream, use_bounds ? &bounds : nullptr));
     if (plan.emit_batched) {
         uint32_t clear[GV_MAX_VIEWS];
         for (uint32_t v = 0; v < view_count; v++) {
@@ -523,20 +530,20 @@ int cull_launch(GvCtx* ctx, uint32_t pool_id, const ViewParams* vps, uint32_t vi
         }
         GV_LAUNCH(ctx, GV_K_EMIT, launch_emit_batch(mesh, xf, vps, vbs, clear, view_count, ctx->stream, emit_world));
     } else if (one_launch) {
-        if ((rc = cull_emit_one_launch(ctx, views[0], mesh, xf, hz, vps[0], vbs[0])) != GV_OK)
+        if ((rc = cull_emit_one_launch(ctx, views[0], mesh, xf, hzs[0], vps[0], vbs[0])) != GV_OK)
             return rc;
     } else if (p.occupancy != 0) {  // (an empty pool launches nothing: gv_cull has zeroed the draw counts)
         for (uint32_t v = 0; v < view_count; v++) {
             if (!plan.batched) {
                 if (plan.fused && v == 0)
-                    GV_LAUNCH(ctx, GV_K_CULL, launch_sweep_cull(mesh, xf, hz, cvps[v], vbs[v], ctx->d_world.ptr, ctx->sweep_with_cull_mfma, ctx->stream));
+                    GV_LAUNCH(ctx, GV_K_CULL, launch_sweep_cull(mesh, xf, hzs[v], cvps[v], vbs[v], ctx->d_world.ptr, ctx->sweep_with_cull_mfma, ctx->stream));
                 else if (use_bounds) {  // classify the workgroups first and cull the kept ones from a list
                     uint32_t* counters = p.d_kept.ptr;
-                    GV_LAUNCH(ctx, GV_K_CULL, launch_cull_listed(mesh, xf, hz, cvps[v], vbs[v], bounds, counters + p.kept_parity,
+                    GV_LAUNCH(ctx, GV_K_CULL, launch_cull_listed(mesh, xf, hzs[v], cvps[v], vbs[v], bounds, counters + p.kept_parity,
                                                                  counters + (p.kept_parity ^ 1u), counters + 4, p.d_kept_flag.ptr, ctx->stream));
                     p.kept_parity ^= 1u;
                 } else
-                    GV_LAUNCH(ctx, GV_K_CULL, launch_cull(mesh, xf, hz, cvps[v], vbs[v], ctx->stream));
+                    GV_LAUNCH(ctx, GV_K_CULL, launch_cull(mesh, xf, hzs[v], cvps[v], vbs[v], ctx->stream));
             }
             if ((rc = emit_view(ctx, views[v], mesh, xf, vps[v], vbs[v], plan.self_prefix, emit_world, seeds)) != GV_OK)
                 return rc;
@@ -559,7 +566,7 @@ int flush_culls(GvCtx* ctx)
     GV_HIP(ctx, hipSetDevice(ctx->device));
     if (jobs.size() == 1) {  // nothing to batch: the ordinary launches (cull + emit in one for a single view) are shorter
         bool batched = jobs[0].view_count > 1;
-        return cull_launch(ctx, jobs[0].pool_id, jobs[0].vps, jobs[0].view_count, batched);
+        return cull_launch(ctx, jobs[0].pool_id, jobs[0].vps, jobs[0].view_count, batched, false);
     }
     const size_t cull_bytes = cull_table_entry_bytes(), emit_bytes = emit_table_entry_bytes();
     uint32_t emit_entries = 0, max_slots = 0;
@@ -579,7 +586,6 @@ int flush_culls(GvCtx* ctx)
     }
     uint8_t* host = ctx->h_tick[turn].ptr;
     const TransformMirror xf = xf_mirror(ctx);
-    const HizDevice hz = hiz_device(ctx);
     uint32_t e = 0;
     for (size_t k = 0; k < jobs.size(); k++) {
         const auto& j = jobs[k];
@@ -593,7 +599,8 @@ int flush_culls(GvCtx* ctx)
             cvps[v] = j.vps[v];
             cvps[v].write_is_visible = 0;
         }
-        fill_cull_table_entry(host + cull_off + k * cull_bytes, mesh, xf, hz, cvps, vbs, j.view_count);
+        // (the table form knows Hi-Z on view 0 only: the pyramid that view named when it was recorded, resolved by index now)
+        fill_cull_table_entry(host + cull_off + k * cull_bytes, mesh, xf, hiz_device(ctx, j.vps[0].hiz_index), cvps, vbs, j.view_count);
         for (uint32_t v = 0; v < j.view_count; v++) {
             ViewState& vs = ctx->views[j.pool_id][v];
             if (int rc = emit_flags_ready(ctx, vs))
@@ -737,6 +744,8 @@ void gv_destroy(GvCtx* ctx)
     ctx->occluder_depth.release();
     ctx->receiver_mask.release();
     ctx->d_depth.release(); ctx->d_mips.release(); ctx->d_mip_offset.release(); ctx->d_tick.release(); ctx->h_done.release();
+    for (auto& k : ctx->parked)
+        k.release();
     for (int k = 0; k < 2; k++) {
         ctx->h_tick[k].release();
         if (ctx->tick_done[k])
@@ -1000,8 +1009,9 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
         return rc;
     GV_HIP(ctx, hipSetDevice(ctx->device));
     for (uint32_t v = 0; v < view_count; v++) {
-        if (views[v].use_hiz && !ctx->hiz_valid)
-            return ctx->fail(GV_E_STATE, "gv_cull: view %u asks for Hi-Z but gv_hiz_build has not run", v);
+        if (views[v].use_hiz && !ctx->pyramid_built(Context::pyramid_of(views[v].use_hiz)))
+            return ctx->fail(GV_E_STATE, "gv_cull: view %u asks for Hi-Z but gv_hiz_build has not run (pyramid %u is not built)", v,
+                             Context::pyramid_of(views[v].use_hiz));
     }
     if (ctx->cull_batching)
         for (const auto& j : ctx->cull_jobs)
@@ -1019,6 +1029,16 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
     bool batched = view_count > 1 && view_count <= kMaxBatchViews && p.occupancy > 0;
     for (uint32_t v = 1; v < view_count && batched; v++)
         batched = memcmp(views[v].camera_position, views[0].camera_position, 12) == 0 && !views[v].use_hiz;
+    // Views that name pyramids of their own (GvView::use_hiz = 1 + k): when they share cameraPosition, ONE pass for all of them all
+    // the same, every view against its own pyramid (cull_multi_hiz_kernel) — a main pass and its masked shadow cascades. Decided
+    // apart from `batched`: a call whose views all say 0 or 1 is planned as it always was.
+    bool multi_hiz = view_count > 1 && view_count <= kMaxBatchViews && p.occupancy > 0 && !ctx->sweep_with_cull;
+    bool names_other = false;  // some view queries a pyramid other than 0
+    for (uint32_t v = 0; v < view_count; v++) {
+        multi_hiz = multi_hiz && memcmp(views[v].camera_position, views[0].camera_position, 12) == 0;
+        names_other = names_other || (views[v].use_hiz && Context::pyramid_of(views[v].use_hiz) != 0);
+    }
+    multi_hiz = multi_hiz && names_other;
     ViewParams vps[GV_MAX_VIEWS];
     for (uint32_t v = 0; v < view_count; v++) {
         ViewState& vs = ctx->views[pool_id][v];
@@ -1036,6 +1056,8 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
                         ctx->cull_jobs.size() < GV_MAX_POOLS;
         for (uint32_t v = 0; v < view_count && eligible; v++)
             eligible = ctx->views[pool_id][v].emitted;
+        if (multi_hiz)  // (the table form knows Hi-Z on view 0 only: this form launches at once)
+            eligible = false;
         if (eligible) {
             Context::CullJob job;
             job.pool_id = pool_id;
@@ -1049,7 +1071,7 @@ int gv_cull(GvCtx* ctx, uint32_t pool_id, const GvView* views, uint32_t view_cou
         }
     }
     ctx->last_pool = pool_id;
-    return cull_launch(ctx, pool_id, vps, view_count, batched);
+    return cull_launch(ctx, pool_id, vps, view_count, batched || multi_hiz, multi_hiz);
 }
 
 int gv_cull_batch_begin(GvCtx* ctx)
@@ -1205,6 +1227,44 @@ int gv_hiz_mip_count(GvCtx* ctx, uint32_t* mip_count)
     if (!ctx->hiz_valid || !mip_count)
         return ctx->fail(GV_E_STATE, "gv_hiz_mip_count: no pyramid");
     *mip_count = ctx->hiz_mips;
+    return GV_OK;
+}
+
+int gv_hiz_select(GvCtx* ctx, uint32_t pyramid)
+{
+    if (!ctx)
+        return GV_E_ARG;
+    if (pyramid >= GV_MAX_PYRAMIDS)
+        return ctx->fail(GV_E_ARG, "gv_hiz_select: pyramid %u (valid 0..%u)", pyramid, GV_MAX_PYRAMIDS - 1);
+    if (int rc = flush_culls(ctx))  // as gv_hiz_build
+        return rc;
+    if (pyramid == ctx->selected)
+        return GV_OK;
+    // pointer moves: the selected pyramid goes to rest in its slot, the named one becomes the live fields
+    ctx->parked[ctx->selected] = ctx->hiz_take_live();
+    ctx->hiz_put_live(ctx->parked[pyramid]);
+    ctx->parked[pyramid] = Context::HizParked{};
+    ctx->selected = pyramid;
+    return GV_OK;
+}
+
+int gv_hiz_drop(GvCtx* ctx, uint32_t pyramid)
+{
+    if (!ctx)
+        return GV_E_ARG;
+    if (pyramid >= GV_MAX_PYRAMIDS)
+        return ctx->fail(GV_E_ARG, "gv_hiz_drop: pyramid %u (valid 0..%u)", pyramid, GV_MAX_PYRAMIDS - 1);
+    if (int rc = flush_culls(ctx))  // recorded culls query the pyramid as it was when they were recorded
+        return rc;
+    const bool live = pyramid == ctx->selected;
+    if (!ctx->hiz_slot(pyramid).holds_anything())
+        return GV_OK;  // never built: nothing to free
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (culls that query it may still be running)
+    Context::HizParked gone = live ? ctx->hiz_take_live() : ctx->parked[pyramid];
+    gone.release();  // its levels and its own depth copy; an image it read (depth_ptr) only loses the reference
+    if (!live)
+        ctx->parked[pyramid] = Context::HizParked{};
     return GV_OK;
 }
 

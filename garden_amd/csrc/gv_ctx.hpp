@@ -720,10 +720,77 @@ struct Context {
     bool hiz_level1_virtual = false;   // decided in gv_hiz_build: sizes whose first six levels take the fused kernel
     bool hiz_level1_stored = false;    // ... and whether gv_hiz_read_level has materialised it since the last build
 
-    // ---- occluder depth (gv_occluders.cpp): TWO images, so that the one the current pyramid reads (depth_ptr: level 0 IS the depth
-    // image) is never cleared, redrawn or reallocated under it. Accumulated state like the delta baselines: end_derived has no line for it.
+    // ---- pyramid slots (gv_hiz_select): the fields above are the SELECTED pyramid — what gv_hiz_build, _rebuild, _read_level and
+    // _mip_count address. Every other slot's pyramid rests here; gv_hiz_select swaps (pointer moves, no device work). A view names
+    // its pyramid by index (GvView::use_hiz); hiz_device(ctx, k) resolves it at the launch, whichever slot is selected then.
+    struct HizParked {
+        DeviceBuf<float> d_depth;
+        const float* depth_ptr = nullptr;
+        DeviceBuf<float2> d_mips;
+        DeviceBuf<uint64_t> d_mip_offset;
+        uint32_t hiz_w = 0, hiz_h = 0, hiz_mips = 0;
+        uint32_t mip_w[GV_MAX_MIPS]{}, mip_h[GV_MAX_MIPS]{};
+        uint64_t mip_off[GV_MAX_MIPS]{};
+        bool hiz_valid = false, hiz_nested = false, hiz_level1_virtual = false, hiz_level1_stored = false;
+        bool holds_anything() const { return d_depth.ptr || d_mips.ptr || d_mip_offset.ptr || depth_ptr; }  // false: never built, or dropped
+        void release() { d_depth.release(), d_mips.release(), d_mip_offset.release(); }  // (the caller has drained the stream)
+    } parked[GV_MAX_PYRAMIDS];         // parked[selected] is empty: that pyramid is in the live fields
+    uint32_t selected = 0;
+    HizParked hiz_live() const         // the live fields in the parked form (pointers and sizes: nothing is moved)
+    {
+        HizParked k;
+        k.d_depth = d_depth, k.depth_ptr = depth_ptr, k.d_mips = d_mips, k.d_mip_offset = d_mip_offset;
+        k.hiz_w = hiz_w, k.hiz_h = hiz_h, k.hiz_mips = hiz_mips;
+        memcpy(k.mip_w, mip_w, sizeof(mip_w)), memcpy(k.mip_h, mip_h, sizeof(mip_h)), memcpy(k.mip_off, mip_off, sizeof(mip_off));
+        k.hiz_valid = hiz_valid, k.hiz_nested = hiz_nested, k.hiz_level1_virtual = hiz_level1_virtual, k.hiz_level1_stored = hiz_level1_stored;
+        return k;
+    }
+    HizParked hiz_slot(uint32_t k) const { return k == selected ? hiz_live() : parked[k]; }  // slot k's state, selected or parked
+    HizParked hiz_take_live()          // ... and the live fields are left empty ("not built")
+    {
+        const HizParked k = hiz_live();
+        hiz_put_live(HizParked{});
+        return k;
+    }
+    void hiz_put_live(const HizParked& k)
+    {
+        d_depth = k.d_depth, depth_ptr = k.depth_ptr, d_mips = k.d_mips, d_mip_offset = k.d_mip_offset;
+        hiz_w = k.hiz_w, hiz_h = k.hiz_h, hiz_mips = k.hiz_mips;
+        memcpy(mip_w, k.mip_w, sizeof(mip_w)), memcpy(mip_h, k.mip_h, sizeof(mip_h)), memcpy(mip_off, k.mip_off, sizeof(mip_off));
+        hiz_valid = k.hiz_valid, hiz_nested = k.hiz_nested, hiz_level1_virtual = k.hiz_level1_virtual, hiz_level1_stored = k.hiz_level1_stored;
+    }
+    // GvView::use_hiz -> the pyramid it names: 1 + k for k < GV_MAX_PYRAMIDS; any larger value means pyramid 0, as every non-zero value once did
+    static uint32_t pyramid_of(uint8_t use_hiz) { return use_hiz >= 1 && use_hiz <= GV_MAX_PYRAMIDS ? use_hiz - 1u : 0u; }
+    bool pyramid_built(uint32_t k) const { return k == selected ? hiz_valid : parked[k].hiz_valid; }
+    // Some pyramid — the selected one or a parked one — reads `image` as its level 0 (a pyramid built from a device image READS it).
+    bool pyramid_reads(const float* image) const
+    {
+        if (!image)
+            return false;
+        bool reads = depth_ptr == image;
+        for (const HizParked& k : parked)
+            reads = reads || k.depth_ptr == image;
+        return reads;
+    }
+    // The image a begin takes, of a set of kHizImages: `current` unless some pyramid reads it; then the lowest-index image that no
+    // pyramid reads (one always exists: GV_MAX_PYRAMIDS pyramids read at most that many of the GV_MAX_PYRAMIDS + 1 images). With
+    // pyramid 0 alone in use these are images 0 and 1 in turn.
+    static constexpr uint32_t kHizImages = GV_MAX_PYRAMIDS + 1;
+    uint32_t free_image(const DeviceBuf<float> (&images)[kHizImages], uint32_t current) const
+    {
+        if (!pyramid_reads(images[current].ptr))
+            return current;
+        for (uint32_t i = 0; i < kHizImages; i++)
+            if (!pyramid_reads(images[i].ptr))
+                return i;
+        return current;  // (not reached)
+    }
+
+    // ---- occluder depth (gv_occluders.cpp): GV_MAX_PYRAMIDS + 1 images, allocated at first use, so that one a pyramid reads
+    // (depth_ptr: level 0 IS the depth image) is never cleared, redrawn or reallocated under it (free_image). Accumulated state like
+    // the delta baselines: end_derived has no line for it.
     struct OccluderDepth {
-        DeviceBuf<float> d_image[2];
+        DeviceBuf<float> d_image[kHizImages];
         uint32_t current = 0;              // the image of the last gv_occluder_begin
         uint32_t width = 0, height = 0;    // ... and its size (0: no begin yet)
         bool open = false;                 // begun and not built since: draws go into it
@@ -735,23 +802,30 @@ struct Context {
         DeviceBuf<unsigned long long> d_base;
         void release()
         {
-            d_image[0].release(), d_image[1].release(), d_counts.release(), h_counts.release(), h_image.release();
+            for (auto& image : d_image)
+                image.release();
+            d_counts.release(), h_counts.release(), h_image.release();
             d_local.release(), d_base.release();
         }
     } occluder_depth;
 
-    // ---- receiver mask (gv_receivers.cpp): TWO images of its own, by the same rule — the one the current pyramid reads is never
+    // ---- receiver mask (gv_receivers.cpp): GV_MAX_PYRAMIDS + 1 images of its own, by the same rule — one a pyramid reads is never
     // cleared, redrawn or reallocated under it. Accumulated state like the occluder images: end_derived has no line for it. A draw's
     // scratch is occluder_depth.d_local / d_base: every user is ordered on the one stream.
     struct ReceiverMask {
-        DeviceBuf<float> d_image[2];
+        DeviceBuf<float> d_image[kHizImages];
         uint32_t current = 0;              // the image of the last gv_receiver_begin
         uint32_t width = 0, height = 0;    // ... and its size (0: no begin yet)
         bool open = false;                 // begun and not built since: draws go into it
         DeviceBuf<ReceiverCounts> d_counts;
         PinnedBuf<ReceiverCounts> h_counts;  // staging of gv_receiver_mask_fetch
         PinnedBuf<float> h_image;
-        void release() { d_image[0].release(), d_image[1].release(), d_counts.release(), h_counts.release(), h_image.release(); }
+        void release()
+        {
+            for (auto& image : d_image)
+                image.release();
+            d_counts.release(), h_counts.release(), h_image.release();
+        }
     } receiver_mask;
 
     // ---- multi-GPU exchange (gv_exchange.cpp) ----
@@ -1005,7 +1079,8 @@ ViewBuffers view_buffers(ViewState& vs);
 // what gv_cull does per view in front of its launches, and the way out behind a cull that left ballot words and chunk totals
 // (gv_pool_cull_second_phase, gv_second.cpp, sets its view up and emits it the same way)
 int begin_view(GvCtx* ctx, ViewState& vs, uint32_t pool_id, const GvView& view, ViewParams* vp);  // buffers, the view's state as of a new cull, *vp
-HizDevice hiz_device(const GvCtx* ctx);
+HizDevice hiz_device(const GvCtx* ctx);                    // of the selected pyramid
+HizDevice hiz_device(const GvCtx* ctx, uint32_t pyramid);  // of pyramid `pyramid`, selected or parked (not built: all zero)
 int emit_view(GvCtx* ctx, ViewState& vs, const MeshMirror& mesh, const TransformMirror& xf, const ViewParams& vp, const ViewBuffers& vb,
               bool self_prefix, const float4* emit_world, const EmitSeed* seeds);
 // gv_results.cpp (the reader side)

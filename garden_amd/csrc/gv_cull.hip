@@ -1175,6 +1175,145 @@ hipError_t launch_cull_multi(const MeshMirror& mesh, const TransformMirror& xf, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The batched pass with a Hi-Z query on EVERY view that asks for one, each against its own pyramid (GvView::use_hiz = 1 + k:
+// a main pass against the renderer's depth, shadow cascades against their receiver masks). An argument struct of its own:
+// MultiCullArgs — the table entries of cull_table_kernel — stays as it is. Streams, model, sphere and corners once per entity as
+// in cull_multi_block; per view the plane tests and, where the view's bit is set, hiz_occluded against hiz[v] / vp[v], fetched
+// like planes[v] / outs[v] by scalar loads at a runtime offset from the kernarg segment inside the loop that is NOT unrolled.
+// ------------------------------------------------------------------------------------------------
+struct MultiHizCullArgs {
+    MultiCullArgs m;                   // first: view_planes / view_outputs read it through the same base (m.hiz, m.vp0, m.use_hiz0: not read)
+    HizDevice hiz[kMaxBatchViews];     // view v's pyramid (all zero where the view does not query)
+    float vp[kMaxBatchViews][16];      // ... and its viewProj
+    uint32_t hiz_views;                // bit v: view v queries
+};
+static_assert(offsetof(MultiHizCullArgs, m) == 0, "view_planes / view_outputs address the embedded MultiCullArgs through the kernarg base");
+static_assert(sizeof(MultiHizCullArgs) <= 4096, "a launch carries 4 KB of arguments by value");
+struct ViewMatrix { float m[16]; };
+typedef const MultiHizCullArgs __attribute__((address_space(4))) * ConstMultiHizArgs;
+__device__ __forceinline__ HizDevice view_hiz(ConstMultiHizArgs base, uint32_t v)
+{
+    HizDevice out;
+    __builtin_memcpy(&out, &base->hiz[v], sizeof(out));
+    return out;
+}
+__device__ __forceinline__ ViewMatrix view_matrix(ConstMultiHizArgs base, uint32_t v)
+{
+    ViewMatrix out;
+    __builtin_memcpy(&out, &base->vp[v], sizeof(out));
+    return out;
+}
+
+template <uint32_t MAP, bool BOUNDS>
+__global__ __launch_bounds__(kCullBlock) void cull_multi_hiz_kernel(const MultiHizCullArgs hargs)
+{
+    __shared__ uint32_t wave_count[kMaxBatchViews][kCullBlock / 64];
+    const MultiCullArgs& args = hargs.m;
+    ConstMultiHizArgs hbase = (ConstMultiHizArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(hbase));  // (opaque: nothing read through it is moved out of the loops)
+    const ConstMultiArgs base = (ConstMultiArgs)hbase;
+    const uint32_t lb = blockIdx.x;
+    const uint32_t i = lb * kCullBlock + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const bool in_range = i < args.mesh.count;
+    const uint32_t nviews = min(args.nviews, kMaxBatchViews);
+    if (BOUNDS) {  // the frustum skip of cull_multi_block: the box is outside EVERY view of the batch (no block-level window test here)
+        const float4 lo = args.bounds.lo[lb], hi = args.bounds.hi[lb];
+        bool skip = true;
+        if (!(lo.x > hi.x)) {
+#pragma unroll 1
+            for (uint32_t v = 0; v < nviews && skip; v++) {
+                const MultiViewPlanes pl = view_planes(base, v);
+                skip = block_behind_planes(lo, hi, pl.planes, pl.plane_count, args.cam, args.xf.max_depth);
+            }
+        }
+        if (threadIdx.x == 0)
+            args.bounds.examined[lb] = skip ? 0 : 1;
+        if (skip) {
+#pragma unroll 1
+            for (uint32_t v = 0; v < nviews; v++) {
+                const ViewBuffers out = view_outputs(base, v);
+                if (base->planes[v].write_is_visible && in_range)
+                    out.is_visible[i] = 0;
+                if (lane == 0)
+                    out.mask[(size_t)lb * (kCullBlock / 64) + wave] = 0ull;
+            }
+            return;
+        }
+    }
+    Mat34 m;
+    float4 box_a;
+    float2 box_b;
+    Corners c;
+    const bool candidate = in_range && prepare_model<MAP>(args.mesh, args.xf, args.cam, i, m, box_a, box_b);
+    const float reach = candidate ? sphere_reach(m, box_a, box_b) : 0.0f;  // one sphere for every view of the batch
+    bool have_corners = false;  // generated once, by the first view that needs them
+#pragma unroll 1
+    for (uint32_t v = 0; v < nviews; v++) {
+        const MultiViewPlanes pl = view_planes(base, v);
+        const bool query = (hargs.hiz_views >> v) & 1u;  // wave-uniform
+        const uint32_t where = candidate ? classify_sphere(m, reach, pl.planes, pl.plane_count) : kSphereOutside;
+        bool visible = settle(where, query, m, box_a, box_b, pl.planes, pl.plane_count, c, have_corners);
+        if (query) {
+            const HizDevice hz = view_hiz(hbase, v);
+            const ViewMatrix vm = view_matrix(hbase, v);
+            if (visible)
+                visible = !hiz_occluded(hz, vm.m, c);
+        }
+        const ViewBuffers out = view_outputs(base, v);
+        if (pl.write_is_visible && in_range)
+            out.is_visible[i] = visible ? 1 : 0;
+        const unsigned long long word = __ballot(visible);
+        if (lane == 0) {
+            out.mask[(size_t)lb * (kCullBlock / 64) + wave] = word;
+            wave_count[v][wave] = (uint32_t)__popcll(word);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < nviews) {
+        uint32_t total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kCullBlock / 64; w++)
+            total += wave_count[threadIdx.x][w];
+        if (total) {
+            uint32_t* counts = base->outs[threadIdx.x].chunk_count;  // (a lane-varying view: an ordinary load from the argument block)
+            atomicAdd(&counts[lb / (kEmitChunk / kCullBlock)], total);
+        }
+    }
+}
+
+hipError_t launch_cull_multi_hiz(const MeshMirror& mesh, const TransformMirror& xf, const HizDevice* hiz, const ViewParams* views,
+                                 const ViewBuffers* outs, uint32_t nviews, hipStream_t stream, const BlockBounds* bounds)
+{
+    if (mesh.count == 0)
+        return hipSuccess;
+    if (nviews == 0 || nviews > kMaxBatchViews)
+        return hipErrorInvalidValue;
+    MultiHizCullArgs a;
+    fill_multi_args(a.m, mesh, xf, HizDevice{}, views, outs, nviews);
+    a.m.use_hiz0 = 0;
+    a.hiz_views = 0;
+    for (uint32_t v = 0; v < kMaxBatchViews; v++) {
+        const bool query = v < nviews && views[v].use_hiz;
+        if (query && !hiz[v].depth)
+            return hipErrorInvalidValue;  // a view that queries a pyramid nobody built: gv_cull has refused it
+        a.hiz[v] = query ? hiz[v] : HizDevice{};
+        for (int k = 0; k < 16; k++)
+            a.vp[v][k] = views[v < nviews ? v : 0].vp[k];
+        a.hiz_views |= query ? 1u << v : 0u;
+    }
+    const dim3 grid((mesh.count + kCullBlock - 1) / kCullBlock), block(kCullBlock);
+    a.m.bounds = bounds ? *bounds : BlockBounds{};
+    with_mapping(mesh.mapping, [&](auto map) {
+        if (bounds)
+            hipLaunchKernelGGL((cull_multi_hiz_kernel<map, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((cull_multi_hiz_kernel<map, false>), grid, block, 0, stream, a);
+    });
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // K2: exclusive scan of the per-block visible counts (one workgroup; <= ~400k blocks at 10^8 slots)
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t kScanBlock = 1024;

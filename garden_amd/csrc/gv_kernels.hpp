@@ -98,7 +98,8 @@ struct ViewParams {
                                 // views, the one-launch cull + emit): with records requested the emit kernel expands them from
                                 // the ballot words it reads anyway, as whole sectors — the byte stores cost the bandwidth-bound
                                 // cull kernel 5-7 us of 105 at 10 M entities for 1.5 % of its bytes (round-3 probe tools/read_probe.hip, in the history)
-    uint32_t use_hiz;
+    uint32_t use_hiz;           // 0 / 1
+    uint32_t hiz_index;         // ... and the pyramid slot the view names (host side: resolved to a HizDevice when the launch is made)
     uint32_t distance_2d;
 };
 
@@ -175,6 +176,10 @@ struct MultiViewPlanes {
 hipError_t launch_cull_multi(const MeshMirror& mesh, const TransformMirror& xf, const HizDevice& hiz,
                              const ViewParams* views, const ViewBuffers* outs, uint32_t nviews, hipStream_t stream,
                              const BlockBounds* bounds = nullptr);
+// ... with the Hi-Z query on every view whose ViewParams::use_hiz is set, view v against hiz[v] (its own pyramid) and views[v].vp:
+// one pass over the streams all the same (cull_multi_hiz_kernel; bounds: the frustum skip of the form above, no window test)
+hipError_t launch_cull_multi_hiz(const MeshMirror& mesh, const TransformMirror& xf, const HizDevice* hiz, const ViewParams* views,
+                                 const ViewBuffers* outs, uint32_t nviews, hipStream_t stream, const BlockBounds* bounds = nullptr);
 // gv_pick (gv_pick.hip): every ray against every entry of one pool that passes the cull's filter chain; keys[r] = min(keys[r], the
 // smallest key (bits(distSq) << 32) | order_bits | slot of a hit), keys initialised to ~0 by the caller
 constexpr uint32_t kPickBlock = 256;

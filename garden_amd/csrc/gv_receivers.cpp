@@ -20,10 +20,8 @@ int gv_receiver_begin(GvCtx* ctx, uint32_t width, uint32_t height)
         return ctx->fail(GV_E_ARG, "gv_receiver_begin: bad image size %ux%u (1 to 32768 each)", width, height);
     Context::ReceiverMask& R = ctx->receiver_mask;
     GV_HIP(ctx, hipSetDevice(ctx->device));
-    // the image the current pyramid does not read; of the two free ones, the one already in use
-    uint32_t take = R.current;
-    if (ctx->depth_ptr && ctx->depth_ptr == R.d_image[take].ptr)
-        take ^= 1u;
+    // an image no pyramid reads: the one already in use if it is free, else the lowest free one (Context::free_image)
+    const uint32_t take = ctx->free_image(R.d_image, R.current);
     const size_t texels = (size_t)width * height;
     GV_HIP(ctx, R.d_counts.reserve(1));
     // (a larger size replaces this image alone, behind whatever still reads it: hipFree waits; if that fails, the image is gone)

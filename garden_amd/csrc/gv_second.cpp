@@ -30,8 +30,9 @@ int gv_pool_cull_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t first_view,
     ViewState& vs2 = ctx->views[pool_id][second_view];
     if (!ctx->xf.bound)
         return ctx->fail(GV_E_STATE, "gv_pool_cull_second_phase: pools not bound");
-    if (view->use_hiz && !ctx->hiz_valid)
-        return ctx->fail(GV_E_STATE, "gv_pool_cull_second_phase: the view asks for Hi-Z but gv_hiz_build has not run");
+    if (view->use_hiz && !ctx->pyramid_built(Context::pyramid_of(view->use_hiz)))
+        return ctx->fail(GV_E_STATE, "gv_pool_cull_second_phase: the view asks for Hi-Z but gv_hiz_build has not run (view %u, pyramid %u is not built)",
+                         second_view, Context::pyramid_of(view->use_hiz));
     if (p.occupancy != vs1.occupancy)
         return ctx->fail(GV_E_STATE, "gv_pool_cull_second_phase: pool %u holds %u slots, view %u was culled with %u (cull again first)", pool_id,
                          p.occupancy, first_view, vs1.occupancy);
@@ -52,7 +53,7 @@ int gv_pool_cull_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t first_view,
     }
     const MeshMirror mesh = mesh_mirror(p);
     const TransformMirror xf = xf_mirror(ctx);
-    const HizDevice hz = hiz_device(ctx);
+    const HizDevice hz = hiz_device(ctx, vp.hiz_index);  // the pyramid the view names
     // the seen set: bit entry(s) for every slot s in the first view's records, whatever order they are in by now
     const size_t words = second_seen_words(p.occupancy);
     GV_HIP(ctx, vs2.seen.reserve(words));

@@ -259,8 +259,8 @@ public:
     // HizRenderSystem::downsampleHiz stand-in: hand over this frame's reversed-Z depth (host memory).
     void setHizDepth(const float* depth, uint32_t width, uint32_t height)
     {
-        for (uint32_t r = 0; r < contexts.size(); r++)  // the pyramid is screen space: every rank builds the whole of it
-            if (gv_hiz_build(contexts[r], depth, width, height, GV_MEM_HOST) != GV_OK)
+        for (uint32_t r = 0; r < contexts.size(); r++)  // screen space: every rank builds the whole of it — into slot 0, the main pass's, whatever a caller left selected
+            if (gv_hiz_select(contexts[r], 0) != GV_OK || gv_hiz_build(contexts[r], depth, width, height, GV_MEM_HOST) != GV_OK)
                 throw GardenError(std::string("gv_hiz_build failed: ") + gv_last_error(contexts[r]));
         useHiz = true;
     }

@@ -10,8 +10,15 @@
 //                                             views where they were, so the main pass's records stay for the next cascade's mask
 // The cascade comes from csm::cascade / csm::fit (csm_lite.hpp): the matrix the mask is drawn with is the one the cascade is culled
 // with, and both passes share the main camera's position — a slot's record model is then the same in both, so a caster the main
-// pass sees keeps itself. The context has ONE pyramid: the main pass's depth pyramid is gone once a mask is built and is rebuilt next
-// frame, as it is every frame anyway; cascades culled this way leave the batched multi-view pass.
+// pass sees keeps itself. In this order the context has ONE pyramid: the main pass's depth pyramid is gone once a mask is built and is
+// rebuilt next frame, as it is every frame anyway; cascades culled this way leave the batched multi-view pass.
+//
+// With pyramid slots (gv_hiz_select) every cascade's mask gets a pyramid of its own and the cascades stay in ONE cull:
+//   per cascade k: begin(w, h, 1 + k), draw(...), build()      the mask's pyramid lands in slot 1 + k; slot 0 is selected again
+//   cullCascades(p, {0, 1, 2}, {1, 2, 3})                     ONE gv_cull of the system's views: the main pass as the system set it
+//                                                             (its own use_hiz, pyramid 0 untouched), shadow pass k against slot 1 + k
+// The main pass's depth pyramid — slot 0, what GpuVisibilitySystem::setHizDepth / adoptPyramid and the next tick mean — is never
+// touched, so GpuSecondPhase of the main pass may run after the masked cascades of the same tick. cull() stays the default.
 //
 // One context only, like the other readers of a view's records: isSupported() is false with several ranks.
 #pragma once
@@ -31,6 +38,11 @@ class GpuShadowReceivers {
     GvReceiverCounts held{};
     std::vector<UnsortedMesh> list;  // cull(): the cascade's records
     uint32_t count = 0;
+    struct CascadeList {             // cullCascades(): the records of one listed cascade
+        std::vector<UnsortedMesh> meshes;  // grown, never shrunk
+        uint32_t count = 0;
+    };
+    std::vector<CascadeList> lists;
 
     void check(int rc, const char* what) const
     {
@@ -45,12 +57,54 @@ class GpuShadowReceivers {
             throw GardenError("GpuShadowReceivers: mesh system " + std::to_string(p) + " was not part of the last frame");
     }
 
+    // Waits; the records of view `target` of mesh system p into `out[0, n)`
+    void fetchList(uint32_t p, uint32_t target, std::vector<UnsortedMesh>& out, uint32_t& n)
+    {
+        GvCtx* ctx = system->getContext();
+        GvResult r{};
+        check(gv_pool_results_fetch(ctx, p, target, 0, &r), "gv_pool_results_fetch");
+        n = r.draw_count;
+        if (out.size() < r.draw_count)
+            out.resize(r.draw_count);
+        if (r.draw_count && !r.visible_idx) {  // the pool has a record layout: the structs arrive as they are
+            const void* records = nullptr;
+            uint32_t held_records = 0;
+            check(gv_pool_results_records(ctx, p, target, &records, &held_records), "gv_pool_results_records");
+            memcpy(static_cast<void*>(out.data()), records, (size_t)held_records * sizeof(UnsortedMesh));
+            return;
+        }
+        const size_t componentSize = system->getMeshSystems()[p]->getMeshComponentSize();
+        for (uint32_t k = 0; k < r.draw_count; k++) {
+            out[k].componentOffset = (size_t)r.visible_idx[k] * componentSize;
+            memcpy(out[k].bakedModel.m, r.baked_model + (size_t)k * 12, 48);
+            out[k].distanceSq = r.distance_sq[k];
+        }
+    }
+
 public:
     explicit GpuShadowReceivers(GpuVisibilitySystem* system) : system(system) {}
 
     bool isSupported() const noexcept { return system->getRankCount() == 1; }
 
     void begin(uint32_t width, uint32_t height) { check(gv_receiver_begin(system->getContext(), width, height), "gv_receiver_begin"); }
+    // ... whose pyramid build() will put into slot `pyramid` (1 .. GV_MAX_PYRAMIDS - 1: slot 0 is the main pass's depth pyramid)
+    // Slot `pyramid` stays selected until build(), which selects slot 0 again — so does abandon(), for a caller who gives the mask up
+    // (a draw() that threw, a cascade dropped half way), and so does GpuVisibilitySystem::setHizDepth before its own build: the next
+    // tick's depth pyramid lands in slot 0 whatever was left selected. A caller who builds pyramids through the C-ABI himself in
+    // between (gv_hiz_build, gv_hiz_build_from_occluders) builds into the slot selected then: call abandon() or build() first.
+    void begin(uint32_t width, uint32_t height, uint32_t pyramid)
+    {
+        check(gv_hiz_select(system->getContext(), pyramid), "gv_hiz_select");
+        try {
+            begin(width, height);
+        } catch (...) {
+            (void)gv_hiz_select(system->getContext(), 0);
+            throw;
+        }
+    }
+    // Gives up the mask of the last begin(w, h, pyramid) without building it: slot 0 is selected again. (The open mask stays open
+    // until the next begin; the slot keeps whatever pyramid it held.)
+    void abandon() { check(gv_hiz_select(system->getContext(), 0), "gv_hiz_select"); }
 
     // The draws of pass `view` (an index among mesh system p's culled passes: the main pass) into the open mask, as the cascade whose
     // viewProj is given sees them. Asynchronous.
@@ -65,7 +119,16 @@ public:
 
     // The pyramid of the mask; the cascade's cull queries it. Closes the mask. (Not adoptPyramid: the pyramid is in the CASCADE's clip
     // space, and the light pass of the next tick must not query it — the renderer's depth, or an occluder image, is built again first.)
-    void build() { check(gv_hiz_build_from_receivers(system->getContext()), "gv_hiz_build_from_receivers"); }
+    // Into the slot begin() selected; slot 0 is selected again afterwards, whether the build succeeded or not (what the system builds
+    // next — setHizDepth, an occluder image — is the main pass's).
+    void build()
+    {
+        const int rc = gv_hiz_build_from_receivers(system->getContext());
+        const std::string why = rc != GV_OK ? gv_last_error(system->getContext()) : "";
+        check(gv_hiz_select(system->getContext(), 0), "gv_hiz_select");
+        if (rc != GV_OK)
+            throw GardenError("gv_hiz_build_from_receivers failed: " + why);
+    }
 
     // The cascade as the view to cull against the pyramid just built: its own viewProj and cameraOffset, the main camera's position
     // (the records of both passes are relative to it), use_hiz on.
@@ -79,6 +142,14 @@ public:
         v.shadow_pass = shadowPass;
         v.use_hiz = 1;
         v.emit_records = emitRecords ? 1 : 0;
+        return v;
+    }
+
+    // ... against the pyramid of slot `pyramid` (cullCascades)
+    static GvView cascadeView(const csm::Cascade& cascade, const f32x4& cameraPosition, int32_t shadowPass, bool emitRecords, uint32_t pyramid)
+    {
+        GvView v = cascadeView(cascade, cameraPosition, shadowPass, emitRecords);
+        v.use_hiz = (uint8_t)(1 + pyramid);
         return v;
     }
 
@@ -111,27 +182,41 @@ public:
         GvCtx* ctx = system->getContext();
         check(gv_pool_set_record_target(ctx, p, target, nullptr, 0), "gv_pool_set_record_target");  // (the result is this object's)
         check(gv_cull(ctx, p, views.data(), (uint32_t)views.size()), "gv_cull");
-        GvResult r{};
-        check(gv_pool_results_fetch(ctx, p, target, 0, &r), "gv_pool_results_fetch");
-        count = r.draw_count;
-        if (list.size() < r.draw_count)
-            list.resize(r.draw_count);
-        if (r.draw_count && !r.visible_idx) {  // the pool has a record layout: the structs arrive as they are
-            const void* records = nullptr;
-            uint32_t n = 0;
-            check(gv_pool_results_records(ctx, p, target, &records, &n), "gv_pool_results_records");
-            memcpy(static_cast<void*>(list.data()), records, (size_t)n * sizeof(UnsortedMesh));
-            return;
-        }
-        const size_t componentSize = system->getMeshSystems()[p]->getMeshComponentSize();
-        for (uint32_t k = 0; k < r.draw_count; k++) {
-            list[k].componentOffset = (size_t)r.visible_idx[k] * componentSize;
-            memcpy(list[k].bakedModel.m, r.baked_model + (size_t)k * 12, 48);
-            list[k].distanceSq = r.distance_sq[k];
-        }
+        fetchList(p, target, list, count);
     }
     const UnsortedMesh* meshes() const noexcept { return list.data(); }
     uint32_t drawCount() const noexcept { return count; }
+
+    // The shadow passes `shadowPasses` of mesh system p again, pass k against the pyramid of slot pyramids[k] (begin(w, h, slot) ...
+    // build() per cascade), in ONE gv_cull of the system's own views of this tick: the main pass exactly as the system set it — its own
+    // use_hiz, against pyramid 0, which no mask has touched — and every pass that is not listed as it was. Views that share the camera
+    // position (a main pass and its cascades do) are culled in one pass over the pool. Waits; afterwards meshes(k)[0, drawCount(k))
+    // are the records of the k-th listed cascade (unsorted mesh systems; in the order of delivery).
+    void cullCascades(uint32_t p, const std::vector<int8_t>& shadowPasses, const std::vector<uint32_t>& pyramids)
+    {
+        if (shadowPasses.size() != pyramids.size())
+            throw GardenError("GpuShadowReceivers: one pyramid per listed shadow pass");
+        const auto& passes = system->getSystemPasses(p);
+        std::vector<GvView> views;
+        for (uint32_t v = 0; v < passes.size(); v++)
+            views.push_back(system->getSystemView(p, v));
+        GvCtx* ctx = system->getContext();
+        std::vector<uint32_t> targets;
+        for (size_t k = 0; k < shadowPasses.size(); k++) {
+            if (shadowPasses[k] < 0 || pyramids[k] >= GV_MAX_PYRAMIDS)
+                throw GardenError("GpuShadowReceivers: cullCascades takes shadow passes and pyramid slots below GV_MAX_PYRAMIDS");
+            targets.push_back(passView(p, shadowPasses[k]));
+            views[targets[k]].use_hiz = (uint8_t)(1 + pyramids[k]);
+            check(gv_pool_set_record_target(ctx, p, targets[k], nullptr, 0), "gv_pool_set_record_target");  // (the result is this object's)
+        }
+        check(gv_cull(ctx, p, views.data(), (uint32_t)views.size()), "gv_cull");
+        if (lists.size() < shadowPasses.size())
+            lists.resize(shadowPasses.size());
+        for (size_t k = 0; k < shadowPasses.size(); k++)
+            fetchList(p, targets[k], lists[k].meshes, lists[k].count);
+    }
+    const UnsortedMesh* meshes(size_t k) const { return lists.at(k).meshes.data(); }
+    uint32_t drawCount(size_t k) const { return lists.at(k).count; }
 
     // Waits; the counts of the last begin's draws: every record in exactly one of drawn, flat, behind, range, outside.
     const GvReceiverCounts& counts()

@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GV_LIB_PATH") or os.path.join(_HERE, "lib", "libgarden_vis.so")
 
 GV_MAX_POOLS, GV_MAX_VIEWS, GV_MAX_MIPS, GV_K_COUNT = 16, 8, 16, 6
+GV_MAX_PYRAMIDS = 8  # pyramid slots of a context (hiz_select)
 GV_OK, GV_E_ARG, GV_E_HIP, GV_E_OOM, GV_E_RCCL, GV_E_STATE, GV_E_NODEVICE, GV_E_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7
 GV_HIZ_RULE_REFERENCE, GV_HIZ_RULE_CONSERVATIVE = 0, 1
 GV_CONFIG_PROFILE_EVENTS = 1
@@ -233,7 +234,7 @@ EXPORTS = [
     "gv_transform_bind_columns", "gv_pool_bind_columns", "gv_pool_bind_ready",
     "gv_mark_dirty", "gv_hierarchy_rebuild", "gv_sync", "gv_cull", "gv_wait", "gv_results_fetch",
     "gv_result_count", "gv_results_device", "gv_results_copy_idx_device", "gv_results_copy_shard_device", "gv_results_copy_mask_device", "gv_pool_mirror_slots", "gv_pool_mirror_epoch", "gv_sort", "gv_sweep", "gv_get_world",
-    "gv_hiz_build", "gv_hiz_rebuild", "gv_hiz_read_level", "gv_hiz_mip_count", "gv_stats", "gv_stats_reset",
+    "gv_hiz_build", "gv_hiz_rebuild", "gv_hiz_read_level", "gv_hiz_mip_count", "gv_hiz_select", "gv_hiz_drop", "gv_stats", "gv_stats_reset",
     "gv_stream", "gv_debug_stream_peak",
     "gv_scene_parse_json", "gv_scene_parse_bson", "gv_scene_destroy", "gv_scene_info", "gv_scene_transform_columns", "gv_scene_mesh_columns",
     "gv_scene_bind", "gv_scene_extract_tile", "gv_scene_extract_rank", "gv_cell_owner", "gv_scene_tile_maps",
@@ -311,6 +312,8 @@ def load():
     lib.gv_hiz_rebuild.argtypes = [P]
     lib.gv_hiz_read_level.argtypes = [P, u32, P, C.POINTER(u32), C.POINTER(u32)]
     lib.gv_hiz_mip_count.argtypes = [P, C.POINTER(u32)]
+    lib.gv_hiz_select.argtypes = [P, u32]
+    lib.gv_hiz_drop.argtypes = [P, u32]
     lib.gv_stats.argtypes = [P, C.POINTER(GvStats)]
     lib.gv_stats_reset.argtypes = [P]
     lib.gv_debug_stream_peak.argtypes = [P, u32, u32, C.POINTER(C.c_double)]
@@ -1185,6 +1188,15 @@ class GpuVisibility:
 
     def hiz_rebuild(self):
         self._check(self.lib.gv_hiz_rebuild(self.ctx))
+
+    def hiz_select(self, pyramid):
+        """gv_hiz_select: pyramid `pyramid` (0 .. GV_MAX_PYRAMIDS - 1) is the one hiz_build, hiz_rebuild, hiz_read_level, hiz_mip_count
+        and the two hiz_build_from_* address from here on. A view names the pyramid it queries itself: make_view(use_hiz=1 + k)."""
+        self._check(self.lib.gv_hiz_select(self.ctx, pyramid))
+
+    def hiz_drop(self, pyramid):
+        """gv_hiz_drop: frees that pyramid's levels (an image it was built from stays); it is not built afterwards"""
+        self._check(self.lib.gv_hiz_drop(self.ctx, pyramid))
 
     # ---- occluder depth ----
     def bind_occluders(self, pool_id, box_min, box_max):

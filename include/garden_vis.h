@@ -36,6 +36,7 @@ extern "C" {
 #define GV_NONE 0xFFFFFFFFu
 #define GV_MAX_POOLS 16u
 #define GV_MAX_VIEWS 8u
+#define GV_MAX_PYRAMIDS 8u /* pyramid slots of a context (gv_hiz_select): one per view of a cull */
 #define GV_MAX_MIPS 16u
 
 typedef enum GvStatus {
@@ -200,7 +201,8 @@ typedef struct GvView {
     float camera_position[4]; /* cc.cameraPos (graphics.cpp:202); xyz used */
     float camera_offset[4];   /* shadow cascades (render/mesh.hpp:166); zero for the main camera */
     int8_t shadow_pass;       /* < 0: main pass, isVisible is produced (mesh.cpp:121) */
-    uint8_t use_hiz;          /* also run the Hi-Z occlusion query (needs gv_hiz_build first) */
+    uint8_t use_hiz;          /* 0: no Hi-Z query. 1 + k with k < GV_MAX_PYRAMIDS: also run the occlusion query against pyramid k
+                                 (which must be built: gv_hiz_select / gv_hiz_build). Any larger value: pyramid 0, as 1 */
     uint8_t distance_2d;      /* sorted twin key translation.z + 1 (mesh.cpp:250) */
     uint8_t emit_records;     /* 1: produce visibleIdx/bakedModel/distanceSq; 0: isVisible + count only */
 } GvView;
@@ -836,8 +838,9 @@ typedef struct GvOccluderCounts { /* 24 bytes; summed over the draws of every gv
  * GV_E_ARG: a NULL ctx; a pool out of range; exactly one of the pointers NULL; stride < 12; occupancy beyond the 28-bit slot range. */
 int gv_pool_bind_occluders(GvCtx* ctx, uint32_t pool_id, const void* box_min, const void* box_max, uint32_t stride, uint32_t occupancy);
 /* Opens an occluder image of width x height (1 .. 32768 each): sized, cleared to 0 (reversed Z: "nothing in front of anything")
- * and its six counts zeroed, asynchronously on gv_stream(ctx). The context owns TWO images and takes the one the current pyramid
- * does not read: the pyramid's level 0 is the depth image, so an image a pyramid reads is never cleared, redrawn or reallocated
+ * and its six counts zeroed, asynchronously on gv_stream(ctx). The context owns GV_MAX_PYRAMIDS + 1 images (each allocated at
+ * first use) and takes the one of the last begin unless a built pyramid reads it, then the lowest-numbered one that no built pyramid
+ * reads (with one pyramid in use: two images in turn): a pyramid's level 0 is the depth image, so an image a pyramid reads is never cleared, redrawn or reallocated
  * under it (gv_hiz_rebuild keeps reproducing the old pyramid). A begin on an open image starts it over.
  * GV_E_ARG: a NULL ctx; a size of 0 or above 32768 (nothing changes). GV_E_OOM: an open image that had to grow is gone; the pyramid's
  * image is not touched. */
@@ -861,7 +864,7 @@ int gv_occluder_depth_device(GvCtx* ctx, const void** depth, uint32_t* width, ui
  * GV_E_ARG: a NULL ctx; both outputs NULL; bytes below width * height * 4 (nothing is written). GV_E_STATE as above. */
 int gv_occluder_depth_fetch(GvCtx* ctx, float* depth, size_t bytes, GvOccluderCounts* counts);
 /* gv_hiz_build(image, width, height, GV_MEM_DEVICE) of the open image, and closes it: further draws need a new gv_occluder_begin
- * (which takes the other image). GV_E_STATE: no open image. Otherwise as gv_hiz_build. A caller who hands the open image's pointer
+ * (which takes another image). GV_E_STATE: no open image. Otherwise as gv_hiz_build. A caller who hands the open image's pointer
  * (gv_occluder_depth_device) to gv_hiz_build himself closes it the same way: no image takes a draw once a pyramid reads it. */
 int gv_hiz_build_from_occluders(GvCtx* ctx);
 
@@ -876,11 +879,16 @@ int gv_hiz_build_from_occluders(GvCtx* ctx);
  * silhouette TOUCHES, grown by the margin the occluder raster shrinks by; each pixel keeps the minimum. The boxes are the ones the cull
  * already mirrors: there is no binding and no binder's contract.
  *   Frame order: 1. gv_cull of the main view (which may itself use Hi-Z against the renderer's depth). 2. For each cascade k:
- *     gv_receiver_begin -> gv_pool_draw_receivers(pool, main view, L_k) for every pool that receives shadows ->
- *     gv_hiz_build_from_receivers -> gv_cull of cascade k with use_hiz = 1. 3. The context has ONE pyramid: the main view's depth
- *     pyramid is rebuilt next frame (as it is every frame anyway), and cascades culled this way go one at a time — they leave the
- *     batched multi-view pass. A gv_cull replaces ALL views of its pool: a cull that names cascade k alone ends the main view's
- *     records, which the next cascade's mask is drawn from — name the main view again in front of it.
+ *     gv_hiz_select(1 + k) -> gv_receiver_begin -> gv_pool_draw_receivers(pool, main view, L_k) for every pool that receives
+ *     shadows -> gv_hiz_build_from_receivers (into the selected slot). 3. gv_hiz_select(0), then ONE gv_cull of [main, cascade 0, cascade 1, ...]
+ *     with use_hiz = [the main view's own, 2, 3, ...]: every view is held against its own image in one pass over the pool (views
+ *     that share the camera position; others take a launch each, against their own pyramids all the same). The main view's depth
+ *     pyramid — slot 0 — is not touched by the masks, so gv_pool_cull_second_phase of the main view may follow in the same frame.
+ *   Frame order without pyramid slots (a caller who never calls gv_hiz_select; it still works): per cascade k gv_receiver_begin ->
+ *     the draws -> gv_hiz_build_from_receivers -> gv_cull of cascade k with use_hiz = 1. The context has ONE pyramid then: the main
+ *     view's depth pyramid is rebuilt next frame (as it is every frame anyway), and cascades culled this way go one at a time — they
+ *     leave the batched multi-view pass. A gv_cull replaces ALL views of its pool: a cull that names cascade k alone ends the main
+ *     view's records, which the next cascade's mask is drawn from — name the main view again in front of it.
  *   The rule, per draw k of the source view (slot s = visible_idx[k], M = the record's own bakedModel, (amin, amax) = the slot's cull
  *   AABB as mirrored, L = light_view_proj):
  *     1. corners and clip coordinates exactly as the Hi-Z query computes them against L: a caster that is also a receiver gets its
@@ -898,9 +906,9 @@ typedef struct GvReceiverCounts { /* 24 bytes; summed over the draws of every gv
     uint32_t drawn, flat, behind, range, outside, reserved; /* every record lands in exactly one of the first five; reserved is 0 */
 } GvReceiverCounts;
 /* Opens a receiver mask of width x height (1 .. 32768 each): sized, every word cleared to +inf (0x7F800000: "no receiver here") and
- * its counts zeroed, asynchronously on gv_stream(ctx). The context owns TWO receiver images of its own, apart from the occluder
- * images, and takes the one the current pyramid does not read: an image a pyramid reads is never cleared, redrawn or reallocated
- * under it. A begin on an open mask starts it over. An open occluder image and an open receiver mask may coexist.
+ * its counts zeroed, asynchronously on gv_stream(ctx). The context owns GV_MAX_PYRAMIDS + 1 receiver images of its own (each
+ * allocated at first use), apart from the occluder images, and takes the one of the last begin unless a built pyramid reads it, then
+ * the lowest-numbered one that no built pyramid reads: an image a pyramid reads is never cleared, redrawn or reallocated under it. A begin on an open mask starts it over. An open occluder image and an open receiver mask may coexist.
  * GV_E_ARG: a NULL ctx; a size of 0 or above 32768 (nothing changes). GV_E_OOM: an open mask that had to grow is gone; the pyramid's
  * image is not touched. */
 int gv_receiver_begin(GvCtx* ctx, uint32_t width, uint32_t height);
@@ -924,7 +932,7 @@ int gv_receiver_mask_device(GvCtx* ctx, const void** mask, uint32_t* width, uint
  * GV_E_ARG: a NULL ctx; both outputs NULL; bytes below width * height * 4 (nothing is written). GV_E_STATE as above. */
 int gv_receiver_mask_fetch(GvCtx* ctx, float* mask, size_t bytes, GvReceiverCounts* counts);
 /* gv_hiz_build(mask, width, height, GV_MEM_DEVICE) of the open mask, and closes it: further draws need a new gv_receiver_begin
- * (which takes the other image). GV_E_STATE: no open mask. Otherwise as gv_hiz_build. A caller who hands the open mask's pointer
+ * (which takes another image). GV_E_STATE: no open mask. Otherwise as gv_hiz_build. A caller who hands the open mask's pointer
  * (gv_receiver_mask_device) to gv_hiz_build himself closes it the same way. */
 int gv_hiz_build_from_receivers(GvCtx* ctx);
 
@@ -1334,6 +1342,19 @@ int gv_hiz_rebuild(GvCtx* ctx);
 /* Copies mip `level` (>= 1) back as (min,max) float pairs; *w, *h receive its size. */
 int gv_hiz_read_level(GvCtx* ctx, uint32_t level, float* out_pairs, uint32_t* w, uint32_t* h);
 int gv_hiz_mip_count(GvCtx* ctx, uint32_t* mip_count);
+/* ---- pyramid slots: several pyramids per context, one per view ----
+ * A context holds up to GV_MAX_PYRAMIDS pyramids. ONE of them is selected (a new context: pyramid 0): the one gv_hiz_build,
+ * gv_hiz_rebuild, gv_hiz_read_level, gv_hiz_mip_count, gv_hiz_build_from_occluders and gv_hiz_build_from_receivers address. Which
+ * pyramid a VIEW queries is not a matter of the selection: the view names it (GvView::use_hiz = 1 + k), and the name is resolved
+ * when the view's cull is launched, recorded culls of a batch included. A caller who never selects sees one pyramid, as before.
+ * gv_hiz_select does no device work and does not synchronise; recorded culls (gv_cull_batch_begin) are launched first, as by
+ * gv_hiz_build. GV_E_ARG: a NULL ctx; pyramid >= GV_MAX_PYRAMIDS (nothing changes). */
+int gv_hiz_select(GvCtx* ctx, uint32_t pyramid);
+/* Frees that pyramid's levels and its own copy of a host depth image (waits for gv_stream(ctx)); it is "not built" afterwards, selected
+ * or not, and the selection does not change. A pyramid built from a device image — an occluder image, a receiver mask, the caller's
+ * memory — only stops reading it: the image stays, and a later gv_occluder_begin / gv_receiver_begin may take it again. Recorded
+ * culls are launched first. GV_OK for a pyramid that was never built. GV_E_ARG: a NULL ctx; pyramid >= GV_MAX_PYRAMIDS. */
+int gv_hiz_drop(GvCtx* ctx, uint32_t pyramid);
 
 /* ---- lifecycle, errors, metrics ---- */
 int gv_create(const GvConfig* config, GvCtx** out_ctx);
