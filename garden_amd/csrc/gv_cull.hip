@@ -725,17 +725,19 @@ hipError_t launch_cull(const MeshMirror& mesh, const TransformMirror& xf, const 
     a.view = vp;
     a.out = out;
     a.nblocks = (mesh.count + kCullBlock - 1) / kCullBlock;
-    // measured: the frustum-only scan gains 6 % from per-XCD runs, the Hi-Z variant does not
+    // measured: the frustum-only scan gains 6 % from per-XCD runs, the Hi-Z variant from no order but the identity (gv_device.hpp)
     a.xcd_run = vp.use_hiz ? 0 : xcd_run_for_tiles(a.nblocks);
     const dim3 grid(grid_for_tiles(a.nblocks, a.xcd_run)), block(kCullBlock);
     const uint32_t k = mesh.hot && mesh.mapping == kMapExact ? hot_tiles_per_workgroup(a.nblocks) : 1u;
-    if (k > 1) {
+    // a Hi-Z view's super-tiles are shorter, or it stays with one tile per workgroup (measured: hot_tiles_per_workgroup_hiz)
+    const uint32_t tiles_each = vp.use_hiz && k > 1 ? hot_tiles_per_workgroup_hiz(a.nblocks) : k;
+    if (tiles_each > 1) {
         // the same XCD runs in super-tiles: each run still covers xcd_run_for_tiles() tiles
-        const uint32_t supers = (a.nblocks + k - 1) / k;
-        a.xcd_run = vp.use_hiz ? 0 : xcd_run_for_tiles(a.nblocks) / k;
+        const uint32_t supers = (a.nblocks + tiles_each - 1) / tiles_each;
+        a.xcd_run = vp.use_hiz ? 0 : xcd_run_for_tiles(a.nblocks) / tiles_each;
         const dim3 hot_grid(grid_for_tiles(supers, a.xcd_run));
         with_variant(vp.use_hiz, kMapExact, [&](auto hiz, auto) {
-            if (k == 4)
+            if (tiles_each == 4)
                 hipLaunchKernelGGL((cull_hot_kernel<hiz, 4>), hot_grid, block, 0, stream, a);
             else
                 hipLaunchKernelGGL((cull_hot_kernel<hiz, 2>), hot_grid, block, 0, stream, a);

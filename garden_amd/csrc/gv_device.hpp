@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "gv_device_math.hpp"
+#include "gv_tile_order.hpp"
 
 namespace gv {
 
@@ -367,26 +368,15 @@ __device__ __forceinline__ bool hiz_sphere_occluded(const HizDevice& hz, const f
 // Hi-Z variant does not move (R = 32) or loses (R = 256: +4 us; one run per XCD: 134-140 us, the queries pile up on
 // two XCDs), the block-bounds variant loses (78 -> 82 -> 89 us), the fused sweep + cull is flat: only the
 // frustum-only scan uses it (profiles/r01b_kbench.txt).
-// run length for a pool of `tiles` tiles: every XCD gets at least 8 runs (no surplus workgroups to speak of)
-inline uint32_t xcd_run_for_tiles(uint32_t tiles)
-{
-    return tiles >= 8u * 256u * 8u ? 256u : (tiles >= 8u * 32u * 8u ? 32u : 0u);
-}
-
-__device__ __forceinline__ uint32_t tile_of_workgroup(uint32_t b, uint32_t run)
-{
-    if (run == 0)
-        return b;
-    const uint32_t xcd = b & 7u, k = b >> 3;
-    return ((k / run) * 8u + xcd) * run + k % run;
-}
-
-// grid size for `tiles` tiles under that mapping: whole groups of 8 runs (surplus workgroups exit at once)
-inline uint32_t grid_for_tiles(uint32_t tiles, uint32_t run)
-{
-    const uint32_t group = run * 8u;
-    return run ? (tiles + group - 1) / group * group : tiles;
-}
+// A Hi-Z view keeps the identity. In the mirror's spatial order its launch runs as two phases, one after the other: the
+// frustum's entries (sphere queries, exact walks: VALU and dependent loads) all lie in the first half of the dispatch
+// order at the bench camera, and the rest is a bare 16-byte stream. Mixing the two over the whole dispatch, so that they
+// overlap, was measured and is slower, the more so the coarser the stripes (sphere-stream cull at 10 M, 63 us: 64 stripes
+// 90 us, 256 stripes 87 us, 1024 stripes 75 us, a modular stride 76 us; the same at 1 M and 2 M, on a harder depth image
+// and with the camera turned round), with the same FETCH_SIZE: the heavy workgroups first and the light ones last is
+// already the order with the shortest tail, and neighbours in the order share what they look up. What the two phases do
+// respond to is the super-tile: hot_tiles_per_workgroup_hiz (profiles/r33_cull_order.md).
+// (the mapping itself and its grid size: gv_tile_order.hpp)
 
 struct CullArgs {
     MeshMirror mesh;
@@ -395,7 +385,7 @@ struct CullArgs {
     ViewParams view;
     ViewBuffers out;
     uint32_t nblocks;
-    uint32_t xcd_run;    // tile_of_workgroup(); 0 = workgroup b takes tile b
+    uint32_t xcd_run;    // tile_of_workgroup() (gv_tile_order.hpp); 0 = workgroup b takes tile b
 };
 
 // The filter chain's verdict on one mesh entry: mesh.cpp:140-142 skips free slots and disabled meshes (`candidate`) and

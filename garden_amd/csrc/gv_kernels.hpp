@@ -64,6 +64,17 @@ inline uint32_t hot_tiles_per_workgroup(uint32_t tiles)
 {
     return tiles >= 16384u ? 4u : (tiles >= 8192u ? 2u : 1u);
 }
+// A Hi-Z view takes fewer tiles per workgroup than a frustum-only view of the same pool: its workgroups inside the frustum run many
+// times longer than the ones outside (pyramid queries, exact walks), and (supposed, not measured) a long super-tile holds its place
+// on the CU while most of its lanes wait. Measured frame of the bench scene, 4096^2 pyramid, K = 1 / 2 / 4: 8 204 tiles 47.6 / 50.1 / 60.2 us,
+// 16 387 tiles 62.8 / 61.9 / 69.5, 23 438 tiles 75.7 / 69.9 / 77.2, 39 063 tiles (the bench) 105.2 / 90.6 / 95.2; K = 2 / 4: 46 875
+// tiles 99.2 / 102.4, 54 688 tiles 109.9 / 109.8, 65 537 tiles 131.6 / 127.9, 78 125 tiles 151.5 / 144.2 (profiles/r33_cull_order.md).
+constexpr uint32_t kHizHotK2Tiles = 16384;
+constexpr uint32_t kHizHotK4Tiles = 57344;
+inline uint32_t hot_tiles_per_workgroup_hiz(uint32_t tiles)
+{
+    return tiles >= kHizHotK4Tiles ? 4u : (tiles >= kHizHotK2Tiles ? 2u : 1u);
+}
 hipError_t launch_hot_build(const MeshMirror& mesh, const TransformMirror& xf, float4* hot, hipStream_t stream);
 // re-derives the entries of the blocks flagged kDirtyHot (flags padded to a multiple of 16) and clears that bit
 hipError_t launch_hot_patch(const MeshMirror& mesh, const TransformMirror& xf, float4* hot, uint8_t* flags, hipStream_t stream);
