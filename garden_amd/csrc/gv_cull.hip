@@ -20,6 +20,7 @@
 // All of it is HBM-bound streaming (DESIGN.md has bytes/entity per kernel); loads are 16- or 12-byte
 // per lane over SoA streams so each wave-instruction touches 1 KiB / 768 B contiguous.
 #include "gv_device.hpp"
+#include "gv_dense_rounds.hpp"
 
 #include <type_traits>
 
@@ -203,17 +204,23 @@ __global__ __launch_bounds__(kCullBlock) void cull_kernel(const CullArgs args)
 //      worked out, their eight texel loads in flight together — and an entry proven occluded from its sphere (hiz_sphere_occluded)
 //      becomes an outside entry: at cfg3 that settles 95 % of the occluded frustum survivors before any of their 49 cold bytes or
 //      corners are asked for (profiles/r12_hiz_sphere.md);
-//   2. the tiles one after another, each through cull_block's HOT per-entity code: only the lanes that need corners run it, and a
-//      wave skips a tile in which none of its lanes does;
+//   2. the entries that need corners (undecided; with Hi-Z also inside and not proven occluded) go through cull_block's HOT per-entity
+//      code. A frustum-only view has few of them: its waves walk the tiles one after another, and a wave skips a tile in which none
+//      of its lanes needs corners. A Hi-Z view has many, thinly spread — at cfg3 398 k candidates in 16 001 64-entry groups, 25 lanes
+//      of 64 — and each pass of that code is long (8 divisions, two dependent rounds of gathers), so its workgroup lists the
+//      super-tile's candidates in LDS and its four waves decide them 256 at a time, every lane busy whichever lane and tile the entry
+//      came from (dense_rounds, gv_dense_rounds.hpp): 8 014 wave passes instead of 16 001. Measured with that step and with 1b
+//      cut out of scratch builds: of the 56.3 us of the cfg3 cull, 26.6 are steps 1 and 3, 9.2 step 1b and 20.5 step 2; the dense
+//      rounds take 7.5 of those 20.5 (48.3 us; profiles/r34_dense_rounds.md). A workgroup without a candidate leaves after the one
+//      barrier it paid before;
 //   3. the 4K ballot words leave as one contiguous store, the super-tile's count as one atomic (K divides the 16 tiles of an emit
-//      chunk: a workgroup never straddles two).
-// Same device functions, same operands: the same decision bits as cull_kernel<HIZ, kMapExact, true>, which K = 1 keeps.
+//      chunk: a workgroup never straddles two); a Hi-Z view's words are ORed together in LDS by the rounds, bit for bit the ballots.
+// Same device functions, same operands, every decision per entry: the same bits as cull_kernel<HIZ, kMapExact, true>, which K = 1 keeps.
 template <bool HIZ, uint32_t K>
 __global__ __launch_bounds__(kCullBlock) void cull_hot_kernel(const CullArgs args)
 {
     static_assert(K >= 2 && K <= 16 && (kEmitChunk / kCullBlock) % K == 0, "a super-tile must not straddle an emit chunk");
-    __shared__ unsigned long long words[K * (kCullBlock / 64)];
-    __shared__ uint32_t wave_count[kCullBlock / 64];
+    static_assert(kCullBlock == kDenseLanes, "dense_rounds takes the cull's workgroup");
     const uint32_t first = tile_of_workgroup(blockIdx.x, args.xcd_run) * K;  // the super-tile's first tile
     if (first >= args.nblocks)
         return;
@@ -258,13 +265,45 @@ __global__ __launch_bounds__(kCullBlock) void cull_hot_kernel(const CullArgs arg
                              "+v"(h[(g + 3) % K].x), "+v"(h[(g + 3) % K].y), "+v"(h[(g + 3) % K].z), "+v"(h[(g + 3) % K].w));
         }
     }
+    if constexpr (HIZ) {  // (the arguments are read afresh at each stage, as in cull_list_kernel: no SGPR spills)
+        __shared__ DenseRoundsLds<K> dense;
+        dense_rounds<K>(
+            dense, where, kSphereUndecided, first,
+            [first](uint32_t slot, bool undecided) {
+                const uint32_t i = first * kCullBlock + slot;
+                CullArgs a1;
+                reload_cull_args(a1);
+                Mat34 m;
+                float4 box_a;
+                float2 box_b;
+                Corners c;
+                bool visible = prepare_model<kMapExact>(a1.mesh, a1.xf, a1.view.cam, i, m, box_a, box_b) &&
+                               settle<true>(undecided ? kSphereUndecided : kSphereInside, m, box_a, box_b, a1.view.planes, a1.view.plane_count, c);
+                if (visible) {
+                    CullArgs a2;
+                    reload_cull_args(a2);
+                    visible = !hiz_occluded(a2.hiz, a2.view.vp, c);
+                }
+                return visible;
+            },
+            [] {
+                CullArgs a3;
+                reload_cull_args(a3);
+                return DenseOutputs{a3.out.mask, a3.out.chunk_count, a3.view.write_is_visible ? a3.out.is_visible : nullptr,  // mesh.cpp:144,152,161,166
+                                    a3.nblocks, a3.mesh.count, kEmitChunk / kCullBlock};
+            });
+        return;
+    }
+    // a frustum-only view: the tiles one after another (the arguments read afresh at each stage here too)
+    __shared__ unsigned long long words[K * (kCullBlock / 64)];
+    __shared__ uint32_t wave_count[kCullBlock / 64];
     uint32_t count = 0;
 #pragma unroll 1
-    for (uint32_t k = 0; k < K; k++) {  // (the arguments are read afresh at each stage, as in cull_list_kernel: no SGPR spills)
+    for (uint32_t k = 0; k < K; k++) {
         const uint32_t i = base + k * kCullBlock;
         const uint32_t wk = (where >> (2u * k)) & 3u;
         bool visible = wk == kSphereInside;
-        if (wk == kSphereUndecided || (HIZ && visible)) {
+        if (wk == kSphereUndecided) {
             CullArgs a1;
             reload_cull_args(a1);
             Mat34 m;
@@ -272,12 +311,7 @@ __global__ __launch_bounds__(kCullBlock) void cull_hot_kernel(const CullArgs arg
             float2 box_b;
             Corners c;
             visible = prepare_model<kMapExact>(a1.mesh, a1.xf, a1.view.cam, i, m, box_a, box_b) &&
-                      settle<HIZ>(wk, m, box_a, box_b, a1.view.planes, a1.view.plane_count, c);
-            if (HIZ && visible) {
-                CullArgs a2;
-                reload_cull_args(a2);
-                visible = !hiz_occluded(a2.hiz, a2.view.vp, c);
-            }
+                      settle<false>(wk, m, box_a, box_b, a1.view.planes, a1.view.plane_count, c);
         }
         CullArgs a3;
         reload_cull_args(a3);

@@ -65,8 +65,11 @@ inline uint32_t hot_tiles_per_workgroup(uint32_t tiles)
     return tiles >= 16384u ? 4u : (tiles >= 8192u ? 2u : 1u);
 }
 // A Hi-Z view takes fewer tiles per workgroup than a frustum-only view of the same pool: its workgroups inside the frustum run many
-// times longer than the ones outside (pyramid queries, exact walks), and (supposed, not measured) a long super-tile holds its place
-// on the CU while most of its lanes wait. Measured frame of the bench scene, 4096^2 pyramid, K = 1 / 2 / 4: 8 204 tiles 47.6 / 50.1 / 60.2 us,
+// times longer than the ones outside (pyramid queries, the exact path of the corner candidates). It is not the walk of a wave over
+// its K tiles one after the other that makes a long super-tile lose: with the candidates of the whole super-tile settled in dense
+// rounds by all four waves (gv_dense_rounds.hpp) K = 4 still takes 52.8 us at the bench's 39 063 tiles where K = 2 takes 48.3, as it
+// took 59.7 against 56.2 before (profiles/r34_dense_rounds.md); why is not known. The steps below are those measured before the
+// dense rounds: frame of the bench scene, 4096^2 pyramid, K = 1 / 2 / 4: 8 204 tiles 47.6 / 50.1 / 60.2 us,
 // 16 387 tiles 62.8 / 61.9 / 69.5, 23 438 tiles 75.7 / 69.9 / 77.2, 39 063 tiles (the bench) 105.2 / 90.6 / 95.2; K = 2 / 4: 46 875
 // tiles 99.2 / 102.4, 54 688 tiles 109.9 / 109.8, 65 537 tiles 131.6 / 127.9, 78 125 tiles 151.5 / 144.2 (profiles/r33_cull_order.md).
 constexpr uint32_t kHizHotK2Tiles = 16384;
