@@ -1,0 +1,477 @@
+// gv_clusters.hip — gfx950 kernels of gv_pool_cull_clusters: every mesh cluster of every draw of the pool's last instance emission
+// tested with the draw's own matrix, one indirect command per survivor. No new arithmetic: a cluster
+// is tested as the cull tests an entity — aabb_corners, behind_frustum and hiz_occluded of gv_device.hpp, unchanged, over the
+// record's bakedModel as delivered. A CANDIDATE is what may become one command: a cluster of a clustered draw, or a whole draw.
+//
+//   cluster_count_kernel   one lane per draw, 256 per workgroup, grid from the views' occupancies. idx -> id (or the selected id) ->
+//                          range; candidates of the draw: 0 (void geometry, no instance, beyond the view's count), 1 (whole) or
+//                          range.count. Workgroup-local exclusive prefix per draw (ballot-free: a wave scan and four wave totals),
+//                          one candidate total and one tested total per workgroup, the draw's id kept for the launches behind.
+//   cluster_scan_kernel    ONE workgroup of 1024 lanes, four entries per lane and turn, a running carry: the table becomes the
+//                          exclusive prefix of itself. <0>: the count workgroups' totals (their number is host-known); also T,
+//                          the candidates in front of every view, the clusters tested per view, and per tile the count workgroup
+//                          that holds its first candidate. <1>: the tiles' survivor
+//                          counts, ceil(T / 256) of them, read from the device; also the survivors in front of every view — a tile
+//                          prefix plus the ballot bits below the view's first candidate — and with them the command counts.
+//   cluster_test_kernel    one lane per candidate, tiles of 256 walked grid-stride by a grid of fixed size (8 workgroups per compute
+//                          unit) with the device-read T as the limit: a bound of 6 x 10^8 candidates costs no empty workgroup.
+//                          Candidate c -> (draw, j): the largest workgroup whose prefix is <= c — searched between the workgroup
+//                          of the tile's first candidate and that of the next tile's, a table cluster_scan_kernel<0> leaves: a
+//                          step or none — then the largest draw of it likewise (8 dependent loads, from tables the L2 holds). The 32-byte cluster as two
+//                          16-byte loads, the draw's 48-byte model as three: neighbouring lanes share it, so it comes from cache.
+//                          Corners once; then per view that has a lane in the wave (a tile may cross a view) the planes, the
+//                          matrix and the pyramid from the kernel arguments at a wave-uniform offset, as cull_multi_hiz_kernel
+//                          takes them, the six plane tests and the Hi-Z query. One ballot per wave: the word is kept (a bit per
+//                          candidate), the tile's sum of popcounts is its survivor count.
+//   cluster_write_kernel   the same walk. A survivor's position is its rank: the tile's prefix + the bits below it. It finds its
+//                          draw again, builds the command and stores every word of the stride. With regions a second grid-stride
+//                          walk writes the all-zero padding positions.
+//
+// Rank + scatter as gv_sort: no workgroup waits for another, no atomics, integer adds only — the order (view, draw, cluster) and
+// every byte are the same run to run. Whatever an id, a range or a count holds, the tables are read inside their bounds: j is below
+// the range's count by construction, a range lies inside the cluster table by the bind's check, T is at most the host's bound.
+#include "gv_device.hpp"
+#include "gv_cluster_kernels.hpp"
+
+namespace gv {
+
+namespace {
+
+typedef const ClusterLaunch __attribute__((address_space(4))) * ConstClusterArgs;
+struct ClusterPlanes { float planes[6][4]; };
+struct ClusterMatrix { float m[16]; };
+__device__ __forceinline__ ClusterPlanes view_planes_of(ConstClusterArgs base, uint32_t v)
+{
+    ClusterPlanes out;
+    __builtin_memcpy(&out, &base->planes[v], sizeof(out));
+    return out;
+}
+__device__ __forceinline__ ClusterMatrix view_matrix_of(ConstClusterArgs base, uint32_t v)
+{
+    ClusterMatrix out;
+    __builtin_memcpy(&out, &base->vp[v], sizeof(out));
+    return out;
+}
+__device__ __forceinline__ HizDevice view_hiz_of(ConstClusterArgs base, uint32_t v)
+{
+    HizDevice out;
+    __builtin_memcpy(&out, &base->hiz[v], sizeof(out));
+    return out;
+}
+
+// draw k of view v: the first instance the emission gave it, and how many (c_k)
+__device__ __forceinline__ uint32_t first_of_draw(const ClusterLaunch& a, uint32_t v, uint32_t k)
+{
+    return a.first_instance_of ? a.first_instance_of[a.draw_starts[v] + k] : a.starts[v] + k;
+}
+__device__ __forceinline__ uint32_t instances_of_draw(const ClusterLaunch& a, uint32_t v, uint32_t k, uint32_t n, uint32_t from)
+{
+    const uint32_t next = k + 1u < n ? first_of_draw(a, v, k + 1u) : a.starts[v + 1];
+    return next - from;
+}
+// what the walks need of view v when v differs from lane to lane: selected, not indexed (an argument array indexed by a lane's
+// value would be copied to scratch)
+struct ViewPick {
+    const float* model;
+    const uint32_t* count;
+    uint32_t first_block;
+};
+__device__ __forceinline__ ViewPick pick_view(const ClusterLaunch& a, uint32_t v)
+{
+    ViewPick p{a.view[0].model, a.view[0].count, a.first_block[0]};
+#pragma unroll
+    for (uint32_t u = 1; u < kMaxInstanceViews; u++)
+        if (v == u)
+            p = ViewPick{a.view[u].model, a.view[u].count, a.first_block[u]};
+    return p;
+}
+__device__ __forceinline__ ClusterRange range_of(const ClusterLaunch& a, uint32_t g)
+{
+    return g < a.range_count ? a.ranges[g] : ClusterRange{0u, 0u};
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_count_kernel(const ClusterLaunch a)
+{
+    __shared__ uint32_t wave_sum[2][kClusterBlock / 64u];
+    if (blockIdx.x >= a.first_block[a.views])
+        return;  // (a call whose views hold no slot launches one workgroup)
+    const uint32_t v = view_of_block(a.first_block, a.views, blockIdx.x);
+    const ClusterView& vw = a.view[v];
+    const uint32_t n = *vw.count;
+    const uint32_t first = (blockIdx.x - a.first_block[v]) * kClusterBlock;
+    if (first >= n) {  // (the whole workgroup, after ONE load) nothing here: the prefix skips it, nobody reads its draws
+        if (threadIdx.x == 0) {
+            a.block_total[blockIdx.x] = 0;
+            a.block_tested[blockIdx.x] = 0;
+        }
+        return;
+    }
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t k = first + threadIdx.x;
+    uint32_t g = kClusterNone, candidates = 0, tested = 0;
+    if (k < n) {
+        uint32_t id;
+        if (a.draw_ids) {  // the selected ids, draw-indexed (wave-uniform choice)
+            uint32_t at = 0;
+            for (uint32_t u = 0; u < v; u++)
+                at += *a.view[u].count;
+            id = stream_load(a.draw_ids + at + k);
+        } else {
+            const uint32_t slot = stream_load(vw.idx + k);
+            id = a.ids ? a.ids[slot] : 0u;
+        }
+        const uint32_t from = first_of_draw(a, v, k);
+        if (id < a.table_count && instances_of_draw(a, v, k, n, from) != 0u) {
+            g = id;
+            tested = range_of(a, id).count;
+            candidates = tested ? tested : 1u;
+        }
+    }
+    // workgroup-local exclusive prefix: a draw beyond the count has no candidate, so its prefix is the total and no search ends on it
+    const uint32_t upto = wave_inclusive_scan(candidates, lane);
+    uint32_t t = tested;
+#pragma unroll
+    for (uint32_t d = 32; d >= 1u; d >>= 1)
+        t += __shfl_xor(t, d, 64);
+    if (lane == 63u)
+        wave_sum[0][wave] = upto;
+    if (lane == 0u)
+        wave_sum[1][wave] = t;
+    __syncthreads();
+    uint32_t before = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kClusterBlock / 64u; w++)
+        before += w < wave ? wave_sum[0][w] : 0u;
+    const size_t at = (size_t)blockIdx.x * kClusterBlock + threadIdx.x;
+    a.draw_geometry[at] = g;
+    a.draw_local[at] = before + upto - candidates;
+    if (threadIdx.x == 0) {
+        a.block_total[blockIdx.x] = wave_sum[0][0] + wave_sum[0][1] + wave_sum[0][2] + wave_sum[0][3];
+        a.block_tested[blockIdx.x] = wave_sum[1][0] + wave_sum[1][1] + wave_sum[1][2] + wave_sum[1][3];
+    }
+}
+
+// t[0, n) becomes its own exclusive prefix, by the whole workgroup of kClusterScanBlock lanes; every lane gets the sum
+__device__ __forceinline__ uint32_t scan_table(uint32_t* t, uint32_t n, uint32_t* wave_part, uint32_t* turn_sum)
+{
+    constexpr uint32_t kWaves = kClusterScanBlock / 64u;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < n; base += kClusterScanBlock * 4u) {
+        const uint32_t at = base + threadIdx.x * 4u;
+        uint32_t x[4] = {0u, 0u, 0u, 0u};
+        if (at + 4u <= n) {  // (the table is 16-byte aligned and `at` a multiple of four)
+            const uint4 q = *reinterpret_cast<const uint4*>(t + at);
+            x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w;
+        } else {
+            for (uint32_t e = 0; e < 4u; e++)
+                x[e] = at + e < n ? t[at + e] : 0u;
+        }
+        const uint32_t own = x[0] + x[1] + x[2] + x[3];
+        const uint32_t upto = wave_inclusive_scan(own, lane);
+        __syncthreads();  // (the parts may still be read from the turn before)
+        if (lane == 63u)
+            wave_part[wave] = upto;
+        __syncthreads();
+        if (wave == 0) {
+            const uint32_t part = lane < kWaves ? wave_part[lane] : 0u, scanned = wave_inclusive_scan(part, lane);
+            if (lane < kWaves)
+                wave_part[lane] = scanned - part;
+            if (lane == kWaves - 1u)
+                *turn_sum = scanned;
+        }
+        __syncthreads();
+        uint32_t run = carry + wave_part[wave] + upto - own;
+        if (at + 4u <= n) {
+            uint4 q;
+            q.x = run, q.y = run + x[0], q.z = run + x[0] + x[1], q.w = run + x[0] + x[1] + x[2];
+            *reinterpret_cast<uint4*>(t + at) = q;
+        } else {
+            for (uint32_t e = 0; e < 4u; e++) {
+                if (at + e < n)
+                    t[at + e] = run;
+                run += x[e];
+            }
+        }
+        carry += *turn_sum;
+    }
+    __syncthreads();
+    return carry;
+}
+
+// survivors in front of candidate c (c <= T): the prefix of its tile and the ballot bits below it; `all` for c == T
+__device__ __forceinline__ uint32_t survivors_before(const ClusterLaunch& a, uint32_t c, uint32_t total, uint32_t all)
+{
+    if (c >= total)
+        return all;
+    const uint32_t tile = c / kClusterTile, in = c % kClusterTile;
+    uint32_t s = a.tile_count[tile];  // (scanned: the survivors in front of the tile)
+    for (uint32_t w = 0; w < in / 64u; w++)
+        s += (uint32_t)__popcll(a.survive[(size_t)tile * 4u + w]);
+    if (in % 64u)
+        s += (uint32_t)__popcll(a.survive[(size_t)tile * 4u + in / 64u] & ((1ull << (in % 64u)) - 1ull));
+    return s;
+}
+
+template <uint32_t kStage>
+__global__ __launch_bounds__(kClusterScanBlock) void cluster_scan_kernel(const ClusterLaunch a)
+{
+    __shared__ uint32_t wave_part[kClusterScanBlock / 64u];
+    __shared__ uint32_t turn_sum;
+    __shared__ uint32_t view_sum[kMaxInstanceViews][kClusterScanBlock / 64u];
+    const uint32_t blocks = a.first_block[a.views];
+    if constexpr (kStage == 0) {
+        // clusters tested per view, in front of the scan (sums of another table: no order to keep)
+        const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+        for (uint32_t v = 0; v < a.views; v++) {
+            uint32_t x = 0;
+            for (uint32_t b = a.first_block[v] + threadIdx.x; b < a.first_block[v + 1]; b += kClusterScanBlock)
+                x += a.block_tested[b];
+#pragma unroll
+            for (uint32_t d = 32; d >= 1u; d >>= 1)
+                x += __shfl_xor(x, d, 64);
+            if (lane == 0u)
+                view_sum[v][wave] = x;
+        }
+        __syncthreads();
+        if (threadIdx.x < a.views) {
+            uint32_t x = 0;
+            for (uint32_t w = 0; w < kClusterScanBlock / 64u; w++)
+                x += view_sum[threadIdx.x][w];
+            a.counts[a.views + threadIdx.x] = x;
+        }
+        const uint32_t total = scan_table(a.block_total, blocks, wave_part, &turn_sum);
+        if (threadIdx.x == 0)
+            a.totals[kClusterTotalCandidates] = total;
+        if (threadIdx.x == 0)  // (the scan's stores are visible to the workgroup behind scan_table's last barrier)
+            for (uint32_t v = 0; v <= a.views; v++)
+                a.totals[kClusterCandidateStart + v] = a.first_block[v] < blocks ? a.block_total[a.first_block[v]] : total;
+        // where the search of a tile's candidates begins: every tile's first candidate lies in exactly one workgroup that has
+        // candidates, and that workgroup writes the tile's entry
+        for (uint32_t b = threadIdx.x; b < blocks; b += kClusterScanBlock) {
+            const uint32_t from = a.block_total[b], end = b + 1u < blocks ? a.block_total[b + 1u] : total;
+            if (end == from)
+                continue;
+            const uint32_t last = (end - 1u) / kClusterTile;
+            for (uint32_t t = from / kClusterTile + (from % kClusterTile ? 1u : 0u); t <= last; t++)
+                a.tile_block[t] = b;
+        }
+    } else {
+        const uint32_t total = a.totals[kClusterTotalCandidates];
+        const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+        const uint32_t all = scan_table(a.tile_count, tiles, wave_part, &turn_sum);
+        if (threadIdx.x <= a.views)
+            view_sum[0][threadIdx.x] = survivors_before(a, a.totals[kClusterCandidateStart + threadIdx.x], total, all);
+        __syncthreads();
+        if (threadIdx.x <= a.views)
+            a.totals[kClusterSurvivorStart + threadIdx.x] = view_sum[0][threadIdx.x];
+        if (threadIdx.x < a.views)
+            a.counts[threadIdx.x] = view_sum[0][threadIdx.x + 1u] - view_sum[0][threadIdx.x];
+    }
+}
+
+// candidate c < T -> the count workgroup of its draw, the draw's place in the scratch and the candidate's number inside the draw
+// (of tile `tile` of `tiles`, `blocks` count workgroups: the workgroup lies between the one of the tile's first candidate and the
+// one of the next tile's — mostly the same one, so the first search is a step or none)
+__device__ __forceinline__ void locate(const ClusterLaunch& a, uint32_t c, uint32_t tile, uint32_t tiles, uint32_t blocks, uint32_t& block,
+                                       uint32_t& at, uint32_t& j)
+{
+    uint32_t lo = a.tile_block[tile], hi = (tile + 1u < tiles ? a.tile_block[tile + 1u] : blocks - 1u) + 1u;
+    while (hi - lo > 1u) {  // the largest workgroup in [lo, hi) whose prefix is <= c (lo's is: it holds the tile's first candidate)
+        const uint32_t mid = (lo + hi) >> 1;
+        if (a.block_total[mid] <= c)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    block = lo;
+    const uint32_t rest = c - a.block_total[lo];
+    const uint32_t* const local = a.draw_local + (size_t)lo * kClusterBlock;
+    lo = 0, hi = kClusterBlock;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (local[mid] <= rest)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    at = block * kClusterBlock + lo;
+    j = rest - local[lo];
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_test_kernel(const ClusterLaunch a)
+{
+    __shared__ uint32_t wave_count[kClusterBlock / 64u];
+    ConstClusterArgs base = (ConstClusterArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(base));  // (opaque: nothing read through it is moved out of the loops)
+    const uint32_t total = a.totals[kClusterTotalCandidates];
+    const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+    const uint32_t blocks = a.first_block[a.views];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint32_t c = tile * kClusterTile + threadIdx.x;
+        const bool live = c < total;
+        bool survives = live;  // a whole draw survives untested
+        bool tested = false;
+        uint32_t v = 0;
+        Corners corners;
+        if (live) {
+            uint32_t block, at, j;
+            locate(a, c, tile, tiles, blocks, block, at, j);
+            v = view_of_block(a.first_block, a.views, block);
+            const ClusterRange range = range_of(a, a.draw_geometry[at]);
+            if (range.count) {
+                tested = true;
+                const float4* const cl = a.clusters + ((size_t)range.first + j) * 2u;
+                const float4 lo = cl[0], hi = cl[1];  // (plain loads: every draw of the geometry reads the cluster again)
+                const ViewPick view = pick_view(a, v);
+                const uint32_t k = at - view.first_block * kClusterBlock;
+                const float4* const rows = reinterpret_cast<const float4*>(view.model) + (size_t)k * 3u;
+                const float4 w0 = rows[0], w1 = rows[1], w2 = rows[2];  // (... and the draw's other clusters its model)
+                aabb_corners(rows_model(w0, w1, w2), lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, corners);
+            }
+        }
+#pragma unroll 1
+        for (uint32_t u = 0; u < a.views; u++) {
+            const bool mine = tested && v == u;
+            if (!__any(mine))
+                continue;  // (wave-uniform)
+            const ClusterPlanes pl = view_planes_of(base, u);
+            const uint32_t plane_count = base->plane_count[u];
+            const bool query = (a.hiz_views >> u) & 1u;
+            if (mine) {
+                bool visible = !behind_frustum(corners, pl.planes, plane_count);
+                if (query && visible) {
+                    const HizDevice hz = view_hiz_of(base, u);
+                    const ClusterMatrix vm = view_matrix_of(base, u);
+                    visible = !hiz_occluded(hz, vm.m, corners);
+                }
+                survives = visible;
+            }
+        }
+        const unsigned long long word = __ballot(survives);
+        if (lane == 0u) {
+            a.survive[(size_t)tile * 4u + wave] = word;
+            wave_count[wave] = (uint32_t)__popcll(word);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            a.tile_count[tile] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+        __syncthreads();  // (the next tile rewrites the wave counts)
+    }
+}
+
+// every word of one command position; a field offset of kNoField matches no word
+__device__ __forceinline__ void put_command(const ClusterLaunch& a, uint32_t position, uint32_t count, uint32_t instances, uint32_t first,
+                                            uint32_t first_instance, uint32_t vertex_offset, uint32_t draw)
+{
+    uint32_t* const to = reinterpret_cast<uint32_t*>(a.dst + (size_t)position * a.stride);
+    for (uint32_t w = 0; w < a.stride / 4u; w++) {
+        const uint32_t byte = w * 4u;
+        uint32_t x = 0u;
+        x = byte == a.count ? count : x;
+        x = byte == a.instance_count ? instances : x;
+        x = byte == a.first ? first : x;
+        x = byte == a.first_instance ? first_instance : x;
+        x = byte == a.vertex_offset ? vertex_offset : x;
+        x = byte == a.draw ? draw : x;
+        to[w] = x;
+    }
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_write_kernel(const ClusterLaunch a)
+{
+    const uint32_t total = a.totals[kClusterTotalCandidates];
+    const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+    const uint32_t blocks = a.first_block[a.views];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const unsigned long long* const words = a.survive + (size_t)tile * 4u;
+        const unsigned long long word = words[wave];
+        if (!((word >> lane) & 1ull))
+            continue;
+        uint32_t rank = a.tile_count[tile] + (uint32_t)__popcll(word & ((1ull << lane) - 1ull));  // (scanned: survivors in front of the tile)
+        for (uint32_t w = 0; w < wave; w++)
+            rank += (uint32_t)__popcll(words[w]);
+        const uint32_t c = tile * kClusterTile + threadIdx.x;
+        uint32_t block, at, j;
+        locate(a, c, tile, tiles, blocks, block, at, j);
+        const uint32_t v = view_of_block(a.first_block, a.views, block);
+        uint32_t position = rank;  // packed: the views' commands back to back are the survivors in order
+        if (a.region) {
+            const uint32_t in_view = rank - a.totals[kClusterSurvivorStart + v];
+            if (in_view >= a.region)
+                continue;
+            position = v * a.region + in_view;
+        }
+        if (position >= a.capacity)
+            continue;
+        const ViewPick view = pick_view(a, v);
+        const uint32_t k = at - view.first_block * kClusterBlock;
+        const uint32_t g = a.draw_geometry[at];  // (below table_count: the draw has candidates)
+        const CommandGeometry geometry = a.table[g];
+        const ClusterRange range = range_of(a, g);
+        uint32_t count = geometry.count, first = geometry.first;
+        if (range.count) {
+            const float4* const cl = a.clusters + ((size_t)range.first + j) * 2u;
+            first += __float_as_uint(cl[0].w);
+            count = __float_as_uint(cl[1].w);
+        }
+        const uint32_t from = first_of_draw(a, v, k);
+        put_command(a, position, count, instances_of_draw(a, v, k, *view.count, from), first, from, (uint32_t)geometry.vertex_offset, k);
+    }
+    if (a.region) {  // the all-zero padding positions C_v <= j < R of every view
+        const uint64_t positions = (uint64_t)a.views * a.region;
+        for (uint64_t p = (uint64_t)blockIdx.x * kClusterBlock + threadIdx.x; p < positions && p < a.capacity; p += (uint64_t)gridDim.x * kClusterBlock) {
+            const uint32_t v = (uint32_t)(p / a.region), in_view = (uint32_t)(p % a.region);
+            if (in_view < a.counts[v])
+                continue;
+            uint32_t* const to = reinterpret_cast<uint32_t*>(a.dst + (size_t)p * a.stride);
+            for (uint32_t w = 0; w < a.stride / 4u; w++)
+                to[w] = 0u;
+        }
+    }
+}
+
+// the fixed grid of the test and write launches: kClusterGridPerCu workgroups per compute unit of the current device
+uint32_t walk_grid()
+{
+    int device = 0, units = 0;
+    if (hipGetDevice(&device) != hipSuccess || hipDeviceGetAttribute(&units, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || units <= 0)
+        units = 256;
+    return (uint32_t)units * kClusterGridPerCu;
+}
+
+}  // namespace
+
+hipError_t launch_cluster_count(const ClusterLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_count_kernel, dim3(std::max(1u, launch.first_block[launch.views])), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_scan_candidates(const ClusterLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_scan_kernel<0>, dim3(1), dim3(kClusterScanBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_test(const ClusterLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_scan_survivors(const ClusterLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_scan_kernel<1>, dim3(1), dim3(kClusterScanBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_write(const ClusterLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_write_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+}  // namespace gv

@@ -110,6 +110,9 @@ int begin_view(GvCtx* ctx, ViewState& vs, uint32_t pool_id, const GvView& view, 
     memcpy(vs.view_proj, view.view_proj, sizeof(vs.view_proj));
     memcpy(vs.camera_position, view.camera_position, sizeof(vs.camera_position));
     build_view_params(view, vp);
+    memcpy(vs.planes, vp->planes, sizeof(vs.planes));
+    vs.plane_count = vp->plane_count;
+    vs.use_hiz = view.use_hiz;
     return GV_OK;
 }
 

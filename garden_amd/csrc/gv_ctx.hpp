@@ -27,6 +27,7 @@
 #include "gv_occluder_kernels.hpp"
 #include "gv_receiver_kernels.hpp"
 #include "gv_previous_kernels.hpp"
+#include "gv_cluster_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -361,6 +362,32 @@ struct PoolState {
             h_data.release(), h_counts.release();
         }
     } commands;
+    // gv_pool_bind_clusters / gv_pool_cull_clusters: the tables as bound and the last call's commands, buffers of their own — no cull
+    // result, no instance data and no per-draw command buffer (Commands above) is touched. Header-only: no other host source calls
+    // gv_clusters.cpp.
+    struct Clusters {
+        bool bound = false;
+        uint32_t range_count = 0, cluster_count = 0;
+        uint32_t max_range = 0;            // the largest count of a bound range: the host's bound of a draw's candidates
+        DeviceBuf<GvClusterRange> d_ranges;  // re-uploaded on every bind
+        DeviceBuf<GvCluster> d_clusters;
+        DeviceBuf<uint8_t> d_data;         // the library-owned target
+        DeviceBuf<uint32_t> d_counts;      // [2 * GV_MAX_VIEWS]: commands per view, then clusters tested per view
+        DeviceBuf<uint32_t> d_draw_geometry, d_draw_local, d_block_total, d_block_tested, d_totals, d_tile_count, d_tile_block;  // scratch of a call
+        DeviceBuf<unsigned long long> d_survive;
+        PinnedBuf<uint8_t> h_data;         // staging of gv_pool_cluster_commands_fetch
+        PinnedBuf<uint32_t> h_counts;
+        // the last call (views 0: none since the pool's last gv_cull, instance emission or gv_pool_bind_clusters)
+        uint8_t* target = nullptr;         // d_data.ptr or the caller's device memory
+        uint32_t capacity = 0;             // command positions the target holds
+        uint32_t views = 0, stride = 0, region = 0;
+        void release()
+        {
+            d_ranges.release(), d_clusters.release(), d_data.release(), d_counts.release(), d_draw_geometry.release(), d_draw_local.release();
+            d_block_total.release(), d_block_tested.release(), d_totals.release(), d_tile_count.release(), d_tile_block.release(), d_survive.release();
+            h_data.release(), h_counts.release();
+        }
+    } clusters;
     // gv_pool_bind_lod / gv_pool_select_lods: the size column as bit patterns, one word per POOL SLOT like the ids above (the mirror
     // exists only once gv_pool_select_lods has been called for a pool with a size column), the table the base ids index, and the
     // selection made behind the pool's last instance emission
@@ -530,7 +557,7 @@ struct PoolState {
         d_orig.release(), d_inv.release(), d_index_map.release();
         d_blk_lo.release(), d_blk_hi.release(), d_blk_dirty.release(), d_hot.release(), d_seed.release(), d_kept.release(), d_kept_flag.release();
         instances.release(), payload.release(), counts.release(), geometry.release(), commands.release(), lod.release(), bounds.release();
-        delta.release(), occluders.release(), models.release(), previous.release();
+        delta.release(), occluders.release(), models.release(), previous.release(), clusters.release();
     }
 };
 
@@ -579,6 +606,9 @@ struct ViewState {
     uint32_t pool_id = 0, occupancy = 0;
     bool main_pass = false, emitted = false, valid = false;
     float view_proj[16] = {};  // GvView::view_proj of this view's cull (gv_pool_emit_instances multiplies the records' models by it)
+    float planes[6][4] = {};   // ... and the planes that cull extracted from it, plane_count of them (gv_pool_cull_clusters tests with the same)
+    uint32_t plane_count = 0;
+    uint8_t use_hiz = 0;       // GvView::use_hiz of this view's cull: 0, or 1 + the pyramid slot it names (Context::pyramid_of)
     float camera_position[3] = {};  // GvView::camera_position likewise (gv_pool_keep_models keeps it, gv_pool_emit_previous takes the difference)
     // fused cull + emit (launch_cull_emit): look-back words, ticket counter and their running epoch / base
     DeviceBuf<unsigned long long> tile_status;
@@ -960,7 +990,7 @@ struct KernelTimer {
 
 // When a derived result ends. The table, stated once:
 //     views     -> {instances, bounds, previous, merges the pool is a member of}
-//     instances -> {commands, selection}
+//     instances -> {commands, cluster commands, selection}
 // A result ends when what it was made from is replaced. A new derived result is one more line here, under what it is made from.
 // PoolState::delta (gv_pool_view_delta) has NO line: its baseline is history — the set a channel saw at its last call, kept in pool
 // slot numbers so that neither a cull nor a re-order of the mirror concerns it — and its answer is self-contained slot numbers that
@@ -989,6 +1019,7 @@ static inline void end_derived(GvCtx* ctx, PoolState& p, Ends cause)
         [[fallthrough]];  // the instances have ended, and with them:
     case Ends::EmissionReplaced:
         p.commands.views = 0;
+        p.clusters.views = 0;
         [[fallthrough]];
     case Ends::SelectionDropped:
         p.lod.views = 0;

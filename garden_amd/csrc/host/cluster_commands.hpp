@@ -1,0 +1,127 @@
+// cluster_commands.hpp — the cluster commands of the drop-in's mesh systems, built on the device: for a mesh system that has declared
+// its clusters (setClusters) — per geometry id a range of model-space boxes with index ranges — GpuDrawCommands::emit(), given this
+// object through GpuDrawCommands::setClusterCommands, follows each of its command emissions with a cluster cull
+// (gv_pool_cull_clusters): every cluster of every delivered draw tested with the draw's own matrix against the pass's frustum and,
+// where the pass named a pyramid, against that pyramid; one indirect command per surviving cluster, a draw without clusters drawn
+// whole. The per-draw commands stand beside them (a depth pre-pass may still take those). Geometry, command struct, LODs and
+// grouping are the ones declared to GpuDrawCommands: the cluster cull takes the same ids — the selected ones behind a selection.
+//
+// The commands land in caller-owned device memory when setTargets names some, else in the library's own buffer; either way they
+// are fetched into host copies (getBase / getShadow) unless setFetch(false). A renderer submits them as one indirect draw per pass:
+// drawCount from counts[] (packed) or the region size (regions: no count has to be read back).
+//
+// Opt-in: a tick that sets no clusters runs exactly as before. One context only, like the writer: isSupported() is false with ranks.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "gpu_visibility_system.hpp"
+
+namespace garden {
+
+class GpuClusterCommands {
+public:
+    // what one cluster cull left behind
+    struct Emitted {
+        std::vector<uint8_t> commands;  // the command positions, stride bytes each (empty with setFetch(false))
+        std::vector<uint32_t> counts;   // commands per listed view: the light pass, or the culled shadow passes in pass order
+        std::vector<uint32_t> tested;   // clusters tested per listed view (draws drawn whole are not tested)
+        uint32_t stride = 0, region = 0;
+    };
+
+private:
+    GpuVisibilitySystem* system;
+    struct PerSystem {
+        bool enabled = false;  // clusters are bound
+        uint32_t flags = 0, region = 0;
+        void *baseDevice = nullptr, *shadowDevice = nullptr;
+        size_t baseBytes = 0, shadowBytes = 0;
+        Emitted base, shadow;
+    } per[GV_MAX_POOLS];
+    bool fetch = true;
+
+    void check(int rc, const char* what) const
+    {
+        if (rc != GV_OK)
+            throw GardenError(std::string(what) + " failed: " + gv_last_error(system->getContext()));
+    }
+    PerSystem& of(uint32_t p)
+    {
+        if (p >= GV_MAX_POOLS)
+            throw GardenError("GpuClusterCommands: mesh system out of range");
+        return per[p];
+    }
+
+public:
+    explicit GpuClusterCommands(GpuVisibilitySystem* system) : system(system) {}
+
+    bool isSupported() const noexcept { return system->getRankCount() == 1; }
+
+    // the clusters of mesh system p: ranges[g] names the clusters of geometry id g (count 0, or g beyond rangeCount: drawn whole);
+    // both tables are copied (gv_pool_bind_clusters). Both NULL: no clusters, the system's ticks run as before.
+    void setClusters(uint32_t p, const GvClusterRange* ranges, uint32_t rangeCount, const GvCluster* clusters, uint32_t clusterCount)
+    {
+        check(gv_pool_bind_clusters(system->getContext(), p, ranges, rangeCount, clusters, clusterCount), "gv_pool_bind_clusters");
+        of(p).enabled = ranges != nullptr;
+    }
+    // flags: 0 or GV_CLUSTERS_FRUSTUM_ONLY; region: 0 packs the passes' commands, R > 0 gives every pass R positions
+    void setMode(uint32_t p, uint32_t flags, uint32_t region)
+    {
+        of(p).flags = flags;
+        of(p).region = region;
+    }
+    // caller-owned, 16-byte aligned device memory for the two command arrays of mesh system p (NULL: the library's buffer)
+    void setTargets(uint32_t p, void* baseDevice, size_t baseBytes, void* shadowDevice, size_t shadowBytes)
+    {
+        PerSystem& s = of(p);
+        s.baseDevice = baseDevice, s.baseBytes = baseBytes, s.shadowDevice = shadowDevice, s.shadowBytes = shadowBytes;
+    }
+    void setFetch(bool on) noexcept { fetch = on; }
+
+    // GpuDrawCommands::emit calls this behind each of its command emissions for mesh system p (shadow: the one behind the shadow
+    // array) with the stride of the system's command struct; also callable behind an instance emission of one's own
+    void cull(uint32_t p, bool shadow, uint32_t stride)
+    {
+        PerSystem& s = of(p);
+        if (!s.enabled)
+            return;
+        if (!isSupported())
+            throw GardenError("GpuClusterCommands: unsupported with several ranks (the merged draw order is made on the host)");
+        GvCtx* ctx = system->getContext();
+        void* const device = shadow ? s.shadowDevice : s.baseDevice;
+        const size_t bytes = shadow ? s.shadowBytes : s.baseBytes;
+        check(gv_pool_cull_clusters(ctx, p, s.flags, s.region, device, bytes), "gv_pool_cull_clusters");
+        Emitted& out = shadow ? s.shadow : s.base;
+        out.stride = stride;
+        out.region = s.region;
+        out.commands.clear();
+        out.counts.clear();
+        out.tested.clear();
+        if (!fetch)
+            return;
+        uint32_t views = 0, counts[2 * GV_MAX_VIEWS];
+        check(gv_pool_instances_info(ctx, p, &views, nullptr, nullptr), "gv_pool_instances_info");
+        check(gv_pool_cluster_commands_fetch(ctx, p, nullptr, 0, counts, 2 * GV_MAX_VIEWS), "gv_pool_cluster_commands_fetch");
+        out.counts.assign(counts, counts + views);
+        out.tested.assign(counts + views, counts + 2 * views);
+        size_t positions = (size_t)views * s.region;
+        if (!s.region)
+            for (uint32_t c : out.counts)
+                positions += c;
+        const size_t room = device ? bytes / stride : positions;
+        out.commands.resize(std::min(positions, room) * stride);
+        check(gv_pool_cluster_commands_fetch(ctx, p, out.commands.data(), out.commands.size(), counts, 2 * GV_MAX_VIEWS), "gv_pool_cluster_commands_fetch");
+    }
+
+    // device pointers of mesh system p's last cluster cull: the commands and uint32 counts[2 * views]
+    void getDevice(uint32_t p, const void** commands, const void** counts)
+    {
+        check(gv_pool_cluster_commands_device(system->getContext(), p, commands, counts), "gv_pool_cluster_commands_device");
+    }
+    const Emitted& getBase(uint32_t p) { return of(p).base; }
+    const Emitted& getShadow(uint32_t p) { return of(p).shadow; }
+};
+
+}  // namespace garden

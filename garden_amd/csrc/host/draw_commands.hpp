@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "cluster_commands.hpp"
 #include "gpu_visibility_system.hpp"
 
 namespace garden {
@@ -57,6 +58,7 @@ private:
         Emitted base, shadow;
     } per[GV_MAX_POOLS];
     bool fetch = true;
+    GpuClusterCommands* clusters = nullptr;
 
     void check(int rc, const char* what) const
     {
@@ -116,6 +118,9 @@ public:
         s.baseDevice = baseDevice, s.baseBytes = baseBytes, s.shadowDevice = shadowDevice, s.shadowBytes = shadowBytes;
     }
     void setFetch(bool on) noexcept { fetch = on; }
+    // optional: emit() then follows each command emission with the cluster cull of the systems that have declared clusters
+    // (cluster_commands.hpp); NULL: none, every tick runs as before
+    void setClusterCommands(GpuClusterCommands* clusterCommands) noexcept { clusters = clusterCommands; }
     // on: the views of mesh system p are grouped by geometry in front of the writer's emissions (see above). Unsorted systems only:
     // GardenError for a sorted one, here when the last frame already knows the system, otherwise at the write().
     void setGrouping(uint32_t p, bool on)
@@ -160,6 +165,8 @@ public:
         }
         check(gv_pool_emit_draw_commands(ctx, p, s.flags, s.region, shadow ? s.shadowDevice : s.baseDevice, shadow ? s.shadowBytes : s.baseBytes),
               "gv_pool_emit_draw_commands");
+        if (clusters)  // (behind the selection, if any: the cluster cull takes the same ids)
+            clusters->cull(p, shadow, s.stride);
         Emitted& out = shadow ? s.shadow : s.base;
         out.stride = s.stride;
         out.region = s.region;

@@ -120,6 +120,23 @@ class GvGeometry(C.Structure):
 GEOMETRY_DTYPE = np.dtype([("count", np.uint32), ("first", np.uint32), ("vertex_offset", np.int32)])
 
 
+GV_MAX_CLUSTERS = 1 << 22
+GV_MAX_GEOMETRY_CLUSTERS = 65535
+GV_CLUSTERS_FRUSTUM_ONLY = 1
+
+
+class GvCluster(C.Structure):
+    _fields_ = [("box_min", C.c_float * 3), ("first", C.c_uint32), ("box_max", C.c_float * 3), ("count", C.c_uint32)]
+
+
+class GvClusterRange(C.Structure):
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32)]
+
+
+CLUSTER_DTYPE = np.dtype([("box_min", np.float32, (3,)), ("first", np.uint32), ("box_max", np.float32, (3,)), ("count", np.uint32)])
+CLUSTER_RANGE_DTYPE = np.dtype([("first", np.uint32), ("count", np.uint32)])
+
+
 GV_MAX_LOD_LEVELS = 8
 
 
@@ -249,6 +266,7 @@ EXPORTS = [
     "gv_merge_sorted", "gv_merge_device", "gv_merge_fetch",
     "gv_pool_bind_geometry", "gv_pool_set_command_layout", "gv_pool_emit_draw_commands", "gv_pool_draw_commands_device",
     "gv_pool_draw_commands_fetch",
+    "gv_pool_bind_clusters", "gv_pool_cull_clusters", "gv_pool_cluster_commands_device", "gv_pool_cluster_commands_fetch",
     "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
     "gv_pool_group_draws",
     "gv_pool_cull_second_phase",
@@ -389,6 +407,10 @@ def load():
     lib.gv_pool_emit_draw_commands.argtypes = [P, u32, u32, u32, P, sz]
     lib.gv_pool_draw_commands_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_draw_commands_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
+    lib.gv_pool_bind_clusters.argtypes = [P, u32, C.POINTER(GvClusterRange), u32, C.POINTER(GvCluster), u32]
+    lib.gv_pool_cull_clusters.argtypes = [P, u32, u32, u32, P, sz]
+    lib.gv_pool_cluster_commands_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_pool_cluster_commands_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
     lib.gv_pool_bind_lod.argtypes = [P, u32, P, u32, u32, C.POINTER(GvLodGeometry), u32]
     lib.gv_pool_select_lods.argtypes = [P, u32, C.POINTER(C.c_float), u32]
     lib.gv_pool_lods_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
@@ -1055,6 +1077,61 @@ class GpuVisibility:
         if dtype is not None:
             out = out.reshape(-1).view(np.uint8)[:positions * stride].view(np.dtype(dtype))
         return out, counts
+
+    # ---- mesh clusters, culled per draw ----
+    def bind_clusters(self, pool_id, ranges, clusters):
+        """gv_pool_bind_clusters: per geometry id a range (CLUSTER_RANGE_DTYPE, or rows of (first, count)) into the cluster table
+        (CLUSTER_DTYPE: a model-space box, first index relative to the geometry's and index count). Both copied at the call; both
+        None removes the binding."""
+        if ranges is None and clusters is None:
+            self._check(self.lib.gv_pool_bind_clusters(self.ctx, pool_id, None, 0, None, 0))
+            return
+        r = np.asarray(ranges)
+        if r.dtype != CLUSTER_RANGE_DTYPE:  # plain rows of two numbers
+            plain = r.reshape(-1, 2)
+            r = np.zeros(len(plain), CLUSTER_RANGE_DTYPE)
+            r["first"], r["count"] = plain[:, 0], plain[:, 1]
+        r = np.ascontiguousarray(r)
+        c = np.ascontiguousarray(clusters)
+        assert c.dtype == CLUSTER_DTYPE and c.dtype.itemsize == C.sizeof(GvCluster) and r.dtype.itemsize == C.sizeof(GvClusterRange)
+        self._check(self.lib.gv_pool_bind_clusters(self.ctx, pool_id, C.cast(r.ctypes.data, C.POINTER(GvClusterRange)), len(r),
+                                                   C.cast(c.ctypes.data, C.POINTER(GvCluster)), len(c)))
+
+    def cull_clusters(self, pool_id, frustum_only=False, region=0, device=None):
+        """gv_pool_cull_clusters: one indirect command per surviving cluster of every draw of the pool's last instance emission
+        (draws without clusters are drawn whole), on the context's stream. frustum_only: no Hi-Z query even for views that named a
+        pyramid. region: 0 packs the views' commands, R > 0 gives every view R positions. device: None for the library's own
+        buffer, or (device pointer, capacity in bytes) of caller-owned device memory."""
+        ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
+        self._check(self.lib.gv_pool_cull_clusters(self.ctx, pool_id, GV_CLUSTERS_FRUSTUM_ONLY if frustum_only else 0, int(region), ptr, cap))
+        stride = self._command_stride[pool_id]
+        self._cluster_commands = getattr(self, "_cluster_commands", {})
+        self._cluster_commands[pool_id] = (stride, int(region), None if device is None else cap // stride)
+
+    def cluster_commands_device(self, pool_id):
+        """(device pointer of the commands, device pointer of uint32 counts[2 * views]) of the pool's last cluster cull"""
+        commands, counts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_pool_cluster_commands_device(self.ctx, pool_id, C.byref(commands), C.byref(counts)))
+        return commands.value, counts.value
+
+    def cluster_commands(self, pool_id, dtype=None, out=None):
+        """gv_pool_cluster_commands_fetch: waits for the pool's last cluster cull; returns (the command positions — packed: the
+        views' commands back to back; regions: views x region — as uint8 [positions, stride] or viewed as the structured `dtype`,
+        counts[views], tested[views]). Positions a too small caller-owned device target does not hold stay as `out` has them
+        (default zeros)."""
+        stride, region, room = self._cluster_commands[pool_id]
+        views = self.instances_info(pool_id)[0]
+        both = np.zeros(2 * views, np.uint32)
+        cp = both.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self.lib.gv_pool_cluster_commands_fetch(self.ctx, pool_id, None, 0, cp, len(both)))
+        positions = views * region if region else int(both[:views].sum())
+        if out is None:
+            out = np.zeros((positions, stride), np.uint8)
+        assert out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.nbytes >= (positions if room is None else min(positions, room)) * stride
+        self._check(self.lib.gv_pool_cluster_commands_fetch(self.ctx, pool_id, out.ctypes.data, out.nbytes, cp, len(both)))
+        if dtype is not None:
+            out = out.reshape(-1).view(np.uint8)[:positions * stride].view(np.dtype(dtype))
+        return out, both[:views].copy(), both[views:].copy()
 
     # ---- level of detail per draw ----
     def bind_lod(self, pool_id, sizes, table):

@@ -581,6 +581,64 @@ int gv_pool_lods_device(GvCtx* ctx, uint32_t pool_id, const void** draw_geometry
 int gv_pool_lods_fetch(GvCtx* ctx, uint32_t pool_id, uint32_t* draw_geometry, uint32_t capacity, uint32_t* level_counts,
                        uint32_t counts_capacity);
 
+/* ---- mesh clusters, culled per draw on the device ----
+ * The commands above draw a geometry whole, however much of it lies outside the frustum or behind the occluders the pyramid
+ * describes. A pool may bind, per geometry id, a range of CLUSTERS: each a model-space box and a range of the geometry's indices.
+ * gv_pool_cull_clusters tests every cluster of every draw of E with the draw's own matrix and writes one indirect command per
+ * surviving cluster. The reference has no clusters (ModelLOD carries index ranges and nothing smaller), so the rule is this
+ * build's; it holds no new arithmetic: a cluster is tested exactly as the cull tests an entity. With E, v,
+ * k, s_k, g_k, first_k, c_k and G(g) as for the draw commands above (g_k the selected id while the pool holds a LOD selection made
+ * behind E, id[s_k] from the id mirror otherwise; pending id marks are consumed as the command emission consumes them):
+ *   M_k = the record's 12 bakedModel floats as delivered, completed with the row (0, 0, 0, 1). VP_v = the view_proj view v was
+ *   culled with, planes = the cull's plane extraction of VP_v; camera_offset plays no part, as in the entity test.
+ *   range_k = ranges[g_k] if g_k < range_count, else {0, 0}.
+ *   A draw with g_k >= table_count (the void geometry) or c_k == 0 emits nothing.
+ *   A draw whose range_k.count == 0 is DRAWN WHOLE: one command exactly as per-draw mode writes it, untested (the draw was culled
+ *   already; sprites beside clustered models keep working).
+ *   Otherwise, for j = 0 .. range_k.count - 1, cl = clusters[range_k.first + j]: cluster j SURVIVES iff its eight corners
+ *   (cl's box through M_k, the cull's packed-fp32 corner form) are not all behind one plane and — unless GV_CLUSTERS_FRUSTUM_ONLY
+ *   is set or view v named no pyramid (use_hiz == 0) — the cull's Hi-Z query of those corners against the pyramid view v names, as
+ *   that pyramid stands when the call is issued, does not find them occluded. A NaN box behaves as it does for an entity.
+ *   A surviving cluster emits {count cl.count, instance_count c_k, first G(g_k).first + cl.first (uint32 add), vertex_offset
+ *   G(g_k).vertex_offset, first_instance first_k, draw k} in the pool's GvCommandLayout.
+ * Order: by view, then draw k ascending, then j ascending; reproducible run to run. counts[v] = commands of view v, always the
+ * true count; counts[m + v] = clusters tested for view v (whole draws are not tested). Placement (region_commands), zero padding,
+ * "every byte of the stride" and "positions at or beyond capacity are not written" as for gv_pool_emit_draw_commands. */
+#define GV_MAX_CLUSTERS          (1u << 22)   /* entries of a pool's cluster table (128 MB) */
+#define GV_MAX_GEOMETRY_CLUSTERS 65535u       /* clusters of one geometry */
+typedef struct GvCluster {      /* 32 bytes */
+    float box_min[3]; uint32_t first;   /* model-space box; first index RELATIVE to G(g).first */
+    float box_max[3]; uint32_t count;   /* index count of the cluster */
+} GvCluster;
+typedef struct GvClusterRange { uint32_t first, count; } GvClusterRange;  /* into the cluster table, indexed by geometry id g */
+#define GV_CLUSTERS_FRUSTUM_ONLY 1u
+/* Both tables are copied at the call (uploaded bytes count in GvStats::upload_bytes); NULL / 0 for both removes the binding. Either
+ * way a cluster result the pool holds ends. Box values are not checked. GV_E_ARG: a pool out of range, one table without the other,
+ * range_count above GV_MAX_GEOMETRIES or cluster_count above GV_MAX_CLUSTERS, a range with count > GV_MAX_GEOMETRY_CLUSTERS or
+ * first + count > cluster_count (64-bit sum). */
+int gv_pool_bind_clusters(GvCtx* ctx, uint32_t pool_id, const GvClusterRange* ranges, uint32_t range_count, const GvCluster* clusters,
+                          uint32_t cluster_count);
+/* The cluster commands of the views of E, in E's order. Asynchronous on gv_stream(ctx), the host reads no count; counts as a read
+ * (recorded culls and deferred sorts are launched first); changes no cull result, no instance data and no per-draw command buffer
+ * (buffers of its own: both kinds of commands coexist). FIVE kernel launches whatever the data holds — candidate counts per draw,
+ * their scan, the test, the survivors' scan, the writer — counted under GvStats::launches[GV_K_EMIT]. The scratch is sized from
+ * the host's bound of the candidates, B = the sum of the listed views' occupancies x max(1, the largest bound range count): 8 bytes
+ * per 256 candidates and one bit per candidate. dst_device NULL: a library-owned buffer, grown and never shrunk, sized for B (with
+ * regions: m * R) commands; where that exceeds 2 GiB the call is refused and asks for a caller-owned target. A non-NULL dst_device
+ * is caller-owned and 16-byte aligned. The result ends at the pool's next gv_cull, second phase, instance emission or
+ * gv_pool_bind_clusters.
+ * GV_E_ARG: a pool out of range or not bound, unknown flag bits, a misaligned dst_device, m * R beyond 32 bits. GV_E_STATE: no
+ * cluster binding, no command layout, no geometry bound, no emission since the pool's last gv_cull, an id column whose occupancy is
+ * below a listed view's, a view that names a pyramid that is not built (without GV_CLUSTERS_FRUSTUM_ONLY), B beyond 2^32 - 1, a
+ * library-owned target beyond 2 GiB. A refused call changes nothing. */
+int gv_pool_cull_clusters(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes);
+/* Device pointers of the pool's last cluster cull, written in stream order: the commands and uint32 counts[2 * m]. */
+int gv_pool_cluster_commands_device(GvCtx* ctx, uint32_t pool_id, const void** commands, const void** counts);
+/* Waits for the pool's last cluster cull; copies counts[0 .. 2 * m) (counts_capacity at least that) and — dst_host non-NULL — the
+ * command positions the target holds (packed: min(sum of counts[v], capacity); regions: min(m * R, capacity)), whole commands.
+ * GV_E_ARG when either array is too small: nothing is written. */
+int gv_pool_cluster_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* counts, uint32_t counts_capacity);
+
 /* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
  * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
  * the record's componentOffset. A pool may bind those bytes (its PAYLOAD: up to GV_MAX_PAYLOAD_FIELDS fields, GV_MAX_PAYLOAD_BYTES

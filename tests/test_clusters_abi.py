@@ -1,0 +1,71 @@
+"""gv_pool_cull_clusters and its companions on the CPU tier: the header declares the four entry points and the two structs with the
+stated signatures and sizes (a compile check against the header itself), GV_ABI_VERSION is still 4 (the change is additive), the
+library exports the symbols, garden_amd/lib.py binds the same signatures, and a NULL context gives GV_E_ARG."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P, U32, SZ = C.c_void_p, C.c_uint32, C.c_size_t
+
+COMPILE_CHECK = r"""
+#include <stddef.h>
+#include "garden_vis.h"
+_Static_assert(sizeof(GvCluster) == 32, "GvCluster is 32 bytes");
+_Static_assert(offsetof(GvCluster, box_min) == 0 && offsetof(GvCluster, first) == 12 && offsetof(GvCluster, box_max) == 16 &&
+               offsetof(GvCluster, count) == 28, "a box corner and a word per 16-byte piece");
+_Static_assert(sizeof(GvClusterRange) == 8 && offsetof(GvClusterRange, count) == 4, "GvClusterRange is {first, count}");
+_Static_assert(GV_MAX_CLUSTERS == (1u << 22) && GV_MAX_GEOMETRY_CLUSTERS == 65535u && GV_CLUSTERS_FRUSTUM_ONLY == 1u, "constants");
+_Static_assert(GV_ABI_VERSION == 4u, "additions only");
+int (*const bind_clusters)(GvCtx*, uint32_t, const GvClusterRange*, uint32_t, const GvCluster*, uint32_t) = gv_pool_bind_clusters;
+int (*const cull_clusters)(GvCtx*, uint32_t, uint32_t, uint32_t, void*, size_t) = gv_pool_cull_clusters;
+int (*const commands_device)(GvCtx*, uint32_t, const void**, const void**) = gv_pool_cluster_commands_device;
+int (*const commands_fetch)(GvCtx*, uint32_t, void*, size_t, uint32_t*, uint32_t) = gv_pool_cluster_commands_fetch;
+"""
+
+
+def signatures():
+    from garden_amd import lib
+    return {
+        "gv_pool_bind_clusters": [P, U32, C.POINTER(lib.GvClusterRange), U32, C.POINTER(lib.GvCluster), U32],
+        "gv_pool_cull_clusters": [P, U32, U32, U32, P, SZ],
+        "gv_pool_cluster_commands_device": [P, U32, C.POINTER(P), C.POINTER(P)],
+        "gv_pool_cluster_commands_fetch": [P, U32, P, SZ, C.POINTER(U32), U32],
+    }
+
+
+def test_header_declares_the_functions_and_structs_as_stated(tmp_path):
+    src = tmp_path / "clusters_abi.c"
+    src.write_text(COMPILE_CHECK)
+    build = subprocess.run(["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
+                            str(tmp_path / "clusters_abi.o")], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-3000:]
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "garden_vis.h")).read(), flags=re.S)
+    assert re.search(r"#define GV_ABI_VERSION 4u?\b", text)
+
+
+def test_library_exports_them_and_lib_py_binds_the_same_signatures():
+    from garden_amd import lib
+    for name in signatures():
+        assert name in lib.EXPORTS, name
+    assert lib.GV_MAX_CLUSTERS == 1 << 22 and lib.GV_MAX_GEOMETRY_CLUSTERS == 65535 and lib.GV_CLUSTERS_FRUSTUM_ONLY == 1
+    assert C.sizeof(lib.GvCluster) == 32 and lib.CLUSTER_DTYPE.itemsize == 32 and lib.GvCluster.first.offset == 12 and lib.GvCluster.count.offset == 28
+    assert C.sizeof(lib.GvClusterRange) == 8 and lib.CLUSTER_RANGE_DTYPE.itemsize == 8
+    for method in ("bind_clusters", "cull_clusters", "cluster_commands_device", "cluster_commands"):
+        assert callable(getattr(lib.GpuVisibility, method)), method
+    handle = lib.load()
+    assert handle.gv_abi_version() == 4
+    for name, argtypes in signatures().items():
+        assert list(getattr(handle, name).argtypes) == argtypes, name
+
+
+def test_a_null_context_gives_gv_e_arg():
+    from garden_amd import lib
+    handle = lib.load()
+    a, b = C.c_void_p(), C.c_void_p()
+    counts = (C.c_uint32 * 16)()
+    assert handle.gv_pool_bind_clusters(None, 0, None, 0, None, 0) == lib.GV_E_ARG
+    assert handle.gv_pool_cull_clusters(None, 0, 0, 0, None, 0) == lib.GV_E_ARG
+    assert handle.gv_pool_cluster_commands_device(None, 0, C.byref(a), C.byref(b)) == lib.GV_E_ARG
+    assert handle.gv_pool_cluster_commands_fetch(None, 0, None, 0, counts, 16) == lib.GV_E_ARG
