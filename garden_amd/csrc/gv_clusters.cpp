@@ -42,6 +42,7 @@ int gv_pool_bind_clusters(GvCtx* ctx, uint32_t pool_id, const GvClusterRange* ra
     GV_HIP(ctx, hipSetDevice(ctx->device));
     GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading the tables)
     K.views = 0;  // a result made from the tables as they were ends
+    K.second.views = 0;
     K.bound = false;
     K.range_count = K.cluster_count = K.max_range = 0;
     if (none) {
@@ -179,6 +180,12 @@ int gv_pool_cull_clusters(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_test(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_survivors(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_write(launch, ctx->stream));
+    K.second.views = 0;  // the bits and prefixes a second phase read are replaced
+    K.launch = launch;   // gv_pool_cull_clusters_second_phase tests with the same arguments
+    K.candidate_bound = bound;
+    for (uint32_t k = 0; k < m; k++)
+        K.pyramid[k] = Context::pyramid_of(view_of(ctx, pool_id, I.listed[k])->use_hiz);
+    K.rebound = false;
     K.target = launch.dst;
     K.capacity = launch.capacity;
     K.views = m;

@@ -30,8 +30,12 @@
 // Rank + scatter as gv_sort: no workgroup waits for another, no atomics, integer adds only — the order (view, draw, cluster) and
 // every byte are the same run to run. Whatever an id, a range or a count holds, the tables are read inside their bounds: j is below
 // the range's count by construction, a range lies inside the cluster table by the bind's check, T is at most the host's bound.
+//
+// Behind them, sharing their device helpers: the five kernels of gv_pool_cull_clusters_second_phase (cluster_second_*, described
+// where they stand), which read what the five above left on the device and write none of it.
 #include "gv_device.hpp"
 #include "gv_cluster_kernels.hpp"
+#include "gv_cluster_second_kernels.hpp"
 
 namespace gv {
 
@@ -433,6 +437,283 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_write_kernel(const Clus
     }
 }
 
+// ---- the second phase (gv_pool_cull_clusters_second_phase) ----
+// A candidate of K1 is PENDING iff K1 tested it, did not keep it and queried a pyramid for its view. Whole draws are kept untested,
+// so the pending candidates are the clear bits of K1's ballot words inside the candidate ranges of the queried views: no search is
+// needed to know them. The five launches mirror K1's, one level up — a PENDING TILE is kClusterTile pending candidates in order:
+//
+//   cluster_second_count_kernel   one lane per CANDIDATE tile, grid-stride: the popcount of its four pending words.
+//   cluster_second_scan_kernel    <0>: those counts become their own exclusive prefix; P, the pending in front of every view and with
+//                                 them counts[m + v]; per pending tile the candidate tile that holds its first pending (as
+//                                 tile_block). <1>: the pending tiles' survivor counts likewise, and counts[v].
+//   cluster_second_test_kernel    one lane per PENDING candidate (dense: where phase 1 kept 99 % a walk over its candidates would
+//                                 run the Hi-Z query with a lane or two per wave). Pending p -> its candidate tile, searched between
+//                                 two entries of that table; the (p - prefix)-th set bit of the tile's pending words is c; then K1's
+//                                 locate and K1's test, unchanged, against the pyramids in this launch's arguments.
+//   cluster_second_write_kernel   the same walk; a survivor's rank is its position; the padding with regions.
+//
+// Nothing K1 wrote is written; no workgroup waits for another, no atomics, integer ranks only.
+static_assert(offsetof(ClusterSecondLaunch, k) == 0, "the per-view arguments are read at K1's offsets");
+
+// the pending bits of ballot word w of candidate tile `tile` (tile below the number of tiles of T)
+__device__ __forceinline__ unsigned long long pending_word(const ClusterLaunch& a, uint32_t tile, uint32_t w)
+{
+    const uint64_t c0 = (uint64_t)tile * kClusterTile + w * 64u;
+    unsigned long long in = 0ull;  // the word's candidates that lie in a queried view (whose end is at most T)
+    for (uint32_t v = 0; v < a.views; v++) {
+        if (!((a.hiz_views >> v) & 1u))
+            continue;
+        const uint64_t first = a.totals[kClusterCandidateStart + v], end = a.totals[kClusterCandidateStart + v + 1u];
+        const uint64_t from = first > c0 ? first : c0, to = end < c0 + 64u ? end : c0 + 64u;
+        if (from >= to)
+            continue;
+        const unsigned long long below_to = to - c0 == 64u ? ~0ull : (1ull << (to - c0)) - 1ull;
+        in |= below_to & ~((1ull << (from - c0)) - 1ull);
+    }
+    return in ? ~a.survive[(size_t)tile * 4u + w] & in : 0ull;
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_second_count_kernel(const ClusterSecondLaunch s)
+{
+    const ClusterLaunch& a = s.k;
+    const uint32_t total = a.totals[kClusterTotalCandidates];
+    const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+    for (uint64_t tile = (uint64_t)blockIdx.x * kClusterBlock + threadIdx.x; tile < tiles; tile += (uint64_t)gridDim.x * kClusterBlock) {
+        uint32_t n = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; w++)
+            n += (uint32_t)__popcll(pending_word(a, (uint32_t)tile, w));
+        s.pending_count[tile] = n;
+    }
+}
+
+// pending in front of candidate c (c <= T): the prefix of its tile and the pending bits below it; `all` for c == T
+__device__ __forceinline__ uint32_t pending_before(const ClusterSecondLaunch& s, uint32_t c, uint32_t total, uint32_t all)
+{
+    if (c >= total)
+        return all;
+    const uint32_t tile = c / kClusterTile, in = c % kClusterTile;
+    uint32_t n = s.pending_count[tile];  // (scanned: the pending in front of the tile)
+    for (uint32_t w = 0; w < in / 64u; w++)
+        n += (uint32_t)__popcll(pending_word(s.k, tile, w));
+    if (in % 64u)
+        n += (uint32_t)__popcll(pending_word(s.k, tile, in / 64u) & ((1ull << (in % 64u)) - 1ull));
+    return n;
+}
+// second-phase survivors in front of pending p (p <= P), likewise
+__device__ __forceinline__ uint32_t kept_before(const ClusterSecondLaunch& s, uint32_t p, uint32_t pending, uint32_t all)
+{
+    if (p >= pending)
+        return all;
+    const uint32_t q = p / kClusterTile, in = p % kClusterTile;
+    uint32_t n = s.kept_count[q];
+    for (uint32_t w = 0; w < in / 64u; w++)
+        n += (uint32_t)__popcll(s.kept[(size_t)q * 4u + w]);
+    if (in % 64u)
+        n += (uint32_t)__popcll(s.kept[(size_t)q * 4u + in / 64u] & ((1ull << (in % 64u)) - 1ull));
+    return n;
+}
+
+template <uint32_t kStage>
+__global__ __launch_bounds__(kClusterScanBlock) void cluster_second_scan_kernel(const ClusterSecondLaunch s)
+{
+    __shared__ uint32_t wave_part[kClusterScanBlock / 64u];
+    __shared__ uint32_t turn_sum;
+    __shared__ uint32_t view_start[kMaxInstanceViews + 1];
+    const ClusterLaunch& a = s.k;
+    if constexpr (kStage == 0) {
+        const uint32_t total = a.totals[kClusterTotalCandidates];
+        const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+        const uint32_t pending = scan_table(s.pending_count, tiles, wave_part, &turn_sum);
+        if (threadIdx.x == 0)
+            s.totals[kSecondTotalPending] = pending;
+        if (threadIdx.x <= a.views)
+            view_start[threadIdx.x] = pending_before(s, a.totals[kClusterCandidateStart + threadIdx.x], total, pending);
+        __syncthreads();
+        if (threadIdx.x <= a.views)
+            s.totals[kSecondPendingStart + threadIdx.x] = view_start[threadIdx.x];
+        if (threadIdx.x < a.views)
+            a.counts[a.views + threadIdx.x] = view_start[threadIdx.x + 1u] - view_start[threadIdx.x];
+        // where the search of a pending tile's candidates begins: every pending tile's first pending lies in exactly one candidate
+        // tile that has pending, and that tile writes the entry
+        for (uint32_t t = threadIdx.x; t < tiles; t += kClusterScanBlock) {
+            const uint32_t from = s.pending_count[t], end = t + 1u < tiles ? s.pending_count[t + 1u] : pending;
+            if (end == from)
+                continue;
+            const uint32_t last = (end - 1u) / kClusterTile;
+            for (uint32_t q = from / kClusterTile + (from % kClusterTile ? 1u : 0u); q <= last; q++)
+                s.pending_tile[q] = t;
+        }
+    } else {
+        const uint32_t pending = s.totals[kSecondTotalPending];
+        const uint32_t ptiles = pending / kClusterTile + (pending % kClusterTile ? 1u : 0u);
+        const uint32_t all = scan_table(s.kept_count, ptiles, wave_part, &turn_sum);
+        if (threadIdx.x <= a.views)
+            view_start[threadIdx.x] = kept_before(s, s.totals[kSecondPendingStart + threadIdx.x], pending, all);
+        __syncthreads();
+        if (threadIdx.x <= a.views)
+            s.totals[kSecondSurvivorStart + threadIdx.x] = view_start[threadIdx.x];
+        if (threadIdx.x < a.views)
+            a.counts[threadIdx.x] = view_start[threadIdx.x + 1u] - view_start[threadIdx.x];
+    }
+}
+
+// pending p < P of pending tile q -> its candidate tile and the candidate c: the largest candidate tile whose prefix is <= p,
+// searched between the tile of q's first pending and that of the next pending tile's; then the (p - prefix)-th set bit of its words
+__device__ __forceinline__ void find_pending(const ClusterSecondLaunch& s, uint32_t p, uint32_t q, uint32_t ptiles, uint32_t tiles, uint32_t& tile,
+                                             uint32_t& c)
+{
+    uint32_t lo = s.pending_tile[q], hi = (q + 1u < ptiles ? s.pending_tile[q + 1u] : tiles - 1u) + 1u;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (s.pending_count[mid] <= p)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    tile = lo;
+    uint32_t rest = p - s.pending_count[lo];  // (below the tile's pending count: the next tile's prefix is above p)
+    uint32_t in = 0;
+    bool found = false;
+#pragma unroll
+    for (uint32_t w = 0; w < 4u; w++) {
+        const unsigned long long word = pending_word(s.k, lo, w);
+        const uint32_t n = (uint32_t)__popcll(word);
+        if (!found && rest < n) {
+            uint32_t at = 0;  // the rest-th set bit: halve the word six times
+#pragma unroll
+            for (uint32_t width = 32; width >= 1u; width >>= 1) {
+                const uint32_t below = (uint32_t)__popcll((word >> at) & ((1ull << width) - 1ull));
+                if (rest >= below) {
+                    rest -= below;
+                    at += width;
+                }
+            }
+            in = w * 64u + at;
+            found = true;
+        }
+        rest -= found ? 0u : n;
+    }
+    c = lo * kClusterTile + in;
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_second_test_kernel(const ClusterSecondLaunch s)
+{
+    __shared__ uint32_t wave_count[kClusterBlock / 64u];
+    const ClusterLaunch& a = s.k;
+    ConstClusterArgs base = (ConstClusterArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(base));  // (opaque: nothing read through it is moved out of the loops)
+    const uint32_t total = a.totals[kClusterTotalCandidates];
+    const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+    const uint32_t pending = s.totals[kSecondTotalPending];
+    const uint32_t ptiles = pending / kClusterTile + (pending % kClusterTile ? 1u : 0u);
+    const uint32_t blocks = a.first_block[a.views];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t q = blockIdx.x; q < ptiles; q += gridDim.x) {
+        const uint32_t p = q * kClusterTile + threadIdx.x;
+        bool tested = false, survives = false;
+        uint32_t v = 0;
+        Corners corners;
+        if (p < pending) {
+            uint32_t tile, c, block, at, j;
+            find_pending(s, p, q, ptiles, tiles, tile, c);
+            locate(a, c, tile, tiles, blocks, block, at, j);
+            v = view_of_block(a.first_block, a.views, block);
+            const ClusterRange range = range_of(a, a.draw_geometry[at]);
+            if (range.count) {  // (a pending candidate is a cluster: K1 tested it)
+                tested = true;
+                const float4* const cl = a.clusters + ((size_t)range.first + j) * 2u;
+                const float4 lo = cl[0], hi = cl[1];
+                const ViewPick view = pick_view(a, v);
+                const uint32_t k = at - view.first_block * kClusterBlock;
+                const float4* const rows = reinterpret_cast<const float4*>(view.model) + (size_t)k * 3u;
+                const float4 w0 = rows[0], w1 = rows[1], w2 = rows[2];
+                aabb_corners(rows_model(w0, w1, w2), lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, corners);
+            }
+        }
+#pragma unroll 1
+        for (uint32_t u = 0; u < a.views; u++) {
+            const bool mine = tested && v == u;
+            if (!__any(mine))
+                continue;  // (wave-uniform)
+            const ClusterPlanes pl = view_planes_of(base, u);
+            const uint32_t plane_count = base->plane_count[u];
+            const bool query = (a.hiz_views >> u) & 1u;  // (set: only a queried view has pending candidates)
+            if (mine) {
+                bool visible = !behind_frustum(corners, pl.planes, plane_count);
+                if (query && visible) {
+                    const HizDevice hz = view_hiz_of(base, u);
+                    const ClusterMatrix vm = view_matrix_of(base, u);
+                    visible = !hiz_occluded(hz, vm.m, corners);
+                }
+                survives = visible;
+            }
+        }
+        const unsigned long long word = __ballot(survives);
+        if (lane == 0u) {
+            s.kept[(size_t)q * 4u + wave] = word;
+            wave_count[wave] = (uint32_t)__popcll(word);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            s.kept_count[q] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+        __syncthreads();  // (the next pending tile rewrites the wave counts)
+    }
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_second_write_kernel(const ClusterSecondLaunch s)
+{
+    const ClusterLaunch& a = s.k;
+    const uint32_t total = a.totals[kClusterTotalCandidates];
+    const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+    const uint32_t pending = s.totals[kSecondTotalPending];
+    const uint32_t ptiles = pending / kClusterTile + (pending % kClusterTile ? 1u : 0u);
+    const uint32_t blocks = a.first_block[a.views];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t q = blockIdx.x; q < ptiles; q += gridDim.x) {
+        const unsigned long long* const words = s.kept + (size_t)q * 4u;
+        const unsigned long long word = words[wave];
+        if (!((word >> lane) & 1ull))
+            continue;
+        uint32_t rank = s.kept_count[q] + (uint32_t)__popcll(word & ((1ull << lane) - 1ull));  // (scanned: survivors in front of the pending tile)
+        for (uint32_t w = 0; w < wave; w++)
+            rank += (uint32_t)__popcll(words[w]);
+        uint32_t tile, c, block, at, j;
+        find_pending(s, q * kClusterTile + threadIdx.x, q, ptiles, tiles, tile, c);
+        locate(a, c, tile, tiles, blocks, block, at, j);
+        const uint32_t v = view_of_block(a.first_block, a.views, block);
+        uint32_t position = rank;
+        if (a.region) {
+            const uint32_t in_view = rank - s.totals[kSecondSurvivorStart + v];
+            if (in_view >= a.region)
+                continue;
+            position = v * a.region + in_view;
+        }
+        if (position >= a.capacity)
+            continue;
+        const ViewPick view = pick_view(a, v);
+        const uint32_t k = at - view.first_block * kClusterBlock;
+        const uint32_t g = a.draw_geometry[at];  // (the id K1 kept; below table_count and ranged: the draw had a tested cluster)
+        const CommandGeometry geometry = a.table[g];
+        const ClusterRange range = range_of(a, g);
+        const float4* const cl = a.clusters + ((size_t)range.first + j) * 2u;
+        const uint32_t from = first_of_draw(a, v, k);
+        put_command(a, position, __float_as_uint(cl[1].w), instances_of_draw(a, v, k, *view.count, from), geometry.first + __float_as_uint(cl[0].w), from,
+                    (uint32_t)geometry.vertex_offset, k);
+    }
+    if (a.region) {  // the all-zero padding positions C_v <= j < R of every view
+        const uint64_t positions = (uint64_t)a.views * a.region;
+        for (uint64_t p = (uint64_t)blockIdx.x * kClusterBlock + threadIdx.x; p < positions && p < a.capacity; p += (uint64_t)gridDim.x * kClusterBlock) {
+            const uint32_t v = (uint32_t)(p / a.region), in_view = (uint32_t)(p % a.region);
+            if (in_view < a.counts[v])
+                continue;
+            uint32_t* const to = reinterpret_cast<uint32_t*>(a.dst + (size_t)p * a.stride);
+            for (uint32_t w = 0; w < a.stride / 4u; w++)
+                to[w] = 0u;
+        }
+    }
+}
+
 // the fixed grid of the test and write launches: kClusterGridPerCu workgroups per compute unit of the current device
 uint32_t walk_grid()
 {
@@ -471,6 +752,36 @@ hipError_t launch_cluster_scan_survivors(const ClusterLaunch& launch, hipStream_
 hipError_t launch_cluster_write(const ClusterLaunch& launch, hipStream_t stream)
 {
     hipLaunchKernelGGL(cluster_write_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_second_count(const ClusterSecondLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_second_count_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_second_scan_pending(const ClusterSecondLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_second_scan_kernel<0>, dim3(1), dim3(kClusterScanBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_second_test(const ClusterSecondLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_second_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_second_scan_survivors(const ClusterSecondLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_second_scan_kernel<1>, dim3(1), dim3(kClusterScanBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_second_write(const ClusterSecondLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_second_write_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
     return hipGetLastError();
 }
 

@@ -30,6 +30,7 @@ int gv_pool_bind_geometry(GvCtx* ctx, uint32_t pool_id, const void* ids, uint32_
     GV_HIP(ctx, hipSetDevice(ctx->device));
     GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading the table or the mirror)
     G.reset();
+    ctx->pools[pool_id].clusters.rebound = true;  // a cluster result's kept ids index the table as it was: no second phase of it
     G.ids = Column{static_cast<const uint8_t*>(ids), ids ? stride : 0};
     G.width = ids ? width : 0;
     G.occupancy = ids ? occupancy : 0;
@@ -76,6 +77,7 @@ int gv_pool_set_command_layout(GvCtx* ctx, uint32_t pool_id, const GvCommandLayo
                              L.first, L.first_instance, L.vertex_offset, L.draw, GV_NONE);
     }
     ctx->pools[pool_id].commands.layout = L;  // read by the next command emission
+    ctx->pools[pool_id].clusters.rebound = true;  // (a cluster result was written in the layout as it was: no second phase of it)
     return GV_OK;
 }
 

@@ -28,6 +28,7 @@
 #include "gv_receiver_kernels.hpp"
 #include "gv_previous_kernels.hpp"
 #include "gv_cluster_kernels.hpp"
+#include "gv_cluster_second_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -381,11 +382,36 @@ struct PoolState {
         uint8_t* target = nullptr;         // d_data.ptr or the caller's device memory
         uint32_t capacity = 0;             // command positions the target holds
         uint32_t views = 0, stride = 0, region = 0;
+        // what the second phase needs of the last call K1 beside what K1 left on the device: its arguments as launched, the host's
+        // bound of its candidates, the pyramid every queried view named, and whether the geometry table or the command layout was
+        // set again since (K1's kept ids may lie outside a new table)
+        ClusterLaunch launch{};
+        uint64_t candidate_bound = 0;
+        uint32_t pyramid[kMaxInstanceViews] = {};
+        bool rebound = false;
+        // gv_pool_cull_clusters_second_phase (gv_clusters_second.cpp): the last call's commands and scratch, buffers of their own —
+        // nothing of K1 above is written. views 0: none since K1 (it ends wherever K1 ends, and at a new K1)
+        struct Second {
+            DeviceBuf<uint8_t> d_data;     // the library-owned target
+            DeviceBuf<uint32_t> d_counts;  // [2 * GV_MAX_VIEWS]: commands per view, then pending clusters re-tested per view
+            DeviceBuf<uint32_t> d_pending_count, d_pending_tile, d_kept_count, d_totals;  // scratch of a call
+            DeviceBuf<unsigned long long> d_kept;
+            PinnedBuf<uint8_t> h_data;     // staging of gv_pool_cluster_second_commands_fetch
+            PinnedBuf<uint32_t> h_counts;
+            uint8_t* target = nullptr;
+            uint32_t capacity = 0;
+            uint32_t views = 0, stride = 0, region = 0;
+            void release()
+            {
+                d_data.release(), d_counts.release(), d_pending_count.release(), d_pending_tile.release(), d_kept_count.release(), d_totals.release();
+                d_kept.release(), h_data.release(), h_counts.release();
+            }
+        } second;
         void release()
         {
             d_ranges.release(), d_clusters.release(), d_data.release(), d_counts.release(), d_draw_geometry.release(), d_draw_local.release();
             d_block_total.release(), d_block_tested.release(), d_totals.release(), d_tile_count.release(), d_tile_block.release(), d_survive.release();
-            h_data.release(), h_counts.release();
+            h_data.release(), h_counts.release(), second.release();
         }
     } clusters;
     // gv_pool_bind_lod / gv_pool_select_lods: the size column as bit patterns, one word per POOL SLOT like the ids above (the mirror
@@ -991,6 +1017,7 @@ struct KernelTimer {
 // When a derived result ends. The table, stated once:
 //     views     -> {instances, bounds, previous, merges the pool is a member of}
 //     instances -> {commands, cluster commands, selection}
+//     cluster commands -> {second-phase cluster commands}   (also ended by gv_pool_bind_clusters and a new gv_pool_cull_clusters)
 // A result ends when what it was made from is replaced. A new derived result is one more line here, under what it is made from.
 // PoolState::delta (gv_pool_view_delta) has NO line: its baseline is history — the set a channel saw at its last call, kept in pool
 // slot numbers so that neither a cull nor a re-order of the mirror concerns it — and its answer is self-contained slot numbers that
@@ -1020,6 +1047,7 @@ static inline void end_derived(GvCtx* ctx, PoolState& p, Ends cause)
     case Ends::EmissionReplaced:
         p.commands.views = 0;
         p.clusters.views = 0;
+        p.clusters.second.views = 0;  // the second phase of the cluster cull reads what that cull left
         [[fallthrough]];
     case Ends::SelectionDropped:
         p.lod.views = 0;

@@ -10,6 +10,9 @@
 // are fetched into host copies (getBase / getShadow) unless setFetch(false). A renderer submits them as one indirect draw per pass:
 // drawCount from counts[] (packed) or the region size (regions: no count has to be read back).
 //
+// In a two-phase frame cullSecond(p, ...) re-tests what a system's last cluster cull left out against the rebuilt pyramid
+// (gv_pool_cull_clusters_second_phase), into host copies of its own (getBaseSecond / getShadowSecond).
+//
 // Opt-in: a tick that sets no clusters runs exactly as before. One context only, like the writer: isSupported() is false with ranks.
 #pragma once
 #include <algorithm>
@@ -38,7 +41,9 @@ private:
         uint32_t flags = 0, region = 0;
         void *baseDevice = nullptr, *shadowDevice = nullptr;
         size_t baseBytes = 0, shadowBytes = 0;
-        Emitted base, shadow;
+        void *baseSecondDevice = nullptr, *shadowSecondDevice = nullptr;
+        size_t baseSecondBytes = 0, shadowSecondBytes = 0;
+        Emitted base, shadow, baseSecond, shadowSecond;
     } per[GV_MAX_POOLS];
     bool fetch = true;
 
@@ -115,13 +120,66 @@ public:
         check(gv_pool_cluster_commands_fetch(ctx, p, out.commands.data(), out.commands.size(), counts, 2 * GV_MAX_VIEWS), "gv_pool_cluster_commands_fetch");
     }
 
+    // The second phase of mesh system p's LAST cluster cull (gv_pool_cull_clusters_second_phase), for a renderer that has drawn that
+    // cull's commands and handed the new depth to GpuVisibilitySystem::setHizDepth: the clusters the cull tested and did not keep,
+    // where its pass queried a pyramid, tested again against the pyramid as it stands now — draw the survivors behind the first
+    // list. shadow: the last cull was the one behind the shadow array (it picks the targets of setSecondTargets and the host copy).
+    // Nothing of the first cull changes. The newly visible DRAWS of GpuSecondPhase::run are an ordinary view: emit it and call
+    // cull(). Opt-in: a tick that does not call this runs as before. Emitted::tested holds the pending clusters re-tested per view.
+    void cullSecond(uint32_t p, bool shadow, uint32_t stride)
+    {
+        PerSystem& s = of(p);
+        if (!s.enabled)
+            return;
+        if (!isSupported())
+            throw GardenError("GpuClusterCommands: unsupported with several ranks (the merged draw order is made on the host)");
+        GvCtx* ctx = system->getContext();
+        void* const device = shadow ? s.shadowSecondDevice : s.baseSecondDevice;
+        const size_t bytes = shadow ? s.shadowSecondBytes : s.baseSecondBytes;
+        check(gv_pool_cull_clusters_second_phase(ctx, p, 0, s.region, device, bytes), "gv_pool_cull_clusters_second_phase");
+        Emitted& out = shadow ? s.shadowSecond : s.baseSecond;
+        out.stride = stride;
+        out.region = s.region;
+        out.commands.clear();
+        out.counts.clear();
+        out.tested.clear();
+        if (!fetch)
+            return;
+        uint32_t views = 0, counts[2 * GV_MAX_VIEWS];
+        check(gv_pool_instances_info(ctx, p, &views, nullptr, nullptr), "gv_pool_instances_info");
+        check(gv_pool_cluster_second_commands_fetch(ctx, p, nullptr, 0, counts, 2 * GV_MAX_VIEWS), "gv_pool_cluster_second_commands_fetch");
+        out.counts.assign(counts, counts + views);
+        out.tested.assign(counts + views, counts + 2 * views);
+        size_t positions = (size_t)views * s.region;
+        if (!s.region)
+            for (uint32_t c : out.counts)
+                positions += c;
+        const size_t room = device ? bytes / stride : positions;
+        out.commands.resize(std::min(positions, room) * stride);
+        check(gv_pool_cluster_second_commands_fetch(ctx, p, out.commands.data(), out.commands.size(), counts, 2 * GV_MAX_VIEWS),
+              "gv_pool_cluster_second_commands_fetch");
+    }
+    // caller-owned, 16-byte aligned device memory for the second phase's two command arrays (NULL: the library's buffer)
+    void setSecondTargets(uint32_t p, void* baseDevice, size_t baseBytes, void* shadowDevice, size_t shadowBytes)
+    {
+        PerSystem& s = of(p);
+        s.baseSecondDevice = baseDevice, s.baseSecondBytes = baseBytes, s.shadowSecondDevice = shadowDevice, s.shadowSecondBytes = shadowBytes;
+    }
+
     // device pointers of mesh system p's last cluster cull: the commands and uint32 counts[2 * views]
     void getDevice(uint32_t p, const void** commands, const void** counts)
     {
         check(gv_pool_cluster_commands_device(system->getContext(), p, commands, counts), "gv_pool_cluster_commands_device");
     }
+    // ... and of its last second phase
+    void getSecondDevice(uint32_t p, const void** commands, const void** counts)
+    {
+        check(gv_pool_cluster_second_commands_device(system->getContext(), p, commands, counts), "gv_pool_cluster_second_commands_device");
+    }
     const Emitted& getBase(uint32_t p) { return of(p).base; }
     const Emitted& getShadow(uint32_t p) { return of(p).shadow; }
+    const Emitted& getBaseSecond(uint32_t p) { return of(p).baseSecond; }
+    const Emitted& getShadowSecond(uint32_t p) { return of(p).shadowSecond; }
 };
 
 }  // namespace garden

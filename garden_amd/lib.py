@@ -267,6 +267,7 @@ EXPORTS = [
     "gv_pool_bind_geometry", "gv_pool_set_command_layout", "gv_pool_emit_draw_commands", "gv_pool_draw_commands_device",
     "gv_pool_draw_commands_fetch",
     "gv_pool_bind_clusters", "gv_pool_cull_clusters", "gv_pool_cluster_commands_device", "gv_pool_cluster_commands_fetch",
+    "gv_pool_cull_clusters_second_phase", "gv_pool_cluster_second_commands_device", "gv_pool_cluster_second_commands_fetch",
     "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
     "gv_pool_group_draws",
     "gv_pool_cull_second_phase",
@@ -411,6 +412,9 @@ def load():
     lib.gv_pool_cull_clusters.argtypes = [P, u32, u32, u32, P, sz]
     lib.gv_pool_cluster_commands_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_cluster_commands_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
+    lib.gv_pool_cull_clusters_second_phase.argtypes = [P, u32, u32, u32, P, sz]
+    lib.gv_pool_cluster_second_commands_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
+    lib.gv_pool_cluster_second_commands_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
     lib.gv_pool_bind_lod.argtypes = [P, u32, P, u32, u32, C.POINTER(GvLodGeometry), u32]
     lib.gv_pool_select_lods.argtypes = [P, u32, C.POINTER(C.c_float), u32]
     lib.gv_pool_lods_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
@@ -1129,6 +1133,39 @@ class GpuVisibility:
             out = np.zeros((positions, stride), np.uint8)
         assert out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.nbytes >= (positions if room is None else min(positions, room)) * stride
         self._check(self.lib.gv_pool_cluster_commands_fetch(self.ctx, pool_id, out.ctypes.data, out.nbytes, cp, len(both)))
+        if dtype is not None:
+            out = out.reshape(-1).view(np.uint8)[:positions * stride].view(np.dtype(dtype))
+        return out, both[:views].copy(), both[views:].copy()
+
+    def cull_clusters_second_phase(self, pool_id, region=0, target=None):
+        """gv_pool_cull_clusters_second_phase: the clusters the pool's last cull_clusters tested and did not keep, in the views for
+        which it queried a pyramid, tested again against that pyramid as it stands now; one indirect command per survivor, in
+        buffers of its own. region and target (None, or (device pointer, capacity in bytes)) as cull_clusters' region and device."""
+        ptr, cap = (None, 0) if target is None else (int(target[0]), int(target[1]))
+        self._check(self.lib.gv_pool_cull_clusters_second_phase(self.ctx, pool_id, 0, int(region), ptr, cap))
+        stride = self._cluster_commands[pool_id][0]  # (the layout of the cluster cull it follows)
+        self._cluster_second = getattr(self, "_cluster_second", {})
+        self._cluster_second[pool_id] = (stride, int(region), None if target is None else cap // stride)
+
+    def cluster_second_commands_device(self, pool_id):
+        """(device pointer of the commands, device pointer of uint32 counts[2 * views]) of the pool's last cluster second phase"""
+        commands, counts = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.gv_pool_cluster_second_commands_device(self.ctx, pool_id, C.byref(commands), C.byref(counts)))
+        return commands.value, counts.value
+
+    def cluster_second_commands(self, pool_id, dtype=None, out=None):
+        """gv_pool_cluster_second_commands_fetch: as cluster_commands, of the pool's last cluster second phase; returns (the
+        command positions, counts[views], pending[views] — the clusters re-tested per view)."""
+        stride, region, room = self._cluster_second[pool_id]
+        views = self.instances_info(pool_id)[0]
+        both = np.zeros(2 * views, np.uint32)
+        cp = both.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(self.lib.gv_pool_cluster_second_commands_fetch(self.ctx, pool_id, None, 0, cp, len(both)))
+        positions = views * region if region else int(both[:views].sum())
+        if out is None:
+            out = np.zeros((positions, stride), np.uint8)
+        assert out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.nbytes >= (positions if room is None else min(positions, room)) * stride
+        self._check(self.lib.gv_pool_cluster_second_commands_fetch(self.ctx, pool_id, out.ctypes.data, out.nbytes, cp, len(both)))
         if dtype is not None:
             out = out.reshape(-1).view(np.uint8)[:positions * stride].view(np.dtype(dtype))
         return out, both[:views].copy(), both[views:].copy()

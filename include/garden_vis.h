@@ -639,6 +639,47 @@ int gv_pool_cluster_commands_device(GvCtx* ctx, uint32_t pool_id, const void** c
  * GV_E_ARG when either array is too small: nothing is written. */
 int gv_pool_cluster_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* counts, uint32_t counts_capacity);
 
+/* ---- the second phase of the cluster cull ----
+ * gv_pool_cull_clusters tests against the pyramid a view names, and that pyramid is a frame old: a cluster that has just come out
+ * from behind an occluder is rejected for a frame. gv_pool_cull_clusters_second_phase tests what the pool's cluster cull left out
+ * again, against the pyramid as it stands now. The draws the draw-level second phase
+ * (gv_pool_cull_second_phase) newly delivers are an ordinary view: an emission and gv_pool_cull_clusters cover them. Frame order:
+ *   cull -> emit -> gv_pool_cull_clusters -> draw -> gv_hiz_build / _rebuild -> gv_pool_cull_clusters_second_phase -> draw ->
+ *   gv_pool_cull_second_phase -> emit -> gv_pool_cull_clusters for the second view.
+ * Let K1 be the pool's current cluster result, and E, v, k, j, M_k, VP_v, the planes, g_k, c_k and first_k exactly the ones K1
+ * used: g_k is the id K1 kept for the draw — an id mark made after K1 plays no part, nor does a LOD selection made or dropped
+ * after K1.
+ *   A cluster candidate is PENDING iff K1 tested it, K1 did not keep it, and K1 queried a pyramid for its view (the view's use_hiz
+ *   != 0 and K1 was made without GV_CLUSTERS_FRUSTUM_ONLY). Whole draws, void draws, K1's survivors and the clusters of a view K1
+ *   did not query are never pending.
+ *   A pending cluster SURVIVES iff the unchanged test keeps it: the same corners through M_k, the same planes, the Hi-Z query
+ *   against the pyramid view v names as that pyramid stands when THIS call is issued. A frustum reject of K1 is pending and is
+ *   rejected again by the same arithmetic.
+ *   A survivor emits the command K1 would have written for it: {cl.count, c_k, G(g_k).first + cl.first, G(g_k).vertex_offset,
+ *   first_k, k} in the pool's GvCommandLayout.
+ * Order: by view, then k, then j. counts[v] = commands of view v, always the true count; counts[m + v] = pending clusters
+ * re-tested for view v. Placement (region_commands), zero padding, "every byte of the stride", "positions at or beyond capacity are
+ * not written", the library-owned (sized for K1's bound B, or m * R) or caller-owned 16-byte aligned target and the 2 GiB refusal
+ * as for gv_pool_cull_clusters. The result lives in buffers of its own: K1's commands, counts, bits and scratch are not written, so
+ * K1's fetch returns the same bytes before and after, the call is repeatable (twice against the same pyramid: identical bytes), and
+ * against the pyramid K1 itself queried it gives zero commands in every view.
+ * Asynchronous on gv_stream(ctx), the host reads no count; counts as a read. FIVE kernel launches whatever the data holds — pending
+ * counts per candidate tile, their scan, the test with one lane per PENDING cluster, the survivors' scan, the writer — counted
+ * under GvStats::launches[GV_K_EMIT]. Scratch from B: 12 bytes per 256 candidates and one bit per candidate. The result ends
+ * wherever K1 ends (gv_cull, gv_pool_cull_second_phase, an instance emission, gv_pool_bind_clusters) and at a new
+ * gv_pool_cull_clusters of the pool.
+ * flags must be 0. GV_E_ARG: a pool out of range or not bound, flags != 0, a misaligned dst_device, m * R beyond 32 bits.
+ * GV_E_STATE: the pool holds no cluster result; a queried view names a pyramid that is not built (gv_hiz_drop);
+ * gv_pool_bind_geometry or gv_pool_set_command_layout was called since K1 (K1's kept ids may lie outside a new table: cull the
+ * clusters again); a library-owned target beyond 2 GiB. A refused call changes nothing. */
+int gv_pool_cull_clusters_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device,
+                                       size_t capacity_bytes);
+/* Device pointers of the pool's last cluster second phase, written in stream order: the commands and uint32 counts[2 * m]. */
+int gv_pool_cluster_second_commands_device(GvCtx* ctx, uint32_t pool_id, const void** commands, const void** counts);
+/* As gv_pool_cluster_commands_fetch, of the pool's last cluster second phase. */
+int gv_pool_cluster_second_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* counts,
+                                          uint32_t counts_capacity);
+
 /* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
  * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
  * the record's componentOffset. A pool may bind those bytes (its PAYLOAD: up to GV_MAX_PAYLOAD_FIELDS fields, GV_MAX_PAYLOAD_BYTES
