@@ -11,107 +11,71 @@ namespace {
 
 constexpr uint64_t kOwnTargetMaxBytes = 1ull << 31;  // a library-owned target beyond this is refused: the caller sizes one for what is drawn
 
-}  // namespace
-
-extern "C" {
-
-int gv_pool_bind_clusters(GvCtx* ctx, uint32_t pool_id, const GvClusterRange* ranges, uint32_t range_count, const GvCluster* clusters,
-                          uint32_t cluster_count)
+// the plain form's five launches: one command per survivor
+int write_survivors(GvCtx* ctx, PoolState::Clusters&, const ClusterLaunch& launch, size_t)
 {
-    static_assert(sizeof(GvCluster) == sizeof(ClusterEntry) && sizeof(GvCluster) == 32, "the kernels read a cluster as two 16-byte pieces");
-    static_assert(sizeof(GvClusterRange) == sizeof(ClusterRange) && sizeof(GvClusterRange) == 8, "the kernels read the ranges as they are bound");
-    if (!ctx)
-        return GV_E_ARG;
-    if (pool_id >= GV_MAX_POOLS)
-        return ctx->fail(GV_E_ARG, "gv_pool_bind_clusters: pool %u out of range", pool_id);
-    const bool none = !ranges && !range_count && !clusters && !cluster_count;
-    if (!none && (!ranges || !range_count || !clusters || !cluster_count))
-        return ctx->fail(GV_E_ARG, "gv_pool_bind_clusters: ranges %p with %u entries, clusters %p with %u entries (both tables, or NULL and 0 for "
-                         "both to remove the binding)", (const void*)ranges, range_count, (const void*)clusters, cluster_count);
-    if (range_count > GV_MAX_GEOMETRIES || cluster_count > GV_MAX_CLUSTERS)
-        return ctx->fail(GV_E_ARG, "gv_pool_bind_clusters: %u ranges (at most %u) and %u clusters (at most %u)", range_count, GV_MAX_GEOMETRIES,
-                         cluster_count, GV_MAX_CLUSTERS);
-    uint32_t max_range = 0;
-    for (uint32_t g = 0; g < range_count; g++) {
-        if (ranges[g].count > GV_MAX_GEOMETRY_CLUSTERS || (uint64_t)ranges[g].first + ranges[g].count > cluster_count)
-            return ctx->fail(GV_E_ARG, "gv_pool_bind_clusters: range %u = {first %u, count %u}: at most %u clusters, inside the table of %u", g,
-                             ranges[g].first, ranges[g].count, GV_MAX_GEOMETRY_CLUSTERS, cluster_count);
-        max_range = std::max(max_range, ranges[g].count);
-    }
-    PoolState::Clusters& K = ctx->pools[pool_id].clusters;
-    GV_HIP(ctx, hipSetDevice(ctx->device));
-    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading the tables)
-    K.views = 0;  // a result made from the tables as they were ends
-    K.second.views = 0;
-    K.bound = false;
-    K.range_count = K.cluster_count = K.max_range = 0;
-    if (none) {
-        K.d_ranges.release();
-        K.d_clusters.release();
-        return GV_OK;
-    }
-    GV_HIP(ctx, K.d_ranges.reserve(range_count));
-    GV_HIP(ctx, K.d_clusters.reserve(cluster_count));
-    GV_HIP(ctx, hipMemcpy(K.d_ranges.ptr, ranges, (size_t)range_count * sizeof(GvClusterRange), hipMemcpyHostToDevice));
-    GV_HIP(ctx, hipMemcpy(K.d_clusters.ptr, clusters, (size_t)cluster_count * sizeof(GvCluster), hipMemcpyHostToDevice));
-    ctx->stats.upload_bytes += (size_t)range_count * sizeof(GvClusterRange) + (size_t)cluster_count * sizeof(GvCluster);
-    K.bound = true;
-    K.range_count = range_count;
-    K.cluster_count = cluster_count;
-    K.max_range = max_range;
+    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_count(launch, ctx->stream));
+    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_candidates(launch, ctx->stream));
+    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_test(launch, ctx->stream));
+    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_survivors(launch, ctx->stream));
+    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_write(launch, ctx->stream));
     return GV_OK;
 }
 
-int gv_pool_cull_clusters(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes)
+}  // namespace
+
+namespace gv {
+
+int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullLaunches enqueue, const char* zone_name, uint32_t pool_id, uint32_t flags, uint32_t region_commands,
+                  void* dst_device, size_t capacity_bytes)
 {
     if (!ctx)
         return GV_E_ARG;
-    const char* const fn = "gv_pool_cull_clusters";
     if (!bound_pool(ctx, fn, pool_id))
         return GV_E_ARG;
     if (flags & ~(uint32_t)GV_CLUSTERS_FRUSTUM_ONLY)
-        return ctx->fail(GV_E_ARG, "gv_pool_cull_clusters: unknown flags 0x%x", flags);
+        return ctx->fail(GV_E_ARG, "%s: unknown flags 0x%x", fn, flags);
     if (dst_device && (uintptr_t)dst_device % 16 != 0)
-        return ctx->fail(GV_E_ARG, "gv_pool_cull_clusters: dst_device must be 16-byte aligned");
+        return ctx->fail(GV_E_ARG, "%s: dst_device must be 16-byte aligned", fn);
     PoolState& p = ctx->pools[pool_id];
     PoolState::Instances& I = p.instances;
     PoolState::Geometry& G = p.geometry;
     PoolState::Clusters& K = p.clusters;
     const GvCommandLayout L = p.commands.layout;
     if (!K.bound)
-        return ctx->fail(GV_E_STATE, "gv_pool_cull_clusters: pool %u has no clusters bound (gv_pool_bind_clusters)", pool_id);
+        return ctx->fail(GV_E_STATE, "%s: pool %u has no clusters bound (gv_pool_bind_clusters)", fn, pool_id);
     if (!L.stride)
-        return ctx->fail(GV_E_STATE, "gv_pool_cull_clusters: pool %u has no command layout (gv_pool_set_command_layout)", pool_id);
+        return ctx->fail(GV_E_STATE, "%s: pool %u has no command layout (gv_pool_set_command_layout)", fn, pool_id);
     if (!G.bound)
-        return ctx->fail(GV_E_STATE, "gv_pool_cull_clusters: pool %u has no geometry bound (gv_pool_bind_geometry)", pool_id);
+        return ctx->fail(GV_E_STATE, "%s: pool %u has no geometry bound (gv_pool_bind_geometry)", fn, pool_id);
     if (!I.views)
-        return ctx->fail(GV_E_STATE, "gv_pool_cull_clusters: pool %u has no instance emission since its last gv_cull", pool_id);
+        return ctx->fail(GV_E_STATE, "%s: pool %u has no instance emission since its last gv_cull", fn, pool_id);
     const uint32_t m = I.views;
     if ((uint64_t)m * region_commands > UINT32_MAX)
-        return ctx->fail(GV_E_ARG, "gv_pool_cull_clusters: %u regions of %u commands are more positions than 32 bits hold", m, region_commands);
+        return ctx->fail(GV_E_ARG, "%s: %u regions of %u commands are more positions than 32 bits hold", fn, m, region_commands);
     const bool frustum_only = (flags & GV_CLUSTERS_FRUSTUM_ONLY) != 0;
     uint64_t slots = 0;  // the sum of the listed views' occupancies
     for (uint32_t k = 0; k < m; k++) {
         const ViewState* vs = view_of(ctx, pool_id, I.listed[k]);
         if (!vs)
-            return ctx->fail(GV_E_STATE, "gv_pool_cull_clusters: pool %u view %u has no results", pool_id, I.listed[k]);
+            return ctx->fail(GV_E_STATE, "%s: pool %u view %u has no results", fn, pool_id, I.listed[k]);
         if (int rc = column_covers(ctx, fn, kGeometryIds, pool_id, G.ids, G.occupancy, *vs, I.listed[k]))
             return rc;
         if (!frustum_only && vs->use_hiz && !ctx->pyramid_built(Context::pyramid_of(vs->use_hiz)))
-            return ctx->fail(GV_E_STATE, "gv_pool_cull_clusters: view %u of pool %u names pyramid %u, which is not built (gv_hiz_build, or "
-                             "GV_CLUSTERS_FRUSTUM_ONLY)", I.listed[k], pool_id, Context::pyramid_of(vs->use_hiz));
+            return ctx->fail(GV_E_STATE, "%s: view %u of pool %u names pyramid %u, which is not built (gv_hiz_build, or "
+                             "GV_CLUSTERS_FRUSTUM_ONLY)", fn, I.listed[k], pool_id, Context::pyramid_of(vs->use_hiz));
         slots += vs->occupancy;
     }
     // the host's bound of the candidates: a view draws a slot at most once, a draw has at most max(1, the largest range) candidates
     const uint64_t bound = slots * std::max(1u, K.max_range);
     if (bound > UINT32_MAX)
-        return ctx->fail(GV_E_STATE, "gv_pool_cull_clusters: %llu slots of pool %u with up to %u clusters each may be %llu candidates, more than "
-                         "32 bits hold: cull fewer views per emission", (unsigned long long)slots, pool_id, K.max_range, (unsigned long long)bound);
+        return ctx->fail(GV_E_STATE, "%s: %llu slots of pool %u with up to %u clusters each may be %llu candidates, more than "
+                         "32 bits hold: cull fewer views per emission", fn, (unsigned long long)slots, pool_id, K.max_range, (unsigned long long)bound);
     const uint64_t positions = region_commands ? (uint64_t)m * region_commands : bound;
     if (!dst_device && positions * L.stride > kOwnTargetMaxBytes)
-        return ctx->fail(GV_E_STATE, "gv_pool_cull_clusters: pool %u may emit %llu commands of %u bytes, more than a library-owned target holds: "
-                         "pass a caller-owned target (dst_device) sized for what is drawn", pool_id, (unsigned long long)positions, L.stride);
-    ZoneScope zone("Meshes Cluster Cull");
+        return ctx->fail(GV_E_STATE, "%s: pool %u may emit %llu commands of %u bytes, more than a library-owned target holds: "
+                         "pass a caller-owned target (dst_device) sized for what is drawn", fn, pool_id, (unsigned long long)positions, L.stride);
+    ZoneScope zone(zone_name);
     if (int rc = flush_sorts(ctx))  // the call is a read: recorded culls and deferred sorts first (as the emissions)
         return rc;
     GV_HIP(ctx, hipSetDevice(ctx->device));
@@ -175,11 +139,8 @@ int gv_pool_cull_clusters(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t
     launch.tile_block = K.d_tile_block.ptr;
     launch.survive = K.d_survive.ptr;
     launch.counts = K.d_counts.ptr;
-    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_count(launch, ctx->stream));
-    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_candidates(launch, ctx->stream));
-    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_test(launch, ctx->stream));
-    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_survivors(launch, ctx->stream));
-    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_write(launch, ctx->stream));
+    if (int rc = enqueue(ctx, K, launch, tiles))
+        return rc;
     K.second.views = 0;  // the bits and prefixes a second phase read are replaced
     K.launch = launch;   // gv_pool_cull_clusters_second_phase tests with the same arguments
     K.candidate_bound = bound;
@@ -192,6 +153,62 @@ int gv_pool_cull_clusters(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t
     K.stride = L.stride;
     K.region = region_commands;
     return GV_OK;
+}
+
+}  // namespace gv
+
+extern "C" {
+
+int gv_pool_bind_clusters(GvCtx* ctx, uint32_t pool_id, const GvClusterRange* ranges, uint32_t range_count, const GvCluster* clusters,
+                          uint32_t cluster_count)
+{
+    static_assert(sizeof(GvCluster) == sizeof(ClusterEntry) && sizeof(GvCluster) == 32, "the kernels read a cluster as two 16-byte pieces");
+    static_assert(sizeof(GvClusterRange) == sizeof(ClusterRange) && sizeof(GvClusterRange) == 8, "the kernels read the ranges as they are bound");
+    if (!ctx)
+        return GV_E_ARG;
+    if (pool_id >= GV_MAX_POOLS)
+        return ctx->fail(GV_E_ARG, "gv_pool_bind_clusters: pool %u out of range", pool_id);
+    const bool none = !ranges && !range_count && !clusters && !cluster_count;
+    if (!none && (!ranges || !range_count || !clusters || !cluster_count))
+        return ctx->fail(GV_E_ARG, "gv_pool_bind_clusters: ranges %p with %u entries, clusters %p with %u entries (both tables, or NULL and 0 for "
+                         "both to remove the binding)", (const void*)ranges, range_count, (const void*)clusters, cluster_count);
+    if (range_count > GV_MAX_GEOMETRIES || cluster_count > GV_MAX_CLUSTERS)
+        return ctx->fail(GV_E_ARG, "gv_pool_bind_clusters: %u ranges (at most %u) and %u clusters (at most %u)", range_count, GV_MAX_GEOMETRIES,
+                         cluster_count, GV_MAX_CLUSTERS);
+    uint32_t max_range = 0;
+    for (uint32_t g = 0; g < range_count; g++) {
+        if (ranges[g].count > GV_MAX_GEOMETRY_CLUSTERS || (uint64_t)ranges[g].first + ranges[g].count > cluster_count)
+            return ctx->fail(GV_E_ARG, "gv_pool_bind_clusters: range %u = {first %u, count %u}: at most %u clusters, inside the table of %u", g,
+                             ranges[g].first, ranges[g].count, GV_MAX_GEOMETRY_CLUSTERS, cluster_count);
+        max_range = std::max(max_range, ranges[g].count);
+    }
+    PoolState::Clusters& K = ctx->pools[pool_id].clusters;
+    GV_HIP(ctx, hipSetDevice(ctx->device));
+    GV_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the stream may still be reading the tables)
+    K.views = 0;  // a result made from the tables as they were ends
+    K.second.views = 0;
+    K.bound = false;
+    K.range_count = K.cluster_count = K.max_range = 0;
+    if (none) {
+        K.d_ranges.release();
+        K.d_clusters.release();
+        return GV_OK;
+    }
+    GV_HIP(ctx, K.d_ranges.reserve(range_count));
+    GV_HIP(ctx, K.d_clusters.reserve(cluster_count));
+    GV_HIP(ctx, hipMemcpy(K.d_ranges.ptr, ranges, (size_t)range_count * sizeof(GvClusterRange), hipMemcpyHostToDevice));
+    GV_HIP(ctx, hipMemcpy(K.d_clusters.ptr, clusters, (size_t)cluster_count * sizeof(GvCluster), hipMemcpyHostToDevice));
+    ctx->stats.upload_bytes += (size_t)range_count * sizeof(GvClusterRange) + (size_t)cluster_count * sizeof(GvCluster);
+    K.bound = true;
+    K.range_count = range_count;
+    K.cluster_count = cluster_count;
+    K.max_range = max_range;
+    return GV_OK;
+}
+
+int gv_pool_cull_clusters(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes)
+{
+    return cull_clusters(ctx, "gv_pool_cull_clusters", write_survivors, "Meshes Cluster Cull", pool_id, flags, region_commands, dst_device, capacity_bytes);
 }
 
 int gv_pool_cluster_commands_device(GvCtx* ctx, uint32_t pool_id, const void** commands, const void** counts)

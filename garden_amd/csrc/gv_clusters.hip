@@ -32,10 +32,13 @@
 // the range's count by construction, a range lies inside the cluster table by the bind's check, T is at most the host's bound.
 //
 // Behind them, sharing their device helpers: the five kernels of gv_pool_cull_clusters_second_phase (cluster_second_*, described
-// where they stand), which read what the five above left on the device and write none of it.
+// where they stand), which read what the five above left on the device and write none of it; and the three kernels of the run form
+// gv_pool_cull_cluster_runs (cluster_run_*, described where they stand), which with the count, the scans and the test's walk above
+// write one command per run of adjacent survivors.
 #include "gv_device.hpp"
 #include "gv_cluster_kernels.hpp"
 #include "gv_cluster_second_kernels.hpp"
+#include "gv_cluster_run_kernels.hpp"
 
 namespace gv {
 
@@ -303,7 +306,12 @@ __device__ __forceinline__ void locate(const ClusterLaunch& a, uint32_t c, uint3
     j = rest - local[lo];
 }
 
-__global__ __launch_bounds__(kClusterBlock) void cluster_test_kernel(const ClusterLaunch a)
+// The walk of cluster_test_kernel. kRuns (cluster_run_test_kernel): it also ballots the LINK bit of every candidate into `link` —
+// cluster j of a draw follows cluster j - 1 in the index buffer, j is no multiple of kClusterRunSpan and the cluster's own interval
+// does not wrap (include/garden_vis.h). A lane holds its cluster's first and count in the .w of its two loads; the predecessor's
+// are in the lane below (lane > 0 and j > 0: candidate c - 1 is cluster j - 1 of the same draw), lane 0 loads them itself.
+template <bool kRuns>
+__device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsigned long long* link)
 {
     __shared__ uint32_t wave_count[kClusterBlock / 64u];
     ConstClusterArgs base = (ConstClusterArgs)__builtin_amdgcn_kernarg_segment_ptr();
@@ -319,15 +327,18 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_test_kernel(const Clust
         bool tested = false;
         uint32_t v = 0;
         Corners corners;
+        uint32_t j = 0, cl_first = 0, cl_count = 0;
+        const float4* cl = nullptr;
         if (live) {
-            uint32_t block, at, j;
+            uint32_t block, at;
             locate(a, c, tile, tiles, blocks, block, at, j);
             v = view_of_block(a.first_block, a.views, block);
             const ClusterRange range = range_of(a, a.draw_geometry[at]);
             if (range.count) {
                 tested = true;
-                const float4* const cl = a.clusters + ((size_t)range.first + j) * 2u;
+                cl = a.clusters + ((size_t)range.first + j) * 2u;
                 const float4 lo = cl[0], hi = cl[1];  // (plain loads: every draw of the geometry reads the cluster again)
+                cl_first = __float_as_uint(lo.w), cl_count = __float_as_uint(hi.w);
                 const ViewPick view = pick_view(a, v);
                 const uint32_t k = at - view.first_block * kClusterBlock;
                 const float4* const rows = reinterpret_cast<const float4*>(view.model) + (size_t)k * 3u;
@@ -354,15 +365,37 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_test_kernel(const Clust
             }
         }
         const unsigned long long word = __ballot(survives);
-        if (lane == 0u) {
-            a.survive[(size_t)tile * 4u + wave] = word;
-            wave_count[wave] = (uint32_t)__popcll(word);
+        if constexpr (kRuns) {
+            // (whole draws and dead lanes: not tested, no link. The survivors are counted as heads by the launch behind.)
+            const uint32_t below_first = (uint32_t)__shfl_up((int)cl_first, 1, 64), below_count = (uint32_t)__shfl_up((int)cl_count, 1, 64);
+            bool linked = false;
+            if (tested && j != 0u && j % kClusterRunSpan != 0u) {
+                uint32_t before_first = below_first, before_count = below_count;
+                if (lane == 0u)
+                    before_first = __float_as_uint(cl[-2].w), before_count = __float_as_uint(cl[-1].w);  // (j > 0: inside the range)
+                linked = (uint64_t)before_first + before_count == cl_first && (uint64_t)cl_first + cl_count <= 0xFFFFFFFFull;
+            }
+            const unsigned long long links = __ballot(linked);
+            if (lane == 0u) {
+                a.survive[(size_t)tile * 4u + wave] = word;
+                link[(size_t)tile * 4u + wave] = links;
+            }
+        } else {
+            if (lane == 0u) {
+                a.survive[(size_t)tile * 4u + wave] = word;
+                wave_count[wave] = (uint32_t)__popcll(word);
+            }
+            __syncthreads();
+            if (threadIdx.x == 0)
+                a.tile_count[tile] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
+            __syncthreads();  // (the next tile rewrites the wave counts)
         }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            a.tile_count[tile] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
-        __syncthreads();  // (the next tile rewrites the wave counts)
     }
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_test_kernel(const ClusterLaunch a)
+{
+    cluster_test_tiles<false>(a, nullptr);
 }
 
 // every word of one command position; a field offset of kNoField matches no word
@@ -714,6 +747,130 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_second_write_kernel(con
     }
 }
 
+// ---- the run form (gv_pool_cull_cluster_runs) ----
+// The plain form's decisions, one command per RUN of adjacent surviving clusters. Six launches: cluster_count_kernel and
+// cluster_scan_kernel<0> as they are, then
+//
+//   cluster_run_test_kernel    cluster_test_kernel's walk, which also ballots the LINK bit of every candidate (above). It leaves
+//                              the survive words exactly as the plain form does, and no survivor counts.
+//   cluster_run_heads_kernel   dense, one lane per TILE (four survive and four link words, 64 bytes read, 36 written): a survivor
+//                              is a HEAD iff it is not linked or its predecessor did not survive, head = s & ~(l & (s << 1 | the top
+//                              bit of the word before)). The head words and the tile's head count.
+//   cluster_scan_kernel<1>     over the head counts and head words (a launch struct that points there): the heads in front of
+//                              every tile and view, and counts[v]. A view's first candidate is a whole draw or has j = 0: never
+//                              linked, so a view's heads are the bits from its first candidate on.
+//   cluster_run_write_kernel   cluster_write_kernel's walk over the head bits: a head's position is its rank. The run ends at the
+//                              first clear bit of link & survive behind the head — inside kClusterRunSpan / 64 + 1 words, because no
+//                              cluster with j % kClusterRunSpan == 0 is linked; a whole draw, a dead lane and the next draw's
+//                              cluster 0 have no link bit, so a run never leaves its draw. One more cluster load for its last cluster.
+//
+// Nothing waits, no atomics, integer ranks only; the second phase finds what the plain form would have left (it reads neither
+// tile_count nor the survivor starts).
+static_assert(offsetof(ClusterRunLaunch, k) == 0, "the per-view arguments are read at the plain form's offsets");
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_run_test_kernel(const ClusterRunLaunch r)
+{
+    cluster_test_tiles<true>(r.k, r.link);
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_run_heads_kernel(const ClusterRunLaunch r)
+{
+    const ClusterLaunch& a = r.k;
+    const uint32_t total = a.totals[kClusterTotalCandidates];
+    const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+    for (uint64_t tile = (uint64_t)blockIdx.x * kClusterBlock + threadIdx.x; tile < tiles; tile += (uint64_t)gridDim.x * kClusterBlock) {
+        const ulonglong2* const sp = reinterpret_cast<const ulonglong2*>(a.survive + tile * 4u);
+        const ulonglong2* const lp = reinterpret_cast<const ulonglong2*>(r.link + tile * 4u);
+        const ulonglong2 s01 = sp[0], s23 = sp[1], l01 = lp[0], l23 = lp[1];
+        const unsigned long long s[4] = {s01.x, s01.y, s23.x, s23.y}, l[4] = {l01.x, l01.y, l23.x, l23.y};
+        unsigned long long before = tile ? a.survive[tile * 4u - 1u] >> 63 : 0ull;  // the candidate in front of the tile survived
+        unsigned long long h[4];
+        uint32_t n = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4u; w++) {
+            h[w] = s[w] & ~(l[w] & ((s[w] << 1) | before));
+            before = s[w] >> 63;
+            n += (uint32_t)__popcll(h[w]);
+        }
+        ulonglong2* const hp = reinterpret_cast<ulonglong2*>(r.head + tile * 4u);
+        hp[0] = ulonglong2{h[0], h[1]};
+        hp[1] = ulonglong2{h[2], h[3]};
+        r.head_count[tile] = n;
+    }
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_run_write_kernel(const ClusterRunLaunch r)
+{
+    const ClusterLaunch& a = r.k;
+    const uint32_t total = a.totals[kClusterTotalCandidates];
+    const uint32_t tiles = total / kClusterTile + (total % kClusterTile ? 1u : 0u);
+    const uint64_t words_written = (uint64_t)tiles * 4u;  // (the words behind them were not written by this call)
+    const uint32_t blocks = a.first_block[a.views];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const unsigned long long* const words = r.head + (size_t)tile * 4u;
+        const unsigned long long word = words[wave];
+        if (!((word >> lane) & 1ull))
+            continue;
+        uint32_t rank = r.head_count[tile] + (uint32_t)__popcll(word & ((1ull << lane) - 1ull));  // (scanned: heads in front of the tile)
+        for (uint32_t w = 0; w < wave; w++)
+            rank += (uint32_t)__popcll(words[w]);
+        const uint32_t c = tile * kClusterTile + threadIdx.x;
+        uint32_t block, at, j;
+        locate(a, c, tile, tiles, blocks, block, at, j);
+        const uint32_t v = view_of_block(a.first_block, a.views, block);
+        uint32_t position = rank;  // packed: the views' commands back to back are the heads in order
+        if (a.region) {
+            const uint32_t in_view = rank - a.totals[kClusterSurvivorStart + v];  // (the scan over the heads left the heads here)
+            if (in_view >= a.region)
+                continue;
+            position = v * a.region + in_view;
+        }
+        if (position >= a.capacity)
+            continue;
+        const ViewPick view = pick_view(a, v);
+        const uint32_t k = at - view.first_block * kClusterBlock;
+        const uint32_t g = a.draw_geometry[at];  // (below table_count: the draw has candidates)
+        const CommandGeometry geometry = a.table[g];
+        const ClusterRange range = range_of(a, g);
+        uint32_t count = geometry.count, first = geometry.first;
+        if (range.count) {
+            // the run's end: the first candidate behind the head that is not linked or did not survive
+            uint64_t end = (uint64_t)c + 1u;
+            for (uint32_t step = 0; step <= kClusterRunSpan / 64u; step++) {
+                const uint64_t w = end / 64u;
+                if (w >= words_written)
+                    break;
+                const unsigned long long open = ~(r.link[w] & a.survive[w]) & (~0ull << (end % 64u));
+                if (open) {
+                    end = w * 64u + (uint32_t)__builtin_ctzll(open);
+                    break;
+                }
+                end = (w + 1u) * 64u;
+            }
+            // (below the range's count by the rule: cluster 0 of the next draw, a whole draw and a dead lane have no link bit)
+            const uint32_t last = min(j + (uint32_t)(end - c) - 1u, range.count - 1u);
+            const float4* const table = a.clusters + (size_t)range.first * 2u;
+            const uint32_t head_first = __float_as_uint(table[(size_t)j * 2u].w);
+            first += head_first;
+            count = __float_as_uint(table[(size_t)last * 2u].w) + __float_as_uint(table[(size_t)last * 2u + 1u].w) - head_first;
+        }
+        const uint32_t from = first_of_draw(a, v, k);
+        put_command(a, position, count, instances_of_draw(a, v, k, *view.count, from), first, from, (uint32_t)geometry.vertex_offset, k);
+    }
+    if (a.region) {  // the all-zero padding positions C_v <= j < R of every view
+        const uint64_t positions = (uint64_t)a.views * a.region;
+        for (uint64_t p = (uint64_t)blockIdx.x * kClusterBlock + threadIdx.x; p < positions && p < a.capacity; p += (uint64_t)gridDim.x * kClusterBlock) {
+            const uint32_t v = (uint32_t)(p / a.region), in_view = (uint32_t)(p % a.region);
+            if (in_view < a.counts[v])
+                continue;
+            uint32_t* const to = reinterpret_cast<uint32_t*>(a.dst + (size_t)p * a.stride);
+            for (uint32_t w = 0; w < a.stride / 4u; w++)
+                to[w] = 0u;
+        }
+    }
+}
+
 // the fixed grid of the test and write launches: kClusterGridPerCu workgroups per compute unit of the current device
 uint32_t walk_grid()
 {
@@ -752,6 +909,33 @@ hipError_t launch_cluster_scan_survivors(const ClusterLaunch& launch, hipStream_
 hipError_t launch_cluster_write(const ClusterLaunch& launch, hipStream_t stream)
 {
     hipLaunchKernelGGL(cluster_write_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_run_test(const ClusterRunLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_run_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_run_heads(const ClusterRunLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_run_heads_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_run_scan(const ClusterRunLaunch& launch, hipStream_t stream)
+{
+    ClusterLaunch heads = launch.k;  // the survivors' scan, pointed at the head counts and head words
+    heads.tile_count = launch.head_count;
+    heads.survive = launch.head;
+    hipLaunchKernelGGL(cluster_scan_kernel<1>, dim3(1), dim3(kClusterScanBlock), 0, stream, heads);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_run_write(const ClusterRunLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_run_write_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
     return hipGetLastError();
 }
 

@@ -29,6 +29,7 @@
 #include "gv_previous_kernels.hpp"
 #include "gv_cluster_kernels.hpp"
 #include "gv_cluster_second_kernels.hpp"
+#include "gv_cluster_run_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -365,7 +366,7 @@ struct PoolState {
     } commands;
     // gv_pool_bind_clusters / gv_pool_cull_clusters: the tables as bound and the last call's commands, buffers of their own — no cull
     // result, no instance data and no per-draw command buffer (Commands above) is touched. Header-only: no other host source calls
-    // gv_clusters.cpp.
+    // gv_clusters.cpp but gv_cluster_runs.cpp, the run form, which shares its body (cull_clusters below).
     struct Clusters {
         bool bound = false;
         uint32_t range_count = 0, cluster_count = 0;
@@ -376,6 +377,8 @@ struct PoolState {
         DeviceBuf<uint32_t> d_counts;      // [2 * GV_MAX_VIEWS]: commands per view, then clusters tested per view
         DeviceBuf<uint32_t> d_draw_geometry, d_draw_local, d_block_total, d_block_tested, d_totals, d_tile_count, d_tile_block;  // scratch of a call
         DeviceBuf<unsigned long long> d_survive;
+        DeviceBuf<unsigned long long> d_link, d_head;  // gv_pool_cull_cluster_runs: a link and a head bit per candidate ...
+        DeviceBuf<uint32_t> d_head_count;              // ... and the heads per tile
         PinnedBuf<uint8_t> h_data;         // staging of gv_pool_cluster_commands_fetch
         PinnedBuf<uint32_t> h_counts;
         // the last call (views 0: none since the pool's last gv_cull, instance emission or gv_pool_bind_clusters)
@@ -411,6 +414,7 @@ struct PoolState {
         {
             d_ranges.release(), d_clusters.release(), d_data.release(), d_counts.release(), d_draw_geometry.release(), d_draw_local.release();
             d_block_total.release(), d_block_tested.release(), d_totals.release(), d_tile_count.release(), d_tile_block.release(), d_survive.release();
+            d_link.release(), d_head.release(), d_head_count.release();
             h_data.release(), h_counts.release(), second.release();
         }
     } clusters;
@@ -1152,6 +1156,14 @@ int wait_for_stream(GvCtx* ctx);                         // until the stream has
 ViewState* view_of(GvCtx* ctx, uint32_t pool_id, uint32_t view_index);  // NULL: no valid results
 bool release_record_target(PoolState::RecordTarget& target);            // false: the range was found unmapped
 int copy_shard_of_pool(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, void* dst_device, uint32_t capacity, uint32_t index_base);
+
+// gv_clusters.cpp
+// The body of both forms of the cluster cull (gv_pool_cull_clusters there, gv_pool_cull_cluster_runs in gv_cluster_runs.cpp): every
+// check, the bound, the target, the shared scratch and the bookkeeping. `enqueue` reserves what scratch the form adds and enqueues
+// its launches — launch is complete, tiles = ceil(B / kClusterTile); `fn` names the entry point in messages.
+typedef int (*ClusterCullLaunches)(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles);
+int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullLaunches enqueue, const char* zone_name, uint32_t pool_id, uint32_t flags, uint32_t region_commands,
+                  void* dst_device, size_t capacity_bytes);
 
 // gv_mirror.cpp
 // brings the device mirror up to date with the bound pools + dirty marks: per side a full rebuild, or growth and the dirty

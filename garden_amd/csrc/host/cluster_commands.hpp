@@ -2,8 +2,8 @@
 // its clusters (setClusters) — per geometry id a range of model-space boxes with index ranges — GpuDrawCommands::emit(), given this
 // object through GpuDrawCommands::setClusterCommands, follows each of its command emissions with a cluster cull
 // (gv_pool_cull_clusters): every cluster of every delivered draw tested with the draw's own matrix against the pass's frustum and,
-// where the pass named a pyramid, against that pyramid; one indirect command per surviving cluster, a draw without clusters drawn
-// whole. The per-draw commands stand beside them (a depth pre-pass may still take those). Geometry, command struct, LODs and
+// where the pass named a pyramid, against that pyramid; one indirect command per surviving cluster — or, with setRuns, per run of
+// adjacent surviving clusters (gv_pool_cull_cluster_runs) — a draw without clusters drawn whole. The per-draw commands stand beside them (a depth pre-pass may still take those). Geometry, command struct, LODs and
 // grouping are the ones declared to GpuDrawCommands: the cluster cull takes the same ids — the selected ones behind a selection.
 //
 // The commands land in caller-owned device memory when setTargets names some, else in the library's own buffer; either way they
@@ -38,6 +38,7 @@ private:
     GpuVisibilitySystem* system;
     struct PerSystem {
         bool enabled = false;  // clusters are bound
+        bool runs = false;     // adjacent surviving clusters are merged into one command (gv_pool_cull_cluster_runs)
         uint32_t flags = 0, region = 0;
         void *baseDevice = nullptr, *shadowDevice = nullptr;
         size_t baseBytes = 0, shadowBytes = 0;
@@ -83,6 +84,10 @@ public:
         PerSystem& s = of(p);
         s.baseDevice = baseDevice, s.baseBytes = baseBytes, s.shadowDevice = shadowDevice, s.shadowBytes = shadowBytes;
     }
+    // on: mesh system p's cluster culls write one command per RUN of adjacent surviving clusters (gv_pool_cull_cluster_runs) — for
+    // a cluster table that lays a geometry's clusters out back to back in the index buffer, the same indices in far fewer commands.
+    // Default off. The second phase (cullSecond) is unchanged and writes one command per cluster.
+    void setRuns(uint32_t p, bool on) { of(p).runs = on; }
     void setFetch(bool on) noexcept { fetch = on; }
 
     // GpuDrawCommands::emit calls this behind each of its command emissions for mesh system p (shadow: the one behind the shadow
@@ -97,7 +102,10 @@ public:
         GvCtx* ctx = system->getContext();
         void* const device = shadow ? s.shadowDevice : s.baseDevice;
         const size_t bytes = shadow ? s.shadowBytes : s.baseBytes;
-        check(gv_pool_cull_clusters(ctx, p, s.flags, s.region, device, bytes), "gv_pool_cull_clusters");
+        if (s.runs)
+            check(gv_pool_cull_cluster_runs(ctx, p, s.flags, s.region, device, bytes), "gv_pool_cull_cluster_runs");
+        else
+            check(gv_pool_cull_clusters(ctx, p, s.flags, s.region, device, bytes), "gv_pool_cull_clusters");
         Emitted& out = shadow ? s.shadow : s.base;
         out.stride = stride;
         out.region = s.region;

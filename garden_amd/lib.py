@@ -123,6 +123,7 @@ GEOMETRY_DTYPE = np.dtype([("count", np.uint32), ("first", np.uint32), ("vertex_
 GV_MAX_CLUSTERS = 1 << 22
 GV_MAX_GEOMETRY_CLUSTERS = 65535
 GV_CLUSTERS_FRUSTUM_ONLY = 1
+GV_CLUSTER_RUN_SPAN = 256
 
 
 class GvCluster(C.Structure):
@@ -268,6 +269,7 @@ EXPORTS = [
     "gv_pool_draw_commands_fetch",
     "gv_pool_bind_clusters", "gv_pool_cull_clusters", "gv_pool_cluster_commands_device", "gv_pool_cluster_commands_fetch",
     "gv_pool_cull_clusters_second_phase", "gv_pool_cluster_second_commands_device", "gv_pool_cluster_second_commands_fetch",
+    "gv_pool_cull_cluster_runs",
     "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
     "gv_pool_group_draws",
     "gv_pool_cull_second_phase",
@@ -415,6 +417,7 @@ def load():
     lib.gv_pool_cull_clusters_second_phase.argtypes = [P, u32, u32, u32, P, sz]
     lib.gv_pool_cluster_second_commands_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_cluster_second_commands_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
+    lib.gv_pool_cull_cluster_runs.argtypes = [P, u32, u32, u32, P, sz]
     lib.gv_pool_bind_lod.argtypes = [P, u32, P, u32, u32, C.POINTER(GvLodGeometry), u32]
     lib.gv_pool_select_lods.argtypes = [P, u32, C.POINTER(C.c_float), u32]
     lib.gv_pool_lods_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
@@ -1101,13 +1104,15 @@ class GpuVisibility:
         self._check(self.lib.gv_pool_bind_clusters(self.ctx, pool_id, C.cast(r.ctypes.data, C.POINTER(GvClusterRange)), len(r),
                                                    C.cast(c.ctypes.data, C.POINTER(GvCluster)), len(c)))
 
-    def cull_clusters(self, pool_id, frustum_only=False, region=0, device=None):
+    def cull_clusters(self, pool_id, frustum_only=False, region=0, device=None, runs=False):
         """gv_pool_cull_clusters: one indirect command per surviving cluster of every draw of the pool's last instance emission
         (draws without clusters are drawn whole), on the context's stream. frustum_only: no Hi-Z query even for views that named a
         pyramid. region: 0 packs the views' commands, R > 0 gives every view R positions. device: None for the library's own
-        buffer, or (device pointer, capacity in bytes) of caller-owned device memory."""
+        buffer, or (device pointer, capacity in bytes) of caller-owned device memory. runs: gv_pool_cull_cluster_runs — the same
+        decisions, one command per run of adjacent surviving clusters (at most GV_CLUSTER_RUN_SPAN of them)."""
         ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
-        self._check(self.lib.gv_pool_cull_clusters(self.ctx, pool_id, GV_CLUSTERS_FRUSTUM_ONLY if frustum_only else 0, int(region), ptr, cap))
+        call = self.lib.gv_pool_cull_cluster_runs if runs else self.lib.gv_pool_cull_clusters
+        self._check(call(self.ctx, pool_id, GV_CLUSTERS_FRUSTUM_ONLY if frustum_only else 0, int(region), ptr, cap))
         stride = self._command_stride[pool_id]
         self._cluster_commands = getattr(self, "_cluster_commands", {})
         self._cluster_commands[pool_id] = (stride, int(region), None if device is None else cap // stride)

@@ -680,6 +680,41 @@ int gv_pool_cluster_second_commands_device(GvCtx* ctx, uint32_t pool_id, const v
 int gv_pool_cluster_second_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* dst_host, size_t bytes, uint32_t* counts,
                                           uint32_t counts_capacity);
 
+/* ---- the cluster cull, adjacent survivors merged into runs ----
+ * A cluster table usually lays a geometry's clusters out back to back in the index buffer (first[j + 1] == first[j] + count[j]), and
+ * most clusters of a delivered draw survive: one command per cluster then writes, and makes the renderer walk, many commands where
+ * a few draw the same indices. gv_pool_cull_cluster_runs makes the decisions of gv_pool_cull_clusters and writes one command per RUN
+ * of adjacent surviving clusters (this build's rule, the reference has no clusters). E, v, k, j, M_k, g_k,
+ * c_k, first_k, G(g), range_k, "drawn whole", "void", SURVIVES and the order are exactly those of gv_pool_cull_clusters: a cluster
+ * survives under precisely the same test. With cl_j = clusters[range_k.first + j]:
+ *   Cluster j of draw k is LINKED to its predecessor iff j > 0, j % GV_CLUSTER_RUN_SPAN != 0, (uint64)cl_{j-1}.first +
+ *   cl_{j-1}.count == cl_j.first, and (uint64)cl_j.first + cl_j.count <= 0xFFFFFFFF. Linked is static: a property of the bound
+ *   tables and j alone, not of the matrix, the view, or which other views or draws E holds.
+ *   A surviving cluster j is a HEAD iff it is not linked, or cluster j - 1 did not survive.
+ *   A RUN is a head plus every following cluster j + 1, j + 2, ... of the same draw, taken while each survives and is linked. So a
+ *   run never leaves its draw, holds at most GV_CLUSTER_RUN_SPAN clusters, and its index range is one interval that cannot wrap.
+ *   A run from head h to last cluster l emits {count cl_l.first + cl_l.count - cl_h.first (= the sum of its clusters' counts),
+ *   instance_count c_k, first G(g_k).first + cl_h.first (uint32 add, as gv_pool_cull_clusters), vertex_offset G(g_k).vertex_offset,
+ *   first_instance first_k, draw k} in the pool's GvCommandLayout. Zero-count clusters need no special case.
+ *   A draw drawn whole emits its one command as gv_pool_cull_clusters writes it and is never merged with anything.
+ * Order: by view, draw k ascending, head j ascending. counts[v] = commands of view v (whole draws + runs), always the true count;
+ * counts[m + v] = clusters tested, as gv_pool_cull_clusters. flags (0 or GV_CLUSTERS_FRUSTUM_ONLY), placement (packed or regions),
+ * zero padding, "every byte of the stride", "positions at or beyond capacity are not written", the library-owned target sized for B
+ * (with regions m * R), its 2 GiB refusal, the 16-byte alignment of a caller-owned one, every GV_E_ARG and GV_E_STATE row and "a
+ * refused call changes nothing": as for gv_pool_cull_clusters.
+ * GV_CLUSTER_RUN_SPAN bounds the writer's walk from a head to its run's end to SPAN / 64 + 1 = five 64-candidate ballot words,
+ * whatever a draw's cluster count; it costs one extra command per 256 clusters of an unbroken layout.
+ * The call IS a cluster cull of the pool: its result replaces the pool's cluster result and is replaced by the next one of either
+ * form; gv_pool_cluster_commands_device / _fetch serve it unchanged, and it ends where a cluster result ends.
+ * gv_pool_cull_clusters_second_phase behind it works as behind the plain form (the same pending set) and writes one command per
+ * cluster. Asynchronous on gv_stream(ctx), the host reads no count; counts as a read. SIX kernel launches whatever the data holds —
+ * candidate counts per draw, their scan, the test (which also marks the links), the heads, their scan, the writer — counted under
+ * GvStats::launches[GV_K_EMIT]. Scratch from B: that of gv_pool_cull_clusters plus two bits per candidate and 4 bytes per 256.
+ * Not built: runs for the second phase's commands, runs longer than the span, merging across draws of one geometry. */
+#define GV_CLUSTER_RUN_SPAN 256u
+int gv_pool_cull_cluster_runs(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device,
+                              size_t capacity_bytes);
+
 /* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
  * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
  * the record's componentOffset. A pool may bind those bytes (its PAYLOAD: up to GV_MAX_PAYLOAD_FIELDS fields, GV_MAX_PAYLOAD_BYTES
