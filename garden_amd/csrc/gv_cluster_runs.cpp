@@ -11,17 +11,11 @@ namespace {
 
 static_assert(kClusterRunSpan == GV_CLUSTER_RUN_SPAN, "the writer's walk is bounded by the header's span");
 
-int write_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles)
+int write_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, const GvClusterEye*)
 {
-    const size_t words = std::max<size_t>(tiles, 1) * (kClusterTile / 64);
-    GV_HIP(ctx, K.d_link.reserve(words));
-    GV_HIP(ctx, K.d_head.reserve(words));
-    GV_HIP(ctx, K.d_head_count.reserve(std::max<size_t>(tiles, 4)));
     ClusterRunLaunch run{};
-    run.k = launch;
-    run.link = K.d_link.ptr;
-    run.head = K.d_head.ptr;
-    run.head_count = K.d_head_count.ptr;
+    if (int rc = reserve_runs(ctx, K, launch, tiles, &run))
+        return rc;
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_count(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_candidates(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_run_test(run, ctx->stream));
@@ -33,12 +27,29 @@ int write_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, 
 
 }  // namespace
 
+namespace gv {
+
+int reserve_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, ClusterRunLaunch* run)
+{
+    const size_t words = std::max<size_t>(tiles, 1) * (kClusterTile / 64);
+    GV_HIP(ctx, K.d_link.reserve(words));
+    GV_HIP(ctx, K.d_head.reserve(words));
+    GV_HIP(ctx, K.d_head_count.reserve(std::max<size_t>(tiles, 4)));
+    run->k = launch;
+    run->link = K.d_link.ptr;
+    run->head = K.d_head.ptr;
+    run->head_count = K.d_head_count.ptr;
+    return GV_OK;
+}
+
+}  // namespace gv
+
 extern "C" {
 
 int gv_pool_cull_cluster_runs(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes)
 {
-    return cull_clusters(ctx, "gv_pool_cull_cluster_runs", write_runs, "Meshes Cluster Cull Runs", pool_id, flags, region_commands, dst_device,
-                         capacity_bytes);
+    return cull_clusters(ctx, "gv_pool_cull_cluster_runs", ClusterCullForms{write_runs, nullptr, nullptr}, GV_CLUSTERS_FRUSTUM_ONLY, nullptr,
+                         "Meshes Cluster Cull Runs", pool_id, flags, region_commands, dst_device, capacity_bytes);
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@ namespace {
 constexpr uint64_t kOwnTargetMaxBytes = 1ull << 31;  // a library-owned target beyond this is refused: the caller sizes one for what is drawn
 
 // the plain form's five launches: one command per survivor
-int write_survivors(GvCtx* ctx, PoolState::Clusters&, const ClusterLaunch& launch, size_t)
+int write_survivors(GvCtx* ctx, PoolState::Clusters&, const ClusterLaunch& launch, size_t, const GvClusterEye*)
 {
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_count(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_candidates(launch, ctx->stream));
@@ -26,15 +26,18 @@ int write_survivors(GvCtx* ctx, PoolState::Clusters&, const ClusterLaunch& launc
 
 namespace gv {
 
-int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullLaunches enqueue, const char* zone_name, uint32_t pool_id, uint32_t flags, uint32_t region_commands,
-                  void* dst_device, size_t capacity_bytes)
+int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullForms forms, uint32_t allowed_flags, const ClusterConeRequest* cones, const char* zone_name,
+                  uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes)
 {
     if (!ctx)
         return GV_E_ARG;
     if (!bound_pool(ctx, fn, pool_id))
         return GV_E_ARG;
-    if (flags & ~(uint32_t)GV_CLUSTERS_FRUSTUM_ONLY)
+    if (flags & ~allowed_flags)
         return ctx->fail(GV_E_ARG, "%s: unknown flags 0x%x", fn, flags);
+    if (cones && !cones->eyes)
+        return ctx->fail(GV_E_ARG, "%s: eyes is NULL (one GvClusterEye per view of the emission)", fn);
+    const ClusterCullLaunches enqueue = (flags & GV_CLUSTERS_RUNS) ? forms.runs : forms.survivors;
     if (dst_device && (uintptr_t)dst_device % 16 != 0)
         return ctx->fail(GV_E_ARG, "%s: dst_device must be 16-byte aligned", fn);
     PoolState& p = ctx->pools[pool_id];
@@ -44,6 +47,8 @@ int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullLaunches enqueue, const
     const GvCommandLayout L = p.commands.layout;
     if (!K.bound)
         return ctx->fail(GV_E_STATE, "%s: pool %u has no clusters bound (gv_pool_bind_clusters)", fn, pool_id);
+    if (cones && !K.cones_bound)
+        return ctx->fail(GV_E_STATE, "%s: pool %u has no cluster cones bound (gv_pool_bind_cluster_cones)", fn, pool_id);
     if (!L.stride)
         return ctx->fail(GV_E_STATE, "%s: pool %u has no command layout (gv_pool_set_command_layout)", fn, pool_id);
     if (!G.bound)
@@ -51,6 +56,8 @@ int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullLaunches enqueue, const
     if (!I.views)
         return ctx->fail(GV_E_STATE, "%s: pool %u has no instance emission since its last gv_cull", fn, pool_id);
     const uint32_t m = I.views;
+    if (cones && cones->eye_count != m)
+        return ctx->fail(GV_E_ARG, "%s: %u eyes for the %u views of pool %u's emission (one each)", fn, cones->eye_count, m, pool_id);
     if ((uint64_t)m * region_commands > UINT32_MAX)
         return ctx->fail(GV_E_ARG, "%s: %u regions of %u commands are more positions than 32 bits hold", fn, m, region_commands);
     const bool frustum_only = (flags & GV_CLUSTERS_FRUSTUM_ONLY) != 0;
@@ -139,8 +146,11 @@ int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullLaunches enqueue, const
     launch.tile_block = K.d_tile_block.ptr;
     launch.survive = K.d_survive.ptr;
     launch.counts = K.d_counts.ptr;
-    if (int rc = enqueue(ctx, K, launch, tiles))
+    if (int rc = enqueue(ctx, K, launch, tiles, cones ? cones->eyes : nullptr))
         return rc;
+    K.second_test = forms.second_test;  // (cones: the second phase behind this result applies the same conjunction, with these eyes)
+    if (cones)
+        memcpy(K.eyes, cones->eyes, (size_t)m * sizeof(GvClusterEye));
     K.second.views = 0;  // the bits and prefixes a second phase read are replaced
     K.launch = launch;   // gv_pool_cull_clusters_second_phase tests with the same arguments
     K.candidate_bound = bound;
@@ -189,6 +199,8 @@ int gv_pool_bind_clusters(GvCtx* ctx, uint32_t pool_id, const GvClusterRange* ra
     K.second.views = 0;
     K.bound = false;
     K.range_count = K.cluster_count = K.max_range = 0;
+    K.cones_bound = false;  // the cones belong to the table as it was
+    K.d_cones.release();
     if (none) {
         K.d_ranges.release();
         K.d_clusters.release();
@@ -208,7 +220,8 @@ int gv_pool_bind_clusters(GvCtx* ctx, uint32_t pool_id, const GvClusterRange* ra
 
 int gv_pool_cull_clusters(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes)
 {
-    return cull_clusters(ctx, "gv_pool_cull_clusters", write_survivors, "Meshes Cluster Cull", pool_id, flags, region_commands, dst_device, capacity_bytes);
+    return cull_clusters(ctx, "gv_pool_cull_clusters", ClusterCullForms{write_survivors, nullptr, nullptr}, GV_CLUSTERS_FRUSTUM_ONLY, nullptr, "Meshes Cluster Cull",
+                         pool_id, flags, region_commands, dst_device, capacity_bytes);
 }
 
 int gv_pool_cluster_commands_device(GvCtx* ctx, uint32_t pool_id, const void** commands, const void** counts)

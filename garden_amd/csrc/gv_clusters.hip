@@ -34,11 +34,13 @@
 // Behind them, sharing their device helpers: the five kernels of gv_pool_cull_clusters_second_phase (cluster_second_*, described
 // where they stand), which read what the five above left on the device and write none of it; and the three kernels of the run form
 // gv_pool_cull_cluster_runs (cluster_run_*, described where they stand), which with the count, the scans and the test's walk above
-// write one command per run of adjacent survivors.
+// write one command per run of adjacent survivors; and the three test kernels of the normal-cone form gv_pool_cull_cluster_cones
+// (cluster_cone_*: the test walks above instantiated with the cone test in their conjunction, described where they stand).
 #include "gv_device.hpp"
 #include "gv_cluster_kernels.hpp"
 #include "gv_cluster_second_kernels.hpp"
 #include "gv_cluster_run_kernels.hpp"
+#include "gv_cluster_cone_kernels.hpp"
 
 namespace gv {
 
@@ -64,6 +66,55 @@ __device__ __forceinline__ HizDevice view_hiz_of(ConstClusterArgs base, uint32_t
     HizDevice out;
     __builtin_memcpy(&out, &base->hiz[v], sizeof(out));
     return out;
+}
+
+// The normal-cone test (gv_pool_cull_cluster_cones). The eye of view v lies in a wrapper struct behind
+// the launch struct the walk reads: at byte `eye_offset` of the argument block, read at a wave-uniform offset like the planes.
+struct ClusterEye { float e[4]; };
+__device__ __forceinline__ ClusterEye view_eye_of(ConstClusterArgs base, uint32_t eye_offset, uint32_t v)
+{
+    ClusterEye out;
+    __builtin_memcpy(&out, reinterpret_cast<const char __attribute__((address_space(4)))*>(base) + eye_offset + v * (uint32_t)sizeof(ClusterEye),
+                     sizeof(out));
+    return out;
+}
+// what a lane keeps of its draw and its cone for the views' tests: adj(A) and det A of the draw's 3x3 block, its translation, the cone
+struct ConeLane {
+    Adj33 adj;
+    float t[3];
+    float apex[3], cutoff, axis[3];
+};
+__device__ __forceinline__ ConeLane cone_lane(const Mat34& model, const float4 c0, const float4 c1)
+{
+    ConeLane c;
+    c.adj = affine_adjugate(model);
+    c.t[0] = model.c3x, c.t[1] = model.c3y, c.t[2] = model.c3z;
+    c.apex[0] = c0.x, c.apex[1] = c0.y, c.apex[2] = c0.z, c.cutoff = c0.w;
+    c.axis[0] = c1.x, c.axis[1] = c1.y, c.axis[2] = c1.z;
+    return c;
+}
+// CONE-REJECTED, in model space: w = det * (apex - the eye in model space) for a point eye (eye.e[3] != 0), adj(A) * D for parallel
+// rays along D. No division, no square root; a NaN anywhere, a zero axis, an eye at the apex, an overflowing square and a model
+// with det <= 0 or not finite all keep the cluster (include/garden_vis.h).
+__device__ __forceinline__ bool cone_rejected(const ConeLane& c, const ClusterEye& eye)
+{
+    const bool facing = c.adj.det > 0.0f && c.adj.det < __builtin_inff();
+    float w[3];
+    if (eye.e[3] != 0.0f) {  // (wave-uniform)
+        const float u0 = eye.e[0] - c.t[0], u1 = eye.e[1] - c.t[1], u2 = eye.e[2] - c.t[2];
+#pragma unroll
+        for (uint32_t r = 0; r < 3u; r++)
+            w[r] = fmaf(c.adj.det, c.apex[r], -fmaf(c.adj.j[r][0], u0, fmaf(c.adj.j[r][1], u1, c.adj.j[r][2] * u2)));
+    } else {
+#pragma unroll
+        for (uint32_t r = 0; r < 3u; r++)
+            w[r] = fmaf(c.adj.j[r][0], eye.e[0], fmaf(c.adj.j[r][1], eye.e[1], c.adj.j[r][2] * eye.e[2]));
+    }
+    const float s = fmaf(w[0], c.axis[0], fmaf(w[1], c.axis[1], w[2] * c.axis[2]));
+    const float ww = fmaf(w[0], w[0], fmaf(w[1], w[1], w[2] * w[2]));
+    const float q = s * s;
+    const float r = (c.cutoff * c.cutoff) * ww;
+    return facing && s > 0.0f && q > 0.0f && q < __builtin_inff() && q >= r;
 }
 
 // draw k of view v: the first instance the emission gave it, and how many (c_k)
@@ -310,8 +361,11 @@ __device__ __forceinline__ void locate(const ClusterLaunch& a, uint32_t c, uint3
 // cluster j of a draw follows cluster j - 1 in the index buffer, j is no multiple of kClusterRunSpan and the cluster's own interval
 // does not wrap (include/garden_vis.h). A lane holds its cluster's first and count in the .w of its two loads; the predecessor's
 // are in the lane below (lane > 0 and j > 0: candidate c - 1 is cluster j - 1 of the same draw), lane 0 loads them itself.
-template <bool kRuns>
-__device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsigned long long* link)
+// kCones (cluster_cone_test_kernel, cluster_cone_run_test_kernel): a cluster survives iff it passes the test above and is not
+// cone-rejected. The cone's two 16-byte loads are issued with the cluster's two — one more step in the chain of dependent loads is
+// what would cost — and the cone test runs behind the plane tests, in front of the Hi-Z query.
+template <bool kRuns, bool kCones>
+__device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsigned long long* link, const float4* cones, uint32_t eye_offset)
 {
     __shared__ uint32_t wave_count[kClusterBlock / 64u];
     ConstClusterArgs base = (ConstClusterArgs)__builtin_amdgcn_kernarg_segment_ptr();
@@ -329,6 +383,7 @@ __device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsig
         Corners corners;
         uint32_t j = 0, cl_first = 0, cl_count = 0;
         const float4* cl = nullptr;
+        [[maybe_unused]] ConeLane cone{};
         if (live) {
             uint32_t block, at;
             locate(a, c, tile, tiles, blocks, block, at, j);
@@ -338,12 +393,19 @@ __device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsig
                 tested = true;
                 cl = a.clusters + ((size_t)range.first + j) * 2u;
                 const float4 lo = cl[0], hi = cl[1];  // (plain loads: every draw of the geometry reads the cluster again)
+                [[maybe_unused]] float4 c0, c1;
+                if constexpr (kCones) {
+                    const float4* const cn = cones + ((size_t)range.first + j) * 2u;  // (the cone table is as long as the cluster table)
+                    c0 = cn[0], c1 = cn[1];
+                }
                 cl_first = __float_as_uint(lo.w), cl_count = __float_as_uint(hi.w);
                 const ViewPick view = pick_view(a, v);
                 const uint32_t k = at - view.first_block * kClusterBlock;
                 const float4* const rows = reinterpret_cast<const float4*>(view.model) + (size_t)k * 3u;
                 const float4 w0 = rows[0], w1 = rows[1], w2 = rows[2];  // (... and the draw's other clusters its model)
                 aabb_corners(rows_model(w0, w1, w2), lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, corners);
+                if constexpr (kCones)
+                    cone = cone_lane(rows_model(w0, w1, w2), c0, c1);
             }
         }
 #pragma unroll 1
@@ -354,8 +416,13 @@ __device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsig
             const ClusterPlanes pl = view_planes_of(base, u);
             const uint32_t plane_count = base->plane_count[u];
             const bool query = (a.hiz_views >> u) & 1u;
+            [[maybe_unused]] ClusterEye eye;
+            if constexpr (kCones)
+                eye = view_eye_of(base, eye_offset, u);
             if (mine) {
                 bool visible = !behind_frustum(corners, pl.planes, plane_count);
+                if constexpr (kCones)
+                    visible = visible && !cone_rejected(cone, eye);
                 if (query && visible) {
                     const HizDevice hz = view_hiz_of(base, u);
                     const ClusterMatrix vm = view_matrix_of(base, u);
@@ -395,7 +462,7 @@ __device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsig
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_test_kernel(const ClusterLaunch a)
 {
-    cluster_test_tiles<false>(a, nullptr);
+    cluster_test_tiles<false, false>(a, nullptr, nullptr, 0u);
 }
 
 // every word of one command position; a field offset of kNoField matches no word
@@ -630,7 +697,10 @@ __device__ __forceinline__ void find_pending(const ClusterSecondLaunch& s, uint3
     c = lo * kClusterTile + in;
 }
 
-__global__ __launch_bounds__(kClusterBlock) void cluster_second_test_kernel(const ClusterSecondLaunch s)
+// kCones (cluster_cone_second_test_kernel): behind a cone result a pending cluster survives iff the unchanged test keeps it and it is
+// not cone-rejected, with the eyes and the cone table of K1 (as cluster_test_tiles).
+template <bool kCones>
+__device__ __forceinline__ void cluster_second_test_tiles(const ClusterSecondLaunch& s, const float4* cones, uint32_t eye_offset)
 {
     __shared__ uint32_t wave_count[kClusterBlock / 64u];
     const ClusterLaunch& a = s.k;
@@ -647,6 +717,7 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_second_test_kernel(cons
         bool tested = false, survives = false;
         uint32_t v = 0;
         Corners corners;
+        [[maybe_unused]] ConeLane cone{};
         if (p < pending) {
             uint32_t tile, c, block, at, j;
             find_pending(s, p, q, ptiles, tiles, tile, c);
@@ -657,11 +728,18 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_second_test_kernel(cons
                 tested = true;
                 const float4* const cl = a.clusters + ((size_t)range.first + j) * 2u;
                 const float4 lo = cl[0], hi = cl[1];
+                [[maybe_unused]] float4 c0, c1;
+                if constexpr (kCones) {
+                    const float4* const cn = cones + ((size_t)range.first + j) * 2u;
+                    c0 = cn[0], c1 = cn[1];
+                }
                 const ViewPick view = pick_view(a, v);
                 const uint32_t k = at - view.first_block * kClusterBlock;
                 const float4* const rows = reinterpret_cast<const float4*>(view.model) + (size_t)k * 3u;
                 const float4 w0 = rows[0], w1 = rows[1], w2 = rows[2];
                 aabb_corners(rows_model(w0, w1, w2), lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, corners);
+                if constexpr (kCones)
+                    cone = cone_lane(rows_model(w0, w1, w2), c0, c1);
             }
         }
 #pragma unroll 1
@@ -672,8 +750,13 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_second_test_kernel(cons
             const ClusterPlanes pl = view_planes_of(base, u);
             const uint32_t plane_count = base->plane_count[u];
             const bool query = (a.hiz_views >> u) & 1u;  // (set: only a queried view has pending candidates)
+            [[maybe_unused]] ClusterEye eye;
+            if constexpr (kCones)
+                eye = view_eye_of(base, eye_offset, u);
             if (mine) {
                 bool visible = !behind_frustum(corners, pl.planes, plane_count);
+                if constexpr (kCones)
+                    visible = visible && !cone_rejected(cone, eye);
                 if (query && visible) {
                     const HizDevice hz = view_hiz_of(base, u);
                     const ClusterMatrix vm = view_matrix_of(base, u);
@@ -692,6 +775,11 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_second_test_kernel(cons
             s.kept_count[q] = wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3];
         __syncthreads();  // (the next pending tile rewrites the wave counts)
     }
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_second_test_kernel(const ClusterSecondLaunch s)
+{
+    cluster_second_test_tiles<false>(s, nullptr, 0u);
 }
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_second_write_kernel(const ClusterSecondLaunch s)
@@ -770,7 +858,7 @@ static_assert(offsetof(ClusterRunLaunch, k) == 0, "the per-view arguments are re
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_run_test_kernel(const ClusterRunLaunch r)
 {
-    cluster_test_tiles<true>(r.k, r.link);
+    cluster_test_tiles<true, false>(r.k, r.link, nullptr, 0u);
 }
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_run_heads_kernel(const ClusterRunLaunch r)
@@ -871,6 +959,28 @@ __global__ __launch_bounds__(kClusterBlock) void cluster_run_write_kernel(const 
     }
 }
 
+// ---- the normal-cone form (gv_pool_cull_cluster_cones) ----
+// The three test kernels above with the cone test in their conjunction; count, scans, heads and writers are the launches above as
+// they are, given the wrapped struct. The wrappers' first members keep the per-view arguments at the plain form's offsets.
+static_assert(offsetof(ClusterConeLaunch, k) == 0 && offsetof(ClusterConeRunLaunch, r) == 0 && offsetof(ClusterConeSecondLaunch, s) == 0,
+              "the per-view arguments are read at the plain form's offsets");
+static_assert(sizeof(ClusterEye) == sizeof(float[4]), "an eye is four floats of the argument block");
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_cone_test_kernel(const ClusterConeLaunch c)
+{
+    cluster_test_tiles<false, true>(c.k, nullptr, c.cone.cones, (uint32_t)(offsetof(ClusterConeLaunch, cone) + offsetof(ClusterConeArgs, eyes)));
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_cone_run_test_kernel(const ClusterConeRunLaunch c)
+{
+    cluster_test_tiles<true, true>(c.r.k, c.r.link, c.cone.cones, (uint32_t)(offsetof(ClusterConeRunLaunch, cone) + offsetof(ClusterConeArgs, eyes)));
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_cone_second_test_kernel(const ClusterConeSecondLaunch c)
+{
+    cluster_second_test_tiles<true>(c.s, c.cone.cones, (uint32_t)(offsetof(ClusterConeSecondLaunch, cone) + offsetof(ClusterConeArgs, eyes)));
+}
+
 // the fixed grid of the test and write launches: kClusterGridPerCu workgroups per compute unit of the current device
 uint32_t walk_grid()
 {
@@ -966,6 +1076,24 @@ hipError_t launch_cluster_second_scan_survivors(const ClusterSecondLaunch& launc
 hipError_t launch_cluster_second_write(const ClusterSecondLaunch& launch, hipStream_t stream)
 {
     hipLaunchKernelGGL(cluster_second_write_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_cone_test(const ClusterConeLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_cone_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_cone_run_test(const ClusterConeRunLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_cone_run_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_cone_second_test(const ClusterConeSecondLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_cone_second_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
     return hipGetLastError();
 }
 

@@ -77,7 +77,12 @@ int gv_pool_cull_clusters_second_phase(GvCtx* ctx, uint32_t pool_id, uint32_t fl
     launch.totals = S.d_totals.ptr;
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_second_count(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_second_scan_pending(launch, ctx->stream));
-    GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_second_test(launch, ctx->stream));
+    if (K.second_test) {  // behind gv_pool_cull_cluster_cones: the same conjunction, with the kept launch's eyes and the cone table
+        if (int rc = K.second_test(ctx, K, launch))
+            return rc;
+    } else {
+        GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_second_test(launch, ctx->stream));
+    }
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_second_scan_survivors(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_second_write(launch, ctx->stream));
     S.target = launch.k.dst;

@@ -30,6 +30,7 @@
 #include "gv_cluster_kernels.hpp"
 #include "gv_cluster_second_kernels.hpp"
 #include "gv_cluster_run_kernels.hpp"
+#include "gv_cluster_cone_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -366,7 +367,8 @@ struct PoolState {
     } commands;
     // gv_pool_bind_clusters / gv_pool_cull_clusters: the tables as bound and the last call's commands, buffers of their own — no cull
     // result, no instance data and no per-draw command buffer (Commands above) is touched. Header-only: no other host source calls
-    // gv_clusters.cpp but gv_cluster_runs.cpp, the run form, which shares its body (cull_clusters below).
+    // gv_clusters.cpp but gv_cluster_runs.cpp, the run form, and gv_cluster_cones.cpp, the normal-cone form, which share its body
+    // (cull_clusters below).
     struct Clusters {
         bool bound = false;
         uint32_t range_count = 0, cluster_count = 0;
@@ -379,6 +381,9 @@ struct PoolState {
         DeviceBuf<unsigned long long> d_survive;
         DeviceBuf<unsigned long long> d_link, d_head;  // gv_pool_cull_cluster_runs: a link and a head bit per candidate ...
         DeviceBuf<uint32_t> d_head_count;              // ... and the heads per tile
+        // gv_pool_bind_cluster_cones (gv_cluster_cones.cpp): one cone per entry of the cluster table; dropped with the tables
+        bool cones_bound = false;
+        DeviceBuf<GvClusterCone> d_cones;
         PinnedBuf<uint8_t> h_data;         // staging of gv_pool_cluster_commands_fetch
         PinnedBuf<uint32_t> h_counts;
         // the last call (views 0: none since the pool's last gv_cull, instance emission or gv_pool_bind_clusters)
@@ -392,6 +397,11 @@ struct PoolState {
         uint64_t candidate_bound = 0;
         uint32_t pyramid[kMaxInstanceViews] = {};
         bool rebound = false;
+        // the last call was gv_pool_cull_cluster_cones (second_test non-NULL): its eyes, kept with the launch, and the test launch
+        // the second phase enqueues in place of its own to apply the same conjunction (gv_cluster_cones.cpp: the sources of the
+        // other forms name no cone launch)
+        int (*second_test)(GvCtx* ctx, Clusters& K, const ClusterSecondLaunch& launch) = nullptr;
+        float eyes[kMaxInstanceViews][4] = {};
         // gv_pool_cull_clusters_second_phase (gv_clusters_second.cpp): the last call's commands and scratch, buffers of their own —
         // nothing of K1 above is written. views 0: none since K1 (it ends wherever K1 ends, and at a new K1)
         struct Second {
@@ -414,7 +424,7 @@ struct PoolState {
         {
             d_ranges.release(), d_clusters.release(), d_data.release(), d_counts.release(), d_draw_geometry.release(), d_draw_local.release();
             d_block_total.release(), d_block_tested.release(), d_totals.release(), d_tile_count.release(), d_tile_block.release(), d_survive.release();
-            d_link.release(), d_head.release(), d_head_count.release();
+            d_link.release(), d_head.release(), d_head_count.release(), d_cones.release();
             h_data.release(), h_counts.release(), second.release();
         }
     } clusters;
@@ -1158,12 +1168,26 @@ bool release_record_target(PoolState::RecordTarget& target);            // false
 int copy_shard_of_pool(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, void* dst_device, uint32_t capacity, uint32_t index_base);
 
 // gv_clusters.cpp
-// The body of both forms of the cluster cull (gv_pool_cull_clusters there, gv_pool_cull_cluster_runs in gv_cluster_runs.cpp): every
-// check, the bound, the target, the shared scratch and the bookkeeping. `enqueue` reserves what scratch the form adds and enqueues
-// its launches — launch is complete, tiles = ceil(B / kClusterTile); `fn` names the entry point in messages.
-typedef int (*ClusterCullLaunches)(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles);
-int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullLaunches enqueue, const char* zone_name, uint32_t pool_id, uint32_t flags, uint32_t region_commands,
-                  void* dst_device, size_t capacity_bytes);
+// The body of every form of the cluster cull (gv_pool_cull_clusters there, gv_pool_cull_cluster_runs in gv_cluster_runs.cpp,
+// gv_pool_cull_cluster_cones in gv_cluster_cones.cpp): every check, the bound, the target, the shared scratch and the bookkeeping.
+// `forms` holds per form what reserves the scratch the form adds and enqueues its launches — launch is complete, tiles = ceil(B /
+// kClusterTile), eyes as below; `fn` names the entry point in messages. `allowed_flags`: the flag bits the entry point takes;
+// GV_CLUSTERS_RUNS among them picks forms.runs. `cones` (NULL: the forms without the cone test): the caller's eyes, checked here
+// against the views of E and kept with the launch.
+typedef int (*ClusterCullLaunches)(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, const GvClusterEye* eyes);
+struct ClusterCullForms {
+    ClusterCullLaunches survivors;  // one command per survivor
+    ClusterCullLaunches runs;       // one command per run (NULL: the entry point has no run flag)
+    int (*second_test)(GvCtx* ctx, PoolState::Clusters& K, const ClusterSecondLaunch& launch);  // PoolState::Clusters::second_test behind the call
+};
+struct ClusterConeRequest {
+    const GvClusterEye* eyes;
+    uint32_t eye_count;
+};
+// gv_cluster_runs.cpp: the run form's scratch reserved and its launch struct around `launch` (the cone form's run launches share it)
+int reserve_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, ClusterRunLaunch* run);
+int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullForms forms, uint32_t allowed_flags, const ClusterConeRequest* cones, const char* zone_name,
+                  uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes);
 
 // gv_mirror.cpp
 // brings the device mirror up to date with the bound pools + dirty marks: per side a full rebuild, or growth and the dirty

@@ -208,6 +208,24 @@ __device__ __forceinline__ Inv33 affine_inverse(const Mat34& a)
     r.m[2][0] = j20 * rdet; r.m[2][1] = j21 * rdet; r.m[2][2] = j22 * rdet;
     return r;
 }
+// adj(A) and det A, by exactly the expressions of affine_inverse above and without its reciprocal: what the normal-cone test of the
+// cluster cull carries an eye into model space with. Row-major: j[r][c].
+struct Adj33 {
+    float j[3][3];
+    float det;
+};
+__device__ __forceinline__ Adj33 affine_adjugate(const Mat34& a)
+{
+    const float a00 = a.c0x, a10 = a.c0y, a20 = a.c0z;
+    const float a01 = a.c1x, a11 = a.c1y, a21 = a.c1z;
+    const float a02 = a.c2x, a12 = a.c2y, a22 = a.c2z;
+    Adj33 r;
+    r.j[0][0] = cross_term(a11, a22, a12, a21); r.j[0][1] = cross_term(a02, a21, a01, a22); r.j[0][2] = cross_term(a01, a12, a02, a11);
+    r.j[1][0] = cross_term(a12, a20, a10, a22); r.j[1][1] = cross_term(a00, a22, a02, a20); r.j[1][2] = cross_term(a02, a10, a00, a12);
+    r.j[2][0] = cross_term(a10, a21, a11, a20); r.j[2][1] = cross_term(a01, a20, a00, a21); r.j[2][2] = cross_term(a00, a11, a01, a10);
+    r.det = fmaf(a00, r.j[0][0], fmaf(a01, r.j[1][0], a02 * r.j[2][0]));
+    return r;
+}
 __device__ __forceinline__ float row_dot(const float (&r)[3], float x, float y, float z) { return fmaf(r[0], x, fmaf(r[1], y, r[2] * z)); }
 
 // One slab of raycast2: the axis interval [lo, hi] of the ray parameter, or for d == 0 the whole line when lo_box <= o <= hi_box

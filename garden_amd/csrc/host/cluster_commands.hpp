@@ -10,6 +10,10 @@
 // are fetched into host copies (getBase / getShadow) unless setFetch(false). A renderer submits them as one indirect draw per pass:
 // drawCount from counts[] (packed) or the region size (regions: no count has to be read back).
 //
+// With setCones a system's cluster culls also reject the clusters whose normal cone faces away from the pass's eye
+// (gv_pool_cull_cluster_cones): the light pass is seen from the camera — the point eye (0, 0, 0, 1) of the camera-relative records —
+// and a cascade along its light's direction (cascadeEye). setRuns, setMode and the targets combine with it.
+//
 // In a two-phase frame cullSecond(p, ...) re-tests what a system's last cluster cull left out against the rebuilt pyramid
 // (gv_pool_cull_clusters_second_phase), into host copies of its own (getBaseSecond / getShadowSecond).
 //
@@ -39,6 +43,9 @@ private:
     struct PerSystem {
         bool enabled = false;  // clusters are bound
         bool runs = false;     // adjacent surviving clusters are merged into one command (gv_pool_cull_cluster_runs)
+        bool cones = false;    // normal cones are bound: the culls are gv_pool_cull_cluster_cones
+        GvClusterEye baseEye{{0.0f, 0.0f, 0.0f, 1.0f}};  // the camera, in the camera-relative space of the records
+        std::vector<GvClusterEye> shadowEyes;            // by the shadow system's pass number; a pass beyond them: all zero, no cone test
         uint32_t flags = 0, region = 0;
         void *baseDevice = nullptr, *shadowDevice = nullptr;
         size_t baseBytes = 0, shadowBytes = 0;
@@ -71,7 +78,26 @@ public:
     {
         check(gv_pool_bind_clusters(system->getContext(), p, ranges, rangeCount, clusters, clusterCount), "gv_pool_bind_clusters");
         of(p).enabled = ranges != nullptr;
+        of(p).cones = false;  // (the library drops the cones with the table they belonged to)
     }
+    // the normal cones of mesh system p's clusters, one per entry of the cluster table and in its order (meshopt_Bounds' cone_apex /
+    // cone_axis / cone_cutoff as they are); copied (gv_pool_bind_cluster_cones). NULL: no cones, the culls run as before. Call it
+    // behind setClusters.
+    void setCones(uint32_t p, const GvClusterCone* cones, uint32_t count)
+    {
+        check(gv_pool_bind_cluster_cones(system->getContext(), p, cones, count), "gv_pool_bind_cluster_cones");
+        of(p).cones = cones != nullptr;
+    }
+    // the eyes of mesh system p's passes: the light pass's (default: the camera, (0, 0, 0, 1)) and one per shadow pass, indexed by the
+    // shadow system's pass number (cascadeEye of the pass's light direction; a pass without one gets no cone test)
+    void setEyes(uint32_t p, const GvClusterEye& baseEye, const GvClusterEye* shadowEyes, uint32_t shadowEyeCount)
+    {
+        of(p).baseEye = baseEye;
+        of(p).shadowEyes.assign(shadowEyes, shadowEyes + shadowEyeCount);
+    }
+    // the eye of a cascade: parallel rays that travel along the light direction given to csm::calcLightViewProj (csm_lite.hpp looks
+    // from center - lightDir to center)
+    static GvClusterEye cascadeEye(const f32x4& lightDir) { return GvClusterEye{{lightDir.x, lightDir.y, lightDir.z, 0.0f}}; }
     // flags: 0 or GV_CLUSTERS_FRUSTUM_ONLY; region: 0 packs the passes' commands, R > 0 gives every pass R positions
     void setMode(uint32_t p, uint32_t flags, uint32_t region)
     {
@@ -91,8 +117,9 @@ public:
     void setFetch(bool on) noexcept { fetch = on; }
 
     // GpuDrawCommands::emit calls this behind each of its command emissions for mesh system p (shadow: the one behind the shadow
-    // array) with the stride of the system's command struct; also callable behind an instance emission of one's own
-    void cull(uint32_t p, bool shadow, uint32_t stride)
+    // array) with the stride of the system's command struct; also callable behind an instance emission of one's own. eyes (with
+    // setCones only): one eye per view of that emission, in its order, in place of the ones setEyes declared.
+    void cull(uint32_t p, bool shadow, uint32_t stride, const GvClusterEye* eyes = nullptr, uint32_t eyeCount = 0)
     {
         PerSystem& s = of(p);
         if (!s.enabled)
@@ -102,7 +129,21 @@ public:
         GvCtx* ctx = system->getContext();
         void* const device = shadow ? s.shadowDevice : s.baseDevice;
         const size_t bytes = shadow ? s.shadowBytes : s.baseBytes;
-        if (s.runs)
+        if (s.cones) {
+            std::vector<GvClusterEye> declared;
+            if (!eyes) {  // the light pass, or the system's culled shadow passes in pass order
+                if (!shadow)
+                    declared.push_back(s.baseEye);
+                else
+                    for (int8_t pass : system->getSystemPasses(p))
+                        if (pass >= 0)
+                            declared.push_back((size_t)pass < s.shadowEyes.size() ? s.shadowEyes[(size_t)pass] : GvClusterEye{{0.0f, 0.0f, 0.0f, 0.0f}});
+                eyes = declared.data();
+                eyeCount = (uint32_t)declared.size();
+            }
+            check(gv_pool_cull_cluster_cones(ctx, p, s.flags | (s.runs ? GV_CLUSTERS_RUNS : 0u), eyes, eyeCount, s.region, device, bytes),
+                  "gv_pool_cull_cluster_cones");
+        } else if (s.runs)
             check(gv_pool_cull_cluster_runs(ctx, p, s.flags, s.region, device, bytes), "gv_pool_cull_cluster_runs");
         else
             check(gv_pool_cull_clusters(ctx, p, s.flags, s.region, device, bytes), "gv_pool_cull_clusters");
@@ -134,6 +175,8 @@ public:
     // list. shadow: the last cull was the one behind the shadow array (it picks the targets of setSecondTargets and the host copy).
     // Nothing of the first cull changes. The newly visible DRAWS of GpuSecondPhase::run are an ordinary view: emit it and call
     // cull(). Opt-in: a tick that does not call this runs as before. Emitted::tested holds the pending clusters re-tested per view.
+    // Behind a cull with cones the library applies the same cone test with that cull's eyes — it kept them, none is passed here — and
+    // the cone-rejected clusters of a queried pass are among the pending ones: re-tested, rejected again, counted in tested.
     void cullSecond(uint32_t p, bool shadow, uint32_t stride)
     {
         PerSystem& s = of(p);

@@ -124,6 +124,7 @@ GV_MAX_CLUSTERS = 1 << 22
 GV_MAX_GEOMETRY_CLUSTERS = 65535
 GV_CLUSTERS_FRUSTUM_ONLY = 1
 GV_CLUSTER_RUN_SPAN = 256
+GV_CLUSTERS_RUNS = 2  # gv_pool_cull_cluster_cones only
 
 
 class GvCluster(C.Structure):
@@ -136,6 +137,8 @@ class GvClusterRange(C.Structure):
 
 CLUSTER_DTYPE = np.dtype([("box_min", np.float32, (3,)), ("first", np.uint32), ("box_max", np.float32, (3,)), ("count", np.uint32)])
 CLUSTER_RANGE_DTYPE = np.dtype([("first", np.uint32), ("count", np.uint32)])
+# GvClusterCone: meshopt_Bounds' cone_apex / cone_axis / cone_cutoff as they are; `reserved` is not read
+CLUSTER_CONE_DTYPE = np.dtype([("apex", np.float32, (3,)), ("cutoff", np.float32), ("axis", np.float32, (3,)), ("reserved", np.uint32)])
 
 
 GV_MAX_LOD_LEVELS = 8
@@ -269,7 +272,7 @@ EXPORTS = [
     "gv_pool_draw_commands_fetch",
     "gv_pool_bind_clusters", "gv_pool_cull_clusters", "gv_pool_cluster_commands_device", "gv_pool_cluster_commands_fetch",
     "gv_pool_cull_clusters_second_phase", "gv_pool_cluster_second_commands_device", "gv_pool_cluster_second_commands_fetch",
-    "gv_pool_cull_cluster_runs",
+    "gv_pool_cull_cluster_runs", "gv_pool_bind_cluster_cones", "gv_pool_cull_cluster_cones",
     "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
     "gv_pool_group_draws",
     "gv_pool_cull_second_phase",
@@ -418,6 +421,8 @@ def load():
     lib.gv_pool_cluster_second_commands_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
     lib.gv_pool_cluster_second_commands_fetch.argtypes = [P, u32, P, sz, C.POINTER(u32), u32]
     lib.gv_pool_cull_cluster_runs.argtypes = [P, u32, u32, u32, P, sz]
+    lib.gv_pool_bind_cluster_cones.argtypes = [P, u32, P, u32]
+    lib.gv_pool_cull_cluster_cones.argtypes = [P, u32, u32, P, u32, u32, P, sz]
     lib.gv_pool_bind_lod.argtypes = [P, u32, P, u32, u32, C.POINTER(GvLodGeometry), u32]
     lib.gv_pool_select_lods.argtypes = [P, u32, C.POINTER(C.c_float), u32]
     lib.gv_pool_lods_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
@@ -1104,15 +1109,33 @@ class GpuVisibility:
         self._check(self.lib.gv_pool_bind_clusters(self.ctx, pool_id, C.cast(r.ctypes.data, C.POINTER(GvClusterRange)), len(r),
                                                    C.cast(c.ctypes.data, C.POINTER(GvCluster)), len(c)))
 
-    def cull_clusters(self, pool_id, frustum_only=False, region=0, device=None, runs=False):
+    def bind_cluster_cones(self, pool_id, cones):
+        """gv_pool_bind_cluster_cones: one normal cone (CLUSTER_CONE_DTYPE) per entry of the bound cluster table, copied at the call;
+        None removes the binding."""
+        if cones is None:
+            self._check(self.lib.gv_pool_bind_cluster_cones(self.ctx, pool_id, None, 0))
+            return
+        c = np.ascontiguousarray(cones)
+        assert c.dtype == CLUSTER_CONE_DTYPE and c.dtype.itemsize == 32
+        self._check(self.lib.gv_pool_bind_cluster_cones(self.ctx, pool_id, c.ctypes.data, len(c)))
+
+    def cull_clusters(self, pool_id, frustum_only=False, region=0, device=None, runs=False, eyes=None):
         """gv_pool_cull_clusters: one indirect command per surviving cluster of every draw of the pool's last instance emission
         (draws without clusters are drawn whole), on the context's stream. frustum_only: no Hi-Z query even for views that named a
         pyramid. region: 0 packs the views' commands, R > 0 gives every view R positions. device: None for the library's own
         buffer, or (device pointer, capacity in bytes) of caller-owned device memory. runs: gv_pool_cull_cluster_runs — the same
-        decisions, one command per run of adjacent surviving clusters (at most GV_CLUSTER_RUN_SPAN of them)."""
+        decisions, one command per run of adjacent surviving clusters (at most GV_CLUSTER_RUN_SPAN of them). eyes: an [m, 4]
+        float32 array, one eye per view of the emission — gv_pool_cull_cluster_cones: a cluster whose bound normal cone faces away
+        from its view's eye is rejected too (w != 0: a point eye, w == 0: parallel rays along xyz, all zero: no cone test); it
+        combines with runs and frustum_only."""
         ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
-        call = self.lib.gv_pool_cull_cluster_runs if runs else self.lib.gv_pool_cull_clusters
-        self._check(call(self.ctx, pool_id, GV_CLUSTERS_FRUSTUM_ONLY if frustum_only else 0, int(region), ptr, cap))
+        if eyes is not None:
+            e = np.ascontiguousarray(eyes, np.float32).reshape(-1, 4)
+            flags = (GV_CLUSTERS_FRUSTUM_ONLY if frustum_only else 0) | (GV_CLUSTERS_RUNS if runs else 0)
+            self._check(self.lib.gv_pool_cull_cluster_cones(self.ctx, pool_id, flags, e.ctypes.data, len(e), int(region), ptr, cap))
+        else:
+            call = self.lib.gv_pool_cull_cluster_runs if runs else self.lib.gv_pool_cull_clusters
+            self._check(call(self.ctx, pool_id, GV_CLUSTERS_FRUSTUM_ONLY if frustum_only else 0, int(region), ptr, cap))
         stride = self._command_stride[pool_id]
         self._cluster_commands = getattr(self, "_cluster_commands", {})
         self._cluster_commands[pool_id] = (stride, int(region), None if device is None else cap // stride)

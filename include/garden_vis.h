@@ -715,6 +715,70 @@ int gv_pool_cluster_second_commands_fetch(GvCtx* ctx, uint32_t pool_id, void* ds
 int gv_pool_cull_cluster_runs(GvCtx* ctx, uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device,
                               size_t capacity_bytes);
 
+/* ---- the cluster cull with normal-cone backface rejection ----
+ * On a closed mesh about half of the clusters that pass the frustum face away from the viewer; neither the frustum test nor the
+ * pyramid removes them. A pool may bind one normal CONE per entry of its cluster table (meshoptimizer's meshopt_Bounds cone_apex /
+ * cone_axis / cone_cutoff fit as they are), and gv_pool_cull_cluster_cones makes the decisions of gv_pool_cull_clusters with one
+ * more rejection (this build's rule, the reference has no clusters). A triangle faces away from an eye
+ * exactly when the eye lies behind its plane, and an affine map with positive determinant keeps that relation: the cone is tested IN
+ * MODEL SPACE. The eye is carried there with the adjugate of the draw's 3x3 block; no normal is transformed, nothing is divided, no
+ * root is taken, and non-uniform scale needs no special case.
+ * An EYE is given per view of E, in the records' space (bakedModel as delivered: relative to the cull's camera_position):
+ *   eye[3] != 0: a point eye P = eye[0..2]; the main camera is (0, 0, 0, 1).
+ *   eye[3] == 0: parallel rays that travel along D = eye[0..2]; a shadow cascade passes the light's direction.
+ *   An all-zero eye switches the cone test off for that view (by the rule below, no special case).
+ * With E, v, k, j, M_k as for gv_pool_cull_clusters, the draw's 12 bakedModel floats f (a_rc = f[3c + r], t_r = f[9 + r]), and
+ * cone = cones[range_k.first + j], in fp32, every step as written (fmaf: one rounding):
+ *   j_rc: the nine adjugate entries, each p * q - r * s as fmaf(p, q, -(r * s)):
+ *     j00 = a11 a22 - a12 a21, j01 = a02 a21 - a01 a22, j02 = a01 a12 - a02 a11,
+ *     j10 = a12 a20 - a10 a22, j11 = a00 a22 - a02 a20, j12 = a02 a10 - a00 a12,
+ *     j20 = a10 a21 - a11 a20, j21 = a01 a20 - a00 a21, j22 = a00 a11 - a01 a10  (the expressions of gv_pick's affine inverse);
+ *   det = fmaf(a00, j00, fmaf(a01, j10, a02 * j20));  facing = det > 0 && det < +inf.
+ *   Point eye, r = 0, 1, 2: u_r = P_r - t_r; w_r = fmaf(det, apex_r, -fmaf(j_r0, u_0, fmaf(j_r1, u_1, j_r2 * u_2))).
+ *   Direction eye: w_r = fmaf(j_r0, D_0, fmaf(j_r1, D_1, j_r2 * D_2)).
+ *   s = fmaf(w_0, axis_0, fmaf(w_1, axis_1, w_2 * axis_2)); ww = fmaf(w_0, w_0, fmaf(w_1, w_1, w_2 * w_2));
+ *   q = s * s; r = (cutoff * cutoff) * ww.
+ *   Cluster j of draw k is CONE-REJECTED in view v iff facing && s > 0 && q > 0 && q < +inf && q >= r.
+ * w is det * (apex - the eye in model space): the test is meshoptimizer's dot(normalize(apex - eye), axis) >= cutoff multiplied
+ * through by positive quantities. Consequences: a NaN anywhere keeps the cluster; a zero axis (meshoptimizer's degenerate cone)
+ * keeps it; an eye at the apex keeps it; an overflowing q keeps it; a mirrored, singular or non-finite model (det <= 0, inf, NaN)
+ * is never cone-rejected — a mirrored model flips the winding, and what the renderer does with that is not ours to guess; cutoff
+ * enters squared, so its sign is not read (a cutoff below 0 names a cone wider than a half-space: give such a cluster a zero axis).
+ * The rule is bit-defined but NOT padded: the tool that builds the cones carries the rounding margin in cutoff.
+ *   A cluster SURVIVES iff it survives gv_pool_cull_clusters' unchanged test and is not cone-rejected.
+ * Whole draws, void draws, the order, the commands, placement, counts[v] and counts[m + v] (a cone-rejected cluster counts as
+ * tested) are exactly those of gv_pool_cull_clusters. */
+typedef struct GvClusterCone {   /* 32 bytes */
+    float apex[3];  float cutoff;
+    float axis[3];  uint32_t reserved;   /* not read */
+} GvClusterCone;
+typedef struct GvClusterEye { float eye[4]; } GvClusterEye;   /* one per view of E */
+#define GV_CLUSTERS_RUNS 2u   /* gv_pool_cull_cluster_cones only: write runs, as gv_pool_cull_cluster_runs */
+/* Binds cones[0 .. cone_count), parallel to the pool's cluster table; copied at the call, the bytes counted in upload_bytes. NULL /
+ * 0 removes the binding. Either way a cluster result the pool holds ends. gv_pool_bind_clusters (a new table, or removal) also drops
+ * the cones. Cone values are not checked. GV_E_ARG: a pool out of range, a pointer without a count or a count without a pointer,
+ * cone_count different from the bound cluster_count. GV_E_STATE: no cluster binding. */
+int gv_pool_bind_cluster_cones(GvCtx* ctx, uint32_t pool_id, const GvClusterCone* cones, uint32_t cone_count);
+/* The cluster commands of the views of E under the rule above. eyes[0 .. eye_count): one per view of E, in E's order, copied at the
+ * call. flags: a subset of {GV_CLUSTERS_FRUSTUM_ONLY, GV_CLUSTERS_RUNS}; only this call takes GV_CLUSTERS_RUNS (gv_pool_cull_clusters
+ * and gv_pool_cull_cluster_runs refuse it). Without GV_CLUSTERS_RUNS one command per survivor, in FIVE kernel launches; with it the
+ * survivors are written as the runs of gv_pool_cull_cluster_runs — the same LINKED / HEAD / RUN rule over these decisions — in SIX.
+ * The launches are those of the form it takes, the test launch carrying the cone test in front of the Hi-Z query; counted under
+ * GvStats::launches[GV_K_EMIT]; the scratch is that of the form it takes. Placement, targets, capacity, counts: as the form it takes.
+ * The call IS a cluster cull of the pool: its result replaces the pool's cluster result and is replaced by the next one of any form;
+ * gv_pool_cluster_commands_device / _fetch serve it, and it ends where a cluster result ends (and at gv_pool_bind_cluster_cones).
+ * gv_pool_cull_clusters_second_phase behind a cone result applies the same conjunction — the unchanged test against the pyramid as
+ * it stands at that call, and the cone test with this call's eyes and the cone table. Its pending set is defined as before (tested,
+ * not kept, in a queried view), so CONE-REJECTED CLUSTERS ARE PENDING: they are re-tested, rejected again, counted in its
+ * counts[m + v], and cost one cone test each. Behind a plain or a run result the second phase is unchanged.
+ * Errors: those of gv_pool_cull_clusters, plus GV_E_ARG: eyes NULL, eye_count different from the views of E; GV_E_STATE: no cone
+ * binding. A refused call changes nothing.
+ * Not built: cones packed into 16 bytes (meshoptimizer's cone_axis_s8 / cone_cutoff_s8), a per-view count of cone-rejected
+ * clusters, leaving cone-rejected clusters out of the second phase's pending set (a second bit per candidate), cones for mirrored
+ * models, eyes derived from view_proj. */
+int gv_pool_cull_cluster_cones(GvCtx* ctx, uint32_t pool_id, uint32_t flags, const GvClusterEye* eyes, uint32_t eye_count,
+                               uint32_t region_commands, void* dst_device, size_t capacity_bytes);
+
 /* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
  * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
  * the record's componentOffset. A pool may bind those bytes (its PAYLOAD: up to GV_MAX_PAYLOAD_FIELDS fields, GV_MAX_PAYLOAD_BYTES
