@@ -14,20 +14,12 @@ static_assert(sizeof(GvClusterCone) == sizeof(ClusterCone) && sizeof(GvClusterCo
 static_assert(sizeof(GvClusterEye) == sizeof(float[4]), "an eye is four floats of the argument block");
 static_assert(GV_CLUSTERS_RUNS == 2u && (GV_CLUSTERS_RUNS & GV_CLUSTERS_FRUSTUM_ONLY) == 0, "two flag bits");
 
-ClusterConeArgs cone_args(const PoolState::Clusters& K, const ClusterLaunch& launch, const GvClusterEye* eyes)
-{
-    ClusterConeArgs args{};
-    args.cones = reinterpret_cast<const float4*>(K.d_cones.ptr);
-    memcpy(args.eyes, eyes, (size_t)launch.views * sizeof(GvClusterEye));  // (the views behind them: all-zero eyes, never read)
-    return args;
-}
-
 // the plain form's five launches, the test with the cone in it
-int write_cone_survivors(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t, const GvClusterEye* eyes)
+int write_cone_survivors(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t, const GvClusterEye* eyes, const GvClusterLodView*)
 {
     ClusterConeLaunch cone{};
     cone.k = launch;
-    cone.cone = cone_args(K, launch, eyes);
+    cone.cone = cluster_cone_args(K, launch.views, eyes);
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_count(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_candidates(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_cone_test(cone, ctx->stream));
@@ -37,12 +29,12 @@ int write_cone_survivors(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch
 }
 
 // the run form's six launches likewise
-int write_cone_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, const GvClusterEye* eyes)
+int write_cone_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, const GvClusterEye* eyes, const GvClusterLodView*)
 {
     ClusterConeRunLaunch cone{};
     if (int rc = reserve_runs(ctx, K, launch, tiles, &cone.r))
         return rc;
-    cone.cone = cone_args(K, launch, eyes);
+    cone.cone = cluster_cone_args(K, launch.views, eyes);
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_count(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_candidates(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_cone_run_test(cone, ctx->stream));
@@ -57,8 +49,7 @@ int cone_second_test(GvCtx* ctx, PoolState::Clusters& K, const ClusterSecondLaun
 {
     ClusterConeSecondLaunch cone{};
     cone.s = launch;
-    cone.cone.cones = reinterpret_cast<const float4*>(K.d_cones.ptr);
-    memcpy(cone.cone.eyes, K.eyes, sizeof(cone.cone.eyes));
+    cone.cone = cluster_cone_args(K, kMaxInstanceViews, K.eyes);
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_cone_second_test(cone, ctx->stream));
     return GV_OK;
 }

@@ -11,7 +11,7 @@ namespace {
 
 static_assert(kClusterRunSpan == GV_CLUSTER_RUN_SPAN, "the writer's walk is bounded by the header's span");
 
-int write_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, const GvClusterEye*)
+int write_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, const GvClusterEye*, const GvClusterLodView*)
 {
     ClusterRunLaunch run{};
     if (int rc = reserve_runs(ctx, K, launch, tiles, &run))

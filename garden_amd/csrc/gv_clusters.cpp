@@ -12,7 +12,7 @@ namespace {
 constexpr uint64_t kOwnTargetMaxBytes = 1ull << 31;  // a library-owned target beyond this is refused: the caller sizes one for what is drawn
 
 // the plain form's five launches: one command per survivor
-int write_survivors(GvCtx* ctx, PoolState::Clusters&, const ClusterLaunch& launch, size_t, const GvClusterEye*)
+int write_survivors(GvCtx* ctx, PoolState::Clusters&, const ClusterLaunch& launch, size_t, const GvClusterEye*, const GvClusterLodView*)
 {
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_count(launch, ctx->stream));
     GV_LAUNCH(ctx, GV_K_EMIT, launch_cluster_scan_candidates(launch, ctx->stream));
@@ -27,7 +27,7 @@ int write_survivors(GvCtx* ctx, PoolState::Clusters&, const ClusterLaunch& launc
 namespace gv {
 
 int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullForms forms, uint32_t allowed_flags, const ClusterConeRequest* cones, const char* zone_name,
-                  uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes)
+                  uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes, const ClusterLodRequest* lods)
 {
     if (!ctx)
         return GV_E_ARG;
@@ -37,6 +37,8 @@ int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullForms forms, uint32_t a
         return ctx->fail(GV_E_ARG, "%s: unknown flags 0x%x", fn, flags);
     if (cones && !cones->eyes)
         return ctx->fail(GV_E_ARG, "%s: eyes is NULL (one GvClusterEye per view of the emission)", fn);
+    if (lods && !lods->views)
+        return ctx->fail(GV_E_ARG, "%s: views is NULL (one GvClusterLodView per view of the emission)", fn);
     const ClusterCullLaunches enqueue = (flags & GV_CLUSTERS_RUNS) ? forms.runs : forms.survivors;
     if (dst_device && (uintptr_t)dst_device % 16 != 0)
         return ctx->fail(GV_E_ARG, "%s: dst_device must be 16-byte aligned", fn);
@@ -49,6 +51,8 @@ int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullForms forms, uint32_t a
         return ctx->fail(GV_E_STATE, "%s: pool %u has no clusters bound (gv_pool_bind_clusters)", fn, pool_id);
     if (cones && !K.cones_bound)
         return ctx->fail(GV_E_STATE, "%s: pool %u has no cluster cones bound (gv_pool_bind_cluster_cones)", fn, pool_id);
+    if (lods && !K.lods_bound)
+        return ctx->fail(GV_E_STATE, "%s: pool %u has no cluster LOD table bound (gv_pool_bind_cluster_lods)", fn, pool_id);
     if (!L.stride)
         return ctx->fail(GV_E_STATE, "%s: pool %u has no command layout (gv_pool_set_command_layout)", fn, pool_id);
     if (!G.bound)
@@ -58,6 +62,12 @@ int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullForms forms, uint32_t a
     const uint32_t m = I.views;
     if (cones && cones->eye_count != m)
         return ctx->fail(GV_E_ARG, "%s: %u eyes for the %u views of pool %u's emission (one each)", fn, cones->eye_count, m, pool_id);
+    if (lods && lods->view_count != m)
+        return ctx->fail(GV_E_ARG, "%s: %u LOD views for the %u views of pool %u's emission (one each)", fn, lods->view_count, m, pool_id);
+    for (uint32_t k = 0; lods && k < m; k++)
+        if (!(lods->views[k].scale >= 0.0f) || !(lods->views[k].near_distance >= 0.0f))  // (negative or NaN)
+            return ctx->fail(GV_E_ARG, "%s: LOD view %u has scale %g and near_distance %g (neither negative nor NaN)", fn, k,
+                             (double)lods->views[k].scale, (double)lods->views[k].near_distance);
     if ((uint64_t)m * region_commands > UINT32_MAX)
         return ctx->fail(GV_E_ARG, "%s: %u regions of %u commands are more positions than 32 bits hold", fn, m, region_commands);
     const bool frustum_only = (flags & GV_CLUSTERS_FRUSTUM_ONLY) != 0;
@@ -146,11 +156,13 @@ int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullForms forms, uint32_t a
     launch.tile_block = K.d_tile_block.ptr;
     launch.survive = K.d_survive.ptr;
     launch.counts = K.d_counts.ptr;
-    if (int rc = enqueue(ctx, K, launch, tiles, cones ? cones->eyes : nullptr))
+    if (int rc = enqueue(ctx, K, launch, tiles, cones ? cones->eyes : nullptr, lods ? lods->views : nullptr))
         return rc;
     K.second_test = forms.second_test;  // (cones: the second phase behind this result applies the same conjunction, with these eyes)
     if (cones)
         memcpy(K.eyes, cones->eyes, (size_t)m * sizeof(GvClusterEye));
+    if (lods)
+        memcpy(K.lod_views, lods->views, (size_t)m * sizeof(GvClusterLodView));
     K.second.views = 0;  // the bits and prefixes a second phase read are replaced
     K.launch = launch;   // gv_pool_cull_clusters_second_phase tests with the same arguments
     K.candidate_bound = bound;
@@ -201,6 +213,8 @@ int gv_pool_bind_clusters(GvCtx* ctx, uint32_t pool_id, const GvClusterRange* ra
     K.range_count = K.cluster_count = K.max_range = 0;
     K.cones_bound = false;  // the cones belong to the table as it was
     K.d_cones.release();
+    K.lods_bound = false;  // ... and so does the LOD table
+    K.d_lods.release();
     if (none) {
         K.d_ranges.release();
         K.d_clusters.release();

@@ -35,12 +35,14 @@
 // where they stand), which read what the five above left on the device and write none of it; and the three kernels of the run form
 // gv_pool_cull_cluster_runs (cluster_run_*, described where they stand), which with the count, the scans and the test's walk above
 // write one command per run of adjacent survivors; and the three test kernels of the normal-cone form gv_pool_cull_cluster_cones
-// (cluster_cone_*: the test walks above instantiated with the cone test in their conjunction, described where they stand).
+// (cluster_cone_*: the test walks above instantiated with the cone test in their conjunction, described where they stand); and the
+// six test kernels of the level-of-detail form gv_pool_cull_cluster_lods (cluster_lod_*: the same walks with the LOD cut in front).
 #include "gv_device.hpp"
 #include "gv_cluster_kernels.hpp"
 #include "gv_cluster_second_kernels.hpp"
 #include "gv_cluster_run_kernels.hpp"
 #include "gv_cluster_cone_kernels.hpp"
+#include "gv_cluster_lod_kernels.hpp"
 
 namespace gv {
 
@@ -115,6 +117,40 @@ __device__ __forceinline__ bool cone_rejected(const ConeLane& c, const ClusterEy
     const float q = s * s;
     const float r = (c.cutoff * c.cutoff) * ww;
     return facing && s > 0.0f && q > 0.0f && q < __builtin_inff() && q >= r;
+}
+
+// The level-of-detail cut (gv_pool_cull_cluster_lods). The ClusterLodView of view v lies in a wrapper
+// struct behind the launch struct the walk reads: at byte `lod_offset` of the argument block, read at a wave-uniform offset.
+__device__ __forceinline__ ClusterLodView view_lod_of(ConstClusterArgs base, uint32_t lod_offset, uint32_t v)
+{
+    ClusterLodView out;
+    __builtin_memcpy(&out, reinterpret_cast<const char __attribute__((address_space(4)))*>(base) + lod_offset + v * (uint32_t)sizeof(ClusterLodView),
+                     sizeof(out));
+    return out;
+}
+// what a lane keeps of its draw and its LOD entry for the views' tests: s2, the two carried centres, the two radii and errors
+struct LodLane {
+    float s2;
+    float self_c[3], parent_c[3];
+    float self_r, parent_r, self_e, parent_e;
+};
+__device__ __forceinline__ LodLane lod_lane(const Mat34& model, const float4 l0, const float4 l1, const float4 l2)
+{
+    LodLane l;
+    l.s2 = lod_scale2(model);
+    lod_carry(model, l0.x, l0.y, l0.z, l.self_c);
+    lod_carry(model, l1.x, l1.y, l1.z, l.parent_c);
+    l.self_r = l0.w, l.parent_r = l1.w, l.self_e = l2.x, l.parent_e = l2.y;
+    return l;
+}
+// LOD-KEPT iff !EXCEEDS(self) && EXCEEDS(parent); scale == 0 (+-0) keeps every cluster. The branches on the view are wave-uniform.
+__device__ __forceinline__ bool lod_kept(const LodLane& l, const ClusterLodView& view)
+{
+    if (view.scale == 0.0f)
+        return true;
+    const bool point = view.eye[3] != 0.0f;
+    return !lod_exceeds(l.self_c, l.self_r, l.self_e, l.s2, view.eye, point, view.scale, view.near_distance) &&
+           lod_exceeds(l.parent_c, l.parent_r, l.parent_e, l.s2, view.eye, point, view.scale, view.near_distance);
 }
 
 // draw k of view v: the first instance the emission gave it, and how many (c_k)
@@ -364,8 +400,12 @@ __device__ __forceinline__ void locate(const ClusterLaunch& a, uint32_t c, uint3
 // kCones (cluster_cone_test_kernel, cluster_cone_run_test_kernel): a cluster survives iff it passes the test above and is not
 // cone-rejected. The cone's two 16-byte loads are issued with the cluster's two — one more step in the chain of dependent loads is
 // what would cost — and the cone test runs behind the plane tests, in front of the Hi-Z query.
-template <bool kRuns, bool kCones>
-__device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsigned long long* link, const float4* cones, uint32_t eye_offset)
+// kLod (cluster_lod_*_test_kernel): a cluster survives iff it is LOD-kept and passes the tests above. The entry's three 16-byte loads
+// are issued with the cluster's two and the model's three; the LOD test runs in front of the plane tests, a LOD-rejected lane does
+// neither them, nor the cone test, nor the Hi-Z query, and a wave with no LOD-kept lane for a view skips them wholesale.
+template <bool kRuns, bool kCones, bool kLod>
+__device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsigned long long* link, const float4* cones, uint32_t eye_offset,
+                                                   const float4* lods, uint32_t lod_offset)
 {
     __shared__ uint32_t wave_count[kClusterBlock / 64u];
     ConstClusterArgs base = (ConstClusterArgs)__builtin_amdgcn_kernarg_segment_ptr();
@@ -384,6 +424,7 @@ __device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsig
         uint32_t j = 0, cl_first = 0, cl_count = 0;
         const float4* cl = nullptr;
         [[maybe_unused]] ConeLane cone{};
+        [[maybe_unused]] LodLane lod{};
         if (live) {
             uint32_t block, at;
             locate(a, c, tile, tiles, blocks, block, at, j);
@@ -398,6 +439,11 @@ __device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsig
                     const float4* const cn = cones + ((size_t)range.first + j) * 2u;  // (the cone table is as long as the cluster table)
                     c0 = cn[0], c1 = cn[1];
                 }
+                [[maybe_unused]] float4 l0, l1, l2;
+                if constexpr (kLod) {
+                    const float4* const ln = lods + ((size_t)range.first + j) * 3u;  // (the LOD table is as long as the cluster table)
+                    l0 = ln[0], l1 = ln[1], l2 = ln[2];
+                }
                 cl_first = __float_as_uint(lo.w), cl_count = __float_as_uint(hi.w);
                 const ViewPick view = pick_view(a, v);
                 const uint32_t k = at - view.first_block * kClusterBlock;
@@ -406,13 +452,24 @@ __device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsig
                 aabb_corners(rows_model(w0, w1, w2), lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, corners);
                 if constexpr (kCones)
                     cone = cone_lane(rows_model(w0, w1, w2), c0, c1);
+                if constexpr (kLod)
+                    lod = lod_lane(rows_model(w0, w1, w2), l0, l1, l2);
             }
         }
 #pragma unroll 1
         for (uint32_t u = 0; u < a.views; u++) {
-            const bool mine = tested && v == u;
+            bool mine = tested && v == u;
             if (!__any(mine))
                 continue;  // (wave-uniform)
+            if constexpr (kLod) {
+                const ClusterLodView lv = view_lod_of(base, lod_offset, u);
+                const bool kept = mine && lod_kept(lod, lv);
+                if (mine && !kept)
+                    survives = false;
+                mine = kept;
+                if (!__any(mine))
+                    continue;  // (wave-uniform: no LOD-kept lane, no plane test, no cone test, no query)
+            }
             const ClusterPlanes pl = view_planes_of(base, u);
             const uint32_t plane_count = base->plane_count[u];
             const bool query = (a.hiz_views >> u) & 1u;
@@ -462,7 +519,7 @@ __device__ __forceinline__ void cluster_test_tiles(const ClusterLaunch& a, unsig
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_test_kernel(const ClusterLaunch a)
 {
-    cluster_test_tiles<false, false>(a, nullptr, nullptr, 0u);
+    cluster_test_tiles<false, false, false>(a, nullptr, nullptr, 0u, nullptr, 0u);
 }
 
 // every word of one command position; a field offset of kNoField matches no word
@@ -699,8 +756,10 @@ __device__ __forceinline__ void find_pending(const ClusterSecondLaunch& s, uint3
 
 // kCones (cluster_cone_second_test_kernel): behind a cone result a pending cluster survives iff the unchanged test keeps it and it is
 // not cone-rejected, with the eyes and the cone table of K1 (as cluster_test_tiles).
-template <bool kCones>
-__device__ __forceinline__ void cluster_second_test_tiles(const ClusterSecondLaunch& s, const float4* cones, uint32_t eye_offset)
+// kLod (cluster_lod_second_test_kernel, cluster_lod_cone_second_test_kernel): the LOD cut of K1's views in front, likewise.
+template <bool kCones, bool kLod>
+__device__ __forceinline__ void cluster_second_test_tiles(const ClusterSecondLaunch& s, const float4* cones, uint32_t eye_offset, const float4* lods,
+                                                          uint32_t lod_offset)
 {
     __shared__ uint32_t wave_count[kClusterBlock / 64u];
     const ClusterLaunch& a = s.k;
@@ -718,6 +777,7 @@ __device__ __forceinline__ void cluster_second_test_tiles(const ClusterSecondLau
         uint32_t v = 0;
         Corners corners;
         [[maybe_unused]] ConeLane cone{};
+        [[maybe_unused]] LodLane lod{};
         if (p < pending) {
             uint32_t tile, c, block, at, j;
             find_pending(s, p, q, ptiles, tiles, tile, c);
@@ -733,6 +793,11 @@ __device__ __forceinline__ void cluster_second_test_tiles(const ClusterSecondLau
                     const float4* const cn = cones + ((size_t)range.first + j) * 2u;
                     c0 = cn[0], c1 = cn[1];
                 }
+                [[maybe_unused]] float4 l0, l1, l2;
+                if constexpr (kLod) {
+                    const float4* const ln = lods + ((size_t)range.first + j) * 3u;  // (the LOD table is as long as the cluster table)
+                    l0 = ln[0], l1 = ln[1], l2 = ln[2];
+                }
                 const ViewPick view = pick_view(a, v);
                 const uint32_t k = at - view.first_block * kClusterBlock;
                 const float4* const rows = reinterpret_cast<const float4*>(view.model) + (size_t)k * 3u;
@@ -740,13 +805,24 @@ __device__ __forceinline__ void cluster_second_test_tiles(const ClusterSecondLau
                 aabb_corners(rows_model(w0, w1, w2), lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, corners);
                 if constexpr (kCones)
                     cone = cone_lane(rows_model(w0, w1, w2), c0, c1);
+                if constexpr (kLod)
+                    lod = lod_lane(rows_model(w0, w1, w2), l0, l1, l2);
             }
         }
 #pragma unroll 1
         for (uint32_t u = 0; u < a.views; u++) {
-            const bool mine = tested && v == u;
+            bool mine = tested && v == u;
             if (!__any(mine))
                 continue;  // (wave-uniform)
+            if constexpr (kLod) {
+                const ClusterLodView lv = view_lod_of(base, lod_offset, u);
+                const bool kept = mine && lod_kept(lod, lv);
+                if (mine && !kept)
+                    survives = false;
+                mine = kept;
+                if (!__any(mine))
+                    continue;  // (wave-uniform: no LOD-kept lane, no plane test, no cone test, no query)
+            }
             const ClusterPlanes pl = view_planes_of(base, u);
             const uint32_t plane_count = base->plane_count[u];
             const bool query = (a.hiz_views >> u) & 1u;  // (set: only a queried view has pending candidates)
@@ -779,7 +855,7 @@ __device__ __forceinline__ void cluster_second_test_tiles(const ClusterSecondLau
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_second_test_kernel(const ClusterSecondLaunch s)
 {
-    cluster_second_test_tiles<false>(s, nullptr, 0u);
+    cluster_second_test_tiles<false, false>(s, nullptr, 0u, nullptr, 0u);
 }
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_second_write_kernel(const ClusterSecondLaunch s)
@@ -858,7 +934,7 @@ static_assert(offsetof(ClusterRunLaunch, k) == 0, "the per-view arguments are re
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_run_test_kernel(const ClusterRunLaunch r)
 {
-    cluster_test_tiles<true, false>(r.k, r.link, nullptr, 0u);
+    cluster_test_tiles<true, false, false>(r.k, r.link, nullptr, 0u, nullptr, 0u);
 }
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_run_heads_kernel(const ClusterRunLaunch r)
@@ -968,18 +1044,63 @@ static_assert(sizeof(ClusterEye) == sizeof(float[4]), "an eye is four floats of 
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_cone_test_kernel(const ClusterConeLaunch c)
 {
-    cluster_test_tiles<false, true>(c.k, nullptr, c.cone.cones, (uint32_t)(offsetof(ClusterConeLaunch, cone) + offsetof(ClusterConeArgs, eyes)));
+    cluster_test_tiles<false, true, false>(c.k, nullptr, c.cone.cones, (uint32_t)(offsetof(ClusterConeLaunch, cone) + offsetof(ClusterConeArgs, eyes)), nullptr, 0u);
 }
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_cone_run_test_kernel(const ClusterConeRunLaunch c)
 {
-    cluster_test_tiles<true, true>(c.r.k, c.r.link, c.cone.cones, (uint32_t)(offsetof(ClusterConeRunLaunch, cone) + offsetof(ClusterConeArgs, eyes)));
+    cluster_test_tiles<true, true, false>(c.r.k, c.r.link, c.cone.cones, (uint32_t)(offsetof(ClusterConeRunLaunch, cone) + offsetof(ClusterConeArgs, eyes)), nullptr,
+                                          0u);
 }
 
 __global__ __launch_bounds__(kClusterBlock) void cluster_cone_second_test_kernel(const ClusterConeSecondLaunch c)
 {
-    cluster_second_test_tiles<true>(c.s, c.cone.cones, (uint32_t)(offsetof(ClusterConeSecondLaunch, cone) + offsetof(ClusterConeArgs, eyes)));
+    cluster_second_test_tiles<true, false>(c.s, c.cone.cones, (uint32_t)(offsetof(ClusterConeSecondLaunch, cone) + offsetof(ClusterConeArgs, eyes)), nullptr,
+                                           0u);
 }
+
+// ---- the level-of-detail form (gv_pool_cull_cluster_lods) ----
+// The six test kernels above with the LOD cut in front of their conjunction; count, scans, heads and writers are the launches above
+// as they are, given the innermost wrapped struct. The wrappers' first members keep every other argument at its form's offsets.
+static_assert(offsetof(ClusterLodLaunch, k) == 0 && offsetof(ClusterLodRunLaunch, r) == 0 && offsetof(ClusterLodConeLaunch, c) == 0 &&
+                  offsetof(ClusterLodConeRunLaunch, c) == 0 && offsetof(ClusterLodSecondLaunch, s) == 0 && offsetof(ClusterLodConeSecondLaunch, c) == 0,
+              "the per-view arguments and the eyes are read at the wrapped form's offsets");
+#define GV_LOD_VIEWS_AT(T) ((uint32_t)(offsetof(T, lod) + offsetof(ClusterLodArgs, views)))
+#define GV_CONE_EYES_AT(T) ((uint32_t)(offsetof(T, cone) + offsetof(ClusterConeArgs, eyes)))
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_lod_test_kernel(const ClusterLodLaunch l)
+{
+    cluster_test_tiles<false, false, true>(l.k, nullptr, nullptr, 0u, l.lod.lods, GV_LOD_VIEWS_AT(ClusterLodLaunch));
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_lod_run_test_kernel(const ClusterLodRunLaunch l)
+{
+    cluster_test_tiles<true, false, true>(l.r.k, l.r.link, nullptr, 0u, l.lod.lods, GV_LOD_VIEWS_AT(ClusterLodRunLaunch));
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_lod_cone_test_kernel(const ClusterLodConeLaunch l)
+{
+    cluster_test_tiles<false, true, true>(l.c.k, nullptr, l.c.cone.cones, GV_CONE_EYES_AT(ClusterConeLaunch), l.lod.lods, GV_LOD_VIEWS_AT(ClusterLodConeLaunch));
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_lod_cone_run_test_kernel(const ClusterLodConeRunLaunch l)
+{
+    cluster_test_tiles<true, true, true>(l.c.r.k, l.c.r.link, l.c.cone.cones, GV_CONE_EYES_AT(ClusterConeRunLaunch), l.lod.lods,
+                                         GV_LOD_VIEWS_AT(ClusterLodConeRunLaunch));
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_lod_second_test_kernel(const ClusterLodSecondLaunch l)
+{
+    cluster_second_test_tiles<false, true>(l.s, nullptr, 0u, l.lod.lods, GV_LOD_VIEWS_AT(ClusterLodSecondLaunch));
+}
+
+__global__ __launch_bounds__(kClusterBlock) void cluster_lod_cone_second_test_kernel(const ClusterLodConeSecondLaunch l)
+{
+    cluster_second_test_tiles<true, true>(l.c.s, l.c.cone.cones, GV_CONE_EYES_AT(ClusterConeSecondLaunch), l.lod.lods,
+                                          GV_LOD_VIEWS_AT(ClusterLodConeSecondLaunch));
+}
+#undef GV_LOD_VIEWS_AT
+#undef GV_CONE_EYES_AT
 
 // the fixed grid of the test and write launches: kClusterGridPerCu workgroups per compute unit of the current device
 uint32_t walk_grid()
@@ -1094,6 +1215,42 @@ hipError_t launch_cluster_cone_run_test(const ClusterConeRunLaunch& launch, hipS
 hipError_t launch_cluster_cone_second_test(const ClusterConeSecondLaunch& launch, hipStream_t stream)
 {
     hipLaunchKernelGGL(cluster_cone_second_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_lod_test(const ClusterLodLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_lod_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_lod_run_test(const ClusterLodRunLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_lod_run_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_lod_cone_test(const ClusterLodConeLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_lod_cone_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_lod_cone_run_test(const ClusterLodConeRunLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_lod_cone_run_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_lod_second_test(const ClusterLodSecondLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_lod_second_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_lod_cone_second_test(const ClusterLodConeSecondLaunch& launch, hipStream_t stream)
+{
+    hipLaunchKernelGGL(cluster_lod_cone_second_test_kernel, dim3(walk_grid()), dim3(kClusterBlock), 0, stream, launch);
     return hipGetLastError();
 }
 

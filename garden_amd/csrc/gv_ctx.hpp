@@ -31,6 +31,7 @@
 #include "gv_cluster_second_kernels.hpp"
 #include "gv_cluster_run_kernels.hpp"
 #include "gv_cluster_cone_kernels.hpp"
+#include "gv_cluster_lod_kernels.hpp"
 #include "gv_workers.hpp"
 #include "gv_dirty_ranges.hpp"
 
@@ -367,8 +368,8 @@ struct PoolState {
     } commands;
     // gv_pool_bind_clusters / gv_pool_cull_clusters: the tables as bound and the last call's commands, buffers of their own — no cull
     // result, no instance data and no per-draw command buffer (Commands above) is touched. Header-only: no other host source calls
-    // gv_clusters.cpp but gv_cluster_runs.cpp, the run form, and gv_cluster_cones.cpp, the normal-cone form, which share its body
-    // (cull_clusters below).
+    // gv_clusters.cpp but gv_cluster_runs.cpp, the run form, gv_cluster_cones.cpp, the normal-cone form, and gv_cluster_lods.cpp, the
+    // level-of-detail form, which share its body (cull_clusters below).
     struct Clusters {
         bool bound = false;
         uint32_t range_count = 0, cluster_count = 0;
@@ -384,6 +385,9 @@ struct PoolState {
         // gv_pool_bind_cluster_cones (gv_cluster_cones.cpp): one cone per entry of the cluster table; dropped with the tables
         bool cones_bound = false;
         DeviceBuf<GvClusterCone> d_cones;
+        // gv_pool_bind_cluster_lods (gv_cluster_lods.cpp): one LOD entry per entry of the cluster table; dropped with the tables
+        bool lods_bound = false;
+        DeviceBuf<GvClusterLod> d_lods;
         PinnedBuf<uint8_t> h_data;         // staging of gv_pool_cluster_commands_fetch
         PinnedBuf<uint32_t> h_counts;
         // the last call (views 0: none since the pool's last gv_cull, instance emission or gv_pool_bind_clusters)
@@ -402,6 +406,8 @@ struct PoolState {
         // other forms name no cone launch)
         int (*second_test)(GvCtx* ctx, Clusters& K, const ClusterSecondLaunch& launch) = nullptr;
         float eyes[kMaxInstanceViews][4] = {};
+        // ... or gv_pool_cull_cluster_lods: its LOD views, kept with the launch likewise (second_test tells which)
+        GvClusterLodView lod_views[kMaxInstanceViews] = {};
         // gv_pool_cull_clusters_second_phase (gv_clusters_second.cpp): the last call's commands and scratch, buffers of their own —
         // nothing of K1 above is written. views 0: none since K1 (it ends wherever K1 ends, and at a new K1)
         struct Second {
@@ -424,7 +430,7 @@ struct PoolState {
         {
             d_ranges.release(), d_clusters.release(), d_data.release(), d_counts.release(), d_draw_geometry.release(), d_draw_local.release();
             d_block_total.release(), d_block_tested.release(), d_totals.release(), d_tile_count.release(), d_tile_block.release(), d_survive.release();
-            d_link.release(), d_head.release(), d_head_count.release(), d_cones.release();
+            d_link.release(), d_head.release(), d_head_count.release(), d_cones.release(), d_lods.release();
             h_data.release(), h_counts.release(), second.release();
         }
     } clusters;
@@ -1169,12 +1175,14 @@ int copy_shard_of_pool(GvCtx* ctx, uint32_t pool_id, uint32_t view_index, void* 
 
 // gv_clusters.cpp
 // The body of every form of the cluster cull (gv_pool_cull_clusters there, gv_pool_cull_cluster_runs in gv_cluster_runs.cpp,
-// gv_pool_cull_cluster_cones in gv_cluster_cones.cpp): every check, the bound, the target, the shared scratch and the bookkeeping.
+// gv_pool_cull_cluster_cones in gv_cluster_cones.cpp, gv_pool_cull_cluster_lods in gv_cluster_lods.cpp): every check, the bound, the
+// target, the shared scratch and the bookkeeping.
 // `forms` holds per form what reserves the scratch the form adds and enqueues its launches — launch is complete, tiles = ceil(B /
 // kClusterTile), eyes as below; `fn` names the entry point in messages. `allowed_flags`: the flag bits the entry point takes;
 // GV_CLUSTERS_RUNS among them picks forms.runs. `cones` (NULL: the forms without the cone test): the caller's eyes, checked here
-// against the views of E and kept with the launch.
-typedef int (*ClusterCullLaunches)(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, const GvClusterEye* eyes);
+// against the views of E and kept with the launch. `lods` (NULL: the forms without the LOD cut): the caller's LOD views, likewise.
+typedef int (*ClusterCullLaunches)(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, const GvClusterEye* eyes,
+                                   const GvClusterLodView* lod_views);
 struct ClusterCullForms {
     ClusterCullLaunches survivors;  // one command per survivor
     ClusterCullLaunches runs;       // one command per run (NULL: the entry point has no run flag)
@@ -1186,8 +1194,21 @@ struct ClusterConeRequest {
 };
 // gv_cluster_runs.cpp: the run form's scratch reserved and its launch struct around `launch` (the cone form's run launches share it)
 int reserve_runs(GvCtx* ctx, PoolState::Clusters& K, const ClusterLaunch& launch, size_t tiles, ClusterRunLaunch* run);
+// the cone table of K and the eyes of `views` views as a launch carries them (the views behind them: all-zero eyes, never read)
+inline ClusterConeArgs cluster_cone_args(const PoolState::Clusters& K, uint32_t views, const void* eyes)
+{
+    ClusterConeArgs args{};
+    args.cones = reinterpret_cast<const float4*>(K.d_cones.ptr);
+    memcpy(args.eyes, eyes, (size_t)views * sizeof(GvClusterEye));
+    return args;
+}
+struct ClusterLodRequest {
+    const GvClusterLodView* views;
+    uint32_t view_count;
+};
 int cull_clusters(GvCtx* ctx, const char* fn, ClusterCullForms forms, uint32_t allowed_flags, const ClusterConeRequest* cones, const char* zone_name,
-                  uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes);
+                  uint32_t pool_id, uint32_t flags, uint32_t region_commands, void* dst_device, size_t capacity_bytes,
+                  const ClusterLodRequest* lods = nullptr);
 
 // gv_mirror.cpp
 // brings the device mirror up to date with the bound pools + dirty marks: per side a full rebuild, or growth and the dirty

@@ -228,6 +228,44 @@ __device__ __forceinline__ Adj33 affine_adjugate(const Mat34& a)
 }
 __device__ __forceinline__ float row_dot(const float (&r)[3], float x, float y, float z) { return fmaf(r[0], x, fmaf(r[1], y, r[2] * z)); }
 
+// The level-of-detail cut of the cluster cull (include/garden_vis.h), fp32, every step as written.
+// Per draw, with a_rc = f[3c + r] of the 12 bakedModel floats: n_c = fmaf(a_2c, a_2c, fmaf(a_1c, a_1c, a_0c * a_0c)) for c = 0, 1,
+// 2; s2 = 0.0f; s2 = n_0 > s2 ? n_0 : s2; then the same for n_1 and n_2 — the largest squared column norm.
+__device__ __forceinline__ float lod_scale2(const Mat34& a)
+{
+    const float n0 = fmaf(a.c0z, a.c0z, fmaf(a.c0y, a.c0y, a.c0x * a.c0x));
+    const float n1 = fmaf(a.c1z, a.c1z, fmaf(a.c1y, a.c1y, a.c1x * a.c1x));
+    const float n2 = fmaf(a.c2z, a.c2z, fmaf(a.c2y, a.c2y, a.c2x * a.c2x));
+    float s2 = 0.0f;
+    s2 = n0 > s2 ? n0 : s2;
+    s2 = n1 > s2 ? n1 : s2;
+    s2 = n2 > s2 ? n2 : s2;
+    return s2;
+}
+// Per triple (c, r, e): C_r = fmaf(a_r0, c_0, fmaf(a_r1, c_1, fmaf(a_r2, c_2, t_r))) — item 5's nesting.
+__device__ __forceinline__ void lod_carry(const Mat34& a, float c0, float c1, float c2, float (&C)[3])
+{
+    C[0] = fmaf(a.c0x, c0, fmaf(a.c1x, c1, fmaf(a.c2x, c2, a.c3x)));
+    C[1] = fmaf(a.c0y, c0, fmaf(a.c1y, c1, fmaf(a.c2y, c2, a.c3y)));
+    C[2] = fmaf(a.c0z, c0, fmaf(a.c1z, c1, fmaf(a.c2z, c2, a.c3z)));
+}
+// u_r = C_r - P_r; D = fmaf(u_2, u_2, fmaf(u_1, u_1, u_0 * u_0)) (item 7's nesting); q = e * k; a = q + r; A = (a * a) * s2;
+// Q = (q * q) * s2; N = near_distance * near_distance. Point eye: EXCEEDS iff Q > N && A > D. Parallel eye: EXCEEDS iff Q > N.
+// A comparison with a NaN is false. `point` is eye[3] != 0.
+__device__ __forceinline__ bool lod_exceeds(const float (&C)[3], float r, float e, float s2, const float (&P)[4], bool point, float k, float near_distance)
+{
+    const float q = e * k;
+    const float a = q + r;
+    const float A = (a * a) * s2;
+    const float Q = (q * q) * s2;
+    const float N = near_distance * near_distance;
+    if (!point)
+        return Q > N;
+    const float u0 = C[0] - P[0], u1 = C[1] - P[1], u2 = C[2] - P[2];
+    const float D = fmaf(u2, u2, fmaf(u1, u1, u0 * u0));
+    return Q > N && A > D;
+}
+
 // One slab of raycast2: the axis interval [lo, hi] of the ray parameter, or for d == 0 the whole line when lo_box <= o <= hi_box
 // (ok = false otherwise). A NaN plane parameter also clears ok: every comparison with a NaN is false.
 __device__ __forceinline__ void slab(float o, float d, float lo_box, float hi_box, float& t_near, float& t_far, bool& ok)

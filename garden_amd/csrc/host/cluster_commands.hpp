@@ -13,6 +13,9 @@
 // With setCones a system's cluster culls also reject the clusters whose normal cone faces away from the pass's eye
 // (gv_pool_cull_cluster_cones): the light pass is seen from the camera — the point eye (0, 0, 0, 1) of the camera-relative records —
 // and a cascade along its light's direction (cascadeEye). setRuns, setMode and the targets combine with it.
+// With setClusterLods a system's cluster culls are made over the CUT through the bound cluster DAG (gv_pool_cull_cluster_lods): a
+// cluster is drawn when its own error is small enough on screen for the pass's LOD view (setLodViews, lodScale) and its parent's is
+// not. It combines with setCones, setRuns, setMode and the targets; cullSecond takes nothing new, the library keeps the views.
 //
 // In a two-phase frame cullSecond(p, ...) re-tests what a system's last cluster cull left out against the rebuilt pyramid
 // (gv_pool_cull_clusters_second_phase), into host copies of its own (getBaseSecond / getShadowSecond).
@@ -20,6 +23,7 @@
 // Opt-in: a tick that sets no clusters runs exactly as before. One context only, like the writer: isSupported() is false with ranks.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -46,6 +50,9 @@ private:
         bool cones = false;    // normal cones are bound: the culls are gv_pool_cull_cluster_cones
         GvClusterEye baseEye{{0.0f, 0.0f, 0.0f, 1.0f}};  // the camera, in the camera-relative space of the records
         std::vector<GvClusterEye> shadowEyes;            // by the shadow system's pass number; a pass beyond them: all zero, no cone test
+        bool lods = false;     // a LOD table is bound: the culls are gv_pool_cull_cluster_lods, over the cut through the cluster DAG
+        GvClusterLodView baseLod{{0.0f, 0.0f, 0.0f, 1.0f}, 0.0f, 1.0f, {0.0f, 0.0f}};  // scale 0: no LOD test until setLodViews
+        std::vector<GvClusterLodView> shadowLods;        // by the shadow system's pass number; a pass beyond them: scale 0, no LOD test
         uint32_t flags = 0, region = 0;
         void *baseDevice = nullptr, *shadowDevice = nullptr;
         size_t baseBytes = 0, shadowBytes = 0;
@@ -79,7 +86,25 @@ public:
         check(gv_pool_bind_clusters(system->getContext(), p, ranges, rangeCount, clusters, clusterCount), "gv_pool_bind_clusters");
         of(p).enabled = ranges != nullptr;
         of(p).cones = false;  // (the library drops the cones with the table they belonged to)
+        of(p).lods = false;   // (... and the LOD table)
     }
+    // the LOD table of mesh system p's clusters, one GvClusterLod per entry of the cluster table and in its order (meshoptimizer
+    // clusterlod bounds as they are); copied (gv_pool_bind_cluster_lods). NULL: no table, the culls run as before. Call it behind
+    // setClusters.
+    void setClusterLods(uint32_t p, const GvClusterLod* table, uint32_t count)
+    {
+        check(gv_pool_bind_cluster_lods(system->getContext(), p, table, count), "gv_pool_bind_cluster_lods");
+        of(p).lods = table != nullptr;
+    }
+    // the LOD views of mesh system p's passes: the light pass's and one per shadow pass, indexed by the shadow system's pass number (a
+    // cascade that wants the camera's cut names the camera's eye and scale; a pass without one gets no LOD test)
+    void setLodViews(uint32_t p, const GvClusterLodView& baseView, const GvClusterLodView* shadowViews, uint32_t shadowViewCount)
+    {
+        of(p).baseLod = baseView;
+        of(p).shadowLods.assign(shadowViews, shadowViews + shadowViewCount);
+    }
+    // k of a perspective view: the projection factor (height / 2) / tan(fovy / 2) divided by the pixel threshold
+    static float lodScale(float fovy, float height, float pixels) { return 0.5f * height / std::tan(0.5f * fovy) / pixels; }
     // the normal cones of mesh system p's clusters, one per entry of the cluster table and in its order (meshopt_Bounds' cone_apex /
     // cone_axis / cone_cutoff as they are); copied (gv_pool_bind_cluster_cones). NULL: no cones, the culls run as before. Call it
     // behind setClusters.
@@ -129,9 +154,9 @@ public:
         GvCtx* ctx = system->getContext();
         void* const device = shadow ? s.shadowDevice : s.baseDevice;
         const size_t bytes = shadow ? s.shadowBytes : s.baseBytes;
-        if (s.cones) {
-            std::vector<GvClusterEye> declared;
-            if (!eyes) {  // the light pass, or the system's culled shadow passes in pass order
+        std::vector<GvClusterEye> declared;
+        if (s.cones || s.lods) {
+            if (!eyes && s.cones) {  // the light pass, or the system's culled shadow passes in pass order
                 if (!shadow)
                     declared.push_back(s.baseEye);
                 else
@@ -141,6 +166,20 @@ public:
                 eyes = declared.data();
                 eyeCount = (uint32_t)declared.size();
             }
+        }
+        if (s.lods) {  // (eyes NULL without cones: no cone test)
+            std::vector<GvClusterLodView> views;
+            if (!shadow)
+                views.push_back(s.baseLod);
+            else
+                for (int8_t pass : system->getSystemPasses(p))
+                    if (pass >= 0)
+                        views.push_back((size_t)pass < s.shadowLods.size() ? s.shadowLods[(size_t)pass]
+                                                                           : GvClusterLodView{{0.0f, 0.0f, 0.0f, 0.0f}, 0.0f, 1.0f, {0.0f, 0.0f}});
+            check(gv_pool_cull_cluster_lods(ctx, p, s.flags | (s.runs ? GV_CLUSTERS_RUNS : 0u), views.data(), (uint32_t)views.size(),
+                                            s.cones ? eyes : nullptr, s.cones ? eyeCount : 0u, s.region, device, bytes),
+                  "gv_pool_cull_cluster_lods");
+        } else if (s.cones) {
             check(gv_pool_cull_cluster_cones(ctx, p, s.flags | (s.runs ? GV_CLUSTERS_RUNS : 0u), eyes, eyeCount, s.region, device, bytes),
                   "gv_pool_cull_cluster_cones");
         } else if (s.runs)

@@ -124,7 +124,7 @@ GV_MAX_CLUSTERS = 1 << 22
 GV_MAX_GEOMETRY_CLUSTERS = 65535
 GV_CLUSTERS_FRUSTUM_ONLY = 1
 GV_CLUSTER_RUN_SPAN = 256
-GV_CLUSTERS_RUNS = 2  # gv_pool_cull_cluster_cones only
+GV_CLUSTERS_RUNS = 2  # gv_pool_cull_cluster_cones and gv_pool_cull_cluster_lods only
 
 
 class GvCluster(C.Structure):
@@ -139,6 +139,11 @@ CLUSTER_DTYPE = np.dtype([("box_min", np.float32, (3,)), ("first", np.uint32), (
 CLUSTER_RANGE_DTYPE = np.dtype([("first", np.uint32), ("count", np.uint32)])
 # GvClusterCone: meshopt_Bounds' cone_apex / cone_axis / cone_cutoff as they are; `reserved` is not read
 CLUSTER_CONE_DTYPE = np.dtype([("apex", np.float32, (3,)), ("cutoff", np.float32), ("axis", np.float32, (3,)), ("reserved", np.uint32)])
+# GvClusterLod: the bounds and error of the group a cluster was simplified from (self) and merged into (parent); `reserved` is not read
+CLUSTER_LOD_DTYPE = np.dtype([("self_center", np.float32, (3,)), ("self_radius", np.float32), ("parent_center", np.float32, (3,)),
+                              ("parent_radius", np.float32), ("self_error", np.float32), ("parent_error", np.float32), ("reserved", np.uint32, (2,))])
+# GvClusterLodView: one per view of the emission; scale 0 switches the LOD test off for the view
+CLUSTER_LOD_VIEW_DTYPE = np.dtype([("eye", np.float32, (4,)), ("scale", np.float32), ("near_distance", np.float32), ("reserved", np.float32, (2,))])
 
 
 GV_MAX_LOD_LEVELS = 8
@@ -273,6 +278,7 @@ EXPORTS = [
     "gv_pool_bind_clusters", "gv_pool_cull_clusters", "gv_pool_cluster_commands_device", "gv_pool_cluster_commands_fetch",
     "gv_pool_cull_clusters_second_phase", "gv_pool_cluster_second_commands_device", "gv_pool_cluster_second_commands_fetch",
     "gv_pool_cull_cluster_runs", "gv_pool_bind_cluster_cones", "gv_pool_cull_cluster_cones",
+    "gv_pool_bind_cluster_lods", "gv_pool_cull_cluster_lods",
     "gv_pool_bind_lod", "gv_pool_select_lods", "gv_pool_lods_device", "gv_pool_lods_fetch",
     "gv_pool_group_draws",
     "gv_pool_cull_second_phase",
@@ -423,6 +429,8 @@ def load():
     lib.gv_pool_cull_cluster_runs.argtypes = [P, u32, u32, u32, P, sz]
     lib.gv_pool_bind_cluster_cones.argtypes = [P, u32, P, u32]
     lib.gv_pool_cull_cluster_cones.argtypes = [P, u32, u32, P, u32, u32, P, sz]
+    lib.gv_pool_bind_cluster_lods.argtypes = [P, u32, P, u32]
+    lib.gv_pool_cull_cluster_lods.argtypes = [P, u32, u32, P, u32, P, u32, u32, P, sz]
     lib.gv_pool_bind_lod.argtypes = [P, u32, P, u32, u32, C.POINTER(GvLodGeometry), u32]
     lib.gv_pool_select_lods.argtypes = [P, u32, C.POINTER(C.c_float), u32]
     lib.gv_pool_lods_device.argtypes = [P, u32, C.POINTER(P), C.POINTER(P)]
@@ -1119,7 +1127,17 @@ class GpuVisibility:
         assert c.dtype == CLUSTER_CONE_DTYPE and c.dtype.itemsize == 32
         self._check(self.lib.gv_pool_bind_cluster_cones(self.ctx, pool_id, c.ctypes.data, len(c)))
 
-    def cull_clusters(self, pool_id, frustum_only=False, region=0, device=None, runs=False, eyes=None):
+    def bind_cluster_lods(self, pool_id, lods):
+        """gv_pool_bind_cluster_lods: one LOD entry (CLUSTER_LOD_DTYPE) per entry of the bound cluster table, copied at the call;
+        None removes the binding."""
+        if lods is None:
+            self._check(self.lib.gv_pool_bind_cluster_lods(self.ctx, pool_id, None, 0))
+            return
+        t = np.ascontiguousarray(lods)
+        assert t.dtype == CLUSTER_LOD_DTYPE and t.dtype.itemsize == 48
+        self._check(self.lib.gv_pool_bind_cluster_lods(self.ctx, pool_id, t.ctypes.data, len(t)))
+
+    def cull_clusters(self, pool_id, frustum_only=False, region=0, device=None, runs=False, eyes=None, lods=None):
         """gv_pool_cull_clusters: one indirect command per surviving cluster of every draw of the pool's last instance emission
         (draws without clusters are drawn whole), on the context's stream. frustum_only: no Hi-Z query even for views that named a
         pyramid. region: 0 packs the views' commands, R > 0 gives every view R positions. device: None for the library's own
@@ -1127,9 +1145,19 @@ class GpuVisibility:
         decisions, one command per run of adjacent surviving clusters (at most GV_CLUSTER_RUN_SPAN of them). eyes: an [m, 4]
         float32 array, one eye per view of the emission — gv_pool_cull_cluster_cones: a cluster whose bound normal cone faces away
         from its view's eye is rejected too (w != 0: a point eye, w == 0: parallel rays along xyz, all zero: no cone test); it
-        combines with runs and frustum_only."""
+        combines with runs and frustum_only. lods: an array of CLUSTER_LOD_VIEW_DTYPE, one per view of the emission —
+        gv_pool_cull_cluster_lods: only the clusters on the cut through the bound cluster DAG are drawn (their own error small enough
+        on screen, their parent's not; scale 0: no LOD test for the view). Every cluster is still visited and counted as tested; a
+        LOD-rejected one skips the plane tests, the cone test and the Hi-Z query. It combines with eyes, runs and frustum_only."""
         ptr, cap = (None, 0) if device is None else (int(device[0]), int(device[1]))
-        if eyes is not None:
+        if lods is not None:
+            lv = np.ascontiguousarray(lods)
+            assert lv.dtype == CLUSTER_LOD_VIEW_DTYPE and lv.dtype.itemsize == 32
+            e = None if eyes is None else np.ascontiguousarray(eyes, np.float32).reshape(-1, 4)
+            flags = (GV_CLUSTERS_FRUSTUM_ONLY if frustum_only else 0) | (GV_CLUSTERS_RUNS if runs else 0)
+            self._check(self.lib.gv_pool_cull_cluster_lods(self.ctx, pool_id, flags, lv.ctypes.data, len(lv), None if e is None else e.ctypes.data,
+                                                           0 if e is None else len(e), int(region), ptr, cap))
+        elif eyes is not None:
             e = np.ascontiguousarray(eyes, np.float32).reshape(-1, 4)
             flags = (GV_CLUSTERS_FRUSTUM_ONLY if frustum_only else 0) | (GV_CLUSTERS_RUNS if runs else 0)
             self._check(self.lib.gv_pool_cull_cluster_cones(self.ctx, pool_id, flags, e.ctypes.data, len(e), int(region), ptr, cap))

@@ -753,7 +753,7 @@ typedef struct GvClusterCone {   /* 32 bytes */
     float axis[3];  uint32_t reserved;   /* not read */
 } GvClusterCone;
 typedef struct GvClusterEye { float eye[4]; } GvClusterEye;   /* one per view of E */
-#define GV_CLUSTERS_RUNS 2u   /* gv_pool_cull_cluster_cones only: write runs, as gv_pool_cull_cluster_runs */
+#define GV_CLUSTERS_RUNS 2u   /* gv_pool_cull_cluster_cones and gv_pool_cull_cluster_lods only: write runs, as gv_pool_cull_cluster_runs */
 /* Binds cones[0 .. cone_count), parallel to the pool's cluster table; copied at the call, the bytes counted in upload_bytes. NULL /
  * 0 removes the binding. Either way a cluster result the pool holds ends. gv_pool_bind_clusters (a new table, or removal) also drops
  * the cones. Cone values are not checked. GV_E_ARG: a pool out of range, a pointer without a count or a count without a pointer,
@@ -778,6 +778,78 @@ int gv_pool_bind_cluster_cones(GvCtx* ctx, uint32_t pool_id, const GvClusterCone
  * models, eyes derived from view_proj. */
 int gv_pool_cull_cluster_cones(GvCtx* ctx, uint32_t pool_id, uint32_t flags, const GvClusterEye* eyes, uint32_t eye_count,
                                uint32_t region_commands, void* dst_device, size_t capacity_bytes);
+
+/* ---- the cluster cull with a level-of-detail cut per draw ----
+ * The tools that build clusters (meshoptimizer's clusterlod, Nanite-style builders) build a DAG of them: the leaves plus coarser
+ * clusters, each simplified from a group of finer ones. Every cluster carries the bounds and error of the group it was simplified
+ * FROM (self) and of the group it was merged INTO (parent), and the renderer draws the CUT: a cluster is drawn exactly when its own
+ * error is small enough on screen and its parent's is not. A pool may bind one GvClusterLod per entry of its cluster table, and
+ * gv_pool_cull_cluster_lods makes the decisions of gv_pool_cull_clusters (and, given eyes, of gv_pool_cull_cluster_cones) over the
+ * cut alone (this build's rule, the reference has no clusters).
+ * A GvClusterLodView is given per view of E, in E's order. The eye is in the records' space (bakedModel as delivered), with the
+ * meaning GvClusterEye has:
+ *   eye[3] != 0: a point P = eye[0..2]; the main camera is (0, 0, 0, 1), and a cascade that wants the main view's cut names the
+ *                same point.
+ *   eye[3] == 0: a parallel projection whose error does not depend on distance.
+ *   scale is k: the projection factor divided by the pixel threshold tau. Perspective: k = (height / 2) / tan(fovy / 2) / tau.
+ *   Parallel: k = pixels per world unit / tau, with near_distance = 1.
+ *   scale == 0 (+-0) switches the test off for that view: every cluster is LOD-kept, the call's bytes equal the plain form's.
+ * With E, v, k, j, M_k as for gv_pool_cull_clusters, the draw's 12 bakedModel floats f (a_rc = f[3c + r], t_r = f[9 + r]) and
+ * lod = lods[range_k.first + j], in fp32, every step as written (fmaf: one rounding):
+ *   Per draw: n_c = fmaf(a_2c, a_2c, fmaf(a_1c, a_1c, a_0c * a_0c)) for c = 0, 1, 2;
+ *     s2 = 0.0f; s2 = n_0 > s2 ? n_0 : s2; then the same for n_1 and n_2 — the largest squared column norm: for one TRS exactly
+ *     the largest scale squared, for sheared chains an approximation.
+ *   Per triple (c, r, e), for the self triple and for the parent triple:
+ *     C_r = fmaf(a_r0, c_0, fmaf(a_r1, c_1, fmaf(a_r2, c_2, t_r)))   (item 5's nesting)
+ *     u_r = C_r - P_r;  D = fmaf(u_2, u_2, fmaf(u_1, u_1, u_0 * u_0))   (item 7's nesting)
+ *     q = e * k;  a = q + r;  A = (a * a) * s2;  Q = (q * q) * s2;  N = near_distance * near_distance.
+ *     Point eye:    EXCEEDS iff Q > N && A > D.
+ *     Parallel eye: EXCEEDS iff Q > N.
+ *   This is e * k * s > max(dist - r * s, near) multiplied through by positive quantities: nothing is divided, no root is taken.
+ *   Cluster j of draw k is LOD-KEPT in view v iff !EXCEEDS(self) && EXCEEDS(parent).
+ * Consequences: a leaf (e = 0) never exceeds; a root (parent_error = +inf) is always refined-from, unless D overflows or s2 is 0;
+ * a comparison with a NaN is false, so a NaN in the self triple makes the cluster "fine enough" and a NaN in the parent triple
+ * rejects it; an eye inside a sphere gives A > D by itself, so refinement goes on until the error is below the near clamp. All
+ * clusters of one group carry the same parent triple, so they get the same bits and the same decision: that is why the cut has no
+ * cracks, and it is the table builder's property, not checked here. The rule is bit-defined and NOT padded: monotone errors and
+ * nested spheres are the builder's business, as the cone's cutoff margin is.
+ *   A cluster SURVIVES iff it is LOD-kept, survives gv_pool_cull_clusters' unchanged test and, when eyes are given, is not
+ *   cone-rejected.
+ * Whole draws, void draws, the order (view, draw, cluster), the commands, placement, counts[v] and counts[m + v] (a LOD-rejected
+ * cluster counts as tested) are exactly those of gv_pool_cull_clusters. */
+typedef struct GvClusterLod {   /* 48 bytes; meshoptimizer clusterlod bounds fit as they are */
+    float self_center[3];   float self_radius;    /* model space: the group this cluster was simplified FROM */
+    float parent_center[3]; float parent_radius;  /* the group this cluster was merged INTO */
+    float self_error, parent_error;               /* model-space units; leaves 0, roots +inf as parent_error */
+    uint32_t reserved[2];                         /* not read */
+} GvClusterLod;
+typedef struct GvClusterLodView { float eye[4]; float scale; float near_distance; float reserved[2]; } GvClusterLodView;   /* 32 bytes */
+/* Binds lods[0 .. lod_count), parallel to the pool's cluster table; copied at the call, the bytes counted in upload_bytes. NULL / 0
+ * removes the binding. Either way a cluster result the pool holds ends. gv_pool_bind_clusters (a new table, or removal) also drops
+ * the LOD table, as it drops the cones. Values are not checked. GV_E_ARG: a pool out of range, a pointer without a count or a count
+ * without a pointer, lod_count different from the bound cluster_count. GV_E_STATE: no cluster binding. */
+int gv_pool_bind_cluster_lods(GvCtx* ctx, uint32_t pool_id, const GvClusterLod* lods, uint32_t lod_count);
+/* The cluster commands of the views of E under the rule above. views[0 .. view_count): one per view of E, copied at the call.
+ * eyes: NULL / 0 for no cone test; otherwise one GvClusterEye per view of E and gv_pool_cull_cluster_cones' test too (it needs a
+ * cone binding). flags: a subset of {GV_CLUSTERS_FRUSTUM_ONLY, GV_CLUSTERS_RUNS} (the three older entry points keep refusing what
+ * they refuse). Without GV_CLUSTERS_RUNS one command per survivor, in FIVE kernel launches; with it the runs of
+ * gv_pool_cull_cluster_runs over these decisions, in SIX — whatever the data holds. The launches are those of the form it takes,
+ * the test launch carrying the LOD test IN FRONT of the plane tests: a LOD-rejected cluster gets no plane test, no cone test and
+ * no Hi-Z query. Counted under GvStats::launches[GV_K_EMIT]. Placement, targets, capacity, counts: as the form it takes.
+ * The call IS a cluster cull of the pool: its result replaces the pool's cluster result and is replaced by the next one of any form;
+ * gv_pool_cluster_commands_device / _fetch serve it, and it ends where a cluster result ends (and at gv_pool_bind_cluster_lods).
+ * gv_pool_cull_clusters_second_phase behind a LOD result applies the same conjunction with this call's LOD views (and eyes, if
+ * any) against the pyramid as it stands at that call. Its pending set keeps its definition (tested, not kept, in a queried view),
+ * so LOD-REJECTED CLUSTERS ARE PENDING: re-tested, rejected again, counted in its counts[m + v]. With a DAG that is MOST of the
+ * pending set — practically every candidate, 180 to 622 times the leaves' own in the measured scenes. Behind the three older forms the second phase is unchanged.
+ * Errors: those of gv_pool_cull_clusters, plus GV_E_ARG: views NULL, view_count different from the views of E, a scale or a
+ * near_distance that is negative or NaN, one of eyes / eye_count without the other, eye_count different from the views of E;
+ * GV_E_STATE: no LOD binding, eyes without a cone binding. A refused call changes nothing.
+ * Not built: a per-view count of LOD-rejected clusters, LOD-rejected clusters left out of the second phase's pending set, LOD
+ * entries packed below 48 bytes, a hierarchical traversal that never visits the rejected sub-DAG, error metrics other than the
+ * sphere form above, LOD views derived from view_proj, clusters for the merged multi-rank order. */
+int gv_pool_cull_cluster_lods(GvCtx* ctx, uint32_t pool_id, uint32_t flags, const GvClusterLodView* views, uint32_t view_count,
+                              const GvClusterEye* eyes, uint32_t eye_count, uint32_t region_commands, void* dst_device, size_t capacity_bytes);
 
 /* ---- instance payload: the component fields a plugin copies next to mvp (sprite.cpp:127-129, 9-slice.cpp:25-44) ----
  * setInstanceData writes mvp and then copies a few fields of the draw's own component — color, uvSize, uvOffset — found through
